@@ -21,6 +21,12 @@ by spawn_ranks(1), init_process_group("nccl"), the ncclUniqueId from rank 0 over
 C4's orchestration that one GPU can execute (tests/test_multi_gpu_launch.py).  The bench line's `runtime` object says which
 librccl / libamdhip64 the process really bound (pt_runtime_info): torch is imported first here, so libptmi.so's imports of
 librccl.so.1 / libamdhip64.so.7 resolve to the copies PyTorch ships -- ONE HIP runtime per process, at every N.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the NIF `roofline` of the timed
+steps, `runtime`).  `--full` adds everything that takes runs of its own after the timed steps: the NIF-alone calibration, the
+reference's step definition, the trace stage alone, the secondary configurations and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step left for a caller (rank 0's worklist as `read_results` returns it, and
+the film where one is assembled) as float32 .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -207,6 +213,26 @@ def cpu_baseline(width, height, depth, layers, meta, mean, c1_gpu, target_second
                     "timing build on this host's cores; never the parity checker"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """Write each array as float32 `directory/<name>.npy`.  Should they exceed DUMP_LIMIT_BYTES together, each array keeps a
+    fixed, seeded sample of its rows (first axis) and `<name>_rows.npy` (float64) says which rows were kept."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / float(total + 8 * sum(a.shape[0] for a in arrays.values()))
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], int(a.shape[0] * frac), replace=False))
+            a = a[rows]
+            np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def spawn_ranks(n):
     """Launch this script as n ranks under torch.distributed.run, as a child process; relay stdout and the exit code.
     Nothing in this (parent) process has initialised the GPU: no exec of a GPU process, only a child."""
@@ -238,6 +264,12 @@ def main():
     ap.add_argument("--max-path-length", type=int, default=8)
     ap.add_argument("--hidden", type=int, default=320)
     ap.add_argument("--layers", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the NIF-alone calibration, the reference's step definition, the trace "
+                         "stage alone, the secondary configurations and the CPU baseline (each reported in the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's worklist results; the film where one is assembled) "
+                         "as float32 DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the two secondary measurements (BASELINE config C5, float32 NIF) reported beside the headline")
@@ -261,6 +293,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     dist_mode = args.dist or os.environ.get("BENCH_FORCE_DIST") == "1"
     if (args.gpus > 1 or dist_mode) and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -454,12 +488,21 @@ def main():
 
     elapsed = max_over_ranks(elapsed)
 
+    outputs = {}
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: read_results of the worklist, into a copy (the host worklist stays as uploaded)
+        res = state["work"].copy()
+        r.read_results(res)
+        outputs = {"radiance_sum_rgb": np.stack([res["r"], res["g"], res["b"]], axis=1),
+                   "sample_count": res["sampleCount"], "path_length": res["pathLength"],
+                   "pixel_uv": np.stack([res["u"], res["v"]], axis=1)}
+
     # Calibration, same invocation (never `value`): the NIF stage of the last step's largest batch again with nothing beside
     # it -- same kernel, same resident queue (pt_calibrate_nif).  `nif_alone_tflops` moves with the device (the pool's boxes
     # differ by 5-7 %); `value_over_alone` = the rate inside the pipelined step / this rate moves only when the pipeline
     # around the kernel changes.  A slow box lowers both numbers; a regression lowers the ratio.
     calib = None
-    if rank == 0 and not (multi and rehearsal):
+    if args.full and rank == 0 and not (multi and rehearsal):
         try:
             cal_ms, cal_evals = r.calibrate_nif(launches=4)
             calib = {"ms_per_launch": cal_ms, "evaluations_per_launch": int(cal_evals), "launches": 4}
@@ -470,23 +513,24 @@ def main():
     # Second leg, same invocation: the step as the reference times it (PathTracerApp.cpp:692-694,764-767): programs
     # setup -> path_trace -> read_results, i.e. with the worklist's H2D and D2H copies (20 B per item each way) inside.
     # `value` above keeps the inputs resident, as this benchmark's contract requires; this is the reference's own clock.
-    ref_work = state["work"].copy()
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        r.setup(ref_work)
-        r.path_trace()
-        r.read_results(ref_work)
-    barrier()
-    ref_elapsed = max_over_ranks(time.perf_counter() - t1)
+    if args.full:
+        ref_work = state["work"].copy()
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            r.setup(ref_work)
+            r.path_trace()
+            r.read_results(ref_work)
+        barrier()
+        ref_elapsed = max_over_ranks(time.perf_counter() - t1)
 
-    # Third leg: the trace stage on its own (constant sky, so no NIF kernel runs beside it), one warm-up + one timed step
-    # of the same worklist.  Gives the stage's stand-alone time and, with the per-path instruction count of the committed
-    # PMC pass, its rate against the VALU issue bound -- the kernel keeps ray state in registers and is VALU-bound.
-    r.set_constant_env((1.0, 1.0, 1.0))
-    r.path_trace()
-    r.path_trace()
-    alone = r.stats()
+        # Third leg: the trace stage on its own (constant sky, so no NIF kernel runs beside it), one warm-up + one timed step
+        # of the same worklist.  Gives the stage's stand-alone time and, with the per-path instruction count of the committed
+        # PMC pass, its rate against the VALU issue bound -- the kernel keeps ray state in registers and is VALU-bound.
+        r.set_constant_env((1.0, 1.0, 1.0))
+        r.path_trace()
+        r.path_trace()
+        alone = r.stats()
 
     if rank == 0:
         flops = int(st.nif_flops_per_sample)
@@ -511,11 +555,6 @@ def main():
                        "trace_dtype": "f32", "nif_flops_per_sample": flops,
                        "escaped_fraction": agg["escaped"] / max(agg["paths"], 1),
                        "segments_per_path": agg["segments"] / max(agg["paths"], 1)},
-            "reference_step_definition": {
-                "value": total_samples / ref_elapsed / 1e6, "unit": "Mpath-samples/s",
-                "ms_per_step": ref_elapsed / args.steps * 1e3, "steps": args.steps,
-                "what": "setup -> path_trace -> read_results per step, worklist H2D + D2H inside the clock "
-                        "(PathTracerApp.cpp:692-694,764-767); measured in this run"},
             "roofline": {"bound": "mfma", "kernel": kernel,
                          "achieved": achieved, "peak": MFMA_F16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / MFMA_F16_DENSE_PEAK_TFLOPS,
@@ -525,39 +564,45 @@ def main():
                                          "rocprofv3 passes, read from %s" % traffic_src,
                          "rank0_stage_ms": {"trace": agg["trace_ms"], "nif": agg["nif_ms"], "accumulate": agg["acc_ms"]}},
         }
-        # Trace stage (ray-gen, intersect, shade, compact; accumulate is its own kernel).  Everything here is measured in
-        # this run except the per-path constants, which come from the named PMC file.  Accounting as SURVEY.md 8(d) /
-        # BASELINE.md section 4 define it: algorithmic bytes = 96 B per path segment + 88 B per escaped path -- the traffic of
-        # a wavefront tracer that keeps ray state in HBM between bounces.  This design keeps it in registers, so the bytes
-        # the counters see are a fraction of that figure (avoided, not wasted) and the stage is bound by the vector ALU:
-        # ONE fraction is reported, the share of all SIMD cycles in which the VALU is executing.
-        pmc, pmc_src = trace_counters_from_profile(depth)
-        alone_s = alone.path_trace_ms * 1e-3
-        seg_step, esc_step = agg["segments"] / args.steps, agg["escaped"] / args.steps
-        ts = {"bound": "valu",
-              "standalone_ms_per_step": alone.path_trace_ms, "standalone_accumulate_ms_per_step": alone.accumulate_ms,
-              "standalone_Mpath_samples_per_s": alone.paths / max(alone_s, 1e-9) / 1e6,
-              "overlapped_ms_per_step": agg["trace_ms"] / args.steps,
-              "rays_per_sec": agg["segments"] * world / elapsed,
-              "algorithmic_bytes_per_step": 96.0 * seg_step + 88.0 * esc_step,
-              "algorithmic_bytes_model": "96 B x path segments + 88 B x escaped paths per step (SURVEY.md 8(d)): assumes ray state "
-                                         "travels through HBM between bounces; here it stays in registers",
-              "what": "stand-alone = one constant-sky step of the same worklist in this run (no NIF kernel beside it); "
-                      "overlapped = the trace kernels' own HIP-event time while the NIF kernel shares the CUs"}
-        if pmc:
-            if pmc.get("hbm_bytes_per_path"):
-                ts["counter_bytes_per_step"] = pmc["hbm_bytes_per_path"] * agg["paths"] / args.steps
-                ts["counter_over_algorithmic"] = ts["counter_bytes_per_step"] / max(ts["algorithmic_bytes_per_step"], 1.0)
-                ts["achieved_hbm_GBps"] = pmc["hbm_bytes_per_path"] * alone.paths / max(alone_s, 1e-9) / 1e9
-                ts["hbm_peak_GBps"] = HBM_PEAK_GBPS
-            ts["frac"] = pmc.get("valu_busy_fraction")
-            ts["frac_is"] = "VALU busy: cycles the SIMDs spend executing vector instructions / all SIMD cycles of the launch"
-            ts["valu_wave_instr_per_path"] = pmc["valu_wave_instr_per_path"]
-            ts["cycles_per_valu_wave_instr"] = pmc.get("cycles_per_valu_wave_instr")
-            ts["lane_utilisation"] = pmc.get("lane_utilisation")
-            ts["G_wave_instr_per_s"] = pmc["valu_wave_instr_per_path"] * alone.paths / max(alone_s, 1e-9) / 1e9
-            ts["counters_from"] = "%s (not measured in this run)" % pmc_src
-        out["trace_stage"] = ts
+        if args.full:
+            out["reference_step_definition"] = {
+                "value": total_samples / ref_elapsed / 1e6, "unit": "Mpath-samples/s",
+                "ms_per_step": ref_elapsed / args.steps * 1e3, "steps": args.steps,
+                "what": "setup -> path_trace -> read_results per step, worklist H2D + D2H inside the clock "
+                        "(PathTracerApp.cpp:692-694,764-767); measured in this run"}
+            # Trace stage (ray-gen, intersect, shade, compact; accumulate is its own kernel).  Everything here is measured in
+            # this run except the per-path constants, which come from the named PMC file.  Accounting as SURVEY.md 8(d) /
+            # BASELINE.md section 4 define it: algorithmic bytes = 96 B per path segment + 88 B per escaped path -- the traffic
+            # of a wavefront tracer that keeps ray state in HBM between bounces.  This design keeps it in registers, so the
+            # bytes the counters see are a fraction of that figure (avoided, not wasted) and the stage is bound by the vector
+            # ALU: ONE fraction is reported, the share of all SIMD cycles in which the VALU is executing.
+            pmc, pmc_src = trace_counters_from_profile(depth)
+            alone_s = alone.path_trace_ms * 1e-3
+            seg_step, esc_step = agg["segments"] / args.steps, agg["escaped"] / args.steps
+            ts = {"bound": "valu",
+                  "standalone_ms_per_step": alone.path_trace_ms, "standalone_accumulate_ms_per_step": alone.accumulate_ms,
+                  "standalone_Mpath_samples_per_s": alone.paths / max(alone_s, 1e-9) / 1e6,
+                  "overlapped_ms_per_step": agg["trace_ms"] / args.steps,
+                  "rays_per_sec": agg["segments"] * world / elapsed,
+                  "algorithmic_bytes_per_step": 96.0 * seg_step + 88.0 * esc_step,
+                  "algorithmic_bytes_model": "96 B x path segments + 88 B x escaped paths per step (SURVEY.md 8(d)): assumes ray "
+                                             "state travels through HBM between bounces; here it stays in registers",
+                  "what": "stand-alone = one constant-sky step of the same worklist in this run (no NIF kernel beside it); "
+                          "overlapped = the trace kernels' own HIP-event time while the NIF kernel shares the CUs"}
+            if pmc:
+                if pmc.get("hbm_bytes_per_path"):
+                    ts["counter_bytes_per_step"] = pmc["hbm_bytes_per_path"] * agg["paths"] / args.steps
+                    ts["counter_over_algorithmic"] = ts["counter_bytes_per_step"] / max(ts["algorithmic_bytes_per_step"], 1.0)
+                    ts["achieved_hbm_GBps"] = pmc["hbm_bytes_per_path"] * alone.paths / max(alone_s, 1e-9) / 1e9
+                    ts["hbm_peak_GBps"] = HBM_PEAK_GBPS
+                ts["frac"] = pmc.get("valu_busy_fraction")
+                ts["frac_is"] = "VALU busy: cycles the SIMDs spend executing vector instructions / all SIMD cycles of the launch"
+                ts["valu_wave_instr_per_path"] = pmc["valu_wave_instr_per_path"]
+                ts["cycles_per_valu_wave_instr"] = pmc.get("cycles_per_valu_wave_instr")
+                ts["lane_utilisation"] = pmc.get("lane_utilisation")
+                ts["G_wave_instr_per_s"] = pmc["valu_wave_instr_per_path"] * alone.paths / max(alone_s, 1e-9) / 1e9
+                ts["counters_from"] = "%s (not measured in this run)" % pmc_src
+            out["trace_stage"] = ts
         if calib and "error" not in calib:
             alone_tf = calib["evaluations_per_launch"] * flops / (calib["ms_per_launch"] * 1e-3) / 1e12
             out["roofline"]["nif_alone_tflops"] = alone_tf
@@ -579,9 +624,9 @@ def main():
                                        "(pt_runtime_info): torch is imported first, so they are the copies PyTorch ships")
         except Exception as e:   # noqa: BLE001
             out["runtime"] = {"error": str(e)}
-        if world == 1 and not args.no_secondary and not wide and not dist_mode:
+        if args.full and world == 1 and not args.no_secondary and not wide and not dist_mode:
             out["secondary"] = secondary_configs(ptmi, nif_assets, W, H, depth, meta, mean)
-        if world == 1 and not args.no_cpu_baseline and not dist_mode:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dist_mode:
             # the GPU's rate on configs[0] first: the CPU legs start 100+ OpenMP threads that keep spinning afterwards
             try:
                 c1_gpu = c1_on_the_gpu(ptmi)
@@ -604,8 +649,12 @@ def main():
             out["config"]["film_nonzero_fraction"] = float((film.sum(axis=2) > 0).mean())
             if args.dump_film:
                 np.save(args.dump_film, film)
+            if args.dump_outputs:
+                outputs["film_bgr"] = film
         if rehearsal:
             out["data"] = "synthetic (REHEARSAL on one shared GPU -- not a measurement)"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     r.close()
     if multi:

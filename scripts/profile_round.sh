@@ -9,13 +9,13 @@ ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1"
+BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1 --full"
 $BENCH > $OUT/bench.json 2> $OUT/bench.err
 echo "[profile_round] bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $BENCH --no-cpu-baseline > $OUT/trace.log 2>&1
 find $OUT/trace -name "*kernel_trace*" -delete
 echo "[profile_round] kernel trace done"
-SHORT="python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline"
+SHORT="python3 $ROOT/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o c -- $SHORT > $OUT/pmc_fetch.log 2>&1
 echo "[profile_round] FETCH_SIZE done"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o c -- $SHORT > $OUT/pmc_write.log 2>&1

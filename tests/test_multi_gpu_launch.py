@@ -209,7 +209,7 @@ def test_bench_takes_the_real_n_rank_branch_at_world_size_one(tmp_path):
     assert "/torch/lib/" in out["runtime"]["librccl"] and out["runtime"]["rccl_version"] > 0
 
     dist_film = str(tmp_path / "dist.npy")
-    out = _bench_line(common + ["--dist", "--dump-film", dist_film])
+    out = _bench_line(common + ["--dist", "--full", "--dump-film", dist_film])
     assert out["n_gpus"] == 1 and out["value"] > 0
     assert out["config"]["hdr_gather"] == "pt_gather_hdr (RCCL inside libptmi.so)", out["config"]
     assert out["runtime"]["torch_imported_first"] and "/torch/lib/" in out["runtime"]["librccl"]
