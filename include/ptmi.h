@@ -174,6 +174,42 @@ int pt_nif_kernel_name(pt_handle h, char* buf, size_t n);
  * number of NIF evaluations per launch (the queue length).  The worklist's accumulators are not touched.  Comparing this
  * rate with the one inside a step separates a slow device from a regression of the pipeline around the kernel. */
 int pt_calibrate_nif(pt_handle h, uint32_t launches, double* ms_per_launch, uint64_t* evaluations);
+/* With NIF sharing on (below), pt_calibrate_nif replays what that step really ran: the NIF stage over the batch's DISTINCT
+ * queue, and `evaluations` is that queue's length. */
+
+/* Exact sharing of NIF evaluations -- an EXTENSION: the reference evaluates the NIF on every escaped path
+ * (PathTracerApp.cpp:147-198).  The NIF output of an escaped path depends on its (u, v) alone (the azimuth is folded in by
+ * PreProcessEscapedRays, codelets.cpp:343-347; the path's throughput multiplies the decoded BGR afterwards, one fp32 multiply
+ * per channel), and camera rays and primary samples are half, so many escaped paths carry bit-identical (u, v).
+ *   PT_NIF_SHARE_OFF    every escaped path is one NIF row (the default; the library runs exactly as without this API).
+ *   PT_NIF_SHARE_BATCH  paths of one kernel batch whose queue entries have bit-identical (u, v) share one NIF evaluation.
+ *   PT_NIF_SHARE_STEP   the same across all batches of one pt_path_trace.
+ * Exact: the key is the 64 raw bits of (u, v), with no tolerance; each distinct key is evaluated once by the unchanged NIF
+ * kernels (every kernel family, float32 and mixed models included), and every path gets owner_bgr[k] * throughput[k], the
+ * same single fp32 multiply the per-path NIF head does.  So every accumulator, record, resident-film value and HDR tile is
+ * bit-identical to sharing off, for any option set and any table capacity.  A key that finds no table slot (full table, or
+ * the key equals the table's empty marker) is evaluated on its own and counted in `overflowed`: never dropped.
+ * No table survives a step: every pt_path_trace starts empty, so hot-swapping the NIF (pt_upload_nif), a new azimuth
+ * (pt_set_render_settings) and a mode switch between steps need no invalidation.
+ * pt_set_nif_sharing takes effect at the next pt_path_trace.  The first switch to a sharing mode allocates the device table
+ * (sized from the batch capacity and the free memory) and the distinct-queue store: PT_ERR_OUT_OF_MEMORY leaves the mode
+ * off.  A step-scope step with more batches than the store holds grows it (pt_path_trace may then return
+ * PT_ERR_OUT_OF_MEMORY).  A bad mode or a NULL handle is PT_ERR_INVALID_ARGUMENT.
+ * pt_stats keeps its meaning (escaped = escaped paths); pt_get_nif_sharing_stats reports the rows the last path_trace really
+ * ran: evaluations == escaped with sharing off, 0 with a constant environment (no sharing pass runs then).  The caller
+ * sets struct_size = sizeof(pt_nif_sharing_stats). */
+enum { PT_NIF_SHARE_OFF = 0, PT_NIF_SHARE_BATCH = 1, PT_NIF_SHARE_STEP = 2 };
+typedef struct pt_nif_sharing_stats {
+  uint32_t struct_size;          /* sizeof(pt_nif_sharing_stats), set by the caller */
+  int32_t mode;                  /* mode the last path_trace ran with (PT_NIF_SHARE_OFF with a constant environment) */
+  uint64_t escaped;              /* = pt_stats.escaped */
+  uint64_t evaluations;          /* NIF rows executed by the last path_trace */
+  uint64_t overflowed;           /* entries evaluated alone because no table slot was free */
+  uint64_t table_slots;          /* table capacity in use (0 with sharing off) */
+  double share_ms;               /* device time of the sharing passes (HIP events, read lazily like the stage times) */
+} pt_nif_sharing_stats;
+int pt_set_nif_sharing(pt_handle h, int32_t mode);
+int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
 
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);

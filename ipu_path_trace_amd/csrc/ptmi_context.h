@@ -90,6 +90,9 @@ struct pt_context {
     hipEvent_t accumulated = nullptr;  // accumulate kernel has consumed this set
     // geometry of the last batch whose NIF stage ran on this set (pt_calibrate_nif replays the larger one): 0 = none yet
     uint32_t last_paths = 0, last_regions = 0, last_region_cap = 0;
+    // ... and, if that batch ran with sharing on, where its distinct queue lies: count index (-1 = not shared), store base
+    int32_t share_batch = -1;
+    uint32_t share_base = 0, share_region_cap = 0;
   } bb[2];
   hipStream_t trace_stream = nullptr;
   hipStream_t acc_stream = nullptr;   // accumulate(b) runs here, so NIF(b+1) follows NIF(b) back to back on `stream`
@@ -142,11 +145,31 @@ struct pt_context {
   unsigned long long* d_stamps = nullptr;   // profiling build: 256 phase stamps of the wide-NIF layer kernel
   int diag_fault_batch = -1;                // test build: batch whose NIF launch fails (pt_diag_inject_fault), -1 = none
 
+  // exact sharing of NIF evaluations (pt_set_nif_sharing, pt_nif_share.h).  Nothing here survives a step: the table is
+  // cleared at the start of every batch (PT_NIF_SHARE_BATCH) or step (PT_NIF_SHARE_STEP), the counts at every step.
+  int32_t share_mode = 0;                    // requested: taken up by the next pt_path_trace
+  int32_t share_mode_last = 0;               // what the last pt_path_trace ran with (0 also for a constant environment)
+  unsigned long long* d_share_keys = nullptr;
+  uint32_t* d_share_vals = nullptr;
+  uint32_t share_slots = 0;                  // table capacity, a power of two
+  uint32_t share_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_share_capacity), 0 = sized from memory
+  uint32_t* d_share_owner[2] = {nullptr, nullptr};   // per batch-buffer set: [queue_cap] store index of every entry's owner
+  // the step's distinct queues and their decoded BGR, region-structured: batch b's at store index (b or b & 1) x queue_cap
+  float *d_share_u = nullptr, *d_share_v = nullptr, *d_share_bgr = nullptr;
+  size_t share_regions = 0;
+  uint32_t* d_share_count = nullptr;         // [batch] distinct-queue length
+  unsigned long long* d_share_over = nullptr;
+  uint32_t* h_share_count = nullptr;         // pinned copies, written at the end of the step on `stream`
+  unsigned long long* h_share_over = nullptr;
+  size_t share_count_cap = 0;
+  uint64_t share_evals = 0, share_overflowed = 0;
+  double share_ms = 0;
+
   // stats.  The per-stage times are read lazily (pt_get_stats / pt_read_results): 3 hipEventElapsedTime calls per batch are
   // host time a step of a small image should not pay (BASELINE configs[0] is one millisecond of device work per step).
   pt_stats stats{};
   std::vector<hipEvent_t> events;
-  struct StageSpan { size_t a, b; int kind; };   // event pair around one stage of one batch: 0 trace, 1 NIF, 2 accumulate
+  struct StageSpan { size_t a, b; int kind; };   // event pair around one stage of one batch: 0 trace, 1 NIF, 2 accumulate, 3 NIF sharing
   std::vector<StageSpan> spans;
   size_t e_begin_i = 0, e_end_i = 0;
   bool spans_pending = false;

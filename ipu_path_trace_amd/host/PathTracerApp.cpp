@@ -87,7 +87,33 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"host-film", 0, "false", false, true, "Run the reference's step loop (worklist to the host every step, host film) even without load balancing."},
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
+      {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
   };
+}
+
+// --share-nif-evaluations (an extension: the reference evaluates the NIF on every escaped path, PathTracerApp.cpp:147-198)
+std::int32_t nifSharingMode(const std::string& name) {
+  if (name == "off") return PT_NIF_SHARE_OFF;
+  if (name == "batch") return PT_NIF_SHARE_BATCH;
+  if (name == "step") return PT_NIF_SHARE_STEP;
+  throw std::runtime_error("--share-nif-evaluations must be one of off, batch, step; got '" + name + "'");
+}
+
+pt_nif_sharing_stats PathTracerApp::sharingStatsRequest() {
+  pt_nif_sharing_stats s{};
+  s.struct_size = sizeof(pt_nif_sharing_stats);
+  return s;
+}
+
+void PathTracerApp::countNifEvaluations(const std::vector<pt_nif_sharing_stats>& share) {
+  for (const auto& s : share) { nifEscaped += s.escaped; nifEvaluations += s.evaluations; }
+}
+
+// NIF rows executed since the last save interval, against the escaped paths (Samples/sec still counts path-samples)
+void PathTracerApp::logNifEvaluations() {
+  const double shared = nifEscaped ? 100.0 * (double)(nifEscaped - std::min(nifEscaped, nifEvaluations)) / (double)nifEscaped : 0.0;
+  pt_log::info_("NIF evaluations: executed {} of {} escaped ({} % shared)", nifEvaluations, nifEscaped, shared);
+  nifEscaped = nifEvaluations = 0;
 }
 
 void PathTracerApp::init(const OptionMap& options) {
@@ -99,6 +125,7 @@ void PathTracerApp::init(const OptionMap& options) {
   if (args.u32("ipus") == 0) throw std::runtime_error("--ipus must be at least 1.");
   if (args.u32("save-interval") == 0) throw std::runtime_error("--save-interval must be at least 1.");
   if (samplesPerIpuStep == 0) throw std::runtime_error("--samples-per-step must be at least 1.");
+  nifSharing = nifSharingMode(args.str("share-nif-evaluations"));
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
   if (!image_io::ldrWriterFor(args.str("outfile")))
@@ -190,6 +217,8 @@ void PathTracerApp::attach() {
     pt_handle h = nullptr;
     if (pt_create(&cfg, &h)) throw std::runtime_error(std::string("Could not attach to device: ") + pt_last_error(nullptr));
     devices.push_back(h);
+    if (pt_set_nif_sharing(h, nifSharing))
+      throw std::runtime_error(std::string("--share-nif-evaluations: ") + pt_last_error(h));
   }
   if (numDevices > 1 && hostGather) {
     pt_log::info_("HDR tiles of {} devices are gathered through the host", numDevices);
@@ -356,12 +385,14 @@ void PathTracerApp::executeResidentFilm(std::uint32_t steps) {
   for (auto step = 1u; step <= steps; ++step) {
     auto loopStartTime = std::chrono::steady_clock::now();
     std::vector<pt_stats> stats(devices.size());
+    std::vector<pt_nif_sharing_stats> share(devices.size(), sharingStatsRequest());
     // path_trace, then on the device what the host task does in the reference's loop: film += (b,g,r)/sampleCount and
     // clear the accumulators (PathTracerApp.cpp:717-745)
     onEveryDevice("Device step", [&](std::size_t d) {
       int rc;
       { pt_trace::Range r("ipu_render"); rc = pt_path_trace(devices[d]) || pt_get_stats(devices[d], &stats[d]); }   // PathTracerApp.cpp:688-699
       if (rc) return rc;
+      if ((rc = pt_get_nif_sharing_stats(devices[d], &share[d]))) return rc;
       pt_trace::Range r("accumulate_framebuffers");                                                                // :725-727, on the device
       return pt_film_accumulate(devices[d]);
     });
@@ -370,8 +401,10 @@ void PathTracerApp::executeResidentFilm(std::uint32_t steps) {
     pt_log::debug_("Path-Trace ms: {}", stats[0].path_trace_ms);
     pt_log::debug_("NIF ms: {}", stats[0].nif_ms);
     pt_log::debug_("Total ms per step: {}", stats[0].total_ms);
+    countNifEvaluations(share);
 
     if (step % saveInterval == 0 || step == steps) {
+      logNifEvaluations();
       { pt_trace::Range r("wait_for_host"); hostProcessing.waitForCompletion(); }   // the previous save still reads filmRecords (:702-706)
       // the ONE exchange of the multi-GPU path: HDR tiles to device 0 over RCCL, then to the host film
       // (--host-gather, or logical devices sharing a GPU: no communicator, every device hands its own tile to the host)
@@ -520,12 +553,16 @@ void PathTracerApp::executeHostFilm(std::uint32_t steps) {
     // cut into equal contiguous slices, one per device, as tiles are cut over IPUs.
     auto& active = traceState->work.getWork().active();
     std::vector<pt_stats> stats(devices.size());
+    std::vector<pt_nif_sharing_stats> share(devices.size(), sharingStatsRequest());
     onEveryDevice("Device step", [&](std::size_t d) {
       auto* slice = reinterpret_cast<pt_trace_record*>(active.data() + d * itemsPerDevice);
       pt_handle h = devices[d];
       pt_trace::Range r("ipu_render");                                        // :688-699
-      return pt_setup(h, slice, itemsPerDevice) || pt_path_trace(h) || pt_read_results(h, slice, itemsPerDevice, &stats[d]);
+      return pt_setup(h, slice, itemsPerDevice) || pt_path_trace(h) || pt_read_results(h, slice, itemsPerDevice, &stats[d]) ||
+             pt_get_nif_sharing_stats(h, &share[d]);
     });
+    countNifEvaluations(share);
+    if (step % saveInterval == 0 || step == steps) logNifEvaluations();
     pt_log::debug_("Path-Trace ms: {}", stats[0].path_trace_ms);
     pt_log::debug_("NIF ms: {}", stats[0].nif_ms);
     pt_log::debug_("Total ms per step: {}", stats[0].total_ms);

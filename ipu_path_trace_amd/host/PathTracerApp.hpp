@@ -54,6 +54,10 @@ private:
   /// Step loop as the reference runs it (setup -> path_trace -> read_results, host film): needed when the balancer
   /// re-deals the worklist from the returned path lengths every step.
   void executeHostFilm(std::uint32_t steps);
+  /// --share-nif-evaluations: NIF rows executed against escaped paths, summed over the devices and logged at save intervals.
+  static pt_nif_sharing_stats sharingStatsRequest();
+  void countNifEvaluations(const std::vector<pt_nif_sharing_stats>& share);
+  void logNifEvaluations();
 
   OptionMap args;
   std::uint32_t samplesPerPixel = 0;
@@ -67,6 +71,8 @@ private:
   std::size_t deviceCapacity = 0;   // work items per device incl. padding (pt_config.max_work_items)
   bool hostGather = false;   ///< HDR tiles through the host (one copy per device) instead of the RCCL gather
   double finalSamplesPerSec = 0.0;
+  std::int32_t nifSharing = PT_NIF_SHARE_OFF;
+  std::uint64_t nifEscaped = 0, nifEvaluations = 0;
   std::chrono::steady_clock::time_point renderStartTime;   // reset when the UI restarts the render (PathTracerApp.cpp:669)
 };
 

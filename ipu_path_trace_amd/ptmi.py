@@ -25,7 +25,9 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_export_hdr_device", "pt_clear_accumulators", "pt_synchronize", "pt_nif_infer", "pt_trace_paths",
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_init_all", "pt_comm_info", "pt_comm_set_timeout", "pt_comm_abort",
            "pt_gather_hdr", "pt_film_accumulate", "pt_tile_costs_enable", "pt_tile_costs", "pt_film_seed",
-           "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info"]
+           "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats"]
+NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
+NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 COMM_ID_BYTES = 128
 HDR_ACCUMULATORS, HDR_FILM = 0, 1
 
@@ -61,6 +63,14 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class NifSharingStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("escaped", C.c_uint64), ("evaluations", C.c_uint64),
+                ("overflowed", C.c_uint64), ("table_slots", C.c_uint64), ("share_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 _libs = {}
 
 
@@ -84,6 +94,9 @@ def load_library(diag=False):
     if L.pt_abi_version() != ABI_VERSION:   # a stale in-tree build: the structs below would not match the library's
         raise RuntimeError("%s has ABI version %d, this binding needs %d: rebuild it (python -c 'import __graft_entry__ as g; "
                            "g.build()')" % (path, L.pt_abi_version(), ABI_VERSION))
+    for sym in EXPORTS:   # same ABI version, fewer entry points: an in-tree build from before they were added
+        if not hasattr(L, sym):
+            raise RuntimeError("%s does not export %s: rebuild it (python -c 'import __graft_entry__ as g; g.build()')" % (path, sym))
     L.pt_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
     L.pt_destroy.argtypes = [C.c_void_p]
     L.pt_last_error.restype = C.c_char_p
@@ -115,7 +128,10 @@ def load_library(diag=False):
     L.pt_nif_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pt_calibrate_nif.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.pt_runtime_info.argtypes = [C.c_char_p, C.c_size_t]
+    L.pt_set_nif_sharing.argtypes = [C.c_void_p, C.c_int32]
+    L.pt_get_nif_sharing_stats.argtypes = [C.c_void_p, C.POINTER(NifSharingStats)]
     if diag:
+        L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_inject_fault.argtypes = [C.c_void_p, C.c_int32]
         L.pt_diag_stamps.argtypes = [C.c_void_p, C.c_void_p]
         L.pt_diag_nif_clock.argtypes = [C.c_void_p, C.c_void_p]
@@ -235,6 +251,22 @@ class Renderer:
         ms, evals = C.c_double(), C.c_uint64()
         self._check(self._lib.pt_calibrate_nif(self.handle, launches, C.byref(ms), C.byref(evals)))
         return ms.value, evals.value
+
+    def set_nif_sharing(self, mode):
+        """Exact sharing of NIF evaluations between paths with bit-identical (u, v): "off", "batch" or "step"
+        (include/ptmi.h, pt_set_nif_sharing).  Takes effect at the next path_trace."""
+        if mode not in NIF_SHARE_MODES:
+            raise ValueError("NIF sharing mode must be one of %s, got %r" % (sorted(NIF_SHARE_MODES), mode))
+        self._check(self._lib.pt_set_nif_sharing(self.handle, NIF_SHARE_MODES[mode]))
+
+    def nif_sharing_stats(self):
+        """NIF rows the last path_trace really ran: dict of mode, escaped, evaluations, overflowed, table_slots, share_ms."""
+        st = NifSharingStats()
+        st.struct_size = C.sizeof(NifSharingStats)
+        self._check(self._lib.pt_get_nif_sharing_stats(self.handle, C.byref(st)))
+        d = st.as_dict()
+        d["mode"] = {v: k for k, v in NIF_SHARE_MODES.items()}.get(d["mode"], d["mode"])
+        return d
 
     def export_hdr_device(self, device_ptr, n):
         self._check(self._lib.pt_export_hdr_device(self.handle, C.c_void_p(device_ptr), n))
