@@ -211,6 +211,43 @@ typedef struct pt_nif_sharing_stats {
 int pt_set_nif_sharing(pt_handle h, int32_t mode);
 int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
 
+/* Persistent memo of NIF evaluations across steps -- an EXTENSION like sharing.  The decoded BGR of a key (the 64 raw bits of
+ * (u, v), azimuth already folded in) depends on the uploaded model alone, so it stays valid from step to step until
+ * pt_upload_nif.  pt_set_nif_memo(h, max_bytes) turns on a device table of at most max_bytes (48 bytes per slot: one 32-byte
+ * slot -- key, state, last-hit step, decoded BGR -- and room to retain it; a power of two, at most 2^30 slots); 0 turns it off
+ * (the default: the library then runs exactly as without this API).  Setting the capacity it already has keeps the entries.
+ * Exact: a key found in the memo gets the fp32 BGR the NIF kernels' out_bgr mode wrote for it, times the path's throughput by
+ * the heads' own single fp32 multiply per channel, so every record, accumulator, resident-film value and HDR tile is
+ * bit-identical to memo off, for every option set, every kernel family (fused fp16, layer-by-layer wide, float32, mixed) and
+ * any capacity.  Independent of the sharing mode: with the memo on every batch looks the memo up first, and the keys it does
+ * not hold are shared as by PT_NIF_SHARE_STEP (in the step store) whatever pt_set_nif_sharing says.  Values of a step are
+ * published into the memo once, at its end, so later batches of the same step reach them through the step store.  A key
+ * that finds no slot within the probe limit is evaluated on its own and counted in `overflowed`: never dropped.  When more
+ * than half of the slots are occupied after a step, the next step starts with a retain pass that keeps only the entries hit
+ * in the last step (`retains` counts them).
+ * Generation: pt_upload_nif, pt_clear_nif_memo and a pt_path_trace that fails start a new generation (every entry is
+ * forgotten).  Nothing else invalidates the memo: not pt_set_render_settings (seed, fov, azimuth, AA), not pt_setup, not
+ * pt_set_constant_env -- with a constant environment no memo pass runs.
+ * Allocation: pt_set_nif_memo can return PT_ERR_OUT_OF_MEMORY and the memo is then left off; max_bytes between 1 and
+ * 48 KiB - 1 is PT_ERR_INVALID_ARGUMENT.  The step store of step-scope sharing (not counted in max_bytes) is used and grown
+ * as with PT_NIF_SHARE_STEP.
+ * pt_nif_sharing_stats keeps its meaning: `evaluations` counts the NIF rows that ran, so evaluations == escaped holds only
+ * when both sharing and the memo are off; with the memo on its passes are timed in memo_ms, not share_ms.  The caller sets
+ * struct_size = sizeof(pt_nif_memo_stats).  A NULL handle is PT_ERR_INVALID_ARGUMENT. */
+typedef struct pt_nif_memo_stats {
+  uint32_t struct_size;          /* sizeof(pt_nif_memo_stats), set by the caller */
+  int32_t enabled;               /* the memo is on */
+  uint64_t slots, occupied;      /* capacity in use; valid entries after the last step */
+  uint64_t escaped, served;      /* escaped paths of the last step; of those, served from entries of EARLIER steps */
+  uint64_t evaluations, inserted;/* NIF rows the last step ran; new entries it published */
+  uint64_t overflowed;           /* evaluated alone: no slot within the probe limit */
+  uint64_t generation, retains;  /* bumped by upload / clear / failed step; retain passes so far */
+  double memo_ms;                /* device time of the memo passes of the last step (HIP events, read lazily) */
+} pt_nif_memo_stats;
+int pt_set_nif_memo(pt_handle h, uint64_t max_bytes);
+int pt_clear_nif_memo(pt_handle h);
+int pt_get_nif_memo_stats(pt_handle h, pt_nif_memo_stats* out);
+
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);
  * the only exchange is the film: mean radiance per work item, BGR float32 [n][3] -- the value

@@ -165,11 +165,27 @@ struct pt_context {
   uint64_t share_evals = 0, share_overflowed = 0;
   double share_ms = 0;
 
+  // persistent memo of decoded NIF values (pt_set_nif_memo, pt_nif_memo.h).  Unlike the sharing table it outlives the step:
+  // it is cleared at allocation, on a new generation (pt_upload_nif, pt_clear_nif_memo, a failed pt_path_trace) and by the
+  // retain pass.  With the memo on, every step uses the step-scope store above (d_share_u / _v / _bgr, d_share_count).
+  ptd::MemoSlot* d_memo = nullptr;
+  uint32_t memo_slots = 0;                   // table capacity, a power of two; 0 = memo off
+  ptd::MemoSlot* d_memo_list = nullptr;      // retain list, memo_slots / 2 entries
+  uint32_t* d_memo_slot = nullptr;           // [store index]: slot the entry is published into (memo_slot_regions x queue_cap)
+  size_t memo_slot_regions = 0;
+  unsigned long long* d_memo_ctr = nullptr;  // ptd::kMemoCounters counters of the memo passes
+  unsigned long long* h_memo_ctr = nullptr;  // pinned copy, written at the end of the step on `stream` (the step's one wait)
+  bool memo_clear = false;                   // clear the table before the next lookup
+  uint32_t memo_step = 0;                    // stamp of the last step that ran the memo passes
+  bool memo_ran = false;                     // the last pt_path_trace ran them
+  uint64_t memo_occupied = 0, memo_served = 0, memo_inserted = 0, memo_generation = 0, memo_retains = 0;
+  double memo_ms = 0;
+
   // stats.  The per-stage times are read lazily (pt_get_stats / pt_read_results): 3 hipEventElapsedTime calls per batch are
   // host time a step of a small image should not pay (BASELINE configs[0] is one millisecond of device work per step).
   pt_stats stats{};
   std::vector<hipEvent_t> events;
-  struct StageSpan { size_t a, b; int kind; };   // event pair around one stage of one batch: 0 trace, 1 NIF, 2 accumulate, 3 NIF sharing
+  struct StageSpan { size_t a, b; int kind; };   // event pair around one stage of one batch: 0 trace, 1 NIF, 2 accumulate, 3 NIF sharing, 4 NIF memo
   std::vector<StageSpan> spans;
   size_t e_begin_i = 0, e_end_i = 0;
   bool spans_pending = false;

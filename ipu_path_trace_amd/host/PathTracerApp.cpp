@@ -88,6 +88,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
+      {"nif-memo-gib", 0, "0", false, false, "GiB of device memory for a memo of decoded NIF values kept across steps, per logical device (0 = off). Exact: the image is bit-identical to off. Escaped paths whose (u, v) an earlier step evaluated are served from it; the memo is forgotten when a new NIF is loaded."},
   };
 }
 
@@ -116,6 +117,32 @@ void PathTracerApp::logNifEvaluations() {
   nifEscaped = nifEvaluations = 0;
 }
 
+// --nif-memo-gib (an extension, like sharing): a non-negative number of GiB
+std::uint64_t nifMemoBytes(const std::string& text) {
+  std::size_t used = 0;
+  double gib = -1.0;
+  try { gib = std::stod(text, &used); } catch (const std::exception&) { used = 0; }
+  if (text.empty() || used != text.size() || !(gib >= 0.0) || gib > 1e6)
+    throw std::runtime_error("--nif-memo-gib must be a non-negative number of GiB; got '" + text + "'");
+  return (std::uint64_t)(gib * (double)(1ull << 30));
+}
+
+pt_nif_memo_stats PathTracerApp::memoStatsRequest() {
+  pt_nif_memo_stats s{};
+  s.struct_size = sizeof(pt_nif_memo_stats);
+  return s;
+}
+
+void PathTracerApp::countMemo(const std::vector<pt_nif_memo_stats>& memo) {
+  for (const auto& s : memo) { memoServed += s.served; memoEscaped += s.escaped; memoRows += s.evaluations; }
+}
+
+// escaped paths the memo served since the last save interval, and the NIF rows that still ran
+void PathTracerApp::logMemo() {
+  if (nifMemo) pt_log::info_("NIF memo: served {} of {} escaped, {} rows executed", memoServed, memoEscaped, memoRows);
+  memoServed = memoEscaped = memoRows = 0;
+}
+
 void PathTracerApp::init(const OptionMap& options) {
   args = options;
   samplesPerPixel = args.u32("samples");
@@ -126,6 +153,7 @@ void PathTracerApp::init(const OptionMap& options) {
   if (args.u32("save-interval") == 0) throw std::runtime_error("--save-interval must be at least 1.");
   if (samplesPerIpuStep == 0) throw std::runtime_error("--samples-per-step must be at least 1.");
   nifSharing = nifSharingMode(args.str("share-nif-evaluations"));
+  nifMemo = nifMemoBytes(args.str("nif-memo-gib"));
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
   if (!image_io::ldrWriterFor(args.str("outfile")))
@@ -219,6 +247,16 @@ void PathTracerApp::attach() {
     devices.push_back(h);
     if (pt_set_nif_sharing(h, nifSharing))
       throw std::runtime_error(std::string("--share-nif-evaluations: ") + pt_last_error(h));
+  }
+  // one memo per logical device: logical devices that share a GPU need room for all of theirs, or none runs with one
+  for (std::size_t d = 0; d < numDevices && nifMemo; ++d) {
+    const int rc = pt_set_nif_memo(devices[d], nifMemo);
+    if (rc == PT_OK) continue;
+    if (rc != PT_ERR_OUT_OF_MEMORY) throw std::runtime_error(std::string("--nif-memo-gib: ") + pt_last_error(devices[d]));
+    pt_log::warn_("--nif-memo-gib {}: {} memos do not fit on their GPUs ({}): rendering without a NIF memo", args.str("nif-memo-gib"),
+                  numDevices, pt_last_error(devices[d]));
+    for (std::size_t o = 0; o < d; ++o) pt_set_nif_memo(devices[o], 0);
+    nifMemo = 0;
   }
   if (numDevices > 1 && hostGather) {
     pt_log::info_("HDR tiles of {} devices are gathered through the host", numDevices);
@@ -386,13 +424,14 @@ void PathTracerApp::executeResidentFilm(std::uint32_t steps) {
     auto loopStartTime = std::chrono::steady_clock::now();
     std::vector<pt_stats> stats(devices.size());
     std::vector<pt_nif_sharing_stats> share(devices.size(), sharingStatsRequest());
+    std::vector<pt_nif_memo_stats> memo(devices.size(), memoStatsRequest());
     // path_trace, then on the device what the host task does in the reference's loop: film += (b,g,r)/sampleCount and
     // clear the accumulators (PathTracerApp.cpp:717-745)
     onEveryDevice("Device step", [&](std::size_t d) {
       int rc;
       { pt_trace::Range r("ipu_render"); rc = pt_path_trace(devices[d]) || pt_get_stats(devices[d], &stats[d]); }   // PathTracerApp.cpp:688-699
       if (rc) return rc;
-      if ((rc = pt_get_nif_sharing_stats(devices[d], &share[d]))) return rc;
+      if ((rc = pt_get_nif_sharing_stats(devices[d], &share[d])) || (rc = pt_get_nif_memo_stats(devices[d], &memo[d]))) return rc;
       pt_trace::Range r("accumulate_framebuffers");                                                                // :725-727, on the device
       return pt_film_accumulate(devices[d]);
     });
@@ -402,9 +441,11 @@ void PathTracerApp::executeResidentFilm(std::uint32_t steps) {
     pt_log::debug_("NIF ms: {}", stats[0].nif_ms);
     pt_log::debug_("Total ms per step: {}", stats[0].total_ms);
     countNifEvaluations(share);
+    countMemo(memo);
 
     if (step % saveInterval == 0 || step == steps) {
       logNifEvaluations();
+      logMemo();
       { pt_trace::Range r("wait_for_host"); hostProcessing.waitForCompletion(); }   // the previous save still reads filmRecords (:702-706)
       // the ONE exchange of the multi-GPU path: HDR tiles to device 0 over RCCL, then to the host film
       // (--host-gather, or logical devices sharing a GPU: no communicator, every device hands its own tile to the host)
@@ -554,15 +595,17 @@ void PathTracerApp::executeHostFilm(std::uint32_t steps) {
     auto& active = traceState->work.getWork().active();
     std::vector<pt_stats> stats(devices.size());
     std::vector<pt_nif_sharing_stats> share(devices.size(), sharingStatsRequest());
+    std::vector<pt_nif_memo_stats> memo(devices.size(), memoStatsRequest());
     onEveryDevice("Device step", [&](std::size_t d) {
       auto* slice = reinterpret_cast<pt_trace_record*>(active.data() + d * itemsPerDevice);
       pt_handle h = devices[d];
       pt_trace::Range r("ipu_render");                                        // :688-699
       return pt_setup(h, slice, itemsPerDevice) || pt_path_trace(h) || pt_read_results(h, slice, itemsPerDevice, &stats[d]) ||
-             pt_get_nif_sharing_stats(h, &share[d]);
+             pt_get_nif_sharing_stats(h, &share[d]) || pt_get_nif_memo_stats(h, &memo[d]);
     });
     countNifEvaluations(share);
-    if (step % saveInterval == 0 || step == steps) logNifEvaluations();
+    countMemo(memo);
+    if (step % saveInterval == 0 || step == steps) { logNifEvaluations(); logMemo(); }
     pt_log::debug_("Path-Trace ms: {}", stats[0].path_trace_ms);
     pt_log::debug_("NIF ms: {}", stats[0].nif_ms);
     pt_log::debug_("Total ms per step: {}", stats[0].total_ms);

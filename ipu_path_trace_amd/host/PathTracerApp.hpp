@@ -58,6 +58,10 @@ private:
   static pt_nif_sharing_stats sharingStatsRequest();
   void countNifEvaluations(const std::vector<pt_nif_sharing_stats>& share);
   void logNifEvaluations();
+  /// --nif-memo-gib: escaped paths served by the memo and NIF rows executed, summed over the devices, logged at save intervals.
+  static pt_nif_memo_stats memoStatsRequest();
+  void countMemo(const std::vector<pt_nif_memo_stats>& memo);
+  void logMemo();
 
   OptionMap args;
   std::uint32_t samplesPerPixel = 0;
@@ -73,6 +77,8 @@ private:
   double finalSamplesPerSec = 0.0;
   std::int32_t nifSharing = PT_NIF_SHARE_OFF;
   std::uint64_t nifEscaped = 0, nifEvaluations = 0;
+  std::uint64_t nifMemo = 0;   ///< --nif-memo-gib in bytes per logical device, 0 = off
+  std::uint64_t memoServed = 0, memoEscaped = 0, memoRows = 0;
   std::chrono::steady_clock::time_point renderStartTime;   // reset when the UI restarts the render (PathTracerApp.cpp:669)
 };
 

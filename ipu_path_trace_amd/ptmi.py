@@ -25,7 +25,8 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_export_hdr_device", "pt_clear_accumulators", "pt_synchronize", "pt_nif_infer", "pt_trace_paths",
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_init_all", "pt_comm_info", "pt_comm_set_timeout", "pt_comm_abort",
            "pt_gather_hdr", "pt_film_accumulate", "pt_tile_costs_enable", "pt_tile_costs", "pt_film_seed",
-           "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats"]
+           "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats",
+           "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 COMM_ID_BYTES = 128
@@ -66,6 +67,15 @@ class Stats(C.Structure):
 class NifSharingStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("escaped", C.c_uint64), ("evaluations", C.c_uint64),
                 ("overflowed", C.c_uint64), ("table_slots", C.c_uint64), ("share_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class NifMemoStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_int32), ("slots", C.c_uint64), ("occupied", C.c_uint64),
+                ("escaped", C.c_uint64), ("served", C.c_uint64), ("evaluations", C.c_uint64), ("inserted", C.c_uint64),
+                ("overflowed", C.c_uint64), ("generation", C.c_uint64), ("retains", C.c_uint64), ("memo_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
@@ -130,8 +140,12 @@ def load_library(diag=False):
     L.pt_runtime_info.argtypes = [C.c_char_p, C.c_size_t]
     L.pt_set_nif_sharing.argtypes = [C.c_void_p, C.c_int32]
     L.pt_get_nif_sharing_stats.argtypes = [C.c_void_p, C.POINTER(NifSharingStats)]
+    L.pt_set_nif_memo.argtypes = [C.c_void_p, C.c_uint64]
+    L.pt_clear_nif_memo.argtypes = [C.c_void_p]
+    L.pt_get_nif_memo_stats.argtypes = [C.c_void_p, C.POINTER(NifMemoStats)]
     if diag:
         L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
+        L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_inject_fault.argtypes = [C.c_void_p, C.c_int32]
         L.pt_diag_stamps.argtypes = [C.c_void_p, C.c_void_p]
         L.pt_diag_nif_clock.argtypes = [C.c_void_p, C.c_void_p]
@@ -258,6 +272,24 @@ class Renderer:
         if mode not in NIF_SHARE_MODES:
             raise ValueError("NIF sharing mode must be one of %s, got %r" % (sorted(NIF_SHARE_MODES), mode))
         self._check(self._lib.pt_set_nif_sharing(self.handle, NIF_SHARE_MODES[mode]))
+
+    def set_nif_memo(self, max_bytes):
+        """Persistent memo of decoded NIF values across steps, at most `max_bytes` of device memory; 0 turns it off
+        (include/ptmi.h, pt_set_nif_memo).  Exact: the film is bit-identical to memo off."""
+        self._check(self._lib.pt_set_nif_memo(self.handle, int(max_bytes)))
+
+    def clear_nif_memo(self):
+        """Forget every memo entry: the next path_trace starts a new generation."""
+        self._check(self._lib.pt_clear_nif_memo(self.handle))
+
+    def nif_memo_stats(self):
+        """dict of enabled, slots, occupied, escaped, served, evaluations, inserted, overflowed, generation, retains, memo_ms."""
+        st = NifMemoStats()
+        st.struct_size = C.sizeof(NifMemoStats)
+        self._check(self._lib.pt_get_nif_memo_stats(self.handle, C.byref(st)))
+        d = st.as_dict()
+        d["enabled"] = bool(d["enabled"])
+        return d
 
     def nif_sharing_stats(self):
         """NIF rows the last path_trace really ran: dict of mode, escaped, evaluations, overflowed, table_slots, share_ms."""
