@@ -227,7 +227,7 @@ int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
  * in the last step (`retains` counts them).
  * Generation: pt_upload_nif, pt_clear_nif_memo and a pt_path_trace that fails start a new generation (every entry is
  * forgotten).  Nothing else invalidates the memo: not pt_set_render_settings (seed, fov, azimuth, AA), not pt_setup, not
- * pt_set_constant_env -- with a constant environment no memo pass runs.
+ * pt_set_scene, not pt_set_constant_env -- with a constant environment no memo pass runs.
  * Allocation: pt_set_nif_memo can return PT_ERR_OUT_OF_MEMORY and the memo is then left off; max_bytes between 1 and
  * 48 KiB - 1 is PT_ERR_INVALID_ARGUMENT.  The step store of step-scope sharing (not counted in max_bytes) is used and grown
  * as with PT_NIF_SHARE_STEP.
@@ -247,6 +247,43 @@ typedef struct pt_nif_memo_stats {
 int pt_set_nif_memo(pt_handle h, uint64_t max_bytes);
 int pt_clear_nif_memo(pt_handle h);
 int pt_get_nif_memo_stats(pt_handle h, pt_nif_memo_stats* out);
+
+/* Runtime scene -- an EXTENSION: the reference's scene is compile-time, five spheres and a floor disc on the stack of
+ * RayTraceKernel::compute ("For now the scene is hard coded", codelets.cpp:90,110-144).  pt_set_scene replaces it with up to
+ * PT_MAX_SCENE_OBJECTS spheres and discs, tested for the nearest hit in the order given (Scene::intersect, codelets.cpp:183).
+ *   shape     PT_SHAPE_SPHERE or PT_SHAPE_DISC (a disc is the set of points of its plane within `radius` of `centre`).
+ *   material  PT_MATERIAL_DIFFUSE: colour is the factor the kernel multiplies by (the built-in scene's values include the
+ *             reference's colourGain 2, codelets.cpp:127); PT_MATERIAL_SPECULAR: colour is kept but unused (the reference's
+ *             tint is one); PT_MATERIAL_REFRACTIVE: colour is the tint of a refracted ray (the refractive index stays
+ *             pt_config.refractive_index); PT_MATERIAL_EMISSIVE: colour is the emitted radiance.
+ *   normal    disc only, normalised by the library once on the host as n / sqrtf(dot(n, n)) in binary32; stored as 0 for a sphere.
+ * Validation: PT_ERR_INVALID_ARGUMENT, and pt_last_error names the object's index and the bad field, for n outside 1..32, a
+ * shape or material out of range, any value that is not finite, radius <= 0, a negative colour component, a disc normal of
+ * length zero, or a NULL table with n > 0.  After a rejection the previous scene stays in force.  (NULL, 0) restores the
+ * built-in scene.  The built-in table passed through pt_set_scene renders bit-identically to no call.
+ * A new scene takes effect at the next pt_path_trace / pt_trace_paths.  It does not touch the worklist, the accumulators, the
+ * resident film, tile costs, NIF sharing or the NIF memo (memo keys depend on (u, v) and the model only).
+ * Emitters: a hit on an emissive object ends the path with an EMIT entry (codelets.cpp:192-196; the material type is not
+ * consulted), folded like an escape (:269-271): the path's radiance is emission * T per channel, T its throughput including
+ * that segment's roulette factor, by one fp32 multiply as with a constant environment.  The EMIT entry counts in the path's
+ * length (pt_stats.segments, TraceRecord pathLength).  pt_stats.escaped keeps its meaning -- paths that reached the
+ * environment, = NIF evaluations -- and does not count emitter paths; a step in which no path escapes is valid in NIF mode.
+ * pt_trace_paths reports an emitter path with escaped = 2, its throughput T and the direction of the ray that hit the emitter.
+ * pt_get_scene copies the table in force (the stored, normalised values) into out[0 .. capacity) and its size into *n;
+ * h == NULL gives the built-in table and needs no device.  out may be NULL with capacity 0 to ask for the size; a smaller
+ * capacity is PT_ERR_INVALID_ARGUMENT.  A NULL handle given to pt_set_scene is PT_ERR_INVALID_ARGUMENT. */
+enum { PT_SHAPE_SPHERE = 0, PT_SHAPE_DISC = 1 };
+enum { PT_MATERIAL_DIFFUSE = 0, PT_MATERIAL_SPECULAR = 1, PT_MATERIAL_REFRACTIVE = 2, PT_MATERIAL_EMISSIVE = 3 };
+#define PT_MAX_SCENE_OBJECTS 32
+typedef struct pt_scene_object {     /* 48 bytes */
+  int32_t shape, material;
+  float centre[3];
+  float radius;
+  float normal[3];                   /* disc only; normalised by the library; 0 for spheres */
+  float colour[3];                   /* diffuse: factor; refractive: tint; specular: unused; emissive: emitted radiance */
+} pt_scene_object;
+int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n);
+int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t* n);
 
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);

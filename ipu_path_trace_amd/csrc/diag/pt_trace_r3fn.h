@@ -12,7 +12,7 @@ __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3
   int best = -1;
   tbest = kInf;
 #pragma unroll 1
-  for (int i = 0; i < kNumObjects; ++i) {
+  for (int i = 0; i < (int)P.n_objects; ++i) {
     const SceneObject ob = P.obj[i];
     float t = ob.is_disc ? disc_intersect(o, d, ob) : sphere_intersect(o, d, ob);
     if (t > kEps && t < tbest) { tbest = t; best = i; }

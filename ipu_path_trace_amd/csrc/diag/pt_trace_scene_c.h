@@ -85,6 +85,6 @@ __device__ __forceinline__ int nearest_hit_primary_c(Vec3 d, float& tbest, std::
   (hit_object_primary_c<I>(d, b, tbest, best), ...);
   return best;
 }
-using SceneIndices = std::make_integer_sequence<int, kNumObjects>;
+using SceneIndices = std::make_integer_sequence<int, kBuiltinObjects>;
 
 }  // namespace ptd

@@ -28,19 +28,21 @@
 
 namespace ptd {
 
-enum { MAT_DIFFUSE = 0, MAT_SPECULAR = 1, MAT_REFRACTIVE = 2 };
-constexpr int kNumObjects = 6;
+enum { MAT_DIFFUSE = 0, MAT_SPECULAR = 1, MAT_REFRACTIVE = 2, MAT_EMISSIVE = 3 };   // = PT_MATERIAL_* (include/ptmi.h)
+constexpr int kMaxObjects = 32;         // PT_MAX_SCENE_OBJECTS: capacity of the kernel-argument scene (pt_set_scene)
+constexpr int kBuiltinObjects = 6;      // the reference's scene (scene_const below)
 constexpr float kEps = 1e-5f;           // INFERRED intersection epsilon (< 1e-4 clear-coat gap)
 constexpr float kInf = 3.402823466e+38f;
 constexpr float kPi = 3.1415927410125732421875f;
 
-// Scene of src/codelets/codelets.cpp:111-144 as kernel-argument data (wave-uniform -> SGPRs).
+// One object of the scene as kernel-argument data (wave-uniform -> SGPRs): the reference's (src/codelets/codelets.cpp:111-144)
+// unless pt_set_scene gave another.
 struct SceneObject {
   float cx, cy, cz;     // centre
   float radius, r2;     // r2 = radius*radius
   float nx, ny, nz;     // disc normal
   float colr, colg, colb;
-  int32_t type;         // MAT_*
+  int32_t type;         // MAT_* (MAT_EMISSIVE: col = emitted radiance)
   int32_t is_disc;
   // Camera rays start at the origin (codelets.cpp:162): what Sphere / Disc::intersect compute from (origin, object) alone
   // is a constant of the object, formed on the host by the SAME binary32 expressions in the same order (fill_scene):
@@ -51,7 +53,8 @@ struct SceneObject {
 };
 
 struct TraceParams {
-  SceneObject obj[kNumObjects];
+  SceneObject obj[kMaxObjects];   // obj[0 .. n_objects): the scene in declaration order
+  uint32_t n_objects;        // 1 .. kMaxObjects; the launch's dynamic LDS holds one HitRow per object
   float width_f, height_f;   // image size as float (pixelToRay)
   uint32_t width, height;    // ... and as integers: an item with u >= width or v >= height is worklist padding (not traced)
   float tx, ty;              // tan(fov/2), (h/w) tan(fov/2)
@@ -79,7 +82,9 @@ struct TraceParams {
   size_t state_stride;       // gridDim.x * region_cap
   uint32_t div_magic, div_shift;   // idx / n_items = (idx * div_magic) >> div_shift, exact for idx < 2^31 (ptmi_context.h: item_divider)
   unsigned long long* diag;        // profiling build: secondary-phase occupancy counters (OPT bit 4), else nullptr
+  unsigned long long* emitted;     // paths that ended on an emitter (pt_context::d_counters[3]; pt_stats.escaped excludes them)
 };
+static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
 
 // path index -> (work item, sample iteration).  A 32-bit division costs ~25 vector instructions on this chip and every path
 // needs one (survivors two more); n_items is fixed per launch, so the host supplies the round-up reciprocal.
@@ -190,11 +195,12 @@ __device__ __forceinline__ int nearest_hit(const TraceParams& P, Vec3 o, Vec3 d,
   int best = -1;
   tbest = kInf;
   float b = 0.f, oc2 = 0.f;
+  const int n = (int)P.n_objects;
   SceneObject nxt = P.obj[0];
 #pragma unroll 1
-  for (int i = 0; i < kNumObjects; ++i) {
+  for (int i = 0; i < n; ++i) {
     SceneObject ob;
-    if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < kNumObjects ? i + 1 : kNumObjects - 1]; }
+    if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < n ? i + 1 : n - 1]; }
     else ob = P.obj[i];
     float t;
     if (ob.is_disc) {
@@ -228,11 +234,12 @@ __device__ __forceinline__ int nearest_hit_primary(const TraceParams& P, Vec3 d,
   int best = -1;
   tbest = kInf;
   float b = 0.f;
+  const int n = (int)P.n_objects;
   SceneObject nxt = P.obj[0];
 #pragma unroll 1
-  for (int i = 0; i < kNumObjects; ++i) {
+  for (int i = 0; i < n; ++i) {
     SceneObject ob;
-    if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < kNumObjects ? i + 1 : kNumObjects - 1]; }
+    if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < n ? i + 1 : n - 1]; }
     else ob = P.obj[i];
     float t;
     if (ob.is_disc) {
@@ -276,7 +283,7 @@ struct SceneConst {
 };
 constexpr float kColourGain = 2.f;                                                                        // :127
 __host__ __device__ constexpr SceneConst scene_const(int i) {
-  constexpr SceneConst table[kNumObjects] = {
+  constexpr SceneConst table[kBuiltinObjects] = {
       {false, -1.8575f, -0.98714f, -3.6f, 0.6f, 0.f, 0.f, 0.f, 1.f * kColourGain, .89f * kColourGain, .55f * kColourGain, MAT_DIFFUSE},      // :112,:128,:137
       {false, 0.74795f, -0.55f, -4.3816f, 1.05f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, MAT_SPECULAR},                                              // :113,:138
       {false, 1.9929f, -1.08666f, (float)-3.23, 0.5f, 0.f, 0.f, 0.f, 0.75f, 0.75f, 0.75f, MAT_REFRACTIVE},                                 // :114,:131,:139
@@ -297,20 +304,22 @@ __host__ __device__ constexpr bool scene_same_centre(int i) {
 namespace ptd {
 #endif
 
-enum StepResult { STEP_CONTINUE = 0, STEP_ESCAPED = 1, STEP_DEAD = 2 };
+enum StepResult { STEP_CONTINUE = 0, STEP_ESCAPED = 1, STEP_DEAD = 2, STEP_EMITTED = 3 };
 
 // Per-object data a lane needs once it knows WHICH object it hit, in LDS so that the lane fetches its own object's
 // row by index.  (The scene also sits in the kernel arguments; holding all 6 x 13 constants in SGPRs across the
 // bounce loop for a select chain overflowed the SGPR file: 600 of the kernel's 2600 instructions were
-// v_writelane/v_readlane spill traffic.)
+// v_writelane/v_readlane spill traffic.)  The table is the launch's dynamic LDS, sized by the scene (hit_table_bytes): a
+// fixed 32-row table would be 1.5 KiB, and the trace kernel runs beside the NIF kernel's 157 KiB of the CU's 160.
 struct HitRow {
   float4 centre;   // cx, cy, cz, -
   float4 normal;   // nx, ny, nz (disc), -
   float4 colour;   // r, g, b, bits of (type | is_disc << 8)
 };
+constexpr size_t hit_table_bytes(uint32_t n_objects) { return (size_t)n_objects * sizeof(HitRow); }
 __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab) {
-#pragma unroll
-  for (int i = 0; i < kNumObjects; ++i) {
+#pragma unroll 1
+  for (int i = 0; i < (int)P.n_objects; ++i) {
     tab[i].centre = make_float4(P.obj[i].cx, P.obj[i].cy, P.obj[i].cz, 0.f);
     tab[i].normal = make_float4(P.obj[i].nx, P.obj[i].ny, P.obj[i].nz, 0.f);
     tab[i].colour = make_float4(P.obj[i].colr, P.obj[i].colg, P.obj[i].colb,
@@ -376,6 +385,15 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
   const float cx = hc.x, cy = hc.y, cz = hc.z, nx = hn.x, ny = hn.y, nz = hn.z, cr = hcol.x, cg = hcol.y, cb = hcol.z;
   const uint32_t bits = __float_as_uint(hcol.w);
   const int type = (int)(bits & 0xffu), is_disc = (int)(bits >> 8);
+  if (type == MAT_EMISSIVE) {                                 // :192-196 EMIT (the material type is not consulted), folded like ESCAPED (:269-271)
+    // the radiance emission (.) T goes back in s.o (the path needs no hit point); s.d stays the ray that hit.  Tested before
+    // the hit point and normal are formed: 62 VGPRs (63 with the per-wave emitter count); in the mirror / glass branch or after it
+    // 63 to 70 before that count (the kernel must stay <= 64: profiles/r08_scene.txt)
+    s.T = scale(s.T, rr);
+    s.o = mk(cr * s.T.x, cg * s.T.y, cb * s.T.z);
+    length = s.depth + 1u;
+    return STEP_EMITTED;
+  }
   Vec3 hp = add(s.o, scale(s.d, tbest));
   s.o = hp;
   Vec3 n = is_disc ? mk(nx, ny, nz) : normalise(sub(hp, mk(cx, cy, cz)));
@@ -454,6 +472,15 @@ __device__ __forceinline__ void dir_to_uv(Vec3 d, float azimuth, float& u, float
 constexpr int kTraceBlock = 256;
 constexpr uint32_t kRefillThreshold = 16;  // secondary phase: refill once this many lanes are idle (or none is active); 1..24 measured within 1 %
 
+// A path that ended on an emitter: its radiance (shade_hit: in st.o) straight into the per-path result, whatever the
+// environment (the accumulate pass adds it like an escaped path: bit 7 of plen).  Returns the wave's count of such paths, a
+// wave-uniform sum the kernel adds to P.emitted once per wave at its end: an atomic per wave and trip on that one address
+// made a scene whose emitter covers a few % of the image 60 % slower.
+__device__ __forceinline__ uint32_t emit_emitted(const TraceParams& P, bool emitted, Vec3 rad, uint32_t idx) {
+  if (emitted) { P.rad_r[idx] = rad.x; P.rad_g[idx] = rad.y; P.rad_b[idx] = rad.z; }
+  return (uint32_t)__popcll(__ballot(emitted));
+}
+
 // An escaped path: constant environment -> radiance straight into the per-path result; NIF -> one entry in the
 // workgroup's region of the queue (wave ballot + prefix count, ONE LDS atomic per wave, uv of PreProcessEscapedRays).
 __device__ __forceinline__ void emit_escaped(const TraceParams& P, bool escaped, const PathState& st, uint32_t idx, uint32_t lane,
@@ -509,7 +536,8 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
   __shared__ uint32_t wg_front, wg_back;   // camera rays of this workgroup that hit a diffuse / a mirror or glass object
   __shared__ uint32_t wg_state;            // survivors still alive after their first shading
-  __shared__ HitRow hit_table[kNumObjects];
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  HitRow* const hit_table = reinterpret_cast<HitRow*>(smem);   // P.n_objects rows (dynamic LDS: hit_table_bytes)
   if (threadIdx.x == 0) { wg_count = 0; wg_front = 0; wg_back = 0; wg_state = 0; fill_hit_table(P, hit_table); }
   __syncthreads();
 
@@ -524,6 +552,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   // paths this wave owns: chunk j -> idx = (j * n_waves + gw) * 64 + lane
   const uint32_t n_chunks = (P.total_paths + 63u) / 64u;
   const uint32_t my_chunks = (n_chunks > gw) ? (n_chunks - gw + P.n_waves - 1u) / P.n_waves : 0u;
+  uint32_t wave_emitted = 0;   // paths of this wave that ended on an emitter (wave-uniform)
 
   // ---- primary phase: every lane starts a new path each trip (GenerateCameraRays + the first Scene::intersect)
   for (uint32_t j = 0; j < my_chunks; ++j) {
@@ -555,9 +584,19 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     const bool escaped = valid && !hit;
     if (escaped) P.plen[idx] = (uint8_t)(1u | 0x80u);
     emit_escaped(P, escaped, st, idx, lane, region_base, &wg_count);
-    // survivors: diffuse hits fill the list from the front, mirror / glass hits from the back
-    const bool diffuse = hit && (__float_as_uint(hit_table[hit ? best : 0].colour.w) & 0xffu) == (uint32_t)MAT_DIFFUSE;
-    const bool other = hit && !diffuse;
+    // survivors: diffuse hits fill the list from the front, mirror / glass hits from the back; an emitter hit is final
+    // (codelets.cpp:192-196 at depth 0: no roulette, T = (1, 1, 1) x 1 as shade_hit would leave it) and queues nothing
+    const uint32_t mat = __float_as_uint(hit_table[hit ? best : 0].colour.w) & 0xffu;
+    const bool diffuse = hit && mat == (uint32_t)MAT_DIFFUSE;
+    const bool emitted = hit && mat == (uint32_t)MAT_EMISSIVE;
+    const bool other = hit && !diffuse && !emitted;
+    Vec3 erad = mk(0.f, 0.f, 0.f);
+    if (emitted) {
+      const float4 e = hit_table[best].colour;
+      erad = mk(e.x * st.T.x, e.y * st.T.y, e.z * st.T.z);
+      P.plen[idx] = (uint8_t)(1u | 0x80u);
+    }
+    wave_emitted += emit_emitted(P, emitted, erad, idx);
     const uint64_t dmask = __ballot(diffuse), omask = __ballot(other);
     uint32_t pos = 0;
     if (dmask) {
@@ -572,7 +611,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       base = __shfl(base, __ffsll((long long)omask) - 1, 64);
       if (other) pos = P.region_cap - 1u - (base + __builtin_amdgcn_mbcnt_hi((uint32_t)(omask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)omask, 0u)));
     }
-    if (hit) surv[pos] = make_uint4(idx, pack_half2(camx, camy), __float_as_uint(tbest), (uint32_t)best);
+    if (diffuse || other) surv[pos] = make_uint4(idx, pack_half2(camx, camy), __float_as_uint(tbest), (uint32_t)best);
   }
   __syncthreads();   // the workgroup's survivor list is complete (and visible: the workgroup's own global stores, first read now)
   const uint32_t n_front = wg_front, n_surv = (OPT & 8) ? 0u : n_front + wg_back;   // (bit 3, timing only: primary phase alone)
@@ -609,6 +648,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       res = shade_hit(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       if (res == STEP_CONTINUE) alive = true;
       else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full
+      // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
     }
     const uint64_t amask = __ballot(alive);
     if (amask) {
@@ -680,10 +720,12 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE>(P, hit_table, st, length);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
+    const bool emitted = active && res == STEP_EMITTED;
     if (ended) {
-      P.plen[idx] = (uint8_t)(length | (escaped ? 0x80u : 0u));
+      P.plen[idx] = (uint8_t)(length | (res != STEP_DEAD ? 0x80u : 0u));   // bit 7: the path contributes (escaped or emitter)
       active = false;
     }
+    wave_emitted += emit_emitted(P, emitted, st.o, idx);
     emit_escaped(P, escaped, st, idx, lane, region_base, &wg_count);
   }
   if constexpr ((OPT & 16) != 0) {
@@ -692,6 +734,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       atomicAdd(&P.diag[2], (unsigned long long)dg_tail_trips); atomicAdd(&P.diag[3], (unsigned long long)dg_tail_active);
     }
   }
+  if (wave_emitted && lane == 0) atomicAdd(P.emitted, (unsigned long long)wave_emitted);
   __syncthreads();
   if (threadIdx.x == 0) P.region_count[blockIdx.x] = wg_count;
 }
@@ -710,7 +753,8 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
 // One thread per requested path; same device functions as trace_kernel.
 __global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                    uint32_t n, PathRecordOut* out) {
-  __shared__ HitRow hit_table[kNumObjects];
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  HitRow* const hit_table = reinterpret_cast<HitRow*>(smem);   // P.n_objects rows (dynamic LDS)
   if (threadIdx.x == 0) fill_hit_table(P, hit_table);
   __syncthreads();
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -723,11 +767,11 @@ __global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const
   do { res = bounce(P, hit_table, st, length); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
-  r.escaped = (res == STEP_ESCAPED);
+  r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
   r.cam[0] = camx; r.cam[1] = camy;
   if (r.escaped) {
     r.dir[0] = st.d.x; r.dir[1] = st.d.y; r.dir[2] = st.d.z;
-    dir_to_uv(st.d, P.azimuth, r.uv[0], r.uv[1]);
+    if (res == STEP_ESCAPED) dir_to_uv(st.d, P.azimuth, r.uv[0], r.uv[1]);
     r.throughput[0] = st.T.x; r.throughput[1] = st.T.y; r.throughput[2] = st.T.z;
   }
   out[i] = r;

@@ -35,6 +35,7 @@
 #include "pt_nif_memo.h"
 
 #include "ptmi_comm_worker.h"
+#include "ptmi_scene.h"
 #include "ptmi_context.h"
 #include "ptmi_nif_pack.h"
 #include "ptmi_nif_launch.h"
@@ -121,8 +122,8 @@ int pt_create(const pt_config* cfg, pt_handle* out) {
   PT_HIPC(dev_alloc(&h->acc.b, n));
   PT_HIPC(dev_alloc(&h->acc.count, n));
   PT_HIPC(dev_alloc(&h->acc.length, n));
-  PT_HIPC(dev_alloc(&h->d_counters, 3));   // segments, escaped (per step); real work items (per pt_setup)
-  PT_HIPC(hipHostMalloc(reinterpret_cast<void**>(&h->h_counters), 3 * sizeof(unsigned long long), hipHostMallocDefault));
+  PT_HIPC(dev_alloc(&h->d_counters, 4));   // segments, contributing paths, emitter paths (per step); real work items (per pt_setup)
+  PT_HIPC(hipHostMalloc(reinterpret_cast<void**>(&h->h_counters), 4 * sizeof(unsigned long long), hipHostMallocDefault));
   h->trace_blocks = std::min<uint32_t>((uint32_t)ptd::kMaxRegions, (uint32_t)pt_context::kTraceBlocksPerCu * (uint32_t)h->n_cus);
 #ifdef PTMI_DIAG_BUILD
   if (const char* e = getenv("PTMI_TRACE_BLOCKS")) h->trace_blocks = std::min<uint32_t>((uint32_t)ptd::kMaxRegions, (uint32_t)std::max(1, atoi(e)));   // grid-size sweep of the profiling build
@@ -654,7 +655,7 @@ static ptd::MemoParams memo_params(pt_handle h, const pt_context::BatchBuffers& 
 static int enqueue_path_trace(pt_handle h, std::vector<StageSpan>& spans, size_t& e_begin_i, size_t& e_end_i) {
   const uint32_t n = h->n_items;
   forget_replay_state(h);
-  PT_HIP(hipMemsetAsync(h->d_counters, 0, 2 * sizeof(unsigned long long), h->stream));
+  PT_HIP(hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));   // ([2] was consumed by pt_setup)
   ptd::TraceParams P;
   fill_trace_params(h, P);
   P.n_items = n;
@@ -733,7 +734,7 @@ static int enqueue_path_trace(pt_handle h, std::vector<StageSpan>& spans, size_t
 #ifdef PTMI_DIAG_BUILD
     if (!launch_trace_variant(h, P, g))   // A/B switches of the profiling build (diag/ptmi_trace_variants.h), read per launch
 #endif
-    hipLaunchKernelGGL(ptd::trace_kernel, dim3(g.blocks), dim3(ptd::kTraceBlock), 0, h->trace_stream, P);
+    hipLaunchKernelGGL(ptd::trace_kernel, dim3(g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     PT_HIP(hipGetLastError());
     PT_HIP(hipEventRecord(t1, h->trace_stream));
     spans.push_back({ev, ev + 1, 0});
@@ -859,8 +860,8 @@ static int enqueue_path_trace(pt_handle h, std::vector<StageSpan>& spans, size_t
     spans.push_back({ev, ev + 1, 4});
     ev += 2;
   }
-  // the two counters travel to pinned host memory on the stream itself: the host waits once, for e_end
-  PT_HIP(hipMemcpyAsync(h->h_counters, h->d_counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  // the counters travel to pinned host memory on the stream itself: the host waits once, for e_end
+  PT_HIP(hipMemcpyAsync(h->h_counters, h->d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   if (grouped) {   // the distinct-queue lengths and the overflow count travel with them: still one wait
     PT_HIP(hipMemcpyAsync(h->h_share_count, h->d_share_count, (size_t)batch * 4, hipMemcpyDeviceToHost, h->stream));
     PT_HIP(hipMemcpyAsync(h->h_share_over, h->d_share_over, 8, hipMemcpyDeviceToHost, h->stream));
@@ -929,7 +930,7 @@ int pt_path_trace(pt_handle h) {
   h->sample_cursor += h->samples_per_step;
   h->stats.paths = (uint64_t)h->n_real * h->samples_per_step;   // padding items are not traced (pt_setup)
   h->stats.segments = h->h_counters[0];
-  h->stats.escaped = h->h_counters[1];
+  h->stats.escaped = h->h_counters[1] - h->h_counters[3];   // the accumulate pass counts every contributing path, emitters too
   if (h->share_mode_last || h->memo_ran) {
     for (uint32_t b = 0; b < h->stats.trace_launches; ++b) h->share_evals += h->h_share_count[b];
     h->share_overflowed = *h->h_share_over;
@@ -1159,6 +1160,33 @@ int pt_nif_infer(pt_handle h, const float* u, const float* v, size_t n, float* b
   return PT_OK;
 }
 
+int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!objects && n == 0) { h->scene_n = 0; return PT_OK; }   // the built-in scene
+  const std::string bad = ptscene::check(objects, n);
+  if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the scene in force stays
+  std::copy(objects, objects + n, h->scene);
+  ptscene::normalise(h->scene, n);
+  h->scene_n = n;
+  return PT_OK;
+}
+
+int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t* n) {
+  if (!n) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "null count") : PT_ERR_INVALID_ARGUMENT;
+  pt_scene_object builtin[ptd::kBuiltinObjects];
+  builtin_scene(builtin);
+  const bool custom = h && h->scene_n;
+  const pt_scene_object* src = custom ? h->scene : builtin;
+  const uint32_t count = custom ? h->scene_n : (uint32_t)ptd::kBuiltinObjects;
+  *n = count;
+  if (!out && capacity == 0) return PT_OK;   // size query
+  if (!out || capacity < count)
+    return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_scene: capacity " + std::to_string(capacity) + " < " + std::to_string(count) + " objects")
+             : PT_ERR_INVALID_ARGUMENT;
+  std::copy(src, src + count, out);
+  return PT_OK;
+}
+
 int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint32_t* sample_index, size_t n,
                    pt_path_record* out) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
@@ -1180,7 +1208,8 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   PT_HIP(hipMemcpyAsync(d_v, v, n * 2, hipMemcpyHostToDevice, h->stream));
   ptd::TraceParams P;
   fill_trace_params(h, P);
-  hipLaunchKernelGGL(ptd::trace_paths_kernel, dim3(((uint32_t)n + 127) / 128), dim3(128), 0, h->stream, P, d_u, d_v, d_s,
+  P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
+  hipLaunchKernelGGL(ptd::trace_paths_kernel, dim3(((uint32_t)n + 127) / 128), dim3(128), ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s,
                      (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_path_record), hipMemcpyDeviceToHost, h->stream));

@@ -60,7 +60,7 @@ struct pt_context {
   ptd::TraceRecordDev* d_records = nullptr;
   ptd::Accum acc{};
   uint32_t n_real = 0;                       // work items that are not padding (u < width and v < height: AccumulatedImage.cpp:66)
-  unsigned long long* d_counters = nullptr;  // [0] segments, [1] escaped
+  unsigned long long* d_counters = nullptr;  // [0] segments, [1] escaped or emitter paths, [2] real items (pt_setup), [3] emitter paths
   unsigned long long* h_counters = nullptr;  // the same in pinned host memory: copied on the stream at the end of a step (no blocking hipMemcpy)
 
   // batch buffers, double-buffered: the trace kernel of batch b+1 runs on `trace_stream` while the NIF
@@ -104,6 +104,10 @@ struct pt_context {
   float aa_scale = 0, fov = 0, azimuth = 0;
   uint32_t samples_per_step = 0;
   uint32_t sample_cursor = 0;  // absolute index of the next sample iteration
+
+  // scene (pt_set_scene): the table in force, stored normalised; scene_n = 0: the built-in scene (pt_trace.h::scene_const)
+  pt_scene_object scene[PT_MAX_SCENE_OBJECTS] = {};
+  uint32_t scene_n = 0;
 
   // environment
   bool env_const = false;
@@ -252,23 +256,32 @@ int ensure_scratch(pt_handle h, size_t bytes) {
   return PT_OK;
 }
 
-// Scene constants of src/codelets/codelets.cpp:111-144.
-void fill_scene(ptd::TraceParams& P) {
-  struct Src { int disc; float c[3]; float r; float col[3]; int type; };
-  Src src[ptd::kNumObjects];
-  for (int i = 0; i < ptd::kNumObjects; ++i) {   // ONE table: the kernels' compile-time scene (pt_trace.h::scene_const, codelets.cpp:111-144)
+// The built-in scene (src/codelets/codelets.cpp:111-144) as a pt_scene_object table: ONE source, the kernels' compile-time
+// table pt_trace.h::scene_const.  A disc's normal (0, 1, 0) is already normalised (n / sqrtf(dot(n, n)) leaves it as it is).
+static_assert(ptd::kMaxObjects == PT_MAX_SCENE_OBJECTS && ptd::MAT_EMISSIVE == PT_MATERIAL_EMISSIVE, "scene capacity / materials");
+static_assert(sizeof(pt_scene_object) == 48, "pt_scene_object layout");
+void builtin_scene(pt_scene_object (&out)[ptd::kBuiltinObjects]) {
+  for (int i = 0; i < ptd::kBuiltinObjects; ++i) {
     const ptd::SceneConst S = ptd::scene_const(i);
-    src[i] = Src{S.disc ? 1 : 0, {S.cx, S.cy, S.cz}, S.radius, {S.colr, S.colg, S.colb}, S.type};
+    out[i] = pt_scene_object{S.disc ? PT_SHAPE_DISC : PT_SHAPE_SPHERE, S.type, {S.cx, S.cy, S.cz}, S.radius,
+                             {S.nx, S.ny, S.nz}, {S.colr, S.colg, S.colb}};
   }
-  for (int i = 0; i < ptd::kNumObjects; ++i) {
+}
+
+// Scene constants of a table of n objects (the built-in one or pt_set_scene's) into the kernel arguments: the SAME
+// expressions for every table, so the built-in table passed through pt_set_scene is bit-identical to no call.
+void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n) {
+  P.n_objects = n;
+  for (uint32_t i = 0; i < n; ++i) {
     ptd::SceneObject& o = P.obj[i];
-    o.cx = src[i].c[0]; o.cy = src[i].c[1]; o.cz = src[i].c[2];
-    o.radius = src[i].r;
-    o.r2 = src[i].r * src[i].r;
-    o.nx = 0.f; o.ny = src[i].disc ? 1.f : 0.f; o.nz = 0.f;
-    o.colr = src[i].col[0]; o.colg = src[i].col[1]; o.colb = src[i].col[2];
-    o.type = src[i].type;
-    o.is_disc = src[i].disc;
+    const bool disc = src[i].shape == PT_SHAPE_DISC;
+    o.cx = src[i].centre[0]; o.cy = src[i].centre[1]; o.cz = src[i].centre[2];
+    o.radius = src[i].radius;
+    o.r2 = src[i].radius * src[i].radius;
+    o.nx = src[i].normal[0]; o.ny = src[i].normal[1]; o.nz = src[i].normal[2];
+    o.colr = src[i].colour[0]; o.colg = src[i].colour[1]; o.colb = src[i].colour[2];
+    o.type = src[i].material;
+    o.is_disc = disc ? 1 : 0;
     // constants of a ray that starts at the origin, by the device's own expressions (this file is compiled with
     // -ffp-contract=off like the kernels; volatile keeps every intermediate a rounded binary32 whatever the host's FLT_EVAL_METHOD)
     volatile float ox = 0.f - o.cx, oy = 0.f - o.cy, oz = 0.f - o.cz;          // sub(o, c)
@@ -280,8 +293,8 @@ void fill_scene(ptd::TraceParams& P) {
     volatile float kx = (o.cx - 0.f) * o.nx, ky = (o.cy - 0.f) * o.ny, kz = (o.cz - 0.f) * o.nz;   // dot(sub(c, o), n)
     volatile float k0 = kx + ky, k1 = k0 + kz;
     o.kdisc = k1;
-    o.same_centre = (i > 0 && !src[i].disc && !src[i - 1].disc && src[i].c[0] == src[i - 1].c[0] && src[i].c[1] == src[i - 1].c[1] &&
-                     src[i].c[2] == src[i - 1].c[2]) ? 1 : 0;
+    o.same_centre = (i > 0 && !disc && src[i - 1].shape != PT_SHAPE_DISC && src[i].centre[0] == src[i - 1].centre[0] &&
+                     src[i].centre[1] == src[i - 1].centre[1] && src[i].centre[2] == src[i - 1].centre[2]) ? 1 : 0;
   }
 }
 
@@ -298,7 +311,13 @@ void item_divider(uint32_t n, uint32_t& magic, uint32_t& shift) {
 
 void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   memset(&P, 0, sizeof(P));
-  fill_scene(P);
+  if (h->scene_n) {
+    fill_scene(P, h->scene, h->scene_n);
+  } else {
+    pt_scene_object builtin[ptd::kBuiltinObjects];
+    builtin_scene(builtin);
+    fill_scene(P, builtin, ptd::kBuiltinObjects);
+  }
   const pt_config& c = h->cfg;
   const float w = (float)c.width, hgt = (float)c.height;
   const float fov = host_hround(h->fov);        // field_of_view stream is half (PathTracerApp.cpp:591)
@@ -322,6 +341,7 @@ void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   P.env_const = h->env_const ? 1 : 0;
   P.env_r = h->env_rgb[0]; P.env_g = h->env_rgb[1]; P.env_b = h->env_rgb[2];
   P.pix = h->acc.pix;
+  P.emitted = h->d_counters + 3;
   P.state_stride = h->queue_cap;
   item_divider(h->n_items ? h->n_items : 1u, P.div_magic, P.div_shift);
 }

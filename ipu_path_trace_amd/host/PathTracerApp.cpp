@@ -14,7 +14,9 @@
 #include <thread>
 
 #include "AsyncTask.hpp"
+#include "json.hpp"
 #include "logging.hpp"
+#include "../csrc/ptmi_scene.h"
 #include "trace_ranges.hpp"
 
 /// Adjust samples per pixel to be a multiple of samples per step (PathTracerApp.cpp:19-27).
@@ -88,6 +90,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
+      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}."},
       {"nif-memo-gib", 0, "0", false, false, "GiB of device memory for a memo of decoded NIF values kept across steps, per logical device (0 = off). Exact: the image is bit-identical to off. Escaped paths whose (u, v) an earlier step evaluated are served from it; the memo is forgotten when a new NIF is loaded."},
   };
 }
@@ -127,6 +130,74 @@ std::uint64_t nifMemoBytes(const std::string& text) {
   return (std::uint64_t)(gib * (double)(1ull << 30));
 }
 
+// --scene (an extension: the reference's scene is compile-time, codelets.cpp:90,110-144).  Read and checked before any device is
+// attached, with the library's own checks (ptmi_scene.h) and messages; the table goes to every handle in attach().
+std::vector<pt_scene_object> loadSceneFile(const std::string& path) {
+  const std::string at = "--scene '" + path + "': ";
+  std::ifstream in(path, std::ios::binary);
+  if (!in) throw std::runtime_error(at + "cannot open the file");
+  std::stringstream text;
+  text << in.rdbuf();
+  json::Value root;
+  try { root = json::parse(text.str()); } catch (const std::exception& e) { throw std::runtime_error(at + e.what()); }
+  if (root.type != json::Value::Object || !root.has("objects") || root.at("objects").type != json::Value::Array)
+    throw std::runtime_error(at + "expected an object with an array \"objects\"");
+  const auto& list = root.at("objects").arr;
+  if (list.empty() || list.size() > PT_MAX_SCENE_OBJECTS)
+    throw std::runtime_error(at + "scene: object count must be 1.." + std::to_string(PT_MAX_SCENE_OBJECTS) + " (got " + std::to_string(list.size()) + ")");
+  std::vector<pt_scene_object> objs(list.size());
+  for (std::size_t i = 0; i < list.size(); ++i) {
+    const json::Value& v = list[i];
+    const std::string obj = "scene object " + std::to_string(i) + ": ";
+    if (v.type != json::Value::Object) throw std::runtime_error(at + obj + "expected a JSON object");
+    auto name = [&](const char* key) {
+      if (!v.has(key) || v.at(key).type != json::Value::String) throw std::runtime_error(at + obj + "\"" + key + "\" must be a string");
+      return v.at(key).str;
+    };
+    auto numbers = [&](const char* key, float* out, std::size_t k) {
+      const json::Value& a = v.at(key);
+      const bool scalar = k == 1 && a.type == json::Value::Number;
+      if (!scalar && (a.type != json::Value::Array || a.arr.size() != k))
+        throw std::runtime_error(at + obj + "\"" + key + "\" must be " + (k == 1 ? "a number" : "an array of " + std::to_string(k) + " numbers"));
+      for (std::size_t c = 0; c < k; ++c) {
+        const json::Value& x = scalar ? a : a.arr[c];
+        if (x.type != json::Value::Number) throw std::runtime_error(at + obj + "\"" + key + "\" must hold numbers");
+        out[c] = (float)x.num;
+      }
+    };
+    for (const auto& kv : v.obj)
+      if (kv.first != "shape" && kv.first != "material" && kv.first != "centre" && kv.first != "radius" && kv.first != "normal" &&
+          kv.first != "colour" && kv.first != "emission")
+        throw std::runtime_error(at + obj + "unknown key \"" + kv.first + "\"");
+    pt_scene_object& o = objs[i];
+    o = pt_scene_object{};
+    const std::string shape = name("shape"), material = name("material");
+    if (shape == "sphere") o.shape = PT_SHAPE_SPHERE;
+    else if (shape == "disc") o.shape = PT_SHAPE_DISC;
+    else throw std::runtime_error(at + obj + "unknown shape '" + shape + "' (sphere, disc)");
+    if (material == "diffuse") o.material = PT_MATERIAL_DIFFUSE;
+    else if (material == "specular") o.material = PT_MATERIAL_SPECULAR;
+    else if (material == "refractive") o.material = PT_MATERIAL_REFRACTIVE;
+    else if (material == "emissive") o.material = PT_MATERIAL_EMISSIVE;
+    else throw std::runtime_error(at + obj + "unknown material '" + material + "' (diffuse, specular, refractive, emissive)");
+    for (const char* key : {"centre", "radius"})
+      if (!v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" is missing");
+    numbers("centre", o.centre, 3);
+    numbers("radius", &o.radius, 1);
+    if (o.shape == PT_SHAPE_DISC) {
+      if (!v.has("normal")) throw std::runtime_error(at + obj + "\"normal\" is missing (a disc needs one)");
+      numbers("normal", o.normal, 3);
+    }
+    if (v.has("colour") && v.has("emission")) throw std::runtime_error(at + obj + "give \"colour\" or \"emission\", not both");
+    o.colour[0] = o.colour[1] = o.colour[2] = 1.f;
+    if (v.has("colour")) numbers("colour", o.colour, 3);
+    if (v.has("emission")) numbers("emission", o.colour, 3);
+  }
+  const std::string bad = ptscene::check(objs.data(), (std::uint32_t)objs.size());
+  if (!bad.empty()) throw std::runtime_error(at + bad);
+  return objs;
+}
+
 pt_nif_memo_stats PathTracerApp::memoStatsRequest() {
   pt_nif_memo_stats s{};
   s.struct_size = sizeof(pt_nif_memo_stats);
@@ -154,6 +225,7 @@ void PathTracerApp::init(const OptionMap& options) {
   if (samplesPerIpuStep == 0) throw std::runtime_error("--samples-per-step must be at least 1.");
   nifSharing = nifSharingMode(args.str("share-nif-evaluations"));
   nifMemo = nifMemoBytes(args.str("nif-memo-gib"));
+  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"));
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
   if (!image_io::ldrWriterFor(args.str("outfile")))
@@ -247,6 +319,8 @@ void PathTracerApp::attach() {
     devices.push_back(h);
     if (pt_set_nif_sharing(h, nifSharing))
       throw std::runtime_error(std::string("--share-nif-evaluations: ") + pt_last_error(h));
+    if (!scene.empty() && pt_set_scene(h, scene.data(), (std::uint32_t)scene.size()))
+      throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
   }
   // one memo per logical device: logical devices that share a GPU need room for all of theirs, or none runs with one
   for (std::size_t d = 0; d < numDevices && nifMemo; ++d) {

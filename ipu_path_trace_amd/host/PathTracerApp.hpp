@@ -79,6 +79,7 @@ private:
   std::uint64_t nifEscaped = 0, nifEvaluations = 0;
   std::uint64_t nifMemo = 0;   ///< --nif-memo-gib in bytes per logical device, 0 = off
   std::uint64_t memoServed = 0, memoEscaped = 0, memoRows = 0;
+  std::vector<pt_scene_object> scene;   ///< --scene: the table every handle renders (empty: the built-in scene)
   std::chrono::steady_clock::time_point renderStartTime;   // reset when the UI restarts the render (PathTracerApp.cpp:669)
 };
 

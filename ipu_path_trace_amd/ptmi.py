@@ -15,6 +15,16 @@ PATH_DTYPE = np.dtype([("length", "<u4"), ("escaped", "<u4"), ("dir", "<f4", 3),
                        ("throughput", "<f4", 3), ("cam", "<f4", 2)])
 assert PATH_DTYPE.itemsize == 48
 
+SCENE_DTYPE = np.dtype([("shape", "<i4"), ("material", "<i4"), ("centre", "<f4", 3), ("radius", "<f4"),
+                        ("normal", "<f4", 3), ("colour", "<f4", 3)])
+assert SCENE_DTYPE.itemsize == 48   # pt_scene_object
+MAX_SCENE_OBJECTS = 32
+SHAPE_SPHERE, SHAPE_DISC = 0, 1
+MATERIAL_DIFFUSE, MATERIAL_SPECULAR, MATERIAL_REFRACTIVE, MATERIAL_EMISSIVE = 0, 1, 2, 3
+SHAPES = {"sphere": SHAPE_SPHERE, "disc": SHAPE_DISC}
+MATERIALS = {"diffuse": MATERIAL_DIFFUSE, "specular": MATERIAL_SPECULAR, "refractive": MATERIAL_REFRACTIVE,
+             "emissive": MATERIAL_EMISSIVE}
+
 AA_NORMAL, AA_UNIFORM, AA_TRUNCATED_NORMAL = 0, 1, 2
 SAMPLES_HALF, SAMPLES_FLOAT = 0, 1
 DTYPE_F16, DTYPE_F32 = 0, 1
@@ -26,7 +36,7 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_init_all", "pt_comm_info", "pt_comm_set_timeout", "pt_comm_abort",
            "pt_gather_hdr", "pt_film_accumulate", "pt_tile_costs_enable", "pt_tile_costs", "pt_film_seed",
            "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats",
-           "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats"]
+           "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats", "pt_set_scene", "pt_get_scene"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 COMM_ID_BYTES = 128
@@ -62,6 +72,44 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SceneObject(C.Structure):
+    """pt_scene_object (include/ptmi.h): one sphere or disc of a runtime scene."""
+    _fields_ = [("shape", C.c_int32), ("material", C.c_int32), ("centre", C.c_float * 3), ("radius", C.c_float),
+                ("normal", C.c_float * 3), ("colour", C.c_float * 3)]
+
+
+def scene_array(objects):
+    """A SCENE_DTYPE array from a SCENE_DTYPE array or a list of dicts with the keys shape, material, centre, radius, normal,
+    colour ("emission" is accepted for colour); shape and material may be names ("sphere", "disc"; "diffuse", "specular",
+    "refractive", "emissive") or their numbers.  normal may be left out for a sphere, colour for a specular object."""
+    if isinstance(objects, np.ndarray) and objects.dtype == SCENE_DTYPE:
+        return np.ascontiguousarray(objects)
+    out = np.zeros(len(objects), dtype=SCENE_DTYPE)
+    for i, o in enumerate(objects):
+        unknown = set(o) - {"shape", "material", "centre", "radius", "normal", "colour", "emission"}
+        if unknown:
+            raise ValueError("scene object %d: unknown key(s) %s" % (i, sorted(unknown)))
+        shape, mat = o["shape"], o["material"]
+        out[i]["shape"] = SHAPES[shape] if isinstance(shape, str) else int(shape)
+        out[i]["material"] = MATERIALS[mat] if isinstance(mat, str) else int(mat)
+        out[i]["centre"] = o["centre"]
+        out[i]["radius"] = o["radius"]
+        out[i]["normal"] = o.get("normal", (0.0, 0.0, 0.0))
+        out[i]["colour"] = o.get("colour", o.get("emission", (1.0, 1.0, 1.0)))
+    return out
+
+
+def builtin_scene():
+    """The built-in scene (the reference's five spheres and floor disc) as a SCENE_DTYPE array; needs no GPU."""
+    lib = load_library()
+    n = C.c_uint32()
+    out = np.zeros(MAX_SCENE_OBJECTS, dtype=SCENE_DTYPE)
+    rc = lib.pt_get_scene(None, out.ctypes.data, MAX_SCENE_OBJECTS, C.byref(n))
+    if rc:
+        raise PtError(rc, "pt_get_scene failed")
+    return out[:n.value].copy()
 
 
 class NifSharingStats(C.Structure):
@@ -143,6 +191,8 @@ def load_library(diag=False):
     L.pt_set_nif_memo.argtypes = [C.c_void_p, C.c_uint64]
     L.pt_clear_nif_memo.argtypes = [C.c_void_p]
     L.pt_get_nif_memo_stats.argtypes = [C.c_void_p, C.POINTER(NifMemoStats)]
+    L.pt_set_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.pt_get_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     if diag:
         L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
@@ -299,6 +349,22 @@ class Renderer:
         d = st.as_dict()
         d["mode"] = {v: k for k, v in NIF_SHARE_MODES.items()}.get(d["mode"], d["mode"])
         return d
+
+    def set_scene(self, objects):
+        """Render a scene of 1..32 spheres and discs instead of the built-in one (include/ptmi.h, pt_set_scene): a SCENE_DTYPE
+        array or a list of dicts (scene_array).  None restores the built-in scene.  Takes effect at the next path_trace."""
+        if objects is None:
+            self._check(self._lib.pt_set_scene(self.handle, None, 0))
+            return
+        arr = scene_array(objects)
+        self._check(self._lib.pt_set_scene(self.handle, arr.ctypes.data, arr.size))   # (an empty table is refused)
+
+    def scene(self):
+        """The scene in force as a SCENE_DTYPE array (disc normals as the library normalised them)."""
+        n = C.c_uint32()
+        out = np.zeros(MAX_SCENE_OBJECTS, dtype=SCENE_DTYPE)
+        self._check(self._lib.pt_get_scene(self.handle, out.ctypes.data, MAX_SCENE_OBJECTS, C.byref(n)))
+        return out[:n.value].copy()
 
     def export_hdr_device(self, device_ptr, n):
         self._check(self._lib.pt_export_hdr_device(self.handle, C.c_void_p(device_ptr), n))
