@@ -285,6 +285,45 @@ typedef struct pt_scene_object {     /* 48 bytes */
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n);
 int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t* n);
 
+/* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
+ * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an
+ * optional thin lens.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves.
+ * Basis, computed once on the host, every intermediate a rounded binary32:
+ *   f = normalise(look_at - position), r = normalise(cross(f, up)), u = cross(r, f)    (normalise(v) = v / sqrtf(dot(v, v)))
+ * look_at - position and up are first scaled by the power of two that brings their largest component into [0.5, 1): exact, the
+ * same bits as without it, and any finite non-zero length is accepted (no overflow or underflow in the squares).
+ * A camera-space vector (x, y, z) is the world vector x r + y u - z f; the default camera gives the identity.  The field of
+ * view, the AA noise and the half-rounded (camx, camy) are exactly as before (fov and azimuth stay in pt_set_render_settings;
+ * the azimuth is added after the direction is in world space).  A camera whose basis is exactly (+x, +y, -z) at position 0
+ * IS the built-in one: no transform is applied at all, so it renders bit-identically to no call.
+ * Every quantity the ABI reports is in world space: pt_path_record.dir is the world direction of the escaping ray (or of the
+ * ray that hit an emitter), uv is PreProcessEscapedRays of that world direction, cam is unchanged (camera space).
+ * Thin lens (lens_radius = a > 0, focus_distance = F), in camera space: the focus point is F (camx, camy, -1) -- the focal
+ * plane is perpendicular to the view axis --, the lens point is a (sqrt(x1) cos 2 pi x2, sqrt(x1) sin 2 pi x2, 0), and the ray
+ * goes from the lens point towards the focus point with weight 1 (throughput starts at (1, 1, 1) as for the pinhole).
+ * x1, x2 are words 0 and 1 of Philox block 65 of the path (counter (pixel, sample, 65, 0x5054); AA noise draws block 0 and
+ * bounce d block 1 + d <= 64), on the primary-sample grid of pt_config.sample_precision.  With a == 0 no lens block is drawn
+ * and F is ignored.
+ * Validation: PT_ERR_INVALID_ARGUMENT, the previous camera stays in force and pt_last_error names the field, for a wrong
+ * struct_size, any value that is not finite (look_at - position included), look_at == position, up of length zero or parallel to the view direction
+ * (|cross(f, up / |up|)| < 1e-3), lens_radius < 0, lens_radius > 0 with focus_distance <= 0, and a NULL handle.  A NULL camera
+ * restores the built-in one.
+ * A new camera takes effect at the next pt_path_trace / pt_trace_paths.  It does not touch the worklist, the accumulators,
+ * the resident film, tile costs, the scene, NIF sharing or the NIF memo: sharing and memo keys are the (u, v) bits after
+ * rotation and azimuth, so both stay exact and need no invalidation.
+ * pt_get_camera copies the camera in force, values as given (struct_size = sizeof(pt_camera)); h == NULL gives the default
+ * and needs no device. */
+typedef struct pt_camera {        /* 48 bytes */
+  uint32_t struct_size;           /* sizeof(pt_camera), set by the caller */
+  float position[3];              /* default (0, 0, 0) */
+  float look_at[3];               /* default (0, 0, -1) */
+  float up[3];                    /* default (0, 1, 0); need not be unit or orthogonal */
+  float lens_radius;              /* 0 = pinhole (default) */
+  float focus_distance;           /* distance of the focal plane along the view axis; used when lens_radius > 0 */
+} pt_camera;
+int pt_set_camera(pt_handle h, const pt_camera* cam);   /* NULL restores the built-in camera */
+int pt_get_camera(pt_handle h, pt_camera* out);          /* values as given; h == NULL: the default, needs no device */
+
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);
  * the only exchange is the film: mean radiance per work item, BGR float32 [n][3] -- the value

@@ -1,11 +1,12 @@
 // diag/ptmi_trace_variants.h -- profiling build only: the trace-kernel A/B switch (PTMI_TRACE_KERNEL, read per launch so
-// that the rounds of scripts/ab_trace.py interleave in one process).  Returns false when no variant is selected: the
-// caller launches the product kernel.  Part of the translation unit ptmi.hip.
+// that the rounds of scripts/ab_trace.py interleave in one process).  Returns false when no variant is selected, or when a
+// camera is set (pt_set_camera: the variants carry no camera code): the caller launches the product kernel.  Part of the translation unit ptmi.hip.
 #pragma once
 
 static bool launch_trace_variant(pt_handle h, const ptd::TraceParams& P, const TraceGrid& g) {
   const char* tk = getenv("PTMI_TRACE_KERNEL");
   if (!tk) return false;
+  if (P.cam_pose || P.lens_a > 0.f) return false;   // the variants are instances for the built-in camera only: a camera runs the product kernel
   const dim3 grid(g.blocks), block(ptd::kTraceBlock);
   hipStream_t st = h->trace_stream;
   const size_t lds = ptd::hit_table_bytes(P.n_objects);

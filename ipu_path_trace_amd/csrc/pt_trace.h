@@ -83,6 +83,13 @@ struct TraceParams {
   uint32_t div_magic, div_shift;   // idx / n_items = (idx * div_magic) >> div_shift, exact for idx < 2^31 (ptmi_context.h: item_divider)
   unsigned long long* diag;        // profiling build: secondary-phase occupancy counters (OPT bit 4), else nullptr
   unsigned long long* emitted;     // paths that ended on an emitter (pt_context::d_counters[3]; pt_stats.escaped excludes them)
+  // Camera (pt_set_camera).  The kernels trace in CAMERA space: obj[] above holds the scene as the camera sees it (fill_scene),
+  // and only a direction that leaves the kernel -- an escape's (u, v), a path record's dir -- is rotated to world space, by the
+  // frame below (a camera-space (x, y, z) is the world vector x r + y u - z f).  cam_pose = 0: the built-in camera; obj[] is the
+  // world table and no rotation is applied (not an identity multiply: signed zeros would change atan2).
+  int32_t cam_pose;
+  float cam_r[3], cam_u[3], cam_f[3];
+  float lens_a, lens_f;            // thin lens: radius (0 = pinhole) and distance of the focal plane along the view axis
 };
 static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
 
@@ -159,6 +166,33 @@ __device__ __forceinline__ void start_path(const TraceParams& P, uint32_t pixel,
   s.pixel = pixel;
   s.sample = sample;
   s.depth = 0;
+}
+
+// Camera variants of the trace kernel (template flag): the instance that runs when no camera is set carries none of this.
+enum { CAM_BUILTIN = 0, CAM_POSE = 1, CAM_LENS = 2 };   // CAM_LENS rotates too when P.cam_pose says so (wave-uniform)
+constexpr uint32_t kLensBlock = 65u;   // Philox block of the lens sample: AA noise draws block 0, bounce d block 1 + d <= 64
+
+// Camera space -> world space, x r + y u - z f (wave-uniform frame: SGPRs).
+__device__ __forceinline__ Vec3 to_world(const TraceParams& P, Vec3 d) {
+  return mk((d.x * P.cam_r[0] + d.y * P.cam_u[0]) - d.z * P.cam_f[0],
+            (d.x * P.cam_r[1] + d.y * P.cam_u[1]) - d.z * P.cam_f[1],
+            (d.x * P.cam_r[2] + d.y * P.cam_u[2]) - d.z * P.cam_f[2]);
+}
+
+// Thin lens (include/ptmi.h): from the lens point a (sqrt(x1) cos 2 pi x2, sqrt(x1) sin 2 pi x2, 0) towards the focus point
+// F (camx, camy, -1), weight 1.  The primary phase and the first-shading phase both call this on the same (pixel, sample,
+// camx, camy) -- the survivor note keeps the two halves -- and so form the same origin and direction bit for bit.
+__device__ __forceinline__ void lens_ray(const TraceParams& P, uint32_t pixel, uint32_t sample, float camx, float camy,
+                                         Vec3& o, Vec3& d) {
+  uint32_t w[4];
+  philox4x32_10(pixel, sample, kLensBlock, 0x5054u, P.seed_lo, P.seed_hi, w);
+  const float x1 = uniform01(w[0], P.samples_half);
+  const float x2 = uniform01(w[1], P.samples_half);
+  float sn, cs;
+  dm_sincos2pi(x2, sn, cs);
+  const float rad = P.lens_a * sqrtf(x1);
+  o = mk(rad * cs, rad * sn, 0.f);
+  d = normalise(sub(mk(P.lens_f * camx, P.lens_f * camy, -P.lens_f), o));
 }
 
 __device__ __forceinline__ float sphere_intersect(Vec3 o, Vec3 d, const SceneObject& ob) {
@@ -483,6 +517,7 @@ __device__ __forceinline__ uint32_t emit_emitted(const TraceParams& P, bool emit
 
 // An escaped path: constant environment -> radiance straight into the per-path result; NIF -> one entry in the
 // workgroup's region of the queue (wave ballot + prefix count, ONE LDS atomic per wave, uv of PreProcessEscapedRays).
+template <int CAM = CAM_BUILTIN>
 __device__ __forceinline__ void emit_escaped(const TraceParams& P, bool escaped, const PathState& st, uint32_t idx, uint32_t lane,
                                              uint32_t region_base, uint32_t* wg_count) {
   if (P.env_const) {
@@ -502,7 +537,9 @@ __device__ __forceinline__ void emit_escaped(const TraceParams& P, bool escaped,
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(esc_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)esc_mask, 0u));
     const uint32_t q = region_base + base + rank;
     float u, v;
-    dir_to_uv(st.d, P.azimuth, u, v);
+    Vec3 d = st.d;
+    if constexpr (CAM != CAM_BUILTIN) { if (CAM == CAM_POSE || P.cam_pose) d = to_world(P, d); }   // the NIF is looked up in world space
+    dir_to_uv(d, P.azimuth, u, v);
     P.q_u[q] = u; P.q_v[q] = v;
     P.q_tr[q] = st.T.x; P.q_tg[q] = st.T.y; P.q_tb[q] = st.T.z;
     P.q_path[q] = idx;
@@ -530,7 +567,7 @@ namespace ptd {
 // workgroup barriers per 256 paths) and 2 % slower inside the C2 step -- its 16 KiB of LDS do not fit beside the NIF
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
-template <uint32_t REFILL, int OPT = kTraceOpt>
+template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
@@ -575,6 +612,10 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         if constexpr (SCENE_C) best = nearest_hit_primary_c(st.d, tbest, SceneIndices{});
         else
 #endif
+        if constexpr (CAM == CAM_LENS) {   // the ray starts on the lens, not at the origin: no origin-folded constants
+          lens_ray(P, pixel, st.sample, camx, camy, st.o, st.d);
+          best = nearest_hit<PIPE>(P, st.o, st.d, tbest);
+        } else
         best = PRIMARY ? nearest_hit_primary<PIPE>(P, st.d, tbest) : nearest_hit<PIPE>(P, st.o, st.d, tbest);
       }
     }
@@ -583,7 +624,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     // throughput is (1, 1, 1) x 1 exactly as bounce() would leave it
     const bool escaped = valid && !hit;
     if (escaped) P.plen[idx] = (uint8_t)(1u | 0x80u);
-    emit_escaped(P, escaped, st, idx, lane, region_base, &wg_count);
+    emit_escaped<CAM>(P, escaped, st, idx, lane, region_base, &wg_count);
     // survivors: diffuse hits fill the list from the front, mirror / glass hits from the back; an emitter hit is final
     // (codelets.cpp:192-196 at depth 0: no roulette, T = (1, 1, 1) x 1 as shade_hit would leave it) and queues nothing
     const uint32_t mat = __float_as_uint(hit_table[hit ? best : 0].colour.w) & 0xffu;
@@ -637,6 +678,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       st.pixel = P.pix[item];
       st.sample = P.sample_base + iter;
       st.depth = 0;
+      if constexpr (CAM == CAM_LENS) lens_ray(P, st.pixel, st.sample, (float)cam.h[0], (float)cam.h[1], st.o, st.d);   // as the primary phase
       uint32_t w[4];
       philox4x32_10(st.pixel, st.sample, 1u, 0x5054u, P.seed_lo, P.seed_hi, w);   // the block of bounce 0; no roulette at depth 0
       uint32_t length = 0;
@@ -726,7 +768,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       active = false;
     }
     wave_emitted += emit_emitted(P, emitted, st.o, idx);
-    emit_escaped(P, escaped, st, idx, lane, region_base, &wg_count);
+    emit_escaped<CAM>(P, escaped, st, idx, lane, region_base, &wg_count);
   }
   if constexpr ((OPT & 16) != 0) {
     if (lane == 0 && P.diag) {
@@ -740,6 +782,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
 }
 
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel(const TraceParams P) { trace_body<kRefillThreshold>(P); }
+// pt_set_camera: a moved / rotated pinhole (escapes rotated to world space), and a thin lens (its own primary phase)
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS>(P); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -762,6 +807,7 @@ __global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const
   PathState st;
   float camx, camy;
   start_path(P, (uint32_t)u[i] | ((uint32_t)v[i] << 16), sample[i], st, camx, camy);
+  if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
   do { res = bounce(P, hit_table, st, length); } while (res == STEP_CONTINUE);
@@ -770,8 +816,9 @@ __global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
   r.cam[0] = camx; r.cam[1] = camy;
   if (r.escaped) {
-    r.dir[0] = st.d.x; r.dir[1] = st.d.y; r.dir[2] = st.d.z;
-    if (res == STEP_ESCAPED) dir_to_uv(st.d, P.azimuth, r.uv[0], r.uv[1]);
+    const Vec3 d = P.cam_pose ? to_world(P, st.d) : st.d;   // reported in world space
+    r.dir[0] = d.x; r.dir[1] = d.y; r.dir[2] = d.z;
+    if (res == STEP_ESCAPED) dir_to_uv(d, P.azimuth, r.uv[0], r.uv[1]);
     r.throughput[0] = st.T.x; r.throughput[1] = st.T.y; r.throughput[2] = st.T.z;
   }
   out[i] = r;

@@ -36,6 +36,7 @@
 
 #include "ptmi_comm_worker.h"
 #include "ptmi_scene.h"
+#include "ptmi_camera.h"
 #include "ptmi_context.h"
 #include "ptmi_nif_pack.h"
 #include "ptmi_nif_launch.h"
@@ -734,7 +735,10 @@ static int enqueue_path_trace(pt_handle h, std::vector<StageSpan>& spans, size_t
 #ifdef PTMI_DIAG_BUILD
     if (!launch_trace_variant(h, P, g))   // A/B switches of the profiling build (diag/ptmi_trace_variants.h), read per launch
 #endif
-    hipLaunchKernelGGL(ptd::trace_kernel, dim3(g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
+    {   // the camera picks the instance: the built-in one runs the kernel it always ran
+      auto kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens : (P.cam_pose ? ptd::trace_kernel_pose : ptd::trace_kernel);
+      hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
+    }
     PT_HIP(hipGetLastError());
     PT_HIP(hipEventRecord(t1, h->trace_stream));
     spans.push_back({ev, ev + 1, 0});
@@ -1184,6 +1188,22 @@ int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t*
     return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_scene: capacity " + std::to_string(capacity) + " < " + std::to_string(count) + " objects")
              : PT_ERR_INVALID_ARGUMENT;
   std::copy(src, src + count, out);
+  return PT_OK;
+}
+
+int pt_set_camera(pt_handle h, const pt_camera* cam) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  const pt_camera c = cam ? *cam : ptcamera::default_camera();   // NULL: the built-in camera
+  const std::string bad = ptcamera::check(&c);
+  if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the camera in force stays
+  h->camera = c;
+  h->camera_basis = ptcamera::basis(c);
+  return PT_OK;
+}
+
+int pt_get_camera(pt_handle h, pt_camera* out) {
+  if (!out) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_camera: null output") : PT_ERR_INVALID_ARGUMENT;
+  *out = h ? h->camera : ptcamera::default_camera();
   return PT_OK;
 }
 

@@ -109,6 +109,10 @@ struct pt_context {
   pt_scene_object scene[PT_MAX_SCENE_OBJECTS] = {};
   uint32_t scene_n = 0;
 
+  // camera (pt_set_camera): the values as given, and the frame made from them once (ptmi_camera.h)
+  pt_camera camera = ptcamera::default_camera();
+  ptcamera::Basis camera_basis = ptcamera::basis(ptcamera::default_camera());
+
   // environment
   bool env_const = false;
   float env_rgb[3] = {0, 0, 0};
@@ -270,15 +274,24 @@ void builtin_scene(pt_scene_object (&out)[ptd::kBuiltinObjects]) {
 
 // Scene constants of a table of n objects (the built-in one or pt_set_scene's) into the kernel arguments: the SAME
 // expressions for every table, so the built-in table passed through pt_set_scene is bit-identical to no call.
-void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n) {
+// The kernels trace in camera space: with a camera other than the built-in one (cam != nullptr) a centre enters as
+// R^T (c - position) and a disc normal as R^T n, and the expressions below run on those values.  The built-in camera applies
+// no transform at all (not a multiplication by the identity), so "no camera set" is the same bits by construction.
+void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, const ptcamera::Basis* cam = nullptr) {
   P.n_objects = n;
   for (uint32_t i = 0; i < n; ++i) {
     ptd::SceneObject& o = P.obj[i];
     const bool disc = src[i].shape == PT_SHAPE_DISC;
-    o.cx = src[i].centre[0]; o.cy = src[i].centre[1]; o.cz = src[i].centre[2];
+    float centre[3] = {src[i].centre[0], src[i].centre[1], src[i].centre[2]};
+    float normal[3] = {src[i].normal[0], src[i].normal[1], src[i].normal[2]};
+    if (cam) {
+      ptcamera::to_camera_point(*cam, src[i].centre, centre);
+      if (disc) ptcamera::to_camera_direction(*cam, src[i].normal, normal);
+    }
+    o.cx = centre[0]; o.cy = centre[1]; o.cz = centre[2];
     o.radius = src[i].radius;
     o.r2 = src[i].radius * src[i].radius;
-    o.nx = src[i].normal[0]; o.ny = src[i].normal[1]; o.nz = src[i].normal[2];
+    o.nx = normal[0]; o.ny = normal[1]; o.nz = normal[2];
     o.colr = src[i].colour[0]; o.colg = src[i].colour[1]; o.colb = src[i].colour[2];
     o.type = src[i].material;
     o.is_disc = disc ? 1 : 0;
@@ -311,13 +324,19 @@ void item_divider(uint32_t n, uint32_t& magic, uint32_t& shift) {
 
 void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   memset(&P, 0, sizeof(P));
+  const ptcamera::Basis& cb = h->camera_basis;
+  const ptcamera::Basis* cam = cb.identity ? nullptr : &cb;
   if (h->scene_n) {
-    fill_scene(P, h->scene, h->scene_n);
+    fill_scene(P, h->scene, h->scene_n, cam);
   } else {
     pt_scene_object builtin[ptd::kBuiltinObjects];
     builtin_scene(builtin);
-    fill_scene(P, builtin, ptd::kBuiltinObjects);
+    fill_scene(P, builtin, ptd::kBuiltinObjects, cam);
   }
+  P.cam_pose = cam ? 1 : 0;
+  for (int k = 0; k < 3; ++k) { P.cam_r[k] = cb.r[k]; P.cam_u[k] = cb.u[k]; P.cam_f[k] = cb.f[k]; }
+  P.lens_a = h->camera.lens_radius;
+  P.lens_f = h->camera.lens_radius > 0.f ? h->camera.focus_distance : 0.f;
   const pt_config& c = h->cfg;
   const float w = (float)c.width, hgt = (float)c.height;
   const float fov = host_hround(h->fov);        // field_of_view stream is half (PathTracerApp.cpp:591)

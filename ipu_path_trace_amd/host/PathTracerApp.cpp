@@ -17,6 +17,7 @@
 #include "json.hpp"
 #include "logging.hpp"
 #include "../csrc/ptmi_scene.h"
+#include "../csrc/ptmi_camera.h"
 #include "trace_ranges.hpp"
 
 /// Adjust samples per pixel to be a multiple of samples per step (PathTracerApp.cpp:19-27).
@@ -90,7 +91,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
-      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}."},
+      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"nif-memo-gib", 0, "0", false, false, "GiB of device memory for a memo of decoded NIF values kept across steps, per logical device (0 = off). Exact: the image is bit-identical to off. Escaped paths whose (u, v) an earlier step evaluated are served from it; the memo is forgotten when a new NIF is loaded."},
   };
 }
@@ -132,7 +133,8 @@ std::uint64_t nifMemoBytes(const std::string& text) {
 
 // --scene (an extension: the reference's scene is compile-time, codelets.cpp:90,110-144).  Read and checked before any device is
 // attached, with the library's own checks (ptmi_scene.h) and messages; the table goes to every handle in attach().
-std::vector<pt_scene_object> loadSceneFile(const std::string& path) {
+// `camera` receives the file's optional top-level "camera" (every key optional, defaults of pt_camera), checked like the table.
+std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& camera, bool& hasCamera) {
   const std::string at = "--scene '" + path + "': ";
   std::ifstream in(path, std::ios::binary);
   if (!in) throw std::runtime_error(at + "cannot open the file");
@@ -195,6 +197,36 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path) {
   }
   const std::string bad = ptscene::check(objs.data(), (std::uint32_t)objs.size());
   if (!bad.empty()) throw std::runtime_error(at + bad);
+  camera = ptcamera::default_camera();
+  hasCamera = root.has("camera");
+  if (hasCamera) {
+    const json::Value& v = root.at("camera");
+    if (v.type != json::Value::Object) throw std::runtime_error(at + "camera: expected a JSON object");
+    auto numbers = [&](const char* key, float* out, std::size_t k) {
+      if (!v.has(key)) return;
+      const json::Value& a = v.at(key);
+      const bool scalar = k == 1 && a.type == json::Value::Number;
+      if (!scalar && (a.type != json::Value::Array || a.arr.size() != k))
+        throw std::runtime_error(at + "camera: \"" + key + "\" must be " + (k == 1 ? "a number" : "an array of " + std::to_string(k) + " numbers"));
+      for (std::size_t c = 0; c < k; ++c) {
+        const json::Value& x = scalar ? a : a.arr[c];
+        if (x.type != json::Value::Number) throw std::runtime_error(at + "camera: \"" + key + "\" must hold numbers");
+        out[c] = (float)x.num;
+      }
+    };
+    for (const auto& kv : v.obj)
+      if (kv.first != "position" && kv.first != "look_at" && kv.first != "up" && kv.first != "lens_radius" && kv.first != "focus_distance")
+        throw std::runtime_error(at + "camera: unknown key \"" + kv.first + "\"");
+    numbers("position", camera.position, 3);
+    numbers("look_at", camera.look_at, 3);
+    numbers("up", camera.up, 3);
+    numbers("lens_radius", &camera.lens_radius, 1);
+    // a lens must say where it focuses: the default distance only stands in for a pinhole, which ignores it
+    if (v.has("lens_radius") && camera.lens_radius > 0.f && !v.has("focus_distance")) camera.focus_distance = 0.f;
+    numbers("focus_distance", &camera.focus_distance, 1);
+    const std::string badCamera = ptcamera::check(&camera);
+    if (!badCamera.empty()) throw std::runtime_error(at + badCamera);
+  }
   return objs;
 }
 
@@ -225,7 +257,7 @@ void PathTracerApp::init(const OptionMap& options) {
   if (samplesPerIpuStep == 0) throw std::runtime_error("--samples-per-step must be at least 1.");
   nifSharing = nifSharingMode(args.str("share-nif-evaluations"));
   nifMemo = nifMemoBytes(args.str("nif-memo-gib"));
-  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"));
+  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera);
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
   if (!image_io::ldrWriterFor(args.str("outfile")))
@@ -320,6 +352,8 @@ void PathTracerApp::attach() {
     if (pt_set_nif_sharing(h, nifSharing))
       throw std::runtime_error(std::string("--share-nif-evaluations: ") + pt_last_error(h));
     if (!scene.empty() && pt_set_scene(h, scene.data(), (std::uint32_t)scene.size()))
+      throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
+    if (hasCamera && pt_set_camera(h, &camera))
       throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
   }
   // one memo per logical device: logical devices that share a GPU need room for all of theirs, or none runs with one

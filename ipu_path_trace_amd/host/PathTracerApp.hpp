@@ -80,6 +80,8 @@ private:
   std::uint64_t nifMemo = 0;   ///< --nif-memo-gib in bytes per logical device, 0 = off
   std::uint64_t memoServed = 0, memoEscaped = 0, memoRows = 0;
   std::vector<pt_scene_object> scene;   ///< --scene: the table every handle renders (empty: the built-in scene)
+  pt_camera camera{};                   ///< --scene: the file's "camera", set on every handle when hasCamera
+  bool hasCamera = false;
   std::chrono::steady_clock::time_point renderStartTime;   // reset when the UI restarts the render (PathTracerApp.cpp:669)
 };
 

@@ -36,7 +36,8 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_init_all", "pt_comm_info", "pt_comm_set_timeout", "pt_comm_abort",
            "pt_gather_hdr", "pt_film_accumulate", "pt_tile_costs_enable", "pt_tile_costs", "pt_film_seed",
            "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats",
-           "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats", "pt_set_scene", "pt_get_scene"]
+           "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats", "pt_set_scene", "pt_get_scene",
+           "pt_set_camera", "pt_get_camera"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 COMM_ID_BYTES = 128
@@ -78,6 +79,40 @@ class SceneObject(C.Structure):
     """pt_scene_object (include/ptmi.h): one sphere or disc of a runtime scene."""
     _fields_ = [("shape", C.c_int32), ("material", C.c_int32), ("centre", C.c_float * 3), ("radius", C.c_float),
                 ("normal", C.c_float * 3), ("colour", C.c_float * 3)]
+
+
+class Camera(C.Structure):
+    """pt_camera (include/ptmi.h): position, orientation and thin lens of the runtime camera."""
+    _fields_ = [("struct_size", C.c_uint32), ("position", C.c_float * 3), ("look_at", C.c_float * 3), ("up", C.c_float * 3),
+                ("lens_radius", C.c_float), ("focus_distance", C.c_float)]
+
+    def as_dict(self):
+        return {"position": tuple(self.position), "look_at": tuple(self.look_at), "up": tuple(self.up),
+                "lens_radius": self.lens_radius, "focus_distance": self.focus_distance}
+
+
+assert C.sizeof(Camera) == 48   # pt_camera
+
+
+def make_camera(position=(0.0, 0.0, 0.0), look_at=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), lens_radius=0.0, focus_distance=1.0):
+    """A Camera with struct_size set; the defaults are the built-in camera."""
+    cam = Camera()
+    cam.struct_size = C.sizeof(Camera)
+    cam.position = (C.c_float * 3)(*[float(x) for x in position])
+    cam.look_at = (C.c_float * 3)(*[float(x) for x in look_at])
+    cam.up = (C.c_float * 3)(*[float(x) for x in up])
+    cam.lens_radius = float(lens_radius)
+    cam.focus_distance = float(focus_distance)
+    return cam
+
+
+def default_camera():
+    """The built-in camera as the library reports it (pt_get_camera with no handle); needs no GPU."""
+    cam = Camera()
+    rc = load_library().pt_get_camera(None, C.byref(cam))
+    if rc:
+        raise PtError(rc, "pt_get_camera failed")
+    return cam
 
 
 def scene_array(objects):
@@ -193,6 +228,8 @@ def load_library(diag=False):
     L.pt_get_nif_memo_stats.argtypes = [C.c_void_p, C.POINTER(NifMemoStats)]
     L.pt_set_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.pt_get_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+    L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     if diag:
         L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
@@ -365,6 +402,25 @@ class Renderer:
         out = np.zeros(MAX_SCENE_OBJECTS, dtype=SCENE_DTYPE)
         self._check(self._lib.pt_get_scene(self.handle, out.ctypes.data, MAX_SCENE_OBJECTS, C.byref(n)))
         return out[:n.value].copy()
+
+    def set_camera(self, position=(0.0, 0.0, 0.0), look_at=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), lens_radius=0.0,
+                   focus_distance=1.0):
+        """Place the camera (include/ptmi.h, pt_set_camera): position, the point it looks at, an up vector (need not be unit
+        or orthogonal), and a thin lens of radius lens_radius focused at focus_distance along the view axis (0: pinhole).
+        A lens given without focus_distance focuses at the default, 1.0 (ipu_trace --scene asks for the distance instead).
+        set_camera(None) restores the built-in camera; a Camera struct is taken as it is.  Takes effect at the next
+        path_trace / trace_paths; a rejected camera (PtError) leaves the previous one in force."""
+        if position is None:
+            self._check(self._lib.pt_set_camera(self.handle, None))
+            return
+        cam = position if isinstance(position, Camera) else make_camera(position, look_at, up, lens_radius, focus_distance)
+        self._check(self._lib.pt_set_camera(self.handle, C.byref(cam)))
+
+    def camera(self):
+        """The camera in force as a Camera struct, values as given."""
+        cam = Camera()
+        self._check(self._lib.pt_get_camera(self.handle, C.byref(cam)))
+        return cam
 
     def export_hdr_device(self, device_ptr, n):
         self._check(self._lib.pt_export_hdr_device(self.handle, C.c_void_p(device_ptr), n))
