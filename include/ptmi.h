@@ -142,7 +142,8 @@ int pt_runtime_info(char* buf, size_t n);
  * May be called again to hot-swap the environment (PathTracerApp.cpp:548-557). */
 int pt_upload_nif(pt_handle h, const pt_layer* layers, uint32_t n_layers, uint32_t embedding_dim,
                   float max, const float mean[3], int32_t log_tonemap);
-/* Constant-radiance environment instead of a NIF (BASELINE config C1; no reference program). */
+/* Constant-radiance environment instead of a NIF (BASELINE config C1; no reference program).  A third kind of environment,
+ * an HDR image, is pt_set_env_map below. */
 int pt_set_constant_env(pt_handle h, const float rgb[3]);
 
 /* Program "init_render_settings" (PathTracerApp.cpp:479): streams seed u32[2], anti_alias_scale
@@ -225,8 +226,8 @@ int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
  * that finds no slot within the probe limit is evaluated on its own and counted in `overflowed`: never dropped.  When more
  * than half of the slots are occupied after a step, the next step starts with a retain pass that keeps only the entries hit
  * in the last step (`retains` counts them).
- * Generation: pt_upload_nif, pt_clear_nif_memo and a pt_path_trace that fails start a new generation (every entry is
- * forgotten).  Nothing else invalidates the memo: not pt_set_render_settings (seed, fov, azimuth, AA), not pt_setup, not
+ * Generation: pt_upload_nif, pt_set_env_map, pt_clear_nif_memo and a pt_path_trace that fails start a new generation (every
+ * entry is forgotten).  Nothing else invalidates the memo: not pt_set_render_settings (seed, fov, azimuth, AA), not pt_setup, not
  * pt_set_scene, not pt_set_constant_env -- with a constant environment no memo pass runs.
  * Allocation: pt_set_nif_memo can return PT_ERR_OUT_OF_MEMORY and the memo is then left off; max_bytes between 1 and
  * 48 KiB - 1 is PT_ERR_INVALID_ARGUMENT.  The step store of step-scope sharing (not counted in max_bytes) is used and grown
@@ -323,6 +324,40 @@ typedef struct pt_camera {        /* 48 bytes */
 } pt_camera;
 int pt_set_camera(pt_handle h, const pt_camera* cam);   /* NULL restores the built-in camera */
 int pt_get_camera(pt_handle h, pt_camera* out);          /* values as given; h == NULL: the default, needs no device */
+
+/* HDR environment map -- an EXTENSION: an equirectangular image as the environment light, the third kind next to the NIF and
+ * the constant radiance.  The reference renders with a NIF trained on such an image (its README: "source an
+ * equirectangular-projection HDRI image"); here the image itself can be the light.  Additive: PTMI_ABI_VERSION stays 5.
+ * `bgr` is [height][width][3] float32 in host memory, B, G, R order, rows top to bottom (what the NIF decodes to and what
+ * AccumulatedImage holds).  The library keeps a device copy of one float4 (B, G, R, 0) per texel (16 bytes per texel: 128 MiB
+ * for 4096 x 2048) and retains no host pointer.
+ * Mapping: u runs down the image and v across it (PreProcessEscapedRays, codelets.cpp:333-347; the azimuth is folded into v),
+ * and texel (row r, column c) sits at u = r / height, v = c / width with no half-texel offset (NifModel::makeGridCoordsUV,
+ * NifModel.cpp:474-490): the map is the image a NIF would be trained to reproduce.  Per lookup, in binary32:
+ *   u, v are clamped with fminf(fmaxf(., 0), 1) (NaN becomes 0; no bit pattern reads outside the image);
+ *   y = u * (float)height, x = v * (float)width;
+ *   r0 = (int)floorf(y), fy = y - r0, then r0 = min(r0, height - 1), r1 = min(r0 + 1, height - 1)   (rows clamp at the pole);
+ *   c0 = (int)floorf(x), fx = x - c0, then c0 = c0 mod width, c1 = (c0 + 1) mod width              (columns wrap; v == 1 is column 0).
+ *   PT_ENV_FILTER_NEAREST   texel (r0, c0), bit for bit.
+ *   PT_ENV_FILTER_BILINEAR  per channel top = fmaf(fx, t01 - t00, t00), bot = fmaf(fx, t11 - t10, t10),
+ *                           out = fmaf(fy, bot - top, top).
+ * A path's radiance is out * throughput, the NIF heads' own single fp32 multiply per channel.
+ * pt_set_env_map makes the map the environment; a later pt_upload_nif or pt_set_constant_env replaces it (the last of the three
+ * calls wins) and frees the device copy, as does pt_destroy.  It takes effect at the next pt_path_trace and touches neither the
+ * worklist, the film, the scene nor the camera.  A step with a map runs the NIF-mode schedule with the map kernel in the NIF
+ * stage, so NIF sharing and the NIF memo apply to a map exactly as to a NIF (keys are the (u, v) bits); pt_set_env_map starts a
+ * new memo generation.  pt_stats: escaped keeps its meaning, nif_ms / nif_launches count that stage whichever kernel ran it,
+ * nif_flops_per_sample is 0; pt_nif_kernel_name reports "envmap_nearest" or "envmap_bilinear"; pt_calibrate_nif answers
+ * PT_ERR_NOT_READY as with a constant environment; pt_nif_infer still evaluates the last uploaded NIF.
+ * PT_ERR_INVALID_ARGUMENT for a NULL handle or image, width or height outside 1..PT_ENV_MAP_MAX_SIZE, a filter out of range, or
+ * a texel that is not finite or is negative (pt_last_error names row, column and channel).  After that or
+ * PT_ERR_OUT_OF_MEMORY the previous environment stays in force.
+ * pt_env_map_lookup runs the same kernel over n host (u, v) pairs and returns the BGR it looks up, float32 [n][3]:
+ * PT_ERR_NOT_READY when no map is the environment; n == 0 is a no-op. */
+enum { PT_ENV_FILTER_NEAREST = 0, PT_ENV_FILTER_BILINEAR = 1 };
+#define PT_ENV_MAP_MAX_SIZE 16384
+int pt_set_env_map(pt_handle h, const float* bgr, uint32_t width, uint32_t height, int32_t filter);
+int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, float* bgr);
 
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <condition_variable>
@@ -33,6 +34,7 @@
 #include "pt_trace.h"
 #include "pt_nif_share.h"
 #include "pt_nif_memo.h"
+#include "pt_envmap.h"
 
 #include "ptmi_comm_worker.h"
 #include "ptmi_scene.h"
@@ -48,6 +50,7 @@ static void comm_release(pt_handle h);
 static void free_share_buffers(pt_handle h);
 static void free_memo_buffers(pt_handle h);
 static void memo_new_generation(pt_handle h);
+static void drop_env_map(pt_handle h);
 static void forget_replay_state(pt_handle h);   // ptmi_film_comm.h: orderly end of the handle's communicator (finalize, polled; abort on expiry)
 
 extern "C" {
@@ -179,6 +182,7 @@ int pt_destroy(pt_handle h) {
   free_batch_buffers(h);
   free_share_buffers(h);
   free_memo_buffers(h);
+  drop_env_map(h);
   (void)hipFree(h->d_records);
   (void)hipFree(h->acc.pix); (void)hipFree(h->acc.r); (void)hipFree(h->acc.g); (void)hipFree(h->acc.b); (void)hipFree(h->acc.count); (void)hipFree(h->acc.length);
   (void)hipFree(h->d_counters);
@@ -278,6 +282,7 @@ static int upload_nif_f32(pt_handle h, const pt_layer* layers, uint32_t n_layers
   h->nif_flops = flops;
   h->nif_valid = true;
   h->env_const = false;
+  drop_env_map(h);
   forget_replay_state(h);
   return PT_OK;
 }
@@ -387,6 +392,7 @@ int pt_upload_nif(pt_handle h, const pt_layer* layers, uint32_t n_layers, uint32
   h->nif_flops = flops;
   h->nif_valid = true;
   h->env_const = false;
+  drop_env_map(h);
   forget_replay_state(h);
   return PT_OK;
 }
@@ -394,6 +400,10 @@ int pt_upload_nif(pt_handle h, const pt_layer* layers, uint32_t n_layers, uint32
 int pt_set_constant_env(pt_handle h, const float rgb[3]) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!rgb) return fail(h, PT_ERR_INVALID_ARGUMENT, "null rgb");
+  if (h->env_map) {   // the constant replaces the map
+    PT_HIP(hipSetDevice(h->cfg.device));
+    drop_env_map(h);
+  }
   h->env_const = true;
   memcpy(h->env_rgb, rgb, 12);
   forget_replay_state(h);
@@ -451,6 +461,39 @@ static void launch_accumulate(pt_handle h, uint32_t n, uint32_t iters, const pt_
 // streams either way, so a failure in the middle of the batch loop never leaves kernels running on buffers the host
 // is about to reuse or free.
 using StageSpan = pt_context::StageSpan;
+
+// The map stops being the environment (replaced by a NIF or a constant, or the handle goes): its device copy is freed.  No
+// kernel of the handle is running: every entry point that launches on the texels waits for its stream before it returns.
+static void drop_env_map(pt_handle h) {
+  (void)hipFree(h->d_env_texels);
+  h->d_env_texels = nullptr;
+  h->env_map = false;
+  h->env_w = h->env_h = 0;
+}
+
+// Stage N of a step with a map, and pt_env_map_lookup: the queue described by N (per-path or out_bgr form, exactly as the NIF
+// launchers take it) through the map kernel on the NIF stream.
+static int launch_envmap(pt_handle h, const ptd::NifParams& N) {
+  ptd::EnvMapParams E;
+  E.q_u = N.q_u; E.q_v = N.q_v; E.q_tr = N.q_tr; E.q_tg = N.q_tg; E.q_tb = N.q_tb; E.q_path = N.q_path;
+  E.region_count = N.region_count;
+  E.region_cap = N.region_cap;
+  E.rad_r = N.rad_r; E.rad_g = N.rad_g; E.rad_b = N.rad_b;
+  E.out_bgr = N.out_bgr;
+  E.texels = h->d_env_texels;
+  E.width = h->env_w; E.height = h->env_h;
+  if (N.n_regions == 0 || N.region_cap == 0) return PT_OK;
+  const dim3 grid((N.region_cap + ptd::kEnvBlock - 1u) / ptd::kEnvBlock, N.n_regions);
+  if (h->env_filter == PT_ENV_FILTER_NEAREST) {
+    h->nif_kernel = "envmap_nearest";
+    hipLaunchKernelGGL(ptd::envmap_kernel<ptd::kEnvNearest>, grid, dim3(ptd::kEnvBlock), 0, h->stream, E);
+  } else {
+    h->nif_kernel = "envmap_bilinear";
+    hipLaunchKernelGGL(ptd::envmap_kernel<ptd::kEnvBilinear>, grid, dim3(ptd::kEnvBlock), 0, h->stream, E);
+  }
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
 
 static void forget_replay_state(pt_handle h) {   // pt_calibrate_nif may only replay a batch of the most recent NIF step
   for (auto& B : h->bb) { B.last_paths = 0; B.last_regions = 0; B.last_region_cap = 0; B.share_batch = -1; }
@@ -796,7 +839,7 @@ static int enqueue_path_trace(pt_handle h, std::vector<StageSpan>& spans, size_t
       if (h->diag_fault_batch >= 0 && (uint32_t)h->diag_fault_batch == batch)
         return fail(h, PT_ERR_HIP, "injected fault: NIF launch of batch " + std::to_string(batch));
 #endif
-      if (int rc = launch_nif(h, N, h->n_cus)) return rc;
+      if (int rc = h->env_map ? launch_envmap(h, N) : launch_nif(h, N, h->n_cus)) return rc;
       B.last_paths = total; B.last_regions = g.blocks; B.last_region_cap = g.region_cap;
       B.share_batch = grouped ? (int32_t)batch : -1; B.share_base = share_base; B.share_region_cap = share_cap;
       spans.push_back({ev + 2, ev + 3, 1});
@@ -902,13 +945,14 @@ static int resolve_stage_times(pt_handle h) {
 int pt_path_trace(pt_handle h) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->settings_valid) return fail(h, PT_ERR_NOT_READY, "pt_set_render_settings has not been called");
-  if (!h->env_const && !h->nif_valid) return fail(h, PT_ERR_NOT_READY, "no environment: call pt_upload_nif or pt_set_constant_env");
+  if (!h->env_const && !h->env_map && !h->nif_valid)
+    return fail(h, PT_ERR_NOT_READY, "no environment: call pt_upload_nif, pt_set_env_map or pt_set_constant_env");
   PT_HIP(hipSetDevice(h->cfg.device));
   memset(&h->stats, 0, sizeof(h->stats));
   h->share_mode_last = 0; h->share_evals = 0; h->share_overflowed = 0; h->share_ms = 0;
   h->memo_ran = false; h->memo_served = 0; h->memo_inserted = 0; h->memo_ms = 0;
   h->spans_pending = false;
-  h->stats.nif_flops_per_sample = h->env_const ? 0 : h->nif_flops;
+  h->stats.nif_flops_per_sample = (h->env_const || h->env_map) ? 0 : h->nif_flops;
   h->stats.first_sample = h->sample_cursor;
   const uint32_t n = h->n_items;
   if (n == 0) return PT_OK;
@@ -1029,6 +1073,7 @@ int pt_nif_kernel_name(pt_handle h, char* buf, size_t n) {
 int pt_calibrate_nif(pt_handle h, uint32_t launches, double* ms_per_launch, uint64_t* evaluations) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!ms_per_launch || !evaluations || launches == 0) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_calibrate_nif: bad arguments");
+  if (h->env_map) return fail(h, PT_ERR_NOT_READY, "pt_calibrate_nif: the environment is a map (pt_set_env_map), not a NIF");
   if (!h->nif_valid) return fail(h, PT_ERR_NOT_READY, "pt_upload_nif has not been called");
   const pt_context::BatchBuffers& B = h->bb[h->bb[1].last_paths > h->bb[0].last_paths ? 1 : 0];
   if (B.last_paths == 0) return fail(h, PT_ERR_NOT_READY, "no path_trace with a NIF environment has run on this handle since the last pt_upload_nif / pt_set_constant_env");
@@ -1162,6 +1207,89 @@ int pt_nif_infer(pt_handle h, const float* u, const float* v, size_t n, float* b
   PT_HIP(hipMemcpyAsync(bgr, d_out, n * 12, hipMemcpyDeviceToHost, h->stream));
   PT_HIP(hipStreamSynchronize(h->stream));
   return PT_OK;
+}
+
+int pt_set_env_map(pt_handle h, const float* bgr, uint32_t width, uint32_t height, int32_t filter) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!bgr) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_env_map: null image");
+  if (width == 0 || height == 0 || width > PT_ENV_MAP_MAX_SIZE || height > PT_ENV_MAP_MAX_SIZE)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_env_map: width and height must be in 1.." + std::to_string(PT_ENV_MAP_MAX_SIZE) +
+                                                " (got " + std::to_string(width) + " x " + std::to_string(height) + ")");
+  if (filter != PT_ENV_FILTER_NEAREST && filter != PT_ENV_FILTER_BILINEAR)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_env_map: filter must be PT_ENV_FILTER_NEAREST or PT_ENV_FILTER_BILINEAR");
+  const size_t texels = (size_t)width * height;
+  for (size_t i = 0; i < 3 * texels; ++i)
+    if (!(bgr[i] >= 0.f) || bgr[i] > FLT_MAX) {   // NaN, negative, infinity
+      static const char* const kChannel[3] = {"B", "G", "R"};
+      char value[32];
+      snprintf(value, sizeof(value), "%g", (double)bgr[i]);
+      return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_env_map: texel at row " + std::to_string(i / 3 / width) + ", column " +
+                                                  std::to_string(i / 3 % width) + ", channel " + std::to_string(i % 3) + " (" + kChannel[i % 3] +
+                                                  ") is " + value + ": texels must be finite and not negative");
+    }
+  PT_HIP(hipSetDevice(h->cfg.device));
+  PT_HIP(hipStreamSynchronize(h->stream));
+  // the new copy first: a failure leaves the previous environment in force
+  float4* d_new = nullptr;
+  PT_HIP(dev_alloc(&d_new, texels));
+  const size_t band = std::min<size_t>(texels, (size_t)4 << 20);   // staged in bands of 64 MiB at most
+  std::vector<float4> stage(band);
+  for (size_t t0 = 0; t0 < texels; t0 += band) {
+    const size_t n = std::min(band, texels - t0);
+    for (size_t i = 0; i < n; ++i) stage[i] = make_float4(bgr[3 * (t0 + i)], bgr[3 * (t0 + i) + 1], bgr[3 * (t0 + i) + 2], 0.f);
+    const hipError_t e = hipMemcpy(d_new + t0, stage.data(), n * sizeof(float4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d_new);
+      return fail(h, hip_status(e), std::string("pt_set_env_map: copying the texels: ") + hipGetErrorString(e));
+    }
+  }
+  drop_env_map(h);
+  h->d_env_texels = d_new;
+  h->env_w = width; h->env_h = height;
+  h->env_filter = filter;
+  h->env_map = true;
+  h->env_const = false;
+  memo_new_generation(h);   // the memo's values belong to the environment being replaced
+  forget_replay_state(h);
+  return PT_OK;
+}
+
+int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, float* bgr) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->env_map) return fail(h, PT_ERR_NOT_READY, "pt_set_env_map has not been called (or a NIF or a constant has replaced the map)");
+  if (n == 0) return PT_OK;
+  if (!u || !v || !bgr) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many lookups");
+  PT_HIP(hipSetDevice(h->cfg.device));
+  if (int rc = ensure_scratch(h, n * 4 * 2 + n * 12 + 16)) return rc;
+  float* d_u = static_cast<float*>(h->d_scratch);
+  float* d_v = d_u + n;
+  float* d_out = d_v + n;
+  uint32_t* d_count = reinterpret_cast<uint32_t*>(d_out + 3 * n);
+  const uint32_t cnt = (uint32_t)n;
+  // the copies read the caller's buffers and `cnt`: whatever fails below, none of them is left pending when the call returns
+  auto run = [&]() -> int {
+    PT_HIP(hipMemcpyAsync(d_u, u, n * 4, hipMemcpyHostToDevice, h->stream));
+    PT_HIP(hipMemcpyAsync(d_v, v, n * 4, hipMemcpyHostToDevice, h->stream));
+    PT_HIP(hipMemcpyAsync(d_count, &cnt, 4, hipMemcpyHostToDevice, h->stream));
+    ptd::NifParams N;
+    memset(&N, 0, sizeof(N));
+    N.q_u = d_u; N.q_v = d_v;
+    N.region_count = d_count;
+    N.n_regions = 1;
+    N.region_cap = cnt;
+    N.out_bgr = d_out;
+    const std::string name = h->nif_kernel;   // pt_nif_kernel_name keeps reporting the last step's stage
+    const int rc = launch_envmap(h, N);
+    h->nif_kernel = name;
+    if (rc) return rc;
+    PT_HIP(hipMemcpyAsync(bgr, d_out, n * 12, hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(hipStreamSynchronize(h->stream));
+    return PT_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  return rc;
 }
 
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {

@@ -116,6 +116,11 @@ struct pt_context {
   // environment
   bool env_const = false;
   float env_rgb[3] = {0, 0, 0};
+  // HDR environment map (pt_set_env_map, pt_envmap.h): the third kind; the last of the three calls wins
+  bool env_map = false;
+  float4* d_env_texels = nullptr;    // [env_h][env_w] (B, G, R, 0), row-major
+  uint32_t env_w = 0, env_h = 0;
+  int32_t env_filter = 0;
   bool nif_valid = false;
   int nif_hidden = 0, nif_emb = 0;   // PADDED hidden width / embedding dimension the kernels are instantiated for
   bool nif_gemm = false;  // layer-by-layer path (pt_nif_gemm.h)

@@ -92,6 +92,8 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
       {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
+      {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
+      {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
       {"nif-memo-gib", 0, "0", false, false, "GiB of device memory for a memo of decoded NIF values kept across steps, per logical device (0 = off). Exact: the image is bit-identical to off. Escaped paths whose (u, v) an earlier step evaluated are served from it; the memo is forgotten when a new NIF is loaded."},
   };
 }
@@ -119,6 +121,13 @@ void PathTracerApp::logNifEvaluations() {
   const double shared = nifEscaped ? 100.0 * (double)(nifEscaped - std::min(nifEscaped, nifEvaluations)) / (double)nifEscaped : 0.0;
   pt_log::info_("NIF evaluations: executed {} of {} escaped ({} % shared)", nifEvaluations, nifEscaped, shared);
   nifEscaped = nifEvaluations = 0;
+}
+
+// --env-map-filter
+std::int32_t envMapFilter(const std::string& name) {
+  if (name == "nearest") return PT_ENV_FILTER_NEAREST;
+  if (name == "bilinear") return PT_ENV_FILTER_BILINEAR;
+  throw std::runtime_error("--env-map-filter must be one of nearest, bilinear; got '" + name + "'");
 }
 
 // --nif-memo-gib (an extension, like sharing): a non-negative number of GiB
@@ -263,7 +272,23 @@ void PathTracerApp::init(const OptionMap& options) {
   if (!image_io::ldrWriterFor(args.str("outfile")))
     throw std::runtime_error("--outfile '" + args.str("outfile") + "': could not find a writer for the specified extension "
                              "(built in: .png .jpg .bmp .ppm .pnm .tif .tiff; the HDR image goes to <name>.exr)");
-  if (!args.has("constant-env") || args.str("constant-env").empty()) {
+  // --env-map (an extension): the image is read and checked here, before any device is attached (so --compile-only validates it)
+  const bool constantEnv = args.has("constant-env") && !args.str("constant-env").empty();
+  envMapFilterMode = envMapFilter(args.str("env-map-filter"));
+  if (args.has("env-map") && !args.str("env-map").empty()) {
+    if (constantEnv) throw std::runtime_error("--env-map and --constant-env are both given: the environment is one or the other");
+    try {
+      envMap = env_map::read(args.str("env-map"));
+    } catch (const std::exception& e) {
+      throw std::runtime_error(std::string("--env-map ") + e.what());
+    }
+    for (std::size_t i = 0; i < envMap.bgr.size(); ++i)
+      if (!(envMap.bgr[i] >= 0.f) || !std::isfinite(envMap.bgr[i]))
+        throw std::runtime_error("--env-map '" + args.str("env-map") + "': texel at row " + std::to_string(i / 3 / envMap.width) + ", column " +
+                                 std::to_string(i / 3 % envMap.width) + ", channel " + std::to_string(i % 3) + " is " + std::to_string(envMap.bgr[i]) +
+                                 ": texels must be finite and not negative");
+    pt_log::info_("Environment map '{}': {} x {}, {} filter", args.str("env-map"), envMap.width, envMap.height, args.str("env-map-filter"));
+  } else if (!constantEnv) {
     if (!loadNifModels(args.u32("ipus"), args.str("assets"))) throw std::runtime_error("Could not load NIF model.");
   }
 }
@@ -431,6 +456,9 @@ void PathTracerApp::execute() {
       if (std::sscanf(args.str("constant-env").c_str(), "%f,%f,%f", &rgb[0], &rgb[1], &rgb[2]) != 3)
         throw std::runtime_error("--constant-env expects r,g,b");
       check(devices[d], pt_set_constant_env(devices[d], rgb), "set_constant_env");
+    } else if (!envMap.bgr.empty()) {
+      check(devices[d], pt_set_env_map(devices[d], envMap.bgr.data(), (std::uint32_t)envMap.width, (std::uint32_t)envMap.height, envMapFilterMode),
+            "set_env_map");
     } else {
       models[d]->analyseModel((std::size_t)imageWidth * imageHeight / devices.size());
       models[d]->upload(devices[d]);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "AccumulatedImage.hpp"
+#include "EnvMapReader.hpp"
 #include "InterfaceServer.hpp"
 #include "IpuPathTraceJob.hpp"
 #include "LoadBalancer.hpp"
@@ -81,6 +82,8 @@ private:
   std::uint64_t memoServed = 0, memoEscaped = 0, memoRows = 0;
   std::vector<pt_scene_object> scene;   ///< --scene: the table every handle renders (empty: the built-in scene)
   pt_camera camera{};                   ///< --scene: the file's "camera", set on every handle when hasCamera
+  env_map::Image envMap;                ///< --env-map: the image every handle takes as its environment (empty: NIF or constant)
+  std::int32_t envMapFilterMode = 1;    ///< --env-map-filter (PT_ENV_FILTER_*)
   bool hasCamera = false;
   std::chrono::steady_clock::time_point renderStartTime;   // reset when the UI restarts the render (PathTracerApp.cpp:669)
 };

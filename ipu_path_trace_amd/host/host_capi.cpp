@@ -5,6 +5,7 @@
 
 #include "AccumulatedImage.hpp"
 #include "AsyncTask.hpp"
+#include "EnvMapReader.hpp"
 #include <stdexcept>
 #include "LoadBalancer.hpp"
 #include "NifModel.hpp"
@@ -87,6 +88,23 @@ int pth_read_exr(const char* file, float* bgr, std::size_t capacity, std::size_t
   if (d.size() > capacity) return -2;
   std::memcpy(bgr, d.data(), d.size() * sizeof(float));
   return 0;
+}
+
+void pth_write_exr(const char* file, const float* bgr, std::size_t w, std::size_t h) { image_io::writeExr(file, bgr, w, h); }
+
+// The environment-map reader (EnvMapReader.hpp): BGR rows top to bottom into bgr[capacity]; 0, or -1 with the message in err
+// (a file the reader refuses), or -2 (capacity too small; *w and *h are set).
+int pth_read_env_map(const char* file, float* bgr, std::size_t capacity, std::size_t* w, std::size_t* h, char* err, std::size_t errcap) {
+  try {
+    const env_map::Image img = env_map::read(file);
+    *w = img.width; *h = img.height;
+    if (img.bgr.size() > capacity) return -2;
+    std::memcpy(bgr, img.bgr.data(), img.bgr.size() * sizeof(float));
+    return 0;
+  } catch (const std::exception& e) {
+    if (err && errcap) std::snprintf(err, errcap, "%s", e.what());
+    return -1;
+  }
 }
 
 // Parses nif_metadata.txt; out = {embedding, hidden, layers, logToneMap, max, mean[3] (eps folded)}.

@@ -37,9 +37,11 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_gather_hdr", "pt_film_accumulate", "pt_tile_costs_enable", "pt_tile_costs", "pt_film_seed",
            "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats",
            "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats", "pt_set_scene", "pt_get_scene",
-           "pt_set_camera", "pt_get_camera"]
+           "pt_set_camera", "pt_get_camera", "pt_set_env_map", "pt_env_map_lookup"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
+ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
+ENV_FILTERS = {"nearest": ENV_FILTER_NEAREST, "bilinear": ENV_FILTER_BILINEAR}
 COMM_ID_BYTES = 128
 HDR_ACCUMULATORS, HDR_FILM = 0, 1
 
@@ -230,6 +232,8 @@ def load_library(diag=False):
     L.pt_get_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+    L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
+    L.pt_env_map_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     if diag:
         L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
@@ -313,6 +317,30 @@ class Renderer:
     def set_constant_env(self, rgb):
         v = (C.c_float * 3)(*[float(x) for x in rgb])
         self._check(self._lib.pt_set_constant_env(self.handle, v))
+
+    def set_env_map(self, bgr, filter="bilinear"):
+        """An equirectangular HDR image as the environment light (include/ptmi.h, pt_set_env_map): an (H, W, 3) array in B, G, R
+        order, rows top to bottom, finite and not negative; filter "nearest" or "bilinear" (or the ENV_FILTER_* numbers).
+        Replaces a NIF or a constant environment; takes effect at the next path_trace.  A rejected map (PtError) leaves the
+        previous environment in force."""
+        if isinstance(filter, str):
+            if filter not in ENV_FILTERS:
+                raise ValueError("env-map filter must be one of %s, got %r" % (sorted(ENV_FILTERS), filter))
+            filter = ENV_FILTERS[filter]
+        bgr = np.ascontiguousarray(bgr, dtype=np.float32)
+        if bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("env map must have shape (H, W, 3), got %r" % (bgr.shape,))
+        self._check(self._lib.pt_set_env_map(self.handle, bgr.ctypes.data, bgr.shape[1], bgr.shape[0], int(filter)))
+
+    def env_map_lookup(self, u, v):
+        """The BGR the map kernel looks up for (u, v), float32 [n, 3] (pt_env_map_lookup)."""
+        u = np.ascontiguousarray(u, dtype=np.float32).ravel()
+        v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+        if u.size != v.size:
+            raise ValueError("u and v must have the same size")
+        out = np.empty((u.size, 3), dtype=np.float32)
+        self._check(self._lib.pt_env_map_lookup(self.handle, u.ctypes.data, v.ctypes.data, u.size, out.ctypes.data))
+        return out
 
     # ---- program "init_render_settings"
     def init_render_settings(self, seed=1, aa_noise_scale=0.3, fov_degrees=90.0, env_rotation_degrees=0.0,
