@@ -359,6 +359,84 @@ enum { PT_ENV_FILTER_NEAREST = 0, PT_ENV_FILTER_BILINEAR = 1 };
 int pt_set_env_map(pt_handle h, const float* bgr, uint32_t width, uint32_t height, int32_t filter);
 int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, float* bgr);
 
+/* First-hit feature buffers -- an EXTENSION: what the centre ray of every pixel sees, noise free, for masks, compositing, the
+ * debugging of runtime scenes and as the guide of pt_denoise.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves;
+ * a process that never calls it runs exactly as before.
+ * The ray, for every pixel (u, v) of width x height (all pixels, whatever the worklist holds), is the production camera ray with
+ * zero AA noise and no lens: c = (float)u, r = (float)v, px = ((2 c - width) / width) tx, py = -(((2 r - height) / height) ty),
+ * camx = half(px), camy = half(py), d = normalise((camx, camy, -1)), origin 0 in camera space -- the expressions of the trace
+ * kernels with both noise terms 0.  The hit is the production kernels' nearest hit over the scene in force (pt_set_scene, seen
+ * by the camera of pt_set_camera), so with aa_noise_scale = 0 and no lens object_id is the object the trace kernels hit, bit
+ * for bit.  The thin lens is ignored on purpose: a guide image must be sharp.
+ *   object_id  index into the scene in force (pt_get_scene), -1 for a miss.
+ *   depth      hit distance t along the unit ray, 0 for a miss.
+ *   normal     sphere: (hit - centre) / |hit - centre| (= (hit - centre) / radius but for the rounding of the hit point; unit to
+ *              rounding); disc: its stored normal.  Flipped to face the ray (dot(n, d) > 0 -> -n), then rotated to WORLD space
+ *              (x r + y u - z f, as every quantity the ABI reports) and normalised again when a camera pose is set.  0 for a miss.
+ *   albedo     the object's colour for diffuse and refractive objects; (1, 1, 1) for specular and emissive objects and for a
+ *              miss (the usual demodulation convention).  Stored B, G, R like every other image of the ABI.
+ * The buffers stay on the device as the handle's feature cache, two float4 per pixel, allocated at the first call and freed by
+ * pt_destroy; pt_set_scene, pt_set_camera and pt_set_render_settings (the field of view) make the next call recompute them,
+ * and a call without such a change copies the cache.  Nothing else is touched: not the worklist, the accumulators or the film.
+ * Any pointer of pt_features may be NULL (= not wanted).  PT_ERR_INVALID_ARGUMENT for a NULL handle, a NULL `out` or a wrong
+ * struct_size; PT_ERR_NOT_READY before pt_set_render_settings (no worklist is needed); PT_ERR_OUT_OF_MEMORY if the cache cannot
+ * be allocated, and nothing else changes. */
+typedef struct pt_features {        /* all host pointers, any may be NULL (= not wanted) */
+  uint32_t struct_size;             /* sizeof(pt_features), set by the caller */
+  int32_t* object_id;               /* [height][width]      index into the scene in force, -1 = miss */
+  float*   depth;                   /* [height][width]      hit distance t along the unit ray, 0 for a miss */
+  float*   normal;                  /* [height][width][3]   WORLD-space unit normal facing the camera, 0 for a miss */
+  float*   albedo;                  /* [height][width][3]   B,G,R */
+} pt_features;
+int pt_feature_buffers(pt_handle h, pt_features* out);
+
+/* Film denoiser -- an EXTENSION: an edge-avoiding A-trous wavelet filter (Dammertz et al., HPG 2010) over a finished image, on
+ * the device, steered by the feature buffers above (computed on demand).  It runs after the sampling loop: no trace, NIF or
+ * accumulate kernel is involved and nothing a render produces moves.  Additive: PTMI_ABI_VERSION stays 5.
+ * Source.  PT_DENOISE_HOST_IMAGE: host_bgr_in, [height][width][3] float32 B, G, R (what rank 0 holds after pt_gather_hdr).
+ * The other two scatter THIS handle's work items into a dense image by their (u, v): PT_DENOISE_ACCUMULATORS the mean radiance
+ * (b, g, r) * (1 / sampleCount) as pt_export_hdr_device forms it (0 samples -> 0), PT_DENOISE_FILM the resident film's running
+ * sum times 1 / film_steps (one binary32 multiply by the binary32 reciprocal of the number of pt_film_accumulate calls since
+ * pt_setup).  Pixels the worklist does not hold, and padding items, are 0; a pixel it holds twice gets one of the two values.
+ * Definition, every operation binary32.  Let c_0[p] be the source; with `demodulate`, c_0[p] /= max(albedo[p], 1e-3) per channel
+ * and the result is multiplied by the same factor at the end.  Iteration i = 0 .. iterations - 1 has the step s = 2^i and the
+ * taps q = p + s (dx, dy), dx, dy in {-2 .. 2}; a tap outside the image is skipped (no clamping, no wrap).
+ *   h(dx, dy) = k[|dx|] k[|dy|], k = (3/8, 1/4, 1/16)                                      (the B3 spline)
+ *   w = w_c w_n w_d w_id, a disabled stop being 1:
+ *     w_c  = exp(-|c_i[p] - c_i[q]|^2 / sc_i^2), sc_i = sigma_colour 2^-i                  (the halving of Dammertz et al.)
+ *     w_n  = exp(-|n[p] - n[q]|^2 / sigma_normal^2)
+ *     w_d  = exp(-(d[p] - d[q])^2 / (sigma_depth max(d[p], 1e-6))^2)
+ *     w_id = 1 when the object ids are equal, else 0 -- a hard zero: that tap contributes nothing and its colour is not even
+ *            multiplied, so a non-finite neighbour on another object cannot leak.
+ *   c_{i+1}[p] = sum h w c_i[q] / sum h w.  The centre tap has w = 1 exactly (it is not computed through exp), so the
+ *   denominator is >= 9/64 and the result is a convex combination of the inputs.
+ * As evaluated: the three exponentials are one, expf(-(x_c + x_n + x_d)) with x = squared difference times the binary32
+ * reciprocal of the squared sigma; a stop whose squared difference is exactly 0 adds 0 without forming the product.
+ * Non-finite input colours are not validated and propagate (to every pixel whose taps reach them with a non-zero weight).
+ * pt_denoise_default_params fills the defaults (and struct_size); it needs no handle and no device.  params == NULL means the
+ * defaults.  The dense frames (2 colour + 2 feature float4 per pixel, 64 bytes per pixel) are allocated on first use and freed
+ * by pt_destroy.  The result is host_bgr_out, [height][width][3] float32 B, G, R.  Blocking.
+ * PT_ERR_INVALID_ARGUMENT, pt_last_error naming the field, for a wrong struct_size, iterations outside 1..6, a sigma that is
+ * not finite, a source out of range, a NULL host_bgr_out, a NULL host_bgr_in with PT_DENOISE_HOST_IMAGE, and a NULL handle;
+ * these are checked in this order before anything touches a device, and with h == NULL the message is pt_last_error(NULL)'s.
+ * PT_ERR_NOT_READY before pt_set_render_settings, without a worklist for the two device sources, and with no
+ * pt_film_accumulate since pt_setup for PT_DENOISE_FILM; PT_ERR_OUT_OF_MEMORY if the frames cannot be allocated.
+ * Multi-GPU: every rank's handle sees the whole scene, so the rank that holds the gathered image (rank 0) denoises it with
+ * PT_DENOISE_HOST_IMAGE; the device sources of one rank cover that rank's pixels only. */
+enum { PT_DENOISE_HOST_IMAGE = 0, PT_DENOISE_ACCUMULATORS = 1, PT_DENOISE_FILM = 2 };
+typedef struct pt_denoise_params {
+  uint32_t struct_size;     /* sizeof(pt_denoise_params), set by the caller (pt_denoise_default_params sets it) */
+  uint32_t iterations;      /* 1..6, default 5: step 1, 2, 4, ... */
+  float sigma_colour;       /* default 4;  <= 0 disables the colour stop */
+  float sigma_normal;       /* default 0.5; <= 0 disables */
+  float sigma_depth;        /* default 0.1 (relative); <= 0 disables */
+  int32_t object_stop;      /* default 1: a tap on another object id gets weight 0 */
+  int32_t demodulate;       /* default 1: divide by albedo before, multiply after */
+} pt_denoise_params;
+int pt_denoise_default_params(pt_denoise_params* p);     /* needs no handle and no device */
+int pt_denoise(pt_handle h, const pt_denoise_params* p /* NULL = defaults */, int32_t source,
+               const float* host_bgr_in /* [h][w][3], PT_DENOISE_HOST_IMAGE only */, float* host_bgr_out /* [h][w][3] */);
+
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);
  * the only exchange is the film: mean radiance per work item, BGR float32 [n][3] -- the value

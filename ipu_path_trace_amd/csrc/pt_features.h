@@ -1,0 +1,46 @@
+// pt_features.h -- first-hit feature buffers (pt_feature_buffers, include/ptmi.h): object id, depth, world-space normal and
+// albedo of what every pixel's centre ray sees.  An EXTENSION: the reference has no such output.
+//
+// One thread per pixel of width x height (every pixel, whatever the worklist holds).  The ray is the production camera ray
+// without AA noise and without the lens: start_path itself runs on a copy of the launch parameters whose aa_scale is 0, so
+// hround(aa_scale * n) is a zero, c = (float)u and r = (float)v exactly, and camx, camy, the normalisation and the direction
+// are start_path's own expressions (the Philox block it draws for the noise is multiplied away: a few hundred instructions per
+// pixel, once per scene / camera / settings change).  The hit is nearest_hit_primary over the table in the kernel arguments,
+// which is in camera space when a pose is set: the same function on the same ray as the production kernels' primary phase, so
+// the object index is theirs bit for bit (with aa_noise_scale = 0 and the lens off).  The lens is ignored on purpose: a guide
+// image must be sharp.
+//
+// Two packed float4 per pixel, the handle's feature cache (the denoiser reads them as they are):
+//   f0 = (nx, ny, nz, depth)           f1 = (albedo B, albedo G, albedo R, bits of the object index)
+#pragma once
+#include "pt_trace.h"
+
+namespace ptd {
+
+constexpr int kFeatureBlock = 256;
+
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
+  const uint32_t i = blockIdx.x * kFeatureBlock + threadIdx.x;
+  if (i >= P.width * P.height) return;   // width, height <= 65535: the product fits 32 bits
+  const uint32_t v = i / P.width, u = i - v * P.width;
+  PathState st;
+  float camx, camy, tbest;
+  start_path(P, u | (v << 16), 0u, st, camx, camy);   // P.aa_scale == 0 (the host's copy): the noise-free ray
+  const int best = nearest_hit_primary(P, st.d, tbest);
+  Vec3 n = mk(0.f, 0.f, 0.f), alb = mk(1.f, 1.f, 1.f);
+  float depth = 0.f;
+  if (best >= 0) {
+    const SceneObject ob = P.obj[best];
+    depth = tbest;
+    // sphere: (hit - centre) / |hit - centre| -- (hit - centre) / radius but for the rounding of the hit point, and unit to
+    // rounding as the production shading forms it (shade_hit); disc: its stored normal
+    n = ob.is_disc ? mk(ob.nx, ob.ny, ob.nz) : normalise(sub(scale(st.d, tbest), mk(ob.cx, ob.cy, ob.cz)));
+    if (dot(n, st.d) > 0.0f) n = scale(n, -1.0f);                     // faces the ray
+    if (P.cam_pose) n = normalise(to_world(P, n));                    // reported in world space; unit again after the rotation's roundings
+    if (ob.type == MAT_DIFFUSE || ob.type == MAT_REFRACTIVE) alb = mk(ob.colr, ob.colg, ob.colb);   // mirrors, emitters and misses demodulate by 1
+  }
+  f0[i] = make_float4(n.x, n.y, n.z, depth);
+  f1[i] = make_float4(alb.z, alb.y, alb.x, __int_as_float(best));     // B, G, R like every image of the ABI
+}
+
+}  // namespace ptd

@@ -35,6 +35,8 @@
 #include "pt_nif_share.h"
 #include "pt_nif_memo.h"
 #include "pt_envmap.h"
+#include "pt_features.h"
+#include "pt_denoise.h"
 
 #include "ptmi_comm_worker.h"
 #include "ptmi_scene.h"
@@ -193,6 +195,7 @@ int pt_destroy(pt_handle h) {
   (void)hipFree(h->d_head_partial); (void)hipFree(h->d_head_in);
   (void)hipFree(h->d_f32_weights); (void)hipFree(h->d_f32_act[0]); (void)hipFree(h->d_f32_act[1]); (void)hipFree(h->d_f32_feat);
   (void)hipFree(h->d_scratch);
+  (void)hipFree(h->d_feat[0]); (void)hipFree(h->d_feat[1]); (void)hipFree(h->d_dn_colour[0]); (void)hipFree(h->d_dn_colour[1]);
   (void)hipFree(h->d_hdr_stage); (void)hipFree(h->d_hdr_gather); (void)hipFree(h->d_film);
   (void)hipFree(h->d_slot_check);
   (void)hipFree(h->tiles.cost); (void)hipFree(h->d_tile_tmp);
@@ -421,6 +424,7 @@ int pt_set_render_settings(pt_handle h, uint64_t seed, float aa, float fov, floa
   if (!h->settings_valid || seed != h->seed) h->sample_cursor = 0;
   h->seed = seed; h->aa_scale = aa; h->fov = fov; h->azimuth = azimuth; h->samples_per_step = spp;
   h->settings_valid = true;
+  h->feature_gen += 1;   // the field of view is in there (pt_feature_buffers)
   return PT_OK;
 }
 
@@ -1294,12 +1298,13 @@ int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, flo
 
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!objects && n == 0) { h->scene_n = 0; return PT_OK; }   // the built-in scene
+  if (!objects && n == 0) { h->scene_n = 0; h->feature_gen += 1; return PT_OK; }   // the built-in scene
   const std::string bad = ptscene::check(objects, n);
   if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the scene in force stays
   std::copy(objects, objects + n, h->scene);
   ptscene::normalise(h->scene, n);
   h->scene_n = n;
+  h->feature_gen += 1;
   return PT_OK;
 }
 
@@ -1326,6 +1331,7 @@ int pt_set_camera(pt_handle h, const pt_camera* cam) {
   if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the camera in force stays
   h->camera = c;
   h->camera_basis = ptcamera::basis(c);
+  h->feature_gen += 1;
   return PT_OK;
 }
 
@@ -1368,6 +1374,7 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
 }  // extern "C"
 
 #include "ptmi_film_comm.h"
+#include "ptmi_denoise.h"
 
 extern "C" {
 

@@ -207,6 +207,16 @@ struct pt_context {
   void* d_scratch = nullptr;
   size_t scratch_bytes = 0;
 
+  // first-hit feature cache and the denoiser's dense frames (pt_feature_buffers / pt_denoise; pt_features.h, pt_denoise.h):
+  // allocated on first use, width x height float4 each (64 bytes per pixel in all), freed by pt_destroy
+  float4* d_feat[2] = {nullptr, nullptr};        // f0 = (normal, depth), f1 = (albedo BGR, object index bits)
+  float4* d_dn_colour[2] = {nullptr, nullptr};   // colour ping-pong
+  uint64_t feature_gen = 1;                      // bumped by pt_set_scene, pt_set_camera, pt_set_render_settings
+  uint64_t feature_cached_gen = 0;               // generation d_feat holds (0: none)
+  // A-trous iterations whose step is at most this stage their taps in LDS, the others read global memory (measured:
+  // profiles/r11_denoise.txt); the profiling build can move it (pt_diag_denoise_bench)
+  uint32_t denoise_tiled_max_step = 2;
+
   // multi-GPU film hand-off: RCCL communicator (one rank per handle) and the HDR tile buffers
   ncclComm_t comm = nullptr;
   std::shared_ptr<ptw::BoundedWorker> comm_worker;   // the long-lived thread that makes the handle's RCCL calls (ptmi_comm_worker.h): created with the first communicator call, dropped when a call never returns

@@ -94,6 +94,12 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
       {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
+      {"denoise", 0, "false", false, true, "Also write <basename>_denoised.exr and _denoised.<ext> at every save: the film through the edge-avoiding A-trous filter (pt_denoise), guided by first-hit object id, normal, depth and albedo. The plain outputs are unchanged. One device with the film resident filters the resident film; --host-film, load balancing or several devices filter the host film on device 0."},
+      {"denoise-iterations", 0, "5", false, false, "A-trous iterations, 1..6 (steps 1, 2, 4, ...)."},
+      {"denoise-sigma-colour", 0, "4", false, false, "Colour stop of the denoiser (halved every iteration); <= 0 disables it."},
+      {"denoise-sigma-normal", 0, "0.5", false, false, "Normal stop of the denoiser; <= 0 disables it."},
+      {"denoise-sigma-depth", 0, "0.1", false, false, "Relative depth stop of the denoiser; <= 0 disables it."},
+      {"save-features", 0, "false", false, true, "Also write the first-hit feature buffers at every save: <basename>_normal.exr (world x, y, z in the B, G, R channels), _albedo.exr (B, G, R) and _depth.exr (the hit distance in all three channels)."},
       {"nif-memo-gib", 0, "0", false, false, "GiB of device memory for a memo of decoded NIF values kept across steps, per logical device (0 = off). Exact: the image is bit-identical to off. Escaped paths whose (u, v) an earlier step evaluated are served from it; the memo is forgotten when a new NIF is loaded."},
   };
 }
@@ -266,6 +272,18 @@ void PathTracerApp::init(const OptionMap& options) {
   if (samplesPerIpuStep == 0) throw std::runtime_error("--samples-per-step must be at least 1.");
   nifSharing = nifSharingMode(args.str("share-nif-evaluations"));
   nifMemo = nifMemoBytes(args.str("nif-memo-gib"));
+  // --denoise (an extension): the values are checked here, before any device is attached
+  denoise = args.flag("denoise");
+  saveFeatures = args.flag("save-features");
+  pt_denoise_default_params(&denoiseParams);
+  denoiseParams.iterations = args.u32("denoise-iterations");
+  denoiseParams.sigma_colour = args.f32("denoise-sigma-colour");
+  denoiseParams.sigma_normal = args.f32("denoise-sigma-normal");
+  denoiseParams.sigma_depth = args.f32("denoise-sigma-depth");
+  if (denoiseParams.iterations < 1 || denoiseParams.iterations > 6)
+    throw std::runtime_error("--denoise-iterations must be 1..6; got " + args.str("denoise-iterations"));
+  for (const char* name : {"denoise-sigma-colour", "denoise-sigma-normal", "denoise-sigma-depth"})
+    if (!std::isfinite(args.f32(name))) throw std::runtime_error(std::string("--") + name + " must be finite; got " + args.str(name));
   if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera);
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
@@ -519,6 +537,49 @@ InterfaceServer::Status PathTracerApp::processUserInput(InterfaceServer::State& 
   return InterfaceServer::Status::Restart;
 }
 
+void PathTracerApp::saveDenoisedAndFeatures(const std::string& fileName, std::size_t step, float exposure, float gamma, bool filmOnDevice) {
+  if (!denoise && !saveFeatures) return;
+  const std::size_t w = args.u32("width"), h = args.u32("height");
+  const auto dot = fileName.find_last_of('.');
+  const std::string base = fileName.substr(0, dot), ext = dot == std::string::npos ? std::string() : fileName.substr(dot);
+  auto check = [&](int rc, const char* what) {
+    if (rc) throw std::runtime_error(std::string(what) + " failed: " + pt_last_error(devices[0]));
+  };
+  if (denoise) {
+    pt_trace::Range r("denoise");
+    std::vector<float> out(w * h * 3);
+    if (filmOnDevice) {
+      check(pt_denoise(devices[0], &denoiseParams, PT_DENOISE_FILM, nullptr, out.data()), "pt_denoise");
+    } else {
+      Image3<float> host = traceState->film.getHdrImage();   // the running sum; the saved image is sum * (1 / step) (AccumulatedImage::saveImages)
+      const float s = 1.f / step;
+      for (auto& v : host.data) v *= s;
+      check(pt_denoise(devices[0], &denoiseParams, PT_DENOISE_HOST_IMAGE, host.data.data(), out.data()), "pt_denoise");
+    }
+    image_io::writeExr(base + "_denoised.exr", out.data(), w, h);
+    // tone-mapped as AccumulatedImage::updateLdrImage does the plain image
+    std::vector<std::uint8_t> ldr(out.size());
+    const float exposureScale = std::pow(2.f, exposure), invGamma = 1.f / gamma;
+    for (std::size_t i = 0; i < out.size(); ++i) {
+      const float v = std::pow(out[i] * exposureScale, invGamma) * 255.0f;
+      ldr[i] = (std::uint8_t)std::min(255.0f, std::max(0.0f, std::nearbyint(v)));
+    }
+    image_io::writeLdr(base + "_denoised" + ext, ldr.data(), w, h);
+    pt_log::info_("Saved denoised images at step {}", step);
+  }
+  if (saveFeatures) {
+    std::vector<float> normal(w * h * 3), albedo(w * h * 3), depth(w * h), depth3(w * h * 3);
+    pt_features f{};
+    f.struct_size = sizeof(pt_features);
+    f.normal = normal.data(); f.albedo = albedo.data(); f.depth = depth.data();
+    check(pt_feature_buffers(devices[0], &f), "pt_feature_buffers");
+    for (std::size_t i = 0; i < depth.size(); ++i) depth3[3 * i] = depth3[3 * i + 1] = depth3[3 * i + 2] = depth[i];
+    image_io::writeExr(base + "_normal.exr", normal.data(), w, h);
+    image_io::writeExr(base + "_albedo.exr", albedo.data(), w, h);
+    image_io::writeExr(base + "_depth.exr", depth3.data(), w, h);
+  }
+}
+
 void PathTracerApp::executeResidentFilm(std::uint32_t steps) {
   const auto imageWidth = args.u32("width"), imageHeight = args.u32("height");
   const float configExposure = args.f32("exposure"), configGamma = args.f32("gamma");
@@ -643,6 +704,10 @@ void PathTracerApp::executeResidentFilm(std::uint32_t steps) {
         traceState->film.saveImages(fileName, step, configExposure, configGamma);   // hdr / step, as ever
         pt_log::info_("Saved images at step {}", step);
       });
+      if (denoise || saveFeatures) {
+        hostProcessing.waitForCompletion();   // the plain images first; the device calls below are made from this thread
+        saveDenoisedAndFeatures(fileName, step, configExposure, configGamma, devices.size() == 1 && !loadBalanceEnabled);
+      }
     }
 
     pt_trace::Range logging("log_stats");                                                                           // :765
@@ -781,6 +846,10 @@ void PathTracerApp::executeHostFilm(std::uint32_t steps) {
         }
       }
     });
+    if ((denoise || saveFeatures) && !uiServer && (step % saveInterval == 0 || step == steps)) {
+      hostProcessing.waitForCompletion();   // the host film of this step is complete and saved; device calls are made from this thread
+      saveDenoisedAndFeatures(fileName, step, state.exposure, state.gamma, false);
+    }
 
     auto loopEndTime = std::chrono::steady_clock::now();
     auto secs = std::chrono::duration<double>(loopEndTime - loopStartTime).count();

@@ -63,6 +63,11 @@ private:
   static pt_nif_memo_stats memoStatsRequest();
   void countMemo(const std::vector<pt_nif_memo_stats>& memo);
   void logMemo();
+  /// --denoise / --save-features: at a save, after the plain images are on disk (which stay as they are, byte for byte), write
+  /// <basename>_denoised.exr and _denoised<ext> (pt_denoise on device 0: the resident film when `filmOnDevice`, else the host
+  /// film / step as PT_DENOISE_HOST_IMAGE) and <basename>_normal.exr, _albedo.exr, _depth.exr (pt_feature_buffers).  Called
+  /// from the thread that drives the devices, with no host task running.
+  void saveDenoisedAndFeatures(const std::string& fileName, std::size_t step, float exposure, float gamma, bool filmOnDevice);
 
   OptionMap args;
   std::uint32_t samplesPerPixel = 0;
@@ -85,6 +90,8 @@ private:
   env_map::Image envMap;                ///< --env-map: the image every handle takes as its environment (empty: NIF or constant)
   std::int32_t envMapFilterMode = 1;    ///< --env-map-filter (PT_ENV_FILTER_*)
   bool hasCamera = false;
+  bool denoise = false, saveFeatures = false;   ///< --denoise, --save-features
+  pt_denoise_params denoiseParams{};            ///< --denoise-iterations / -sigma-colour / -sigma-normal / -sigma-depth over the library's defaults
   std::chrono::steady_clock::time_point renderStartTime;   // reset when the UI restarts the render (PathTracerApp.cpp:669)
 };
 

@@ -37,13 +37,16 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_gather_hdr", "pt_film_accumulate", "pt_tile_costs_enable", "pt_tile_costs", "pt_film_seed",
            "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats",
            "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats", "pt_set_scene", "pt_get_scene",
-           "pt_set_camera", "pt_get_camera", "pt_set_env_map", "pt_env_map_lookup"]
+           "pt_set_camera", "pt_get_camera", "pt_set_env_map", "pt_env_map_lookup", "pt_feature_buffers",
+           "pt_denoise_default_params", "pt_denoise"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
 ENV_FILTERS = {"nearest": ENV_FILTER_NEAREST, "bilinear": ENV_FILTER_BILINEAR}
 COMM_ID_BYTES = 128
 HDR_ACCUMULATORS, HDR_FILM = 0, 1
+DENOISE_HOST_IMAGE, DENOISE_ACCUMULATORS, DENOISE_FILM = 0, 1, 2
+DENOISE_SOURCES = {"accumulators": DENOISE_ACCUMULATORS, "film": DENOISE_FILM}
 
 
 class PtError(RuntimeError):
@@ -149,6 +152,37 @@ def builtin_scene():
     return out[:n.value].copy()
 
 
+class Features(C.Structure):
+    """pt_features (include/ptmi.h): host pointers of the first-hit feature buffers, any may be NULL."""
+    _fields_ = [("struct_size", C.c_uint32), ("object_id", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p),
+                ("albedo", C.c_void_p)]
+
+
+class DenoiseParams(C.Structure):
+    """pt_denoise_params (include/ptmi.h): the A-trous filter's settings; default_denoise_params() fills the defaults."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_colour", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("object_stop", C.c_int32), ("demodulate", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+assert C.sizeof(Features) == 40 and C.sizeof(DenoiseParams) == 28   # pt_features, pt_denoise_params
+
+
+def default_denoise_params(**overrides):
+    """The library's default DenoiseParams (pt_denoise_default_params; needs no GPU), with any field overridden by keyword."""
+    p = DenoiseParams()
+    rc = load_library().pt_denoise_default_params(C.byref(p))
+    if rc:
+        raise PtError(rc, "pt_denoise_default_params failed")
+    for k, v in overrides.items():
+        if k not in p.as_dict():
+            raise ValueError("unknown denoise parameter %r (known: %s)" % (k, sorted(p.as_dict())))
+        setattr(p, k, v)
+    return p
+
+
 class NifSharingStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("escaped", C.c_uint64), ("evaluations", C.c_uint64),
                 ("overflowed", C.c_uint64), ("table_slots", C.c_uint64), ("share_ms", C.c_double)]
@@ -234,6 +268,9 @@ def load_library(diag=False):
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
     L.pt_env_map_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pt_feature_buffers.argtypes = [C.c_void_p, C.POINTER(Features)]
+    L.pt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+    L.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_int32, C.c_void_p, C.c_void_p]
     if diag:
         L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
@@ -241,6 +278,7 @@ def load_library(diag=False):
         L.pt_diag_stamps.argtypes = [C.c_void_p, C.c_void_p]
         L.pt_diag_nif_clock.argtypes = [C.c_void_p, C.c_void_p]
         L.pt_diag_comm_self_exchange.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+        L.pt_diag_denoise_bench.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
     _libs[diag] = L
     return L
 
@@ -265,6 +303,7 @@ class Renderer:
         cfg = Config()
         cfg.struct_size = C.sizeof(Config)
         cfg.width, cfg.height = width, height
+        self._width, self._height = width, height
         cfg.max_path_length, cfg.roulette_depth = max_path_length, roulette_depth
         cfg.stop_prob, cfg.refractive_index = stop_prob, refractive_index
         cfg.aa_noise_type, cfg.sample_precision = aa_noise_type, sample_precision
@@ -449,6 +488,39 @@ class Renderer:
         cam = Camera()
         self._check(self._lib.pt_get_camera(self.handle, C.byref(cam)))
         return cam
+
+    def feature_buffers(self):
+        """First-hit feature buffers of every pixel (include/ptmi.h, pt_feature_buffers): a dict of numpy arrays, object_id
+        int32 [H, W] (-1: miss), depth float32 [H, W], normal float32 [H, W, 3] (world space, facing the camera) and albedo
+        float32 [H, W, 3] (B, G, R).  The centre ray without AA noise or lens; needs init_render_settings, no worklist."""
+        shape = (self._height, self._width)
+        out = {"object_id": np.empty(shape, np.int32), "depth": np.empty(shape, np.float32),
+               "normal": np.empty(shape + (3,), np.float32), "albedo": np.empty(shape + (3,), np.float32)}
+        f = Features()
+        f.struct_size = C.sizeof(Features)
+        for k, a in out.items():
+            setattr(f, k, a.ctypes.data)
+        self._check(self._lib.pt_feature_buffers(self.handle, C.byref(f)))
+        return out
+
+    def denoise(self, image=None, source="film", **params):
+        """The edge-avoiding A-trous filter of include/ptmi.h (pt_denoise) on the device; returns float32 [H, W, 3] (B, G, R).
+        image: an [H, W, 3] B, G, R array to denoise; None: this handle's work items scattered into the frame, source "film"
+        (the resident film / film steps) or "accumulators" (mean radiance).  params: fields of DenoiseParams (iterations,
+        sigma_colour, sigma_normal, sigma_depth, object_stop, demodulate), the others at their defaults; or params=DenoiseParams."""
+        p = params.pop("params") if "params" in params else default_denoise_params(**params)
+        out = np.empty((self._height, self._width, 3), np.float32)
+        if image is not None:
+            image = np.ascontiguousarray(image, dtype=np.float32)
+            if image.shape != out.shape:
+                raise ValueError("image must have shape %r, got %r" % (out.shape, image.shape))
+            src, ptr = DENOISE_HOST_IMAGE, image.ctypes.data
+        else:
+            if source not in DENOISE_SOURCES:
+                raise ValueError("denoise source must be one of %s, got %r" % (sorted(DENOISE_SOURCES), source))
+            src, ptr = DENOISE_SOURCES[source], None
+        self._check(self._lib.pt_denoise(self.handle, C.byref(p), src, ptr, out.ctypes.data))
+        return out
 
     def export_hdr_device(self, device_ptr, n):
         self._check(self._lib.pt_export_hdr_device(self.handle, C.c_void_p(device_ptr), n))
