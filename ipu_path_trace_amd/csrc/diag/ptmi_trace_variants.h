@@ -21,7 +21,7 @@ static bool launch_trace_variant(pt_handle h, const ptd::TraceParams& P, const T
   else if (!strcmp(tk, "cut1")) hipLaunchKernelGGL(ptd::trace_kernel_opt<11>, grid, block, lds, st, P);    // timing only: primary phase alone
   else if (!strcmp(tk, "count")) {   // secondary-phase occupancy counters into the stamp buffer (pt_diag_stamps)
     if (!h->d_stamps) {
-      if (hipMalloc(reinterpret_cast<void**>(&h->d_stamps), 256 * 8) != hipSuccess) return false;
+      if (dev_alloc(h->d_stamps, 256) != hipSuccess) return false;
       (void)hipMemset(h->d_stamps, 0, 256 * 8);
     }
     ptd::TraceParams PC = P;

@@ -1,7 +1,12 @@
-// ptmi_context.h -- per-handle device state (pt_context), error helpers, trace-grid geometry
+// ptmi_context.h -- the owners of device and pinned memory, per-handle state (pt_context), error helpers, trace parameters
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h,
+// ptmi_denoise.h.
 #pragma once
+
+using ptplan::TraceGrid;
+using ptplan::trace_grid;
+using ptplan::item_divider;
 
 namespace {
 
@@ -38,6 +43,40 @@ float host_h2f(uint16_t h) {
 
 inline float host_hround(float f) { return host_h2f(host_f2h(f)); }
 
+// Move-only owner of `count` elements of device memory (DevBuf) or of pinned host memory (PinnedBuf).  It converts to T*, so
+// kernel arguments, parameter structs and pointer arithmetic read as with a raw pointer.  Every buffer of a handle is one of
+// these, a member of pt_context: deleting the handle frees them, and that is the only place (pt_destroy makes the device
+// current and drains the streams first).  release() gives the allocation up without freeing it.
+template <typename T, bool kPinned>
+class Buf {
+ public:
+  Buf() = default;
+  Buf(Buf&& o) noexcept : n_(o.n_), p_(o.release()) {}
+  Buf& operator=(Buf&& o) noexcept {   // (deletes the copy operations)
+    if (this != &o) { reset(); n_ = o.n_; p_ = o.release(); }
+    return *this;
+  }
+  ~Buf() { reset(); }
+  // frees what it held first; empty on failure
+  hipError_t alloc(size_t count) {
+    reset();
+    void* p = nullptr;
+    const hipError_t e = kPinned ? hipHostMalloc(&p, count * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, count * sizeof(T));
+    if (e == hipSuccess) { p_ = static_cast<T*>(p); n_ = count; }
+    return e;
+  }
+  void reset() { if (T* p = release()) (void)(kPinned ? hipHostFree(p) : hipFree(p)); }
+  T* release() { n_ = 0; return std::exchange(p_, nullptr); }
+  size_t count() const { return n_; }
+  operator T*() const { return p_; }
+
+ private:
+  size_t n_ = 0;
+  T* p_ = nullptr;
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinnedBuf = Buf<T, true>;
+
 struct HostLayer {
   uint32_t rows, cols;
   std::vector<uint16_t> kernel;  // [rows][cols]
@@ -57,11 +96,13 @@ struct pt_context {
   // worklist
   uint32_t n_items = 0;
   uint32_t capacity = 0;
-  ptd::TraceRecordDev* d_records = nullptr;
-  ptd::Accum acc{};
+  DevBuf<ptd::TraceRecordDev> d_records;
+  ptd::Accum acc{};                          // device-visible: raw pointers into the six owners below
+  DevBuf<uint32_t> d_acc_pix, d_acc_count, d_acc_length;
+  DevBuf<float> d_acc_r, d_acc_g, d_acc_b;
   uint32_t n_real = 0;                       // work items that are not padding (u < width and v < height: AccumulatedImage.cpp:66)
-  unsigned long long* d_counters = nullptr;  // [0] segments, [1] escaped or emitter paths, [2] real items (pt_setup), [3] emitter paths
-  unsigned long long* h_counters = nullptr;  // the same in pinned host memory: copied on the stream at the end of a step (no blocking hipMemcpy)
+  DevBuf<unsigned long long> d_counters;     // [0] segments, [1] escaped or emitter paths, [2] real items (pt_setup), [3] emitter paths
+  PinnedBuf<unsigned long long> h_counters;  // the same in pinned host memory: copied on the stream at the end of a step (no blocking hipMemcpy)
 
   // batch buffers, double-buffered: the trace kernel of batch b+1 runs on `trace_stream` while the NIF
   // kernel of batch b (MFMA-bound) runs on `stream`
@@ -79,13 +120,13 @@ struct pt_context {
   static constexpr uint64_t kBatchBytesPerPath = 2 * (1 + 12 + 24 + 16 + 48);
   uint32_t trace_blocks = 1536;
   struct BatchBuffers {
-    float *q_u = nullptr, *q_v = nullptr, *q_tr = nullptr, *q_tg = nullptr, *q_tb = nullptr;
-    uint32_t* q_path = nullptr;
-    uint4* survivors = nullptr;        // primary-phase notes of the trace kernel, one region per trace workgroup
-    float4* states = nullptr;          // path states after the first shading, three planes of queue_cap float4
-    uint32_t* region_count = nullptr;
-    uint8_t* plen = nullptr;
-    float *rad_r = nullptr, *rad_g = nullptr, *rad_b = nullptr;
+    DevBuf<float> q_u, q_v, q_tr, q_tg, q_tb;
+    DevBuf<uint32_t> q_path;
+    DevBuf<uint4> survivors;           // primary-phase notes of the trace kernel, one region per trace workgroup
+    DevBuf<float4> states;             // path states after the first shading, three planes of queue_cap float4
+    DevBuf<uint32_t> region_count;
+    DevBuf<uint8_t> plen;
+    DevBuf<float> rad_r, rad_g, rad_b;
     hipEvent_t traced = nullptr;       // trace kernel of the batch using this set has finished
     hipEvent_t accumulated = nullptr;  // accumulate kernel has consumed this set
     // geometry of the last batch whose NIF stage ran on this set (pt_calibrate_nif replays the larger one): 0 = none yet
@@ -118,7 +159,7 @@ struct pt_context {
   float env_rgb[3] = {0, 0, 0};
   // HDR environment map (pt_set_env_map, pt_envmap.h): the third kind; the last of the three calls wins
   bool env_map = false;
-  float4* d_env_texels = nullptr;    // [env_h][env_w] (B, G, R, 0), row-major
+  DevBuf<float4> d_env_texels;       // [env_h][env_w] (B, G, R, 0), row-major
   uint32_t env_w = 0, env_h = 0;
   int32_t env_filter = 0;
   bool nif_valid = false;
@@ -128,23 +169,19 @@ struct pt_context {
   bool nif_f32 = false;
   struct F32Layer { size_t w_off, b_off; uint32_t k_act, k_in, ldw, relu, half_out, cast_half; };
   std::vector<F32Layer> f32_layers;
-  float* d_f32_weights = nullptr;
-  float* d_f32_act[2] = {nullptr, nullptr};
-  float* d_f32_feat = nullptr;
+  DevBuf<float> d_f32_weights, d_f32_act[2], d_f32_feat;
   uint32_t f32_chunk = 0, f32_lda = 0, f32_ldf = 0;
-  float4* d_head_partial = nullptr;   // fused head: [2 FB][chunk samples] partial sums
-  float4* d_head_in = nullptr;        // head weights of the Fourier-feature inputs [4][E], if the head concatenates them
+  DevBuf<float4> d_head_partial;      // fused head: [2 FB][chunk samples] partial sums
+  DevBuf<float4> d_head_in;           // head weights of the Fourier-feature inputs [4][E], if the head concatenates them
   float head_bias[3] = {0, 0, 0};
   uint32_t head_piece_base = 0;
   ptd::NifParams nif{};
-  uint4* d_wpack = nullptr;
-  uint4* d_bpack = nullptr;
+  DevBuf<uint4> d_wpack, d_bpack;
   uint64_t nif_flops = 0;
   std::string nif_kernel;   // what launch_nif dispatched last (pt_nif_kernel_name): the bench line quotes the library, not a guess
   // layer-by-layer path of the wide networks (pt_nif_gemm.h): activation ping-pong and feature pieces of one chunk
-  uint4* d_gemm_act[2] = {nullptr, nullptr};
-  uint4* d_gemm_feat = nullptr;
-  uint32_t* d_tile_start = nullptr;
+  DevBuf<uint4> d_gemm_act[2], d_gemm_feat;
+  DevBuf<uint32_t> d_tile_start;
   uint32_t gemm_chunk = 0;   // 32-sample tiles per chunk (multiple of 8); 0 = path not set up
   // The layer-by-layer paths run the chunks of a queue round-robin on the NIF stream and on extra ones (chunk_stream):
   // chunks are independent, so one chunk's layer launch fills the CUs another's is draining (the ramp / drain / gap of a
@@ -155,25 +192,25 @@ struct pt_context {
   int chunk_sets = kChunkSets;                           // profiling build: PTMI_CHUNK_STREAMS lowers it for the A/B
   size_t gemm_act_set = 0, gemm_feat_set = 0, head_partial_set = 0;   // uint4 / uint4 / float4 elements per set
   size_t f32_act_set = 0, f32_feat_set = 0;                            // floats per set
-  unsigned long long* d_stamps = nullptr;   // profiling build: 256 phase stamps of the wide-NIF layer kernel
+  DevBuf<unsigned long long> d_stamps;      // profiling build: 256 phase stamps of the wide-NIF layer kernel
   int diag_fault_batch = -1;                // test build: batch whose NIF launch fails (pt_diag_inject_fault), -1 = none
 
   // exact sharing of NIF evaluations (pt_set_nif_sharing, pt_nif_share.h).  Nothing here survives a step: the table is
   // cleared at the start of every batch (PT_NIF_SHARE_BATCH) or step (PT_NIF_SHARE_STEP), the counts at every step.
   int32_t share_mode = 0;                    // requested: taken up by the next pt_path_trace
   int32_t share_mode_last = 0;               // what the last pt_path_trace ran with (0 also for a constant environment)
-  unsigned long long* d_share_keys = nullptr;
-  uint32_t* d_share_vals = nullptr;
+  DevBuf<unsigned long long> d_share_keys;
+  DevBuf<uint32_t> d_share_vals;
   uint32_t share_slots = 0;                  // table capacity, a power of two
   uint32_t share_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_share_capacity), 0 = sized from memory
-  uint32_t* d_share_owner[2] = {nullptr, nullptr};   // per batch-buffer set: [queue_cap] store index of every entry's owner
+  DevBuf<uint32_t> d_share_owner[2];                 // per batch-buffer set: [queue_cap] store index of every entry's owner
   // the step's distinct queues and their decoded BGR, region-structured: batch b's at store index (b or b & 1) x queue_cap
-  float *d_share_u = nullptr, *d_share_v = nullptr, *d_share_bgr = nullptr;
+  DevBuf<float> d_share_u, d_share_v, d_share_bgr;
   size_t share_regions = 0;
-  uint32_t* d_share_count = nullptr;         // [batch] distinct-queue length
-  unsigned long long* d_share_over = nullptr;
-  uint32_t* h_share_count = nullptr;         // pinned copies, written at the end of the step on `stream`
-  unsigned long long* h_share_over = nullptr;
+  DevBuf<uint32_t> d_share_count;            // [batch] distinct-queue length
+  DevBuf<unsigned long long> d_share_over;
+  PinnedBuf<uint32_t> h_share_count;         // pinned copies, written at the end of the step on `stream`
+  PinnedBuf<unsigned long long> h_share_over;
   size_t share_count_cap = 0;
   uint64_t share_evals = 0, share_overflowed = 0;
   double share_ms = 0;
@@ -181,13 +218,13 @@ struct pt_context {
   // persistent memo of decoded NIF values (pt_set_nif_memo, pt_nif_memo.h).  Unlike the sharing table it outlives the step:
   // it is cleared at allocation, on a new generation (pt_upload_nif, pt_clear_nif_memo, a failed pt_path_trace) and by the
   // retain pass.  With the memo on, every step uses the step-scope store above (d_share_u / _v / _bgr, d_share_count).
-  ptd::MemoSlot* d_memo = nullptr;
+  DevBuf<ptd::MemoSlot> d_memo;
   uint32_t memo_slots = 0;                   // table capacity, a power of two; 0 = memo off
-  ptd::MemoSlot* d_memo_list = nullptr;      // retain list, memo_slots / 2 entries
-  uint32_t* d_memo_slot = nullptr;           // [store index]: slot the entry is published into (memo_slot_regions x queue_cap)
+  DevBuf<ptd::MemoSlot> d_memo_list;         // retain list, memo_slots / 2 entries
+  DevBuf<uint32_t> d_memo_slot;              // [store index]: slot the entry is published into (memo_slot_regions x queue_cap)
   size_t memo_slot_regions = 0;
-  unsigned long long* d_memo_ctr = nullptr;  // ptd::kMemoCounters counters of the memo passes
-  unsigned long long* h_memo_ctr = nullptr;  // pinned copy, written at the end of the step on `stream` (the step's one wait)
+  DevBuf<unsigned long long> d_memo_ctr;     // ptd::kMemoCounters counters of the memo passes
+  PinnedBuf<unsigned long long> h_memo_ctr;  // pinned copy, written at the end of the step on `stream` (the step's one wait)
   bool memo_clear = false;                   // clear the table before the next lookup
   uint32_t memo_step = 0;                    // stamp of the last step that ran the memo passes
   bool memo_ran = false;                     // the last pt_path_trace ran them
@@ -198,19 +235,19 @@ struct pt_context {
   // host time a step of a small image should not pay (BASELINE configs[0] is one millisecond of device work per step).
   pt_stats stats{};
   std::vector<hipEvent_t> events;
-  struct StageSpan { size_t a, b; int kind; };   // event pair around one stage of one batch: 0 trace, 1 NIF, 2 accumulate, 3 NIF sharing, 4 NIF memo
+  enum SpanKind { kSpanNone = -1, kSpanTrace, kSpanNif, kSpanAccumulate, kSpanShare, kSpanMemo };
+  struct StageSpan { size_t a, b; int kind; };   // event pair (indices into `events`) around one stage of one batch
   std::vector<StageSpan> spans;
   size_t e_begin_i = 0, e_end_i = 0;
   bool spans_pending = false;
 
   // scratch for the standalone entry points
-  void* d_scratch = nullptr;
-  size_t scratch_bytes = 0;
+  DevBuf<char> d_scratch;   // grows on demand (ensure_scratch)
 
   // first-hit feature cache and the denoiser's dense frames (pt_feature_buffers / pt_denoise; pt_features.h, pt_denoise.h):
-  // allocated on first use, width x height float4 each (64 bytes per pixel in all), freed by pt_destroy
-  float4* d_feat[2] = {nullptr, nullptr};        // f0 = (normal, depth), f1 = (albedo BGR, object index bits)
-  float4* d_dn_colour[2] = {nullptr, nullptr};   // colour ping-pong
+  // allocated on first use, width x height float4 each (64 bytes per pixel in all)
+  DevBuf<float4> d_feat[2];        // f0 = (normal, depth), f1 = (albedo BGR, object index bits)
+  DevBuf<float4> d_dn_colour[2];   // colour ping-pong
   uint64_t feature_gen = 1;                      // bumped by pt_set_scene, pt_set_camera, pt_set_render_settings
   uint64_t feature_cached_gen = 0;               // generation d_feat holds (0: none)
   // A-trous iterations whose step is at most this stage their taps in LDS, the others read global memory (measured:
@@ -225,15 +262,14 @@ struct pt_context {
   std::atomic<bool> comm_abort_req{false};   // pt_comm_abort from another thread: the polling loops see it and abort
   uint32_t comm_timeout_ms = 120000;         // deadline of every communicator operation (pt_comm_set_timeout)
   size_t comm_slot_agreed = 0;               // slot_items value every rank of the communicator is known to use
-  long long* d_slot_check = nullptr;         // {slot, -slot} for the agreement all-reduce
-  float* d_film = nullptr;         // resident film: [capacity][3] BGR, sum over steps of the per-step means
+  DevBuf<long long> d_slot_check;            // {slot, -slot} for the agreement all-reduce
+  DevBuf<float> d_film;            // resident film: [capacity][3] BGR, sum over steps of the per-step means
   ptd::TileGrid tiles{};           // per-tile path-length sums for the balancer (pt_tile_costs_enable), n_tiles = 0: off
-  unsigned long long* d_tile_tmp = nullptr;   // tracked sums + current accumulators, staged for the copy to the host
+  DevBuf<unsigned long long> d_tile_cost;     // owns tiles.cost (the struct is device-visible: it keeps the raw pointer)
+  DevBuf<unsigned long long> d_tile_tmp;      // tracked sums + current accumulators, staged for the copy to the host
   uint32_t film_steps = 0;
-  float* d_hdr_stage = nullptr;    // this rank's tile: [slot_items][3] mean BGR, zero padded
-  size_t hdr_stage_floats = 0;
-  float* d_hdr_gather = nullptr;   // root only: [world][slot_items][3]
-  size_t hdr_gather_floats = 0;
+  DevBuf<float> d_hdr_stage;       // this rank's tile: [slot_items][3] mean BGR, zero padded
+  DevBuf<float> d_hdr_gather;      // root only: [world][slot_items][3]
 };
 
 namespace {
@@ -260,20 +296,17 @@ int fail(pt_handle h, int code, const std::string& msg) {
   return code;
 }
 
-template <typename T>
-hipError_t dev_alloc(T** p, size_t count) {
-  return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-}
+// (a name for Buf::alloc that an error message quotes: PT_HIP(dev_alloc(h->d_film, n)) reads "dev_alloc(h->d_film, n): ...")
+template <typename T, bool kPinned>
+hipError_t dev_alloc(Buf<T, kPinned>& b, size_t count) { return b.alloc(count); }
 
 int ensure_scratch(pt_handle h, size_t bytes) {
-  if (bytes <= h->scratch_bytes) return PT_OK;
-  if (h->d_scratch) PT_HIP(hipFree(h->d_scratch));
-  h->d_scratch = nullptr;
-  h->scratch_bytes = 0;
-  PT_HIP(hipMalloc(&h->d_scratch, bytes));
-  h->scratch_bytes = bytes;
+  if (bytes <= h->d_scratch.count()) return PT_OK;
+  PT_HIP(dev_alloc(h->d_scratch, bytes));
   return PT_OK;
 }
+template <typename T>
+T* scratch_as(pt_handle h) { return reinterpret_cast<T*>(static_cast<char*>(h->d_scratch)); }
 
 // The built-in scene (src/codelets/codelets.cpp:111-144) as a pt_scene_object table: ONE source, the kernels' compile-time
 // table pt_trace.h::scene_const.  A disc's normal (0, 1, 0) is already normalised (n / sqrtf(dot(n, n)) leaves it as it is).
@@ -326,17 +359,6 @@ void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, con
   }
 }
 
-// Round-up reciprocal of the work-item count: (x * magic) >> shift == x / n for every x < 2^31 (Granlund & Montgomery: with
-// s = ceil(log2 n) and magic = floor(2^(31+s) / n) + 1 the error magic * n - 2^(31+s) lies in (0, 2^s], so the product's excess
-// over x / n stays below 1 / n).  The batch size keeps path indices below 2^31 (pt_create).
-void item_divider(uint32_t n, uint32_t& magic, uint32_t& shift) {
-  uint32_t s = 0;
-  while ((1ull << s) < n) ++s;
-  const uint64_t m = ((1ull << (31 + s)) / n) + 1ull;
-  magic = (uint32_t)m;     // < 2^32: n > 2^(s-1)
-  shift = 31 + s;
-}
-
 void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   memset(&P, 0, sizeof(P));
   const ptcamera::Basis& cb = h->camera_basis;
@@ -387,23 +409,6 @@ void bind_batch(ptd::TraceParams& P, const pt_context::BatchBuffers& B) {
   P.states = B.states;
   P.plen = B.plen;
   P.rad_r = B.rad_r; P.rad_g = B.rad_g; P.rad_b = B.rad_b;
-}
-
-// Trace-grid geometry for a batch of `total` paths.
-struct TraceGrid {
-  uint32_t blocks, n_waves, region_cap;
-};
-// `cap` = pt_context::trace_blocks: the workgroups of the persistent trace kernel that are resident at once (pt_create).
-TraceGrid trace_grid(uint32_t total, uint32_t cap) {
-  const uint32_t n_chunks = (total + 63u) / 64u;
-  uint32_t blocks = (n_chunks + 3u) / 4u;
-  if (blocks > cap) blocks = cap;
-  if (blocks == 0) blocks = 1;
-  TraceGrid g;
-  g.blocks = blocks;
-  g.n_waves = blocks * 4u;
-  g.region_cap = 4u * ((n_chunks + g.n_waves - 1u) / g.n_waves) * 64u;
-  return g;
 }
 
 }  // namespace

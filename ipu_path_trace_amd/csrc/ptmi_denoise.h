@@ -1,16 +1,16 @@
 // ptmi_denoise.h -- host side of pt_feature_buffers and pt_denoise (include/ptmi.h): the feature cache, the dense frames and the
-// A-trous iterations.  Part of the one translation unit ptmi.hip, included after ptmi_film_comm.h.
+// A-trous iterations.  Part of the one translation unit ptmi.hip, included last, after ptmi_film_comm.h.
 #pragma once
 
 namespace {
 
 // Allocate `count` frames of width x height float4 into p[0 .. count) or none of them.
-int alloc_frames(pt_handle h, float4** p, int count, const char* what) {
+int alloc_frames(pt_handle h, DevBuf<float4>* p, int count, const char* what) {
   const size_t px = (size_t)h->cfg.width * h->cfg.height;
   for (int i = 0; i < count; ++i) {
-    const hipError_t e = dev_alloc(&p[i], px);
+    const hipError_t e = dev_alloc(p[i], px);
     if (e != hipSuccess) {
-      for (int j = 0; j <= i; ++j) { (void)hipFree(p[j]); p[j] = nullptr; }
+      for (int j = 0; j < i; ++j) p[j].reset();
       return fail(h, hip_status(e), std::string(what) + ": allocating " + std::to_string(px * sizeof(float4)) + " bytes: " + hipGetErrorString(e));
     }
   }
@@ -146,7 +146,7 @@ int pt_denoise(pt_handle h, const pt_denoise_params* params, int32_t source, con
   }
   const size_t px = (size_t)h->cfg.width * h->cfg.height;
   if (int rc = ensure_scratch(h, px * 12)) return rc;
-  float* d_img = static_cast<float*>(h->d_scratch);
+  float* d_img = scratch_as<float>(h);
   const uint32_t n = (uint32_t)px, blocks = (n + 255) / 256;
   // whatever fails below, no copy from or to the caller's buffers is left pending when the call returns
   auto run = [&]() -> int {

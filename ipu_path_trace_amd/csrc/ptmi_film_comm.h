@@ -1,6 +1,7 @@
 // ptmi_film_comm.h -- resident film, per-tile costs and the RCCL hand-off of HDR tiles (entry points of include/ptmi.h)
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h,
+// ptmi_denoise.h.
 #pragma once
 
 // ---- multi-GPU film hand-off over RCCL --------------------------------------------------------------------------
@@ -258,7 +259,7 @@ static int comm_make_config(ncclConfig_t& cfg, std::string& err) {
 }
 
 static int comm_local_buffers(pt_handle h) {
-  if (!h->d_slot_check) PT_HIP(dev_alloc(&h->d_slot_check, 2));
+  if (!h->d_slot_check) PT_HIP(dev_alloc(h->d_slot_check, 2));
   return PT_OK;
 }
 
@@ -366,7 +367,7 @@ int pt_film_accumulate(pt_handle h) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   PT_HIP(hipSetDevice(h->cfg.device));
   if (!h->d_film) {
-    PT_HIP(dev_alloc(&h->d_film, (size_t)h->capacity * 3));
+    PT_HIP(dev_alloc(h->d_film, (size_t)h->capacity * 3));
     PT_HIP(hipMemsetAsync(h->d_film, 0, (size_t)h->capacity * 12, h->stream));
   }
   if (h->n_items) {
@@ -382,7 +383,7 @@ int pt_film_seed(pt_handle h, const float* host_bgr, size_t n) {
   if (n != h->n_items || (!host_bgr && n)) return fail(h, PT_ERR_INVALID_ARGUMENT, "film seed must cover exactly the current work items");
   PT_HIP(hipSetDevice(h->cfg.device));
   if (!h->d_film) {
-    PT_HIP(dev_alloc(&h->d_film, (size_t)h->capacity * 3));
+    PT_HIP(dev_alloc(h->d_film, (size_t)h->capacity * 3));
     PT_HIP(hipMemsetAsync(h->d_film, 0, (size_t)h->capacity * 12, h->stream));
   }
   if (n) PT_HIP(hipMemcpyAsync(h->d_film, host_bgr, n * 12, hipMemcpyHostToDevice, h->stream));
@@ -397,15 +398,11 @@ int pt_tile_costs_enable(pt_handle h, uint32_t tile_w, uint32_t tile_h) {
   const uint32_t tx = (h->cfg.width + tile_w - 1) / tile_w, ty = (h->cfg.height + tile_h - 1) / tile_h;
   const uint32_t n = tx * ty;
   PT_HIP(hipStreamSynchronize(h->stream));
-  if (h->tiles.cost) PT_HIP(hipFree(h->tiles.cost));
-  if (h->d_tile_tmp) PT_HIP(hipFree(h->d_tile_tmp));
-  h->tiles = ptd::TileGrid{};
-  h->d_tile_tmp = nullptr;
-  unsigned long long* cost = nullptr;
-  PT_HIP(dev_alloc(&cost, n));
-  PT_HIP(dev_alloc(&h->d_tile_tmp, n));
-  PT_HIP(hipMemsetAsync(cost, 0, (size_t)n * 8, h->stream));
-  h->tiles.tile_w = tile_w; h->tiles.tile_h = tile_h; h->tiles.tiles_x = tx; h->tiles.n_tiles = n; h->tiles.cost = cost;
+  h->tiles = ptd::TileGrid{};   // off until both buffers are there
+  PT_HIP(dev_alloc(h->d_tile_cost, n));
+  PT_HIP(dev_alloc(h->d_tile_tmp, n));
+  PT_HIP(hipMemsetAsync(h->d_tile_cost, 0, (size_t)n * 8, h->stream));
+  h->tiles = ptd::TileGrid{tile_w, tile_h, tx, n, h->d_tile_cost};
   return PT_OK;
 }
 
@@ -438,21 +435,11 @@ int pt_gather_hdr(pt_handle h, int32_t source, size_t slot_items, float* root_ho
   if (slot_items * 3 >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "tile too large");
   PT_HIP(hipSetDevice(h->cfg.device));
   const size_t floats = slot_items * 3;
-  if (h->hdr_stage_floats < floats) {
-    if (h->d_hdr_stage) PT_HIP(hipFree(h->d_hdr_stage));
-    h->d_hdr_stage = nullptr; h->hdr_stage_floats = 0;
-    PT_HIP(dev_alloc(&h->d_hdr_stage, floats));
-    h->hdr_stage_floats = floats;
-  }
+  if (h->d_hdr_stage.count() < floats) PT_HIP(dev_alloc(h->d_hdr_stage, floats));
   const bool root = h->comm_rank == 0;
   const size_t world = (size_t)h->comm_world;
   const bool exchange = h->comm != nullptr;   // also at world size 1: the same calls (slot all-reduce, grouped receives -- none --, polled waits) as for N ranks
-  if (root && exchange && h->hdr_gather_floats < world * floats) {
-    if (h->d_hdr_gather) PT_HIP(hipFree(h->d_hdr_gather));
-    h->d_hdr_gather = nullptr; h->hdr_gather_floats = 0;
-    PT_HIP(dev_alloc(&h->d_hdr_gather, world * floats));
-    h->hdr_gather_floats = world * floats;
-  }
+  if (root && exchange && h->d_hdr_gather.count() < world * floats) PT_HIP(dev_alloc(h->d_hdr_gather, world * floats));
   if (h->n_items < slot_items)
     PT_HIP(hipMemsetAsync(h->d_hdr_stage + 3 * (size_t)h->n_items, 0, (slot_items - h->n_items) * 12, h->stream));
   if (h->n_items) {

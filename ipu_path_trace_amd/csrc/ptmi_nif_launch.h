@@ -1,9 +1,36 @@
-// ptmi_nif_launch.h -- launchers of the NIF kernels: fused (pt_nif.h), layer by layer (pt_nif_gemm.h), float32 (pt_nif_f32.h)
+// ptmi_nif_launch.h -- the two bindings of a NIF queue, the launchers of the NIF kernels: fused (pt_nif.h), layer by layer
+// (pt_nif_gemm.h), float32 (pt_nif_f32.h), and the event allocator of a step
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h,
+// ptmi_denoise.h.
 #pragma once
 
 namespace {
+
+// ---- the queue fields of a NifParams, in the two forms the kernels take.  Nothing else assigns them.
+// Per path: the region-structured queue the trace kernel wrote into a set of batch buffers, radiance out per path.
+void bind_path_queue(ptd::NifParams& N, const pt_context::BatchBuffers& B, uint32_t n_regions, uint32_t region_cap) {
+  N.q_u = B.q_u; N.q_v = B.q_v; N.q_tr = B.q_tr; N.q_tg = B.q_tg; N.q_tb = B.q_tb; N.q_path = B.q_path;
+  N.region_count = B.region_count;
+  N.n_regions = n_regions;
+  N.region_cap = region_cap;
+  N.rad_r = B.rad_r; N.rad_g = B.rad_g; N.rad_b = B.rad_b;
+  N.out_bgr = nullptr;
+}
+// Dense: one region of *count <= cap lookups (u, v), no throughput and no path, decoded BGR [slot][3] out.
+void bind_dense_queue(ptd::NifParams& N, const float* u, const float* v, const uint32_t* count, uint32_t cap, float* out_bgr) {
+  N.q_u = u; N.q_v = v;
+  N.q_tr = N.q_tg = N.q_tb = nullptr; N.q_path = nullptr;
+  N.region_count = count;
+  N.n_regions = 1;
+  N.region_cap = cap;
+  N.rad_r = N.rad_g = N.rad_b = nullptr;
+  N.out_bgr = out_bgr;
+}
+// ... the distinct queue of batch `batch` in the step store of NIF sharing and the memo, at store index `base`
+void bind_store_queue(pt_handle h, ptd::NifParams& N, uint32_t batch, uint32_t base, uint32_t cap) {
+  bind_dense_queue(N, h->d_share_u + base, h->d_share_v + base, h->d_share_count + batch, cap, h->d_share_bgr + 3 * (size_t)base);
+}
 
 // Dynamic-LDS opt-in of a kernel, once per device (one bit per device: the host app drives devices from threads).
 int set_dynamic_lds(pt_handle h, const void* fn, int bytes, std::atomic<unsigned long long>& done) {
@@ -376,17 +403,6 @@ int launch_nif(pt_handle h, const ptd::NifParams& N, int blocks) {
   return fail(h, PT_ERR_UNSUPPORTED_MODEL, "unsupported embedding dimension");
 }
 
-void free_batch_buffers(pt_handle h) {
-  for (auto& B : h->bb) {
-    (void)hipFree(B.q_u); (void)hipFree(B.q_v); (void)hipFree(B.q_tr); (void)hipFree(B.q_tg); (void)hipFree(B.q_tb);
-    (void)hipFree(B.q_path); (void)hipFree(B.survivors); (void)hipFree(B.states); (void)hipFree(B.region_count); (void)hipFree(B.plen);
-    (void)hipFree(B.rad_r); (void)hipFree(B.rad_g); (void)hipFree(B.rad_b);
-    if (B.traced) (void)hipEventDestroy(B.traced);
-    if (B.accumulated) (void)hipEventDestroy(B.accumulated);
-    B = pt_context::BatchBuffers();
-  }
-}
-
 hipEvent_t get_event(pt_handle h, size_t i) {
   while (h->events.size() <= i) {
     hipEvent_t e = nullptr;
@@ -395,5 +411,32 @@ hipEvent_t get_event(pt_handle h, size_t i) {
   }
   return h->events[i];
 }
+
+// The events of one step, handed out in order from h->events: created on first use, reused by every later step.
+struct StepEvents {
+  pt_handle h;
+  size_t next = 0;
+  // The next event, recorded on stream `s`; `index`: where it lies in h->events.
+  int record(hipStream_t s, hipEvent_t& e, size_t& index) {
+    e = get_event(h, next);
+    if (!e) return fail(h, PT_ERR_HIP, "hipEventCreate failed");
+    index = next++;
+    PT_HIP(hipEventRecord(e, s));
+    return PT_OK;
+  }
+  // A timed stage on stream `s`: a begin event, the body, an end event (also into *end, if given), and the pair as a span of
+  // `kind` (kSpanNone: none).  A failing body ends the stage there.
+  template <class F>
+  int timed(hipStream_t s, int kind, F body, hipEvent_t* end = nullptr) {
+    size_t a = 0, b = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (int rc = record(s, e0, a)) return rc;
+    if (int rc = body()) return rc;
+    if (int rc = record(s, e1, b)) return rc;
+    if (kind != pt_context::kSpanNone) h->spans.push_back({a, b, kind});
+    if (end) *end = e1;
+    return PT_OK;
+  }
+};
 
 }  // namespace

@@ -220,6 +220,41 @@ def test_failed_step_starts_a_new_generation(ptmi_lib):
     assert nxt["generation"] == after["generation"] and nxt["served"] == 0
 
 
+def test_calibrate_after_a_memo_step_leaves_the_next_step_alone(ptmi_lib):
+    """pt_calibrate_nif after a step with the memo replays the distinct queue of the step's largest batch out of the step store:
+    it reports that queue's length and a time, and the step after it equals the one of a handle that never calibrated --
+    records and memo statistics (all but memo_ms, a device time).  6 iterations at 2 per batch are dealt 1 + 2 + 2 + 1, so the
+    replayed batch is the third, in store region 2.  The forced memo (test build hook) has 2^16 slots: more than twice the
+    13,824 paths of a step, so no key overflows and every count is decided by the keys alone."""
+    P, layers = ptmi_lib, nif_assets.synthetic_nif()
+    W = H = 48
+
+    def two_steps(calibrate):
+        r = P.Renderer(W, H, max_path_length=6, iterations_per_batch=2, diag=True)
+        try:
+            r.init_nif_weights(layers, 12, META["max"], nif_assets.folded_mean())
+            r.init_render_settings(samples_per_step=6)
+            assert P.load_library(diag=True).pt_diag_set_nif_memo_slots(r.handle, 1 << 16) == 0
+            rec = P.worklist(W, H)
+            r.setup(rec)
+            r.path_trace()
+            first = r.nif_memo_stats()
+            if calibrate:
+                ms, evals = r.calibrate_nif(2)
+                assert 0 < evals <= first["evaluations"] and ms > 0
+            r.path_trace()
+            second = r.nif_memo_stats()
+            r.read_results(rec)
+            return rec.tobytes(), [{k: v for k, v in m.items() if k != "memo_ms"} for m in (first, second)]
+        finally:
+            r.close()
+
+    rec, stats = two_steps(True)
+    ref_rec, ref_stats = two_steps(False)
+    assert rec == ref_rec and stats == ref_stats
+    assert stats[0]["enabled"] and stats[0]["slots"] == 1 << 16 and stats[0]["evaluations"] > 0 and stats[1]["served"] > 0
+
+
 def test_memo_with_each_sharing_mode(ptmi_lib):
     P, layers = ptmi_lib, nif_assets.synthetic_nif()
     off_rec, off_film, _, _ = _render(P, 160, 120, layers, steps=3)
