@@ -437,6 +437,80 @@ int pt_denoise_default_params(pt_denoise_params* p);     /* needs no handle and 
 int pt_denoise(pt_handle h, const pt_denoise_params* p /* NULL = defaults */, int32_t source,
                const float* host_bgr_in /* [h][w][3], PT_DENOISE_HOST_IMAGE only */, float* host_bgr_out /* [h][w][3] */);
 
+/* NIF trainer -- an EXTENSION: an HDR environment map in, a NIF out, on the device.  The reference sends its users to an external
+ * TensorFlow script ("Train your own Environment Lighting Network"); here the library makes its own assets from the map
+ * pt_set_env_map holds.  It runs beside the sampling loop on the handle's stream: no trace, NIF or accumulate kernel is involved
+ * and nothing a render produces moves.  Additive: PTMI_ABI_VERSION stays 5.  Everything is binary32 (the matrix products on
+ * v_mfma_f32_32x32x2_f32); mixed-precision training is not part of it.
+ * Model: layer_count ReLU layers of width hidden, the first on the 4 E Fourier features [sin u, sin v, cos u, cos v] x E
+ * (E = embedding_dim), layer layer_count / 2 (when that is not layer 0) on concat(x, features), and a linear head of 3
+ * outputs: layer_count + 1 layers in pt_layer layout, kernel row-major [in][out].  A feature is half(sin(a)) / half(cos(a)) of
+ * a = half((coord - 1) 2 2^j), the sine correctly rounded to binary32 first: the oracle's orc_nif_encode bit for bit.
+ * pt_nif_train_begin needs a map on the handle (PT_ERR_NOT_READY otherwise).  With L = log(texel + eps) in log mode and the
+ * texel itself otherwise (binary64 from the binary32 texel and eps) it computes mean[c] = the per-channel mean of L, rounded to
+ * binary32, and max = the largest |L - mean[c]|, rounded to binary32, by per-block partial sums added in block order; a
+ * constant image (max = 0) is PT_ERR_INVALID_ARGUMENT.  It keeps the image as targets t = (L - mean) / max (binary64 from the
+ * binary32 mean and max, rounded once) in device memory of its own, 16 bytes per texel, so training goes on after the map is
+ * replaced.  It allocates master weights, Adam moments, activations and gradients for `batch` samples, draws the kernels
+ * Glorot-uniform -- w[i] = (2 x - 1) sqrt(6 / (in + out)), x = ((word 0 >> 8) + 1/2) 2^-24 of Philox4x32-10 block
+ * (i, layer, 0, "NIFW") keyed by seed -- and zeroes the biases.  PT_ERR_INVALID_ARGUMENT, pt_last_error naming the field, for a
+ * wrong struct_size, embedding_dim outside 1..15 (with 16 the argument of the highest
+ * frequency is half(-2 x 2^15) = -inf at u = 0 or v = 0 and its sine NaN), hidden not a multiple of 32 in 32..1024, layer_count outside 1..15, batch not
+ * a multiple of 256 in 256..2^20, a learning_rate, adam_eps or eps that is not finite or not positive (eps may be 0 without
+ * log_tone_map), a beta outside [0, 1), log_tone_map other than 0 or 1, and a NULL handle; these are checked in this order
+ * before anything touches a device, and with h == NULL the message is pt_last_error(NULL)'s.  After a rejection or
+ * PT_ERR_OUT_OF_MEMORY an earlier trainer of the handle stays in force; a successful begin replaces it.
+ * pt_nif_train_steps runs n Adam steps and returns the loss of the last one (before its update) in *last_loss (may be NULL).
+ * Step t = 0, 1, ... (counted since begin or pt_nif_train_set_weights):
+ *   sample i < batch: texel index floor(word 0 x H W / 2^32) of Philox block (i, t low, t high, "NIFB") keyed by seed,
+ *   r = index / W, c = index mod W, u = (float)r / (float)H, v = (float)c / (float)W (one binary32 division each: the map's
+ *   own mapping), target = t[r][c];
+ *   forward pass y, loss = mean over batch x 3 of (y - target)^2 (summed in binary64), backward pass, then for every weight
+ *   and bias  m = b1 m + (1 - b1) g,  v = b2 v + (1 - b2) g^2,  w -= lr (m c1) / (sqrt(v c2) + adam_eps),
+ *   c1 = 1 / (1 - b1^(t+1)), c2 = 1 / (1 - b2^(t+1)) (the bias-corrected Adam of Kingma and Ba).
+ * Deterministic: sums over the batch are per-slab partials added in slab order, there is no float atomic, and two runs with one
+ * seed on one device give the same bits.
+ * pt_nif_train_get_weights / _set_weights / _export / _gradients take an array of pt_layer whose kernel and bias point to CALLER
+ * buffers of rows x cols and cols elements (the getters write through them; bias may be NULL = not wanted, or for set_weights
+ * = zeros); n_layers must be layer_count + 1 and every rows, cols must be the model's -- pt_nif_train_layer_shapes fills rows,
+ * cols, dtype (PT_DTYPE_F32) and relu and touches no pointer.  get / set move the binary32 master weights (dtype PT_DTYPE_F32);
+ * set_weights resets the Adam moments and the step counter.  pt_nif_train_export gives the layers rounded to binary16 (round
+ * to nearest even) as PT_DTYPE_F16; a finite weight that rounds to infinity is PT_ERR_UNSUPPORTED_MODEL naming the layer.
+ * pt_nif_train_get_encode_params returns max and mean as computed; the -eps fold stays where it is, in the metadata loaders.
+ * pt_nif_train_install is pt_upload_nif of exactly the exported layers with max, the folded mean (float)(mean - eps) in log
+ * mode and log_tone_map: the NIF is the environment from then on, the memo generation advances and the map is dropped as any
+ * pt_upload_nif drops it; the trainer stays and can go on.  pt_nif_train_end frees everything, as does pt_destroy; every
+ * call but begin answers PT_ERR_NOT_READY without a trainer.
+ * Two kernel-level hooks: pt_nif_train_batch copies out the batch step `step` would draw (u, v [batch], target [batch][3]) and
+ * changes nothing; pt_nif_train_gradients runs the forward and backward pass on n <= batch caller samples with the current
+ * weights and returns the loss and every dW, db in binary32 -- neither weights, moments nor the step counter move. */
+typedef struct pt_nif_train_params {
+  uint32_t struct_size;          /* sizeof(pt_nif_train_params), set by the caller (pt_nif_train_default_params sets it) */
+  uint32_t embedding_dim;        /* 1..15, default 12 */
+  uint32_t hidden;               /* a multiple of 32 in 32..1024, default 320 */
+  uint32_t layer_count;          /* hidden ReLU layers, 1..15, default 6 */
+  uint32_t batch;                /* samples per step, a multiple of 256, default 65536 */
+  float learning_rate;           /* default 1e-3 */
+  float beta1, beta2;            /* default 0.9, 0.999 */
+  float adam_eps;                /* default 1e-7 */
+  uint64_t seed;                 /* default 1 */
+  int32_t log_tone_map;          /* default 1 */
+  float eps;                     /* default 1e-8 */
+} pt_nif_train_params;
+int pt_nif_train_default_params(pt_nif_train_params* p);     /* needs no handle and no device */
+int pt_nif_train_begin(pt_handle h, const pt_nif_train_params* p);
+int pt_nif_train_layer_shapes(pt_handle h, pt_layer* layers, uint32_t n_layers);
+int pt_nif_train_steps(pt_handle h, uint32_t n, float* last_loss);
+int pt_nif_train_get_weights(pt_handle h, pt_layer* layers, uint32_t n_layers);
+int pt_nif_train_set_weights(pt_handle h, const pt_layer* layers, uint32_t n_layers);
+int pt_nif_train_get_encode_params(pt_handle h, float* max, float mean[3]);
+int pt_nif_train_export(pt_handle h, pt_layer* layers, uint32_t n_layers);
+int pt_nif_train_install(pt_handle h);
+int pt_nif_train_end(pt_handle h);
+int pt_nif_train_batch(pt_handle h, uint64_t step, float* u, float* v, float* target);
+int pt_nif_train_gradients(pt_handle h, const float* u, const float* v, const float* target, uint32_t n, float* loss,
+                           pt_layer* gradients, uint32_t n_layers);
+
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);
  * the only exchange is the film: mean radiance per work item, BGR float32 [n][3] -- the value

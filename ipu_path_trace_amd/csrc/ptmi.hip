@@ -39,10 +39,12 @@
 #include "pt_envmap.h"
 #include "pt_features.h"
 #include "pt_denoise.h"
+#include "pt_nif_train.h"
 
 #include "ptmi_comm_worker.h"
 #include "ptmi_scene.h"
 #include "ptmi_camera.h"
+#include "ptmi_nif_train_check.h"
 #include "ptmi_step_plan.h"
 #include "ptmi_context.h"
 #include "ptmi_nif_pack.h"
@@ -1284,6 +1286,7 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
 
 #include "ptmi_film_comm.h"
 #include "ptmi_denoise.h"
+#include "ptmi_nif_train.h"
 
 extern "C" {
 

@@ -1,7 +1,7 @@
 // ptmi_context.h -- the owners of device and pinned memory, per-handle state (pt_context), error helpers, trace parameters
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
 // ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h,
-// ptmi_denoise.h.
+// ptmi_denoise.h, ptmi_nif_train.h.
 #pragma once
 
 using ptplan::TraceGrid;
@@ -82,6 +82,31 @@ struct HostLayer {
   std::vector<uint16_t> kernel;  // [rows][cols]
   std::vector<uint16_t> bias;    // [cols] or empty
   bool relu;
+};
+
+// Everything pt_nif_train_begin makes (ptmi_nif_train.h): parameters, the target image, master weights, Adam moments, the
+// per-layer input buffers and gradients.  One object, owned by the handle: pt_nif_train_end (or a new begin, or pt_destroy)
+// drops it and every DevBuf in it frees itself.
+struct NifTrainState {
+  pt_nif_train_params p{};
+  struct Layer { uint32_t rows, cols, relu; size_t w_off, b_off; };   // offsets into the parameter blob: kernel, then bias
+  std::vector<Layer> layers;
+  size_t n_params = 0;
+  uint32_t map_w = 0, map_h = 0, skip = 0;
+  float mean[3] = {0, 0, 0}, max = 0;
+  uint64_t step = 0;
+  DevBuf<float4> d_target;                  // [map_h][map_w] (t_b, t_g, t_r, 0)
+  DevBuf<float> d_w, d_g, d_m, d_v;         // parameter blob, its gradient, Adam moments
+  DevBuf<float> d_u, d_vv, d_t;             // the batch: u, v [batch], target [batch][3]
+  std::vector<DevBuf<float>> d_act;         // d_act[l]: input of layer l, [batch][rows_l]
+  DevBuf<float> d_y;                        // head output [batch][3]
+  DevBuf<float> d_dz[2];                    // gradient w.r.t. a layer's pre-activation, ping-pong, [batch][hidden]
+  DevBuf<float> d_partial;                  // [kTrainSlabs][largest rows x cols + cols]
+  size_t partial_stride = 0;
+  DevBuf<double> d_red;                     // kTrainStatBlocks x 3 partials of the statistics / the loss
+  DevBuf<float> d_enc;                      // mean0..2, max, then the loss
+  DevBuf<uint16_t> d_half;                  // the blob rounded to binary16 (export)
+  DevBuf<uint32_t> d_overflow;              // [layers]
 };
 
 }  // namespace
@@ -243,6 +268,9 @@ struct pt_context {
 
   // scratch for the standalone entry points
   DevBuf<char> d_scratch;   // grows on demand (ensure_scratch)
+
+  // NIF trainer (pt_nif_train_begin .. pt_nif_train_end, ptmi_nif_train.h): null without one
+  std::unique_ptr<NifTrainState> train;
 
   // first-hit feature cache and the denoiser's dense frames (pt_feature_buffers / pt_denoise; pt_features.h, pt_denoise.h):
   // allocated on first use, width x height float4 each (64 bytes per pixel in all)

@@ -3,6 +3,7 @@
 #include <iostream>
 #include <stdexcept>
 
+#include "NifTrainer.hpp"
 #include "PathTracerApp.hpp"
 #include "logging.hpp"
 
@@ -40,7 +41,8 @@ static OptionMap parseOptions(int argc, char** argv, const std::vector<OptionSpe
     }
     throw std::runtime_error("Show help");
   }
-  for (auto& s : specs) if (s.required && !vm.has(s.name)) throw std::runtime_error("the option '--" + s.name + "' is required but missing");
+  // --train-nif trains instead of rendering: it needs neither --outfile nor --assets
+  for (auto& s : specs) if (s.required && !vm.has(s.name) && !nif_train::requested(vm)) throw std::runtime_error("the option '--" + s.name + "' is required but missing");
   if (!vm.str("save-exe").empty() && !vm.str("load-exe").empty())
     throw std::logic_error("You can not set both save-exe and load-exe.");   // main.cpp:63-66
   return vm;
@@ -50,8 +52,13 @@ int main(int argc, char** argv) {
   try {
     PathTracerApp app;
     auto specs = PathTracerApp::addToolOptions();
+    nif_train::addOptions(specs);
     auto opts = parseOptions(argc, argv, specs);
     pt_log::setLevel(opts.str("log-level"));
+    if (nif_train::requested(opts)) {
+      nif_train::run(opts);
+      return EXIT_SUCCESS;
+    }
     app.init(opts);
     if (opts.flag("compile-only")) {
       // The reference builds and compiles its graph (validating options and the NIF on the way), optionally saves the

@@ -122,13 +122,16 @@ def write_ptnif(path, layers, embedding_dim):
                 f.write(np.ascontiguousarray(b, dtype=dt).tobytes())
 
 
-def write_metadata(path, meta=URBAN_ALLEY_META):
-    """nif_metadata.txt with the fields NifMetaData.cpp reads."""
+def write_metadata(path, meta=URBAN_ALLEY_META, name="synthetic"):
+    """nif_metadata.txt with the fields NifMetaData.cpp reads.  `meta` may be ptmi.NifTrainer.metadata(...): the trainer's
+    embedding, stack, max, unfolded mean, eps and log_tone_map (the loaders fold -eps into the mean)."""
+    meta = dict(meta, mean=[float(m) for m in meta["mean"]], max=float(meta["max"]), eps=float(meta["eps"]),
+                log_tone_map=bool(meta["log_tone_map"]))
     doc = {
         "embedding_dimension": meta["embedding_dimension"],
         "encode_params": {"eps": meta["eps"], "log_tone_map": meta["log_tone_map"], "max": meta["max"],
-                          "mean": meta["mean"], "transfer_function": "log"},
-        "name": "synthetic", "original_image_shape": meta["original_image_shape"],
+                          "mean": meta["mean"], "transfer_function": "log" if meta["log_tone_map"] else "linear"},
+        "name": name, "original_image_shape": meta["original_image_shape"],
         "train_command": ["train_nif.py", "--layer-count", str(meta["layer_count"]), "--layer-size",
                           str(meta["hidden_size"]), "--embedding-dimension", str(meta["embedding_dimension"])],
     }

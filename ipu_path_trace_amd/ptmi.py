@@ -38,7 +38,10 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats",
            "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats", "pt_set_scene", "pt_get_scene",
            "pt_set_camera", "pt_get_camera", "pt_set_env_map", "pt_env_map_lookup", "pt_feature_buffers",
-           "pt_denoise_default_params", "pt_denoise"]
+           "pt_denoise_default_params", "pt_denoise", "pt_nif_train_default_params", "pt_nif_train_begin",
+           "pt_nif_train_layer_shapes", "pt_nif_train_steps", "pt_nif_train_get_weights", "pt_nif_train_set_weights",
+           "pt_nif_train_get_encode_params", "pt_nif_train_export", "pt_nif_train_install", "pt_nif_train_end",
+           "pt_nif_train_batch", "pt_nif_train_gradients"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
@@ -183,6 +186,33 @@ def default_denoise_params(**overrides):
     return p
 
 
+class NifTrainParams(C.Structure):
+    """pt_nif_train_params (include/ptmi.h): model, batch, Adam constants, seed and encode mode of the NIF trainer;
+    default_nif_train_params() fills the defaults."""
+    _fields_ = [("struct_size", C.c_uint32), ("embedding_dim", C.c_uint32), ("hidden", C.c_uint32), ("layer_count", C.c_uint32),
+                ("batch", C.c_uint32), ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("adam_eps", C.c_float), ("seed", C.c_uint64), ("log_tone_map", C.c_int32), ("eps", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+assert C.sizeof(NifTrainParams) == 56   # pt_nif_train_params
+
+
+def default_nif_train_params(**overrides):
+    """The library's default NifTrainParams (pt_nif_train_default_params; needs no GPU), with any field overridden by keyword."""
+    p = NifTrainParams()
+    rc = load_library().pt_nif_train_default_params(C.byref(p))
+    if rc:
+        raise PtError(rc, "pt_nif_train_default_params failed")
+    for k, v in overrides.items():
+        if k not in p.as_dict():
+            raise ValueError("unknown NIF training parameter %r (known: %s)" % (k, sorted(p.as_dict())))
+        setattr(p, k, v)
+    return p
+
+
 class NifSharingStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("escaped", C.c_uint64), ("evaluations", C.c_uint64),
                 ("overflowed", C.c_uint64), ("table_slots", C.c_uint64), ("share_ms", C.c_double)]
@@ -271,6 +301,19 @@ def load_library(diag=False):
     L.pt_feature_buffers.argtypes = [C.c_void_p, C.POINTER(Features)]
     L.pt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
     L.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_int32, C.c_void_p, C.c_void_p]
+    L.pt_nif_train_default_params.argtypes = [C.POINTER(NifTrainParams)]
+    L.pt_nif_train_begin.argtypes = [C.c_void_p, C.POINTER(NifTrainParams)]
+    L.pt_nif_train_layer_shapes.argtypes = [C.c_void_p, C.POINTER(Layer), C.c_uint32]
+    L.pt_nif_train_steps.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+    L.pt_nif_train_get_weights.argtypes = [C.c_void_p, C.POINTER(Layer), C.c_uint32]
+    L.pt_nif_train_set_weights.argtypes = [C.c_void_p, C.POINTER(Layer), C.c_uint32]
+    L.pt_nif_train_get_encode_params.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pt_nif_train_export.argtypes = [C.c_void_p, C.POINTER(Layer), C.c_uint32]
+    L.pt_nif_train_install.argtypes = [C.c_void_p]
+    L.pt_nif_train_end.argtypes = [C.c_void_p]
+    L.pt_nif_train_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_nif_train_gradients.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float),
+                                         C.POINTER(Layer), C.c_uint32]
     if diag:
         L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
@@ -522,6 +565,22 @@ class Renderer:
         self._check(self._lib.pt_denoise(self.handle, C.byref(p), src, ptr, out.ctypes.data))
         return out
 
+    def train_nif(self, params=None, **overrides):
+        """Start training a NIF on the environment map this renderer holds (include/ptmi.h, pt_nif_train_begin): returns a
+        NifTrainer.  params: a NifTrainParams, or None for the library's defaults with any field overridden by keyword
+        (embedding_dim, hidden, layer_count, batch, learning_rate, beta1, beta2, adam_eps, seed, log_tone_map, eps).  A
+        renderer has one trainer at a time: a new one replaces the old."""
+        if params is None:
+            params = default_nif_train_params(**overrides)
+        elif overrides:
+            raise ValueError("give params or keyword overrides, not both")
+        self._check(self._lib.pt_nif_train_begin(self.handle, C.byref(params)))
+        old = getattr(self, "_trainer", None)
+        if old is not None:
+            old._r = None          # the handle's trainer is the new one: the old object must not end or drive it
+        self._trainer = NifTrainer(self, params)
+        return self._trainer
+
     def export_hdr_device(self, device_ptr, n):
         self._check(self._lib.pt_export_hdr_device(self.handle, C.c_void_p(device_ptr), n))
 
@@ -596,6 +655,116 @@ class Renderer:
         self._check(self._lib.pt_trace_paths(self.handle, u.ctypes.data, v.ctypes.data, s.ctypes.data, u.size,
                                              out.ctypes.data))
         return out
+
+
+class NifTrainer:
+    """The trainer of one Renderer (Renderer.train_nif).  Weights travel as [(kernel [in, out], bias [out], relu)] triples of
+    float32 arrays, the layout of nif_assets.synthetic_nif; export() gives the same in float16."""
+
+    def __init__(self, renderer, params):
+        self._r = renderer
+        self.params = params
+        self._loss = None
+        n = params.layer_count + 1
+        arr = (Layer * n)()
+        renderer._check(renderer._lib.pt_nif_train_layer_shapes(renderer.handle, arr, n))
+        self.shapes = [(arr[i].rows, arr[i].cols, bool(arr[i].relu)) for i in range(n)]
+
+    def _layers_out(self, dtype):
+        arr = (Layer * len(self.shapes))()
+        out = []
+        for i, (rows, cols, relu) in enumerate(self.shapes):
+            k, b = np.empty((rows, cols), dtype), np.empty(cols, dtype)
+            arr[i].rows, arr[i].cols, arr[i].kernel, arr[i].bias = rows, cols, k.ctypes.data, b.ctypes.data
+            out.append((k, b, relu))
+        return arr, out
+
+    def _call(self, fn, *args):
+        if self._r is None:
+            raise PtError(-5, "this NifTrainer is closed, or a later Renderer.train_nif() has replaced it")
+        self._r._check(getattr(self._r._lib, fn)(self._r.handle, *args))
+
+    def steps(self, n=1):
+        """n Adam steps; returns the loss of the last one (before its update)."""
+        loss = C.c_float()
+        self._call("pt_nif_train_steps", int(n), C.byref(loss))
+        if n:
+            self._loss = loss.value
+        return self._loss
+
+    def loss(self):
+        """The loss steps() returned last (None before the first step)."""
+        return self._loss
+
+    def weights(self):
+        arr, out = self._layers_out(np.float32)
+        self._call("pt_nif_train_get_weights", arr, len(out))
+        return out
+
+    def set_weights(self, layers):
+        """Replace the float32 master weights; resets the Adam moments and the step counter."""
+        arr = (Layer * len(layers))()
+        keep = []
+        for i, (k, b, relu) in enumerate(layers):
+            k = np.ascontiguousarray(k, dtype=np.float32)
+            keep.append(k)
+            arr[i].rows, arr[i].cols = k.shape
+            arr[i].kernel = k.ctypes.data
+            if b is not None:
+                b = np.ascontiguousarray(b, dtype=np.float32)
+                keep.append(b)
+                arr[i].bias = b.ctypes.data
+            arr[i].dtype, arr[i].relu = DTYPE_F32, int(bool(relu))
+        self._call("pt_nif_train_set_weights", arr, len(layers))
+
+    def encode_params(self):
+        """{"max", "mean" (as computed, not folded), "eps", "log_tone_map"}."""
+        mx, mean = C.c_float(), (C.c_float * 3)()
+        self._call("pt_nif_train_get_encode_params", C.byref(mx), mean)
+        return {"max": mx.value, "mean": [mean[0], mean[1], mean[2]], "eps": float(np.float32(self.params.eps)),
+                "log_tone_map": bool(self.params.log_tone_map)}
+
+    def metadata(self, image_shape):
+        """The dict nif_assets.write_metadata takes, for an image of shape (H, W)."""
+        enc = self.encode_params()
+        return {"embedding_dimension": self.params.embedding_dim, "hidden_size": self.params.hidden,
+                "layer_count": self.params.layer_count, "eps": enc["eps"], "log_tone_map": enc["log_tone_map"], "max": enc["max"],
+                "mean": enc["mean"], "original_image_shape": [int(image_shape[0]), int(image_shape[1]), 3]}
+
+    def export(self):
+        """The layers rounded to float16 (round to nearest even)."""
+        arr, out = self._layers_out(np.float16)
+        self._call("pt_nif_train_export", arr, len(out))
+        return out
+
+    def install(self):
+        """Make the exported NIF the renderer's environment (pt_upload_nif of export()); training can go on afterwards."""
+        self._call("pt_nif_train_install")
+
+    def batch(self, step):
+        """(u, v, target [batch, 3]) of the batch step `step` draws."""
+        n = self.params.batch
+        u, v, t = np.empty(n, np.float32), np.empty(n, np.float32), np.empty((n, 3), np.float32)
+        self._call("pt_nif_train_batch", int(step), u.ctypes.data, v.ctypes.data, t.ctypes.data)
+        return u, v, t
+
+    def gradients(self, u, v, target):
+        """(loss, [(dW, db, relu)]) of the current weights on the given samples; moves nothing."""
+        u = np.ascontiguousarray(u, dtype=np.float32).ravel()
+        v = np.ascontiguousarray(v, dtype=np.float32).ravel()
+        t = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 3)
+        if not (u.size == v.size == t.shape[0]):
+            raise ValueError("u, v and target must have the same number of samples")
+        arr, out = self._layers_out(np.float32)
+        loss = C.c_float()
+        self._call("pt_nif_train_gradients", u.ctypes.data, v.ctypes.data, t.ctypes.data, u.size, C.byref(loss), arr, len(out))
+        return loss.value, out
+
+    def close(self):
+        if self._r is not None and getattr(self._r, "handle", None):
+            self._call("pt_nif_train_end")
+            self._r._trainer = None
+        self._r = None
 
 
 def runtime_info(diag=False):
