@@ -441,7 +441,7 @@ int pt_denoise(pt_handle h, const pt_denoise_params* p /* NULL = defaults */, in
  * TensorFlow script ("Train your own Environment Lighting Network"); here the library makes its own assets from the map
  * pt_set_env_map holds.  It runs beside the sampling loop on the handle's stream: no trace, NIF or accumulate kernel is involved
  * and nothing a render produces moves.  Additive: PTMI_ABI_VERSION stays 5.  Everything is binary32 (the matrix products on
- * v_mfma_f32_32x32x2_f32); mixed-precision training is not part of it.
+ * v_mfma_f32_32x32x2_f32) unless pt_nif_train_set_precision asks for PT_NIF_TRAIN_MIXED_F16 (below).
  * Model: layer_count ReLU layers of width hidden, the first on the 4 E Fourier features [sin u, sin v, cos u, cos v] x E
  * (E = embedding_dim), layer layer_count / 2 (when that is not layer 0) on concat(x, features), and a linear head of 3
  * outputs: layer_count + 1 layers in pt_layer layout, kernel row-major [in][out].  A feature is half(sin(a)) / half(cos(a)) of
@@ -510,6 +510,56 @@ int pt_nif_train_end(pt_handle h);
 int pt_nif_train_batch(pt_handle h, uint64_t step, float* u, float* v, float* target);
 int pt_nif_train_gradients(pt_handle h, const float* u, const float* v, const float* target, uint32_t n, float* loss,
                            pt_layer* gradients, uint32_t n_layers);
+
+/* Mixed precision for the trainer -- opt-in: binary16 inputs to the matrix products (v_mfma_f32_32x32x16_f16, exact products,
+ * binary32 sums), a loss scale S, binary32 master weights.  A successful pt_nif_train_begin always starts in PT_NIF_TRAIN_F32,
+ * and a process that never calls pt_nif_train_set_precision runs exactly what it ran before this call existed.  Additive:
+ * PTMI_ABI_VERSION stays 5 and pt_nif_train_params stays as it is.
+ * pt_nif_train_set_precision may be called at any time between steps (PT_ERR_NOT_READY without a trainer).  It keeps the master
+ * weights, the Adam moments and applied_steps, allocates (mixed) or frees (f32) the half buffers, and resets S to loss_scale,
+ * good_steps and skipped_steps to 0; the step counter that draws the batches continues at applied_steps.  PT_ERR_INVALID_ARGUMENT,
+ * pt_last_error naming the field, in this order and before any device call: NULL struct, wrong struct_size, mode other than 0 or
+ * 1, loss_scale not a power of two in 1 .. 2^30, dynamic other than 0 or 1, growth_interval outside 1 .. 2^31, NULL handle (the
+ * message is pt_last_error(NULL)'s then).  After a rejection or PT_ERR_OUT_OF_MEMORY the previous mode stays in force.
+ * A mixed step:
+ *   weights: the masters w, b stay binary32; w16 = half(w) (round to nearest even) is refreshed by the Adam kernel and by
+ *   set_weights / set_precision; biases are used in binary32.
+ *   forward, hidden layer: z = the binary32-accumulated sum over the half inputs times w16, plus b in binary32; the stored
+ *   activation is a = half(max(z, 0)), one rounding; features are half values already.  The head gives y = sum + b in binary32,
+ *   not rounded.  loss = mean of (y - t)^2 summed in binary64, unscaled: what last_loss returns, also for a skipped step.
+ *   backward: head dZ = half((y - t) c), c = (float)(2 S / (3 n)); dW = X^T dZ and db = the column sums of dZ accumulate in
+ *   binary32 over the half values, in the 32 batch slabs, added in slab order; dZ below = half((dZ w16^T)[:, :cols below] (a > 0))
+ *   on the stored half activation; feature columns carry no gradient.
+ *   unscale: g = g_scaled (1 / S), exact.  If any element of any dW or db is not finite the step is SKIPPED: weights, w16 and
+ *   moments keep their bits, skipped_steps advances and, with dynamic, S halves (floor 1) and good_steps returns to 0.
+ *   Otherwise Adam applies as above with t + 1 = applied_steps + 1, applied_steps and good_steps advance and, with dynamic, S
+ *   doubles (cap 2^30) and good_steps returns to 0 when good_steps reaches growth_interval.
+ *   The batch drawn is that of step applied_steps + skipped_steps since begin / set_weights / set_precision: a skipped step
+ *   draws the next batch.  S, 1 / S, c, the counters and Adam's c1, c2 (binary64 on the device) live in a device control block
+ *   that one single-thread kernel updates per step; pt_nif_train_steps still waits once, at its end.  Deterministic as above.
+ * In mixed mode pt_nif_train_gradients runs this pass with the current S and returns the unscaled binary32 gradients (an
+ * overflow shows as non-finite values); S, counters, weights and moments do not move.  export / install are unchanged (the
+ * export equals w16 bit for bit); get_weights / set_weights move the masters, and set_weights also zeroes applied_steps and
+ * skipped_steps.  In PT_NIF_TRAIN_F32 pt_nif_train_get_precision_state reports loss_scale 1, good_steps 0, skipped_steps 0. */
+#define PT_NIF_TRAIN_F32        0
+#define PT_NIF_TRAIN_MIXED_F16  1
+typedef struct pt_nif_train_precision {
+  uint32_t struct_size;      /* sizeof(pt_nif_train_precision), set by the caller (pt_nif_train_default_precision sets it) */
+  int32_t  mode;             /* PT_NIF_TRAIN_F32 | PT_NIF_TRAIN_MIXED_F16, default PT_NIF_TRAIN_F32 */
+  float    loss_scale;       /* initial scale S, a power of two in 1 .. 2^30, default 65536 */
+  int32_t  dynamic;          /* 0 | 1, default 1 */
+  uint32_t growth_interval;  /* applied steps without overflow before S doubles, 1 .. 2^31, default 2000 */
+} pt_nif_train_precision;
+typedef struct pt_nif_train_precision_state {
+  uint32_t struct_size;      /* sizeof(pt_nif_train_precision_state), set by the caller */
+  int32_t  mode;
+  float    loss_scale;       /* the current S */
+  uint32_t good_steps;       /* applied steps since S last changed */
+  uint64_t applied_steps, skipped_steps;
+} pt_nif_train_precision_state;
+int pt_nif_train_default_precision(pt_nif_train_precision* p);          /* needs no handle and no device */
+int pt_nif_train_set_precision(pt_handle h, const pt_nif_train_precision* p);
+int pt_nif_train_get_precision_state(pt_handle h, pt_nif_train_precision_state* s);
 
 /* Multi-GPU film hand-off.  The path shards over pixels with no exchange of ray data (reference: one NIF
  * replica per IPU, "no inter-ipu exchange of ray data", PathTracerApp.cpp:205-252, shard_utils.cpp:28-38);

@@ -107,6 +107,16 @@ struct NifTrainState {
   DevBuf<float> d_enc;                      // mean0..2, max, then the loss
   DevBuf<uint16_t> d_half;                  // the blob rounded to binary16 (export)
   DevBuf<uint32_t> d_overflow;              // [layers]
+
+  // mixed precision (pt_nif_train_set_precision): everything below is empty in PT_NIF_TRAIN_F32, the mode begin starts in
+  pt_nif_train_precision prec{};            // the mode in force and its initial scale, dynamic, growth_interval
+  struct Layer16 { uint32_t ldx, ldw, ldt; size_t w16_off, w16t_off; };   // leading dimensions in halves: input, w16, w16^T
+  std::vector<Layer16> layers16;
+  std::vector<DevBuf<uint16_t>> d_act16;    // d_act16[l]: input of layer l, [batch][ldx_l], padding zero
+  DevBuf<uint16_t> d_dz16[2];               // hidden gradients, ping-pong, [batch][hidden]
+  DevBuf<uint16_t> d_dzh16;                 // the head's gradient, [batch][32], columns 3.. zero
+  DevBuf<uint16_t> d_w16, d_w16t;           // half(w) per layer as [rows][ldw] and [cols][ldt], padding zero
+  DevBuf<ptd::TrainCtl> d_ctl;              // the control block
 };
 
 }  // namespace

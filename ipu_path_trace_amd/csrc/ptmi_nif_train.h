@@ -6,6 +6,7 @@
 namespace {
 
 inline uint32_t train_blocks(size_t n) { return (uint32_t)((n + 255) / 256); }
+void train_draw_batch(pt_handle h, NifTrainState& st, uint64_t step);
 
 template <int EPI>
 void train_launch_gemm(pt_handle h, const ptd::TrainGemm& G, uint32_t slabs) {
@@ -67,6 +68,172 @@ int train_forward_backward(pt_handle h, NifTrainState& st, uint32_t n) {
   }
   PT_HIP(hipGetLastError());
   return PT_OK;
+}
+
+// ---- mixed precision (pt_nif_train_set_precision): the same sequence on the half kernels
+
+inline uint32_t train_round32(uint32_t x) { return (x + 31u) / 32u * 32u; }
+inline bool train_mixed(const NifTrainState& st) { return st.prec.mode == PT_NIF_TRAIN_MIXED_F16; }
+
+template <int EPI, bool KSLOW>
+void train_launch_gemm16(pt_handle h, const ptd::TrainGemm16& G, uint32_t slabs) {
+  const dim3 grid((G.M + ptd::kHgBM - 1) / ptd::kHgBM, (G.N + ptd::kHgBN - 1) / ptd::kHgBN, slabs);
+  hipLaunchKernelGGL((ptd::train_gemm16_kernel<EPI, KSLOW>), grid, dim3(256), 0, h->stream, G);
+}
+
+// The control block's kernel: kTrainCtlInit (S and the counters), kTrainCtlCommit (a finished step) or kTrainCtlPrepare; each
+// leaves the block ready for a pass over n samples.
+void train_ctl(pt_handle h, NifTrainState& st, int op, uint32_t n, float S0 = 0.f, uint64_t applied0 = 0) {
+  hipLaunchKernelGGL(ptd::train_ctl_kernel, dim3(1), dim3(1), 0, h->stream, st.d_ctl, op, S0, (unsigned long long)applied0,
+                     st.prec.dynamic, st.prec.growth_interval, n, st.p.beta1, st.p.beta2);
+}
+
+// w16 and its transpose from the masters.
+void train_refresh_half(pt_handle h, NifTrainState& st) {
+  for (size_t l = 0; l < st.layers.size(); ++l) {
+    const NifTrainState::Layer& Y = st.layers[l];
+    const NifTrainState::Layer16& H = st.layers16[l];
+    hipLaunchKernelGGL(ptd::train_half_copy_kernel, dim3(train_blocks((size_t)Y.rows * Y.cols)), dim3(256), 0, h->stream, st.d_w + Y.w_off, Y.rows,
+                       Y.cols, (_Float16*)(uint16_t*)st.d_w16 + H.w16_off, H.ldw, (_Float16*)(uint16_t*)st.d_w16t + H.w16t_off, H.ldt);
+  }
+}
+
+void train_encode16(pt_handle h, NifTrainState& st, uint32_t n) {
+  const uint32_t E = st.p.embedding_dim;
+  _Float16* x1 = st.skip ? (_Float16*)(uint16_t*)st.d_act16[st.skip] : nullptr;
+  hipLaunchKernelGGL(ptd::train_encode16_kernel, dim3(train_blocks((size_t)n * 2 * E)), dim3(256), 0, h->stream, st.d_u, st.d_vv, n, E,
+                     (_Float16*)(uint16_t*)st.d_act16[0], st.layers16[0].ldx, x1, st.skip ? st.layers16[st.skip].ldx : 0u, st.p.hidden);
+}
+
+// train_forward_backward in mixed precision: the scaled loss gradient from the control block's c, every dW and db unscaled
+// into the gradient blob, the control block's flag set where one is not finite.
+int train_forward_backward_mixed(pt_handle h, NifTrainState& st, uint32_t n) {
+  const size_t L = st.layers.size();
+  auto act = [&](size_t l) { return (_Float16*)(uint16_t*)st.d_act16[l]; };
+  _Float16* w16 = (_Float16*)(uint16_t*)st.d_w16;
+  _Float16* w16t = (_Float16*)(uint16_t*)st.d_w16t;
+  _Float16* dzh = (_Float16*)(uint16_t*)st.d_dzh16;
+  _Float16* dz[2] = {(_Float16*)(uint16_t*)st.d_dz16[0], (_Float16*)(uint16_t*)st.d_dz16[1]};
+  for (size_t l = 0; l < L; ++l) {   // Y = X w16 + b, ReLU, half: straight into the next layer's input buffer
+    const NifTrainState::Layer& Y = st.layers[l];
+    const NifTrainState::Layer16& H = st.layers16[l];
+    ptd::TrainGemm16 G{};
+    G.A = act(l); G.lda = H.ldx; G.a_rows = n;
+    G.B = w16t + H.w16t_off; G.ldb = H.ldt; G.b_rows = Y.cols;
+    G.C = l + 1 < L ? (void*)act(l + 1) : (void*)(float*)st.d_y;
+    G.ldc = l + 1 < L ? st.layers16[l + 1].ldx : 3u;
+    G.out_f32 = l + 1 < L ? 0u : 1u;
+    G.M = n; G.N = Y.cols; G.K = Y.rows; G.k_slab = Y.rows;
+    G.bias = st.d_w + Y.b_off; G.relu = Y.relu;
+    train_launch_gemm16<ptd::kTrainEpiBias, false>(h, G, 1);
+  }
+  hipLaunchKernelGGL(ptd::train_loss16_kernel, dim3(ptd::kTrainStatBlocks), dim3(256), 0, h->stream, st.d_y, st.d_t, 3u * n, st.d_ctl, dzh, st.d_red);
+  hipLaunchKernelGGL(ptd::train_loss_final_kernel, dim3(1), dim3(256), 0, h->stream, st.d_red, 3u * n, st.d_enc + 4);
+  const uint32_t slab_rows = ((n + ptd::kTrainSlabs - 1) / ptd::kTrainSlabs + ptd::kHgBK - 1) / ptd::kHgBK * ptd::kHgBK;
+  const _Float16* g = dzh;   // dZ of the layer at hand and its leading dimension
+  uint32_t ldg = 32u;
+  int next = 0;
+  for (size_t l = L; l-- > 0;) {
+    const NifTrainState::Layer& Y = st.layers[l];
+    const NifTrainState::Layer16& H = st.layers16[l];
+    ptd::TrainGemm16 W{};   // dW = X^T dZ over the batch, one binary32 partial per slab
+    W.A = act(l); W.lda = H.ldx; W.a_rows = H.ldx;
+    W.B = g; W.ldb = ldg; W.b_rows = ldg;
+    W.C = (float*)st.d_partial; W.ldc = Y.cols;
+    W.M = Y.rows; W.N = Y.cols; W.K = n; W.k_slab = slab_rows; W.c_slab = (uint32_t)st.partial_stride;
+    train_launch_gemm16<ptd::kTrainEpiNone, true>(h, W, ptd::kTrainSlabs);
+    hipLaunchKernelGGL(ptd::train_colsum16_kernel, dim3((Y.cols + 63) / 64, ptd::kTrainSlabs), dim3(256), 0, h->stream, g, n, Y.cols, ldg, slab_rows,
+                       st.d_partial + (size_t)Y.rows * Y.cols, (uint32_t)st.partial_stride);
+    const uint32_t count = Y.rows * Y.cols + Y.cols;
+    hipLaunchKernelGGL(ptd::train_slab_sum_mixed_kernel, dim3(train_blocks(count)), dim3(256), 0, h->stream, st.d_partial, count,
+                       (uint32_t)st.partial_stride, st.d_g + Y.w_off, st.d_ctl);
+    if (l == 0) break;
+    const NifTrainState::Layer& X = st.layers[l - 1];
+    ptd::TrainGemm16 D{};   // dZ below = half((dZ w16^T)[:, :cols below] . (a > 0)); B(k, n) = w16[n][k], the rows below X.cols only
+    D.A = g; D.lda = ldg; D.a_rows = n;
+    D.B = w16 + H.w16_off; D.ldb = H.ldw; D.b_rows = X.cols;
+    D.C = dz[next]; D.ldc = X.cols;
+    D.M = n; D.N = X.cols; D.K = Y.cols; D.k_slab = Y.cols;
+    D.mask = act(l); D.ldmask = H.ldx;
+    train_launch_gemm16<ptd::kTrainEpiMask, false>(h, D, 1);
+    g = dz[next]; ldg = X.cols;
+    next ^= 1;
+  }
+  PT_HIP(hipGetLastError());
+  return PT_OK;
+}
+
+// The half buffers and the control block of the model in st, into `to` (which may be st itself only through a temporary).
+int train_alloc_mixed(pt_handle h, const NifTrainState& st, NifTrainState& to) {
+  const size_t L = st.layers.size(), batch = st.p.batch;
+  to.layers16.clear();
+  size_t w16 = 0, w16t = 0;
+  for (size_t l = 0; l < L; ++l) {
+    const NifTrainState::Layer& Y = st.layers[l];
+    NifTrainState::Layer16 H{train_round32(Y.rows), train_round32(Y.cols), train_round32(Y.rows), w16, w16t};
+    w16 += (size_t)Y.rows * H.ldw;
+    w16t += (size_t)Y.cols * H.ldt;
+    to.layers16.push_back(H);
+  }
+  to.d_act16.clear();
+  to.d_act16.resize(L);
+  for (size_t l = 0; l < L; ++l) PT_HIP(dev_alloc(to.d_act16[l], batch * to.layers16[l].ldx));
+  for (auto& g : to.d_dz16) PT_HIP(dev_alloc(g, batch * st.p.hidden));
+  PT_HIP(dev_alloc(to.d_dzh16, batch * 32));
+  PT_HIP(dev_alloc(to.d_w16, w16));
+  PT_HIP(dev_alloc(to.d_w16t, w16t));
+  PT_HIP(dev_alloc(to.d_ctl, 1));
+  // the padding is zeroed here, once: no kernel writes it
+  for (size_t l = 0; l < L; ++l) PT_HIP(hipMemsetAsync(to.d_act16[l], 0, batch * to.layers16[l].ldx * 2, h->stream));
+  for (auto& g : to.d_dz16) PT_HIP(hipMemsetAsync(g, 0, batch * st.p.hidden * 2, h->stream));
+  PT_HIP(hipMemsetAsync(to.d_dzh16, 0, batch * 32 * 2, h->stream));
+  PT_HIP(hipMemsetAsync(to.d_w16, 0, w16 * 2, h->stream));
+  PT_HIP(hipMemsetAsync(to.d_w16t, 0, w16t * 2, h->stream));
+  PT_HIP(hipMemsetAsync(to.d_ctl, 0, sizeof(ptd::TrainCtl), h->stream));
+  return PT_OK;
+}
+
+void train_free_mixed(NifTrainState& st) {
+  st.layers16.clear();
+  st.d_act16.clear();
+  for (auto& g : st.d_dz16) g.reset();
+  st.d_dzh16.reset(); st.d_w16.reset(); st.d_w16t.reset(); st.d_ctl.reset();
+}
+
+int train_read_ctl(pt_handle h, NifTrainState& st, ptd::TrainCtl* out) {
+  PT_HIP(hipMemcpyAsync(out, st.d_ctl, sizeof(ptd::TrainCtl), hipMemcpyDeviceToHost, h->stream));
+  PT_HIP(hipStreamSynchronize(h->stream));
+  return PT_OK;
+}
+
+// pt_nif_train_steps in mixed precision: per step one control-block kernel, no host round trip.
+int train_steps_mixed(pt_handle h, NifTrainState& st, uint32_t n, float* last_loss) {
+  auto run = [&]() -> int {
+    for (uint32_t i = 0; i < n; ++i) {
+      train_draw_batch(h, st, st.step);
+      train_encode16(h, st, st.p.batch);
+      if (int rc = train_forward_backward_mixed(h, st, st.p.batch)) return rc;
+      for (size_t l = 0; l < st.layers.size(); ++l) {
+        const NifTrainState::Layer& Y = st.layers[l];
+        const NifTrainState::Layer16& H = st.layers16[l];
+        hipLaunchKernelGGL(ptd::train_adam_mixed_kernel, dim3(train_blocks((size_t)Y.rows * Y.cols + Y.cols)), dim3(256), 0, h->stream, st.d_w + Y.w_off,
+                           st.d_m + Y.w_off, st.d_v + Y.w_off, st.d_g + Y.w_off, Y.rows, Y.cols, st.p.learning_rate, st.p.beta1, st.p.beta2,
+                           st.p.adam_eps, st.d_ctl, (_Float16*)(uint16_t*)st.d_w16 + H.w16_off, H.ldw, (_Float16*)(uint16_t*)st.d_w16t + H.w16t_off,
+                           H.ldt);
+      }
+      train_ctl(h, st, ptd::kTrainCtlCommit, st.p.batch);
+      st.step += 1;
+    }
+    PT_HIP(hipGetLastError());
+    float loss = 0.f;
+    PT_HIP(hipMemcpyAsync(&loss, st.d_enc + 4, sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(hipStreamSynchronize(h->stream));
+    if (last_loss) *last_loss = loss;
+    return PT_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  return rc;
 }
 
 void train_draw_batch(pt_handle h, NifTrainState& st, uint64_t step) {
@@ -152,6 +319,7 @@ int pt_nif_train_begin(pt_handle h, const pt_nif_train_params* params) {
   auto fresh = std::make_unique<NifTrainState>();
   NifTrainState& st = *fresh;
   st.p = *params;
+  st.prec = ptniftrain::default_precision();
   st.map_w = h->env_w; st.map_h = h->env_h;
   st.skip = params->layer_count / 2;
   size_t largest = 0;
@@ -229,6 +397,7 @@ int pt_nif_train_steps(pt_handle h, uint32_t n, float* last_loss) {
   if (n == 0) return PT_OK;
   NifTrainState& st = *h->train;
   PT_HIP(hipSetDevice(h->cfg.device));
+  if (train_mixed(st)) return train_steps_mixed(h, st, n, last_loss);
   auto run = [&]() -> int {
     for (uint32_t i = 0; i < n; ++i) {
       train_draw_batch(h, st, st.step);
@@ -279,6 +448,14 @@ int pt_nif_train_set_weights(pt_handle h, const pt_layer* layers, uint32_t n_lay
   PT_HIP(hipMemcpyAsync(st.d_w, host.data(), st.n_params * sizeof(float), hipMemcpyHostToDevice, h->stream));
   PT_HIP(hipMemsetAsync(st.d_m, 0, st.n_params * sizeof(float), h->stream));
   PT_HIP(hipMemsetAsync(st.d_v, 0, st.n_params * sizeof(float), h->stream));
+  if (train_mixed(st)) {   // w16 follows the masters; applied and skipped steps return to 0, S stays
+    ptd::TrainCtl now{};
+    PT_HIP(hipMemcpyAsync(&now, st.d_ctl, sizeof(now), hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(hipStreamSynchronize(h->stream));
+    train_refresh_half(h, st);
+    train_ctl(h, st, ptd::kTrainCtlInit, st.p.batch, now.S, 0);
+    PT_HIP(hipGetLastError());
+  }
   PT_HIP(hipStreamSynchronize(h->stream));
   st.step = 0;
   return PT_OK;
@@ -324,6 +501,70 @@ int pt_nif_train_install(pt_handle h) {
   return pt_upload_nif(h, layers.data(), (uint32_t)layers.size(), st.p.embedding_dim, st.max, mean, st.p.log_tone_map);
 }
 
+int pt_nif_train_default_precision(pt_nif_train_precision* p) {
+  if (!p) return PT_ERR_INVALID_ARGUMENT;
+  *p = ptniftrain::default_precision();
+  return PT_OK;
+}
+
+int pt_nif_train_set_precision(pt_handle h, const pt_nif_train_precision* p) {
+  const std::string bad = ptniftrain::check_precision(p);
+  if (!bad.empty()) {
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) { g_create_error = "pt_nif_train_set_precision: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  if (int rc = train_need(h, "pt_nif_train_set_precision")) return rc;
+  NifTrainState& st = *h->train;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  uint64_t applied = st.step;   // PT_NIF_TRAIN_F32 skips nothing
+  if (train_mixed(st)) {
+    ptd::TrainCtl now{};
+    if (int rc = train_read_ctl(h, st, &now)) return rc;
+    applied = now.applied;
+  } else {
+    PT_HIP(hipStreamSynchronize(h->stream));
+  }
+  if (p->mode == PT_NIF_TRAIN_MIXED_F16 && !train_mixed(st)) {
+    NifTrainState fresh;   // built aside: whatever fails, the mode in force stays
+    const int rc = train_alloc_mixed(h, st, fresh);
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+    st.layers16 = std::move(fresh.layers16);
+    st.d_act16 = std::move(fresh.d_act16);
+    for (int i = 0; i < 2; ++i) st.d_dz16[i] = std::move(fresh.d_dz16[i]);
+    st.d_dzh16 = std::move(fresh.d_dzh16);
+    st.d_w16 = std::move(fresh.d_w16);
+    st.d_w16t = std::move(fresh.d_w16t);
+    st.d_ctl = std::move(fresh.d_ctl);
+  }
+  if (p->mode == PT_NIF_TRAIN_F32 && train_mixed(st)) train_free_mixed(st);
+  st.prec = *p;
+  st.step = applied;
+  if (train_mixed(st)) {
+    train_refresh_half(h, st);
+    train_ctl(h, st, ptd::kTrainCtlInit, st.p.batch, st.prec.loss_scale, applied);
+    PT_HIP(hipGetLastError());
+    PT_HIP(hipStreamSynchronize(h->stream));
+  }
+  return PT_OK;
+}
+
+int pt_nif_train_get_precision_state(pt_handle h, pt_nif_train_precision_state* s) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (int rc = train_need(h, "pt_nif_train_get_precision_state")) return rc;
+  if (!s || s->struct_size != sizeof(pt_nif_train_precision_state))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_nif_train_get_precision_state: pt_nif_train_precision_state.struct_size mismatch");
+  NifTrainState& st = *h->train;
+  s->mode = st.prec.mode;
+  s->loss_scale = 1.0f; s->good_steps = 0; s->applied_steps = st.step; s->skipped_steps = 0;
+  if (!train_mixed(st)) return PT_OK;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  ptd::TrainCtl now{};
+  if (int rc = train_read_ctl(h, st, &now)) return rc;
+  s->loss_scale = now.S; s->good_steps = now.good; s->applied_steps = now.applied; s->skipped_steps = now.skipped;
+  return PT_OK;
+}
+
 int pt_nif_train_end(pt_handle h) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->train) return PT_OK;
@@ -367,8 +608,15 @@ int pt_nif_train_gradients(pt_handle h, const float* u, const float* v, const fl
     PT_HIP(hipMemcpyAsync(st.d_u, u, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     PT_HIP(hipMemcpyAsync(st.d_vv, v, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     PT_HIP(hipMemcpyAsync(st.d_t, target, (size_t)n * 12, hipMemcpyHostToDevice, h->stream));
-    train_encode(h, st, n);
-    if (int rc = train_forward_backward(h, st, n)) return rc;
+    if (train_mixed(st)) {   // c for n samples, the pass, then the block as a step expects it: S and the counters stay
+      train_ctl(h, st, ptd::kTrainCtlPrepare, n);
+      train_encode16(h, st, n);
+      if (int rc = train_forward_backward_mixed(h, st, n)) return rc;
+      train_ctl(h, st, ptd::kTrainCtlPrepare, st.p.batch);
+    } else {
+      train_encode(h, st, n);
+      if (int rc = train_forward_backward(h, st, n)) return rc;
+    }
     PT_HIP(hipMemcpyAsync(loss, st.d_enc + 4, sizeof(float), hipMemcpyDeviceToHost, h->stream));
     return train_blob_out<float>(h, st, st.d_g, gradients, PT_DTYPE_F32);
   };

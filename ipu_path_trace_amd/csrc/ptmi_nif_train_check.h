@@ -55,6 +55,32 @@ inline std::string check(const pt_nif_train_params* p) {
   return "";
 }
 
+// pt_nif_train_set_precision: the defaults and the check, in field order.
+inline pt_nif_train_precision default_precision() {
+  pt_nif_train_precision p{};
+  p.struct_size = (uint32_t)sizeof(pt_nif_train_precision);
+  p.mode = PT_NIF_TRAIN_F32;
+  p.loss_scale = 65536.0f;
+  p.dynamic = 1;
+  p.growth_interval = 2000;
+  return p;
+}
+
+inline std::string check_precision(const pt_nif_train_precision* p) {
+  const std::string at = "pt_nif_train_set_precision: ";
+  if (!p) return at + "null pt_nif_train_precision";
+  if (p->struct_size != sizeof(pt_nif_train_precision)) return at + "pt_nif_train_precision.struct_size mismatch";
+  if (p->mode != PT_NIF_TRAIN_F32 && p->mode != PT_NIF_TRAIN_MIXED_F16)
+    return at + "mode must be PT_NIF_TRAIN_F32 (0) or PT_NIF_TRAIN_MIXED_F16 (1) (got " + std::to_string(p->mode) + ")";
+  int exponent = 0;
+  const bool power_of_two = std::isfinite(p->loss_scale) && p->loss_scale > 0.f && std::frexp(p->loss_scale, &exponent) == 0.5f;
+  if (!power_of_two || p->loss_scale < 1.0f || p->loss_scale > 1073741824.0f) return at + "loss_scale must be a power of two in 1 .. 2^30";
+  if (p->dynamic != 0 && p->dynamic != 1) return at + "dynamic must be 0 or 1 (got " + std::to_string(p->dynamic) + ")";
+  if (p->growth_interval < 1u || p->growth_interval > 2147483648u)
+    return at + "growth_interval must be 1 .. 2^31 (got " + std::to_string(p->growth_interval) + ")";
+  return "";
+}
+
 // The stack synthetic_nif builds: layer_count ReLU layers of width hidden, the 4 E Fourier features concatenated to the input
 // of layer layer_count / 2 (when that is not layer 0), and a linear head of 3 outputs.
 struct Shape { uint32_t rows, cols; bool relu; };

@@ -25,6 +25,7 @@ struct MetaData {
   std::uint32_t imageHeight = 0, imageWidth = 0;
   float eps = 0.f, max = 0.f, mean[3] = {0.f, 0.f, 0.f};   ///< mean as computed: the loaders fold -eps into it
   bool logToneMap = true;
+  std::string precision = "f32";   ///< --train-precision, recorded in train_command when it is not the default
 };
 
 inline std::string jsonString(const std::string& s) {
@@ -56,7 +57,8 @@ inline std::string metadataText(const MetaData& m) {
   t += "  \"name\": " + jsonString(m.name) + ",\n";
   t += "  \"original_image_shape\": [" + std::to_string(m.imageHeight) + ", " + std::to_string(m.imageWidth) + ", 3],\n";
   t += "  \"train_command\": [\"ipu_trace\", \"--train-nif\", \"--layer-count\", \"" + std::to_string(m.layerCount) + "\", \"--layer-size\", \"" +
-       std::to_string(m.hiddenSize) + "\", \"--embedding-dimension\", \"" + std::to_string(m.embeddingDimension) + "\"]\n";
+       std::to_string(m.hiddenSize) + "\", \"--embedding-dimension\", \"" + std::to_string(m.embeddingDimension) + "\"" +
+       (m.precision == "f32" ? std::string() : ", \"--train-precision\", " + jsonString(m.precision)) + "]\n";
   return t + "}\n";
 }
 

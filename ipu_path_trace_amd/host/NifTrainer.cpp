@@ -26,6 +26,9 @@ void addOptions(std::vector<OptionSpec>& specs) {
   specs.push_back({"train-batch", 0, std::to_string(d.batch), false, false, "Texels per Adam step, a multiple of 256."});
   specs.push_back({"train-learning-rate", 0, "0.001", false, false, "Adam learning rate."});
   specs.push_back({"train-seed", 0, "1", false, false, "Seed of the weight initialisation and of the batches."});
+  specs.push_back({"train-precision", 0, "f32", false, false, "f32|mixed: precision of the trainer's matrix products. mixed = binary16 inputs with loss scaling and binary32 master weights (pt_nif_train_set_precision)."});
+  specs.push_back({"train-loss-scale", 0, "65536", false, false, "Initial loss scale of --train-precision mixed, a power of two in 1..2^30."});
+  specs.push_back({"train-loss-scale-static", 0, "false", false, true, "Keep the loss scale of --train-precision mixed fixed (no halving on overflow, no growth)."});
 }
 
 bool requested(const OptionMap& args) { return args.has("train-nif") && !args.str("train-nif").empty(); }
@@ -64,6 +67,14 @@ void run(const OptionMap& args) {
   try { p.learning_rate = args.f32("train-learning-rate"); } catch (const std::exception&) { p.learning_rate = NAN; }
   const std::string bad = ptniftrain::check(&p);
   if (!bad.empty()) throw std::runtime_error("--train-nif: " + bad);
+  pt_nif_train_precision prec = ptniftrain::default_precision();
+  const std::string precision = args.str("train-precision");
+  if (precision != "f32" && precision != "mixed") throw std::runtime_error("--train-precision must be f32 or mixed; got '" + precision + "'");
+  prec.mode = precision == "mixed" ? PT_NIF_TRAIN_MIXED_F16 : PT_NIF_TRAIN_F32;
+  try { prec.loss_scale = args.f32("train-loss-scale"); } catch (const std::exception&) { prec.loss_scale = NAN; }
+  prec.dynamic = args.flag("train-loss-scale-static") ? 0 : 1;
+  const std::string bad_precision = ptniftrain::check_precision(&prec);
+  if (!bad_precision.empty()) throw std::runtime_error("--train-nif: " + bad_precision);
   const std::uint64_t steps = number(args, "train-steps");
   if (steps < 1 || steps > 0xffffffffu) throw std::runtime_error("--train-steps must be at least 1; got " + args.str("train-steps"));
   const std::string out = args.str("train-out");
@@ -78,8 +89,8 @@ void run(const OptionMap& args) {
     if (!(img.bgr[i] >= 0.f) || !std::isfinite(img.bgr[i]))
       throw std::runtime_error("--train-nif '" + file + "': texel at row " + std::to_string(i / 3 / img.width) + ", column " + std::to_string(i / 3 % img.width) +
                                ", channel " + std::to_string(i % 3) + " is " + std::to_string(img.bgr[i]) + ": texels must be finite and not negative");
-  pt_log::info_("Training image '{}': {} x {}; NIF {} x {}, embedding {}, batch {}, {} steps", file, img.width, img.height, p.layer_count, p.hidden,
-                p.embedding_dim, p.batch, steps);
+  pt_log::info_("Training image '{}': {} x {}; NIF {} x {}, embedding {}, batch {}, {} steps, precision {}", file, img.width, img.height, p.layer_count,
+                p.hidden, p.embedding_dim, p.batch, steps, precision);
   if (args.flag("compile-only")) {
     pt_log::info_("Compile only mode selected: finished.");
     return;
@@ -96,6 +107,7 @@ void run(const OptionMap& args) {
   struct Closer { pt_handle h; ~Closer() { pt_destroy(h); } } closer{h};
   check(h, pt_set_env_map(h, img.bgr.data(), (std::uint32_t)img.width, (std::uint32_t)img.height, PT_ENV_FILTER_NEAREST), "set_env_map");
   check(h, pt_nif_train_begin(h, &p), "nif_train_begin");
+  if (prec.mode != PT_NIF_TRAIN_F32) check(h, pt_nif_train_set_precision(h, &prec), "nif_train_set_precision");
   const std::uint32_t interval = (std::uint32_t)std::max<std::uint64_t>(1, steps / 10);
   float loss = 0.f;
   for (std::uint64_t done = 0; done < steps;) {
@@ -119,13 +131,18 @@ void run(const OptionMap& args) {
   meta.embeddingDimension = p.embedding_dim; meta.hiddenSize = p.hidden; meta.layerCount = p.layer_count;
   meta.imageHeight = (std::uint32_t)img.height; meta.imageWidth = (std::uint32_t)img.width;
   meta.eps = p.eps; meta.logToneMap = p.log_tone_map != 0;
+  meta.precision = precision;
   check(h, pt_nif_train_get_encode_params(h, &meta.max, meta.mean), "nif_train_get_encode_params");
+  pt_nif_train_precision_state state{};
+  state.struct_size = sizeof(state);
+  check(h, pt_nif_train_get_precision_state(h, &state), "nif_train_get_precision_state");
   check(h, pt_nif_train_end(h), "nif_train_end");
   makeDirectory(out);
   makeDirectory(out + "/assets.extra");
   writeMetadata(out + "/assets.extra/nif_metadata.txt", meta);
   writePtnif(out + "/assets.extra/converted.ptnif", layers, p.embedding_dim);
-  pt_log::info_("Wrote '{}/assets.extra/nif_metadata.txt' and 'converted.ptnif' (final loss {})", out, loss);
+  pt_log::info_("Wrote '{}/assets.extra/nif_metadata.txt' and 'converted.ptnif' (final loss {}; precision {}, loss scale {}, {} steps applied, {} skipped)", out,
+                loss, precision, state.loss_scale, state.applied_steps, state.skipped_steps);
 }
 
 }  // namespace nif_train

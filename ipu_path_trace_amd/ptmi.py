@@ -41,7 +41,8 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_denoise_default_params", "pt_denoise", "pt_nif_train_default_params", "pt_nif_train_begin",
            "pt_nif_train_layer_shapes", "pt_nif_train_steps", "pt_nif_train_get_weights", "pt_nif_train_set_weights",
            "pt_nif_train_get_encode_params", "pt_nif_train_export", "pt_nif_train_install", "pt_nif_train_end",
-           "pt_nif_train_batch", "pt_nif_train_gradients"]
+           "pt_nif_train_batch", "pt_nif_train_gradients", "pt_nif_train_default_precision", "pt_nif_train_set_precision",
+           "pt_nif_train_get_precision_state"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
@@ -200,6 +201,45 @@ class NifTrainParams(C.Structure):
 assert C.sizeof(NifTrainParams) == 56   # pt_nif_train_params
 
 
+NIF_TRAIN_MODES = {"f32": 0, "mixed": 1}   # PT_NIF_TRAIN_F32, PT_NIF_TRAIN_MIXED_F16
+
+
+class NifTrainPrecision(C.Structure):
+    """pt_nif_train_precision (include/ptmi.h): the trainer's precision mode and its loss scaling."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("loss_scale", C.c_float), ("dynamic", C.c_int32),
+                ("growth_interval", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class NifTrainPrecisionState(C.Structure):
+    """pt_nif_train_precision_state (include/ptmi.h): the mode in force, the current scale and the step counts."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("loss_scale", C.c_float), ("good_steps", C.c_uint32),
+                ("applied_steps", C.c_uint64), ("skipped_steps", C.c_uint64)]
+
+
+assert C.sizeof(NifTrainPrecision) == 20 and C.sizeof(NifTrainPrecisionState) == 32
+
+
+def default_nif_train_precision(**overrides):
+    """The library's default NifTrainPrecision (pt_nif_train_default_precision; needs no GPU), with any field overridden by
+    keyword; mode may be "f32" / "mixed" or the header's constant."""
+    p = NifTrainPrecision()
+    rc = load_library().pt_nif_train_default_precision(C.byref(p))
+    if rc:
+        raise PtError(rc, "pt_nif_train_default_precision failed")
+    for k, v in overrides.items():
+        if k not in p.as_dict():
+            raise ValueError("unknown NIF training precision field %r (known: %s)" % (k, sorted(p.as_dict())))
+        if k == "mode" and isinstance(v, str):
+            if v not in NIF_TRAIN_MODES:
+                raise ValueError("unknown NIF training precision mode %r (known: %s)" % (v, sorted(NIF_TRAIN_MODES)))
+            v = NIF_TRAIN_MODES[v]
+        setattr(p, k, v)
+    return p
+
+
 def default_nif_train_params(**overrides):
     """The library's default NifTrainParams (pt_nif_train_default_params; needs no GPU), with any field overridden by keyword."""
     p = NifTrainParams()
@@ -312,6 +352,9 @@ def load_library(diag=False):
     L.pt_nif_train_install.argtypes = [C.c_void_p]
     L.pt_nif_train_end.argtypes = [C.c_void_p]
     L.pt_nif_train_batch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_nif_train_default_precision.argtypes = [C.POINTER(NifTrainPrecision)]
+    L.pt_nif_train_set_precision.argtypes = [C.c_void_p, C.POINTER(NifTrainPrecision)]
+    L.pt_nif_train_get_precision_state.argtypes = [C.c_void_p, C.POINTER(NifTrainPrecisionState)]
     L.pt_nif_train_gradients.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float),
                                          C.POINTER(Layer), C.c_uint32]
     if diag:
@@ -565,11 +608,12 @@ class Renderer:
         self._check(self._lib.pt_denoise(self.handle, C.byref(p), src, ptr, out.ctypes.data))
         return out
 
-    def train_nif(self, params=None, **overrides):
+    def train_nif(self, params=None, precision=None, **overrides):
         """Start training a NIF on the environment map this renderer holds (include/ptmi.h, pt_nif_train_begin): returns a
         NifTrainer.  params: a NifTrainParams, or None for the library's defaults with any field overridden by keyword
         (embedding_dim, hidden, layer_count, batch, learning_rate, beta1, beta2, adam_eps, seed, log_tone_map, eps).  A
-        renderer has one trainer at a time: a new one replaces the old."""
+        renderer has one trainer at a time: a new one replaces the old.  precision: None (float32, as begin leaves it), "f32" /
+        "mixed", a dict of NifTrainer.set_precision's keywords, or a NifTrainPrecision."""
         if params is None:
             params = default_nif_train_params(**overrides)
         elif overrides:
@@ -579,6 +623,11 @@ class Renderer:
         if old is not None:
             old._r = None          # the handle's trainer is the new one: the old object must not end or drive it
         self._trainer = NifTrainer(self, params)
+        if precision is not None:
+            if isinstance(precision, (str, NifTrainPrecision)):
+                self._trainer.set_precision(precision)
+            else:
+                self._trainer.set_precision(**dict(precision))
         return self._trainer
 
     def export_hdr_device(self, device_ptr, n):
@@ -759,6 +808,21 @@ class NifTrainer:
         loss = C.c_float()
         self._call("pt_nif_train_gradients", u.ctypes.data, v.ctypes.data, t.ctypes.data, u.size, C.byref(loss), arr, len(out))
         return loss.value, out
+
+    def set_precision(self, mode="mixed", **fields):
+        """Switch the precision mode between steps (pt_nif_train_set_precision): mode "mixed" / "f32" (or a NifTrainPrecision),
+        fields loss_scale, dynamic, growth_interval.  Keeps weights, moments and applied steps; resets the scale's state."""
+        p = mode if isinstance(mode, NifTrainPrecision) else default_nif_train_precision(mode=mode, **fields)
+        self._call("pt_nif_train_set_precision", C.byref(p))
+
+    def precision_state(self):
+        """{"mode": "f32" | "mixed", "loss_scale", "good_steps", "applied_steps", "skipped_steps"}."""
+        s = NifTrainPrecisionState()
+        s.struct_size = C.sizeof(NifTrainPrecisionState)
+        self._call("pt_nif_train_get_precision_state", C.byref(s))
+        names = {v: k for k, v in NIF_TRAIN_MODES.items()}
+        return {"mode": names[s.mode], "loss_scale": s.loss_scale, "good_steps": s.good_steps, "applied_steps": s.applied_steps,
+                "skipped_steps": s.skipped_steps}
 
     def close(self):
         if self._r is not None and getattr(self._r, "handle", None):
