@@ -359,6 +359,61 @@ enum { PT_ENV_FILTER_NEAREST = 0, PT_ENV_FILTER_BILINEAR = 1 };
 int pt_set_env_map(pt_handle h, const float* bgr, uint32_t width, uint32_t height, int32_t filter);
 int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, float* bgr);
 
+/* Environment-guided diffuse sampling -- an EXTENSION, opt-in: a diffuse bounce draws its next direction, with probability
+ * alpha, from a distribution that follows the luminance of an HDR image, and otherwise uniformly over the hemisphere as the
+ * reference does (codelets.cpp:199-204).  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves; a process that never
+ * calls pt_set_env_guide launches the kernels it launched before and renders the same bits.
+ * The guide describes SAMPLING, not light: the estimator stays unbiased for any environment (NIF, map or constant), because the
+ * guide only enters as a density that is mixed with the hemisphere's and is therefore positive wherever the integrand is.  A
+ * NIF render is typically guided by the image the NIF was trained from.
+ * Tables (host, binary64; csrc/ptmi_env_guide.h): the image bgr[height][width][3] (layout and validity rules of pt_set_env_map)
+ * is reduced to a grid of rows x cols cells -- both powers of two, rows <= PT_ENV_GUIDE_MAX_ROWS and height, cols <=
+ * PT_ENV_GUIDE_MAX_COLS and width.  Cell (i, j) covers u in [i / rows, (i + 1) / rows), v in [j / cols, (j + 1) / cols) (u down the
+ * image, v across it); texel (r, c) belongs to cell (floor(r rows / height), floor(c cols / width)) and adds
+ * (0.0722 B + 0.7152 G + 0.2126 R) sin(pi (r + 0.5) / height) to its mass.  One alias table (Vose) over the n = rows cols cells,
+ * entries {uint32 threshold, uint32 alias}: cell k is kept when a 32-bit word is < threshold[k].  The density table is made from
+ * the quantised table: P(cell) = (threshold[cell] + sum over k with alias[k] = cell of (2^32 - threshold[k])) / (n 2^32),
+ * q[cell] = P(cell) n / pi (float32), so that g(w) = q[cell(w)] / sin(theta) is 2 pi times the solid-angle density the kernel
+ * really draws from.  alpha is used as alpha_thr / 2^32 with alpha_thr = (uint32)(alpha 2^32).
+ * A guided diffuse bounce at depth d (first bounce: d = 0) draws Philox block 66 + d of the path, words g0..g3 (blocks 0..64 are
+ * the AA noise and the bounces, 65 the lens).  g0 < alpha_thr: k = g1 >> (32 - log2 n), cell = g2 < threshold[k] ? k : alias[k],
+ * (i, j) = (cell / cols, cell mod cols), u = (i + ((g3 >> 16) + 0.5) / 65536) / rows, v = (j + ((g3 & 0xffff) + 0.5) / 65536) / cols,
+ * theta = pi u, phi = 2 pi v - azimuth, world direction (sin theta cos phi, cos theta, sin theta sin phi) -- the inverse of the
+ * escape's direction-to-(u, v) map -- rotated into camera space when a pose is set.  Otherwise: the reference's hemisphere
+ * direction from words 1 and 2 of the bounce's own block, unchanged.  Whichever branch gave the direction w: cos = dot(w, n), the
+ * cell of w is (min((int)(u rows), rows - 1), (int)(v cols) mod cols) of its (u, v), sin theta = max(sqrtf(1 - y^2), 1e-30f) with y
+ * the world y, g = q[cell] / sin theta, and T = T (.) colour x (cos x rr / ((1 - alpha) + alpha g)).  With alpha = 0 the factor is
+ * cos x rr / 1: the unguided bits.
+ * A guide-branch direction with cos <= 0 ends the path with no contribution.  Length rule: such a path has length d + 1 -- the
+ * bounce's own record stands, exactly the length of a path whose contribution stack fills at that bounce -- and it counts in
+ * pt_stats.paths, in pt_stats.segments and in TraceRecord pathLength with that length, not in pt_stats.escaped; pt_trace_paths
+ * reports it with escaped = 0 and throughput 0.  Mirror, glass, emitters, roulette and the escape are untouched.
+ * pt_set_env_guide takes effect at the next pt_path_trace / pt_trace_paths and touches neither the environment, the worklist,
+ * the film, the scene, the camera, NIF sharing nor the memo (their keys are (u, v) bits); it survives pt_upload_nif,
+ * pt_set_env_map and pt_set_constant_env.  g == NULL clears the guide.  The library keeps the two tables on the device (12 bytes
+ * per cell) and retains no host pointer.  PT_ERR_INVALID_ARGUMENT, pt_last_error naming the field, for a NULL handle, a wrong
+ * struct_size, a NULL image, a size outside 1..PT_ENV_MAP_MAX_SIZE, a grid that is not powers of two within the caps and the
+ * image, alpha outside [0, PT_ENV_GUIDE_MAX_ALPHA], a texel that is not finite or is negative, or an image whose total mass is 0;
+ * after that or PT_ERR_OUT_OF_MEMORY the previous guide stays in force.
+ * pt_env_guide_sample runs the kernels' own sampling function over n caller word triples: out_uv float32 [n][2], out_cell
+ * uint32 [n].  pt_env_guide_eval runs the kernels' own density function over n caller world directions (float32 [n][3], unit
+ * length, with the azimuth of pt_set_render_settings): out_cell uint32 [n], out_g float32 [n].  Both: PT_ERR_NOT_READY without
+ * a guide; n == 0 is a no-op. */
+#define PT_ENV_GUIDE_MAX_ROWS 1024
+#define PT_ENV_GUIDE_MAX_COLS 2048
+#define PT_ENV_GUIDE_MAX_ALPHA 0.9f
+typedef struct pt_env_guide {
+  uint32_t struct_size;          /* = sizeof(pt_env_guide) */
+  uint32_t width, height;        /* of the image */
+  uint32_t rows, cols;           /* of the grid */
+  float alpha;                   /* probability of the guide branch, 0 .. PT_ENV_GUIDE_MAX_ALPHA */
+  const float* bgr;              /* [height][width][3], host memory */
+} pt_env_guide;
+int pt_set_env_guide(pt_handle h, const pt_env_guide* g);   /* NULL clears the guide */
+int pt_env_guide_sample(pt_handle h, const uint32_t* g1, const uint32_t* g2, const uint32_t* g3, size_t n, float* out_uv,
+                        uint32_t* out_cell);
+int pt_env_guide_eval(pt_handle h, const float* dir_world, size_t n, uint32_t* out_cell, float* out_g);
+
 /* First-hit feature buffers -- an EXTENSION: what the centre ray of every pixel sees, noise free, for masks, compositing, the
  * debugging of runtime scenes and as the guide of pt_denoise.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves;
  * a process that never calls it runs exactly as before.

@@ -23,6 +23,7 @@
 // bit-identical paths (tests/test_gpu_parity.py).
 #pragma once
 #include "pt_device_math.h"
+#include "pt_env_guide.h"
 
 #include <utility>
 
@@ -90,6 +91,9 @@ struct TraceParams {
   int32_t cam_pose;
   float cam_r[3], cam_u[3], cam_f[3];
   float lens_a, lens_f;            // thin lens: radius (0 = pinhole) and distance of the focal plane along the view axis
+  // Environment guide (pt_set_env_guide, pt_env_guide.h): read by the guided instances alone, which are launched only while a
+  // guide is set.  Last on purpose: no field the other instances read moves.
+  GuideParams guide;
 };
 static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
 
@@ -177,6 +181,12 @@ __device__ __forceinline__ Vec3 to_world(const TraceParams& P, Vec3 d) {
   return mk((d.x * P.cam_r[0] + d.y * P.cam_u[0]) - d.z * P.cam_f[0],
             (d.x * P.cam_r[1] + d.y * P.cam_u[1]) - d.z * P.cam_f[1],
             (d.x * P.cam_r[2] + d.y * P.cam_u[2]) - d.z * P.cam_f[2]);
+}
+
+// World space -> camera space, the transpose: (w . r, w . u, -(w . f)).
+__device__ __forceinline__ Vec3 to_camera(const TraceParams& P, Vec3 w) {
+  return mk(dot(w, mk(P.cam_r[0], P.cam_r[1], P.cam_r[2])), dot(w, mk(P.cam_u[0], P.cam_u[1], P.cam_u[2])),
+            0.f - dot(w, mk(P.cam_f[0], P.cam_f[1], P.cam_f[2])));
 }
 
 // Thin lens (include/ptmi.h): from the lens point a (sqrt(x1) cos 2 pi x2, sqrt(x1) sin 2 pi x2, 0) towards the focus point
@@ -361,6 +371,9 @@ __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab
   }
 }
 
+// GUIDE: the diffuse bounce mixes the hemisphere with the environment guide (pt_env_guide.h); CAM tells it whether directions
+// are rotated between camera and world space, as in emit_escaped (CAM_LENS: when P.cam_pose says so).
+template <bool GUIDE = false, int CAM = CAM_BUILTIN>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length);
 
@@ -368,14 +381,14 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
 // AccumulateContributions fold (codelets.cpp:255-292) carried forward as throughput T.
 // Returns the path length (contribution-stack size, codelets.cpp:253) through `length` when the
 // path ends.
-template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false>
+template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length);
 #ifdef PTMI_DIAG_BUILD
 __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3 d, float& tbest);
 __device__ __forceinline__ int shade_hit_r3(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                             const uint32_t (&w)[4], float rr, uint32_t& length);
 #endif
-template <bool LEGACY, bool SCENE_C, bool PIPE>
+template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length) {
   uint32_t w[4];
   philox4x32_10(s.pixel, s.sample, 1u + s.depth, 0x5054u, P.seed_lo, P.seed_hi, w);
@@ -407,11 +420,32 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
 #ifdef PTMI_DIAG_BUILD
   if constexpr (LEGACY) return shade_hit_r3(P, tab, s, best, tbest, w, rr, length);
 #endif
-  return shade_hit(P, tab, s, best, tbest, w, rr, length);
+  return shade_hit<GUIDE, CAM>(P, tab, s, best, tbest, w, rr, length);
+}
+
+// light::diffuse (codelets.cpp:199-204): a direction uniform over the hemisphere about n from words 1 and 2 of the bounce's block.
+__device__ __forceinline__ Vec3 hemisphere_direction(const TraceParams& P, Vec3 n, const uint32_t (&w)[4]) {
+  float u1 = uniform01(w[1], P.samples_half);
+  float u2 = uniform01(w[2], P.samples_half);
+  Vec3 rx, ry;
+  {   // the branch of light::diffuse's basis as selects: one square root and one division per lane, not two of each per wave
+    const bool xmajor = fabsf(n.x) > fabsf(n.y);
+    const float m = xmajor ? n.x : n.y;
+    const float inv = 1.0f / sqrtf(m * m + n.z * n.z);
+    const float a = n.z * inv, b = m * inv;
+    rx = xmajor ? mk(-a, 0.0f, b) : mk(0.0f, a, -b);
+  }
+  ry = cross(n, rx);
+  float r = sqrtf(1.0f - u1 * u1);
+  float sn, cs;
+  dm_sincos2pi(u2, sn, cs);
+  Vec3 h = mk(cs * r, sn * r, u1);
+  return mk(dot(mk(rx.x, ry.x, n.x), h), dot(mk(rx.y, ry.y, n.y), h), dot(mk(rx.z, ry.z, n.z), h));
 }
 
 // The second half of a loop trip of RayTraceKernel::compute (codelets.cpp:192-216): the ray has hit object `best` at
 // distance `tbest`; w = the bounce's Philox block, rr = its roulette weight.
+template <bool GUIDE, int CAM>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length) {
   // the hit object's row, by per-lane index
@@ -431,23 +465,33 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
   Vec3 hp = add(s.o, scale(s.d, tbest));
   s.o = hp;
   Vec3 n = is_disc ? mk(nx, ny, nz) : normalise(sub(hp, mk(cx, cy, cz)));
-  if (type == MAT_DIFFUSE) {                                  // :199-204, light::diffuse
-    float u1 = uniform01(w[1], P.samples_half);
-    float u2 = uniform01(w[2], P.samples_half);
-    Vec3 rx, ry;
-    {   // the branch of light::diffuse's basis as selects: one square root and one division per lane, not two of each per wave
-      const bool xmajor = fabsf(n.x) > fabsf(n.y);
-      const float m = xmajor ? n.x : n.y;
-      const float inv = 1.0f / sqrtf(m * m + n.z * n.z);
-      const float a = n.z * inv, b = m * inv;
-      rx = xmajor ? mk(-a, 0.0f, b) : mk(0.0f, a, -b);
+  if (GUIDE && type == MAT_DIFFUSE) {
+    // Guided diffuse bounce (include/ptmi.h, pt_set_env_guide): with probability alpha the direction comes from the guide's
+    // alias table, otherwise from the hemisphere by the expressions of the branch below; either way the weight divides by the
+    // mixture density at the direction actually taken, (1 - alpha) + alpha g, in units of the hemisphere's 1 / 2 pi.
+    const GuideParams& G = P.guide;
+    const bool rotate = CAM == CAM_POSE || (CAM == CAM_LENS && P.cam_pose);
+    uint32_t gw[4];
+    philox4x32_10(s.pixel, s.sample, kGuideBlock + s.depth, 0x5054u, P.seed_lo, P.seed_hi, gw);
+    const bool guided = gw[0] < G.alpha_thr;
+    if (guided) {
+      float gu, gv;
+      (void)guide_sample(G, gw[1], gw[2], gw[3], gu, gv);
+      const Vec3 dw = guide_direction(gu, gv, P.azimuth);
+      s.d = rotate ? to_camera(P, dw) : dw;
+    } else {
+      s.d = hemisphere_direction(P, n, w);
     }
-    ry = cross(n, rx);
-    float r = sqrtf(1.0f - u1 * u1);
-    float sn, cs;
-    dm_sincos2pi(u2, sn, cs);
-    Vec3 h = mk(cs * r, sn * r, u1);
-    s.d = mk(dot(mk(rx.x, ry.x, n.x), h), dot(mk(rx.y, ry.y, n.y), h), dot(mk(rx.z, ry.z, n.z), h));
+    const float cost = dot(s.d, n);
+    if (guided && !(cost > 0.0f)) {                           // the guide pointed below the surface: no contribution
+      length = s.depth + 1u;                                  // the bounce's record stands, as when the stack fills at this bounce
+      return STEP_DEAD;
+    }
+    uint32_t cell;
+    const float g = guide_density(G, rotate ? to_world(P, s.d) : s.d, P.azimuth, cell);
+    s.T = scale(cwise(s.T, mk(cr, cg, cb)), (cost * rr) / (G.one_minus_alpha + G.alpha * g));
+  } else if (type == MAT_DIFFUSE) {                           // :199-204, light::diffuse
+    s.d = hemisphere_direction(P, n, w);
     float cost = dot(s.d, n);
     s.T = scale(cwise(s.T, mk(cr, cg, cb)), cost * rr);
   } else {
@@ -567,7 +611,7 @@ namespace ptd {
 // workgroup barriers per 256 paths) and 2 % slower inside the C2 step -- its 16 KiB of LDS do not fit beside the NIF
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
-template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN>
+template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
@@ -687,9 +731,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if constexpr ((OPT & 64) != 0) res = shade_hit_r3(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       else
 #endif
-      res = shade_hit(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
+      res = shade_hit<GUIDE, CAM>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       if (res == STEP_CONTINUE) alive = true;
-      else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full
+      else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full (guided: or the guide pointed below the surface)
       // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
     }
     const uint64_t amask = __ballot(alive);
@@ -759,7 +803,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     int res = STEP_CONTINUE;
     uint32_t length = 0;
-    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE>(P, hit_table, st, length);
+    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM>(P, hit_table, st, length);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
     const bool emitted = active && res == STEP_EMITTED;
@@ -785,6 +829,11 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(const TraceParams P)
 // pt_set_camera: a moved / rotated pinhole (escapes rotated to world space), and a thin lens (its own primary phase)
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE>(P); }
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS>(P); }
+// pt_set_env_guide: the same three with the guided diffuse bounce, launched only while a guide is set (one per camera kind: a
+// single instance reading the camera flags would carry the lens instance's primary phase for every camera)
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true>(P); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -795,9 +844,11 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
   float dir[3], uv[2], throughput[3], cam[2];
 };
 
-// One thread per requested path; same device functions as trace_kernel.
-__global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                   uint32_t n, PathRecordOut* out) {
+// One thread per requested path; same device functions as trace_kernel.  GUIDE: the guided twin (the camera is read at run
+// time either way: CAM_LENS rotates when P.cam_pose says so).
+template <bool GUIDE>
+__device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                                 uint32_t n, PathRecordOut* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   HitRow* const hit_table = reinterpret_cast<HitRow*>(smem);   // P.n_objects rows (dynamic LDS)
   if (threadIdx.x == 0) fill_hit_table(P, hit_table);
@@ -810,7 +861,7 @@ __global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const
   if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
-  do { res = bounce(P, hit_table, st, length); } while (res == STEP_CONTINUE);
+  do { res = bounce<false, false, false, GUIDE, CAM_LENS>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
@@ -823,5 +874,9 @@ __global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const
   }
   out[i] = r;
 }
+__global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                   uint32_t n, PathRecordOut* out) { trace_paths_body<false>(P, u, v, sample, n, out); }
+__global__ void trace_paths_guide_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                         uint32_t n, PathRecordOut* out) { trace_paths_body<true>(P, u, v, sample, n, out); }
 
 }  // namespace ptd

@@ -37,6 +37,7 @@
 #include "pt_nif_share.h"
 #include "pt_nif_memo.h"
 #include "pt_envmap.h"
+#include "pt_env_guide.h"
 #include "pt_features.h"
 #include "pt_denoise.h"
 #include "pt_nif_train.h"
@@ -44,6 +45,7 @@
 #include "ptmi_comm_worker.h"
 #include "ptmi_scene.h"
 #include "ptmi_camera.h"
+#include "ptmi_env_guide.h"
 #include "ptmi_nif_train_check.h"
 #include "ptmi_step_plan.h"
 #include "ptmi_context.h"
@@ -665,8 +667,10 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
 #ifdef PTMI_DIAG_BUILD
     if (!launch_trace_variant(h, P, b.g))   // A/B switches of the profiling build (diag/ptmi_trace_variants.h), read per launch
 #endif
-    {   // the camera picks the instance: the built-in one runs the kernel it always ran
+    {   // the camera picks the instance: the built-in one runs the kernel it always ran; a guide, the guided twin of each
       auto kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens : (P.cam_pose ? ptd::trace_kernel_pose : ptd::trace_kernel);
+      if (h->guide_set)
+        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide : (P.cam_pose ? ptd::trace_kernel_pose_guide : ptd::trace_kernel_guide);
       hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
     PT_HIP(hipGetLastError());
@@ -881,6 +885,32 @@ static int resolve_stage_times(pt_handle h) {
   PT_HIP(hipEventElapsedTime(&total_ms, h->events[h->e_begin_i], h->events[h->e_end_i]));
   h->stats.total_ms = total_ms;
   return PT_OK;
+}
+
+// n caller items through one of the guide's hook kernels: inputs up, `launch` on the stream, outputs back, one wait.
+// Whatever fails, no copy from or to the caller's buffers is left pending when the call returns.
+struct GuideSpan { const void* host_in; void* host_out; size_t bytes; char* dev; };
+template <class Launch>
+static int guide_hook(pt_handle h, GuideSpan* spans, int n_spans, Launch launch) {
+  PT_HIP(hipSetDevice(h->cfg.device));
+  auto run = [&]() -> int {
+    size_t total = 0;
+    for (int i = 0; i < n_spans; ++i) total += (spans[i].bytes + 15) / 16 * 16;
+    if (int rc = ensure_scratch(h, total)) return rc;
+    char* p = h->d_scratch;
+    for (int i = 0; i < n_spans; ++i) { spans[i].dev = p; p += (spans[i].bytes + 15) / 16 * 16; }
+    for (int i = 0; i < n_spans; ++i)
+      if (spans[i].host_in) PT_HIP(hipMemcpyAsync(spans[i].dev, spans[i].host_in, spans[i].bytes, hipMemcpyHostToDevice, h->stream));
+    launch();
+    PT_HIP(hipGetLastError());
+    for (int i = 0; i < n_spans; ++i)
+      if (spans[i].host_out) PT_HIP(hipMemcpyAsync(spans[i].host_out, spans[i].dev, spans[i].bytes, hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(hipStreamSynchronize(h->stream));
+    return PT_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  return rc;
 }
 
 extern "C" {
@@ -1207,6 +1237,79 @@ int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, flo
   return scratch_lookup(h, true, u, v, n, bgr);
 }
 
+// The guide's two tables are built on the host (ptmi_env_guide.h) and copied; the new copies are complete before the old ones
+// go, so a failure leaves the previous guide in force.  No kernel of the handle is running: every entry point that launches a
+// trace kernel waits for its streams before it returns.
+int pt_set_env_guide(pt_handle h, const pt_env_guide* g) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!g) {
+    PT_HIP(hipSetDevice(h->cfg.device));
+    PT_HIP(hipStreamSynchronize(h->stream));
+    h->d_guide_alias.reset(); h->d_guide_q.reset();
+    h->guide = ptd::GuideParams{};
+    h->guide_set = false;
+    return PT_OK;
+  }
+  const std::string bad = ptguide::check(g);
+  if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);
+  ptguide::Table T;
+  const std::string why = ptguide::build(*g, T);
+  if (!why.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, why);
+  const size_t n = (size_t)T.rows * T.cols;
+  std::vector<uint2> entries(n);
+  for (size_t k = 0; k < n; ++k) entries[k] = make_uint2(T.threshold[k], T.alias[k]);
+  PT_HIP(hipSetDevice(h->cfg.device));
+  PT_HIP(hipStreamSynchronize(h->stream));
+  DevBuf<uint2> d_alias;
+  DevBuf<float> d_q;
+  PT_HIP(dev_alloc(d_alias, n));
+  PT_HIP(dev_alloc(d_q, n));
+  PT_HIP(hipMemcpy(d_alias, entries.data(), n * sizeof(uint2), hipMemcpyHostToDevice));
+  PT_HIP(hipMemcpy(d_q, T.q.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  h->d_guide_alias = std::move(d_alias);
+  h->d_guide_q = std::move(d_q);
+  ptd::GuideParams G{};
+  G.alias = h->d_guide_alias; G.q = h->d_guide_q;
+  G.rows = T.rows; G.cols = T.cols; G.log2n = T.log2n; G.log2cols = T.log2cols;
+  G.alpha_thr = T.alpha_thr;
+  G.alpha = (float)T.alpha; G.one_minus_alpha = (float)(1.0 - T.alpha);
+  G.inv_rows = 1.0f / (float)T.rows; G.inv_cols = 1.0f / (float)T.cols;
+  h->guide = G;
+  h->guide_set = true;
+  return PT_OK;
+}
+
+int pt_env_guide_sample(pt_handle h, const uint32_t* g1, const uint32_t* g2, const uint32_t* g3, size_t n, float* out_uv,
+                        uint32_t* out_cell) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->guide_set) return fail(h, PT_ERR_NOT_READY, "pt_set_env_guide has not been called (or the guide has been cleared)");
+  if (n == 0) return PT_OK;
+  if (!g1 || !g2 || !g3 || !out_uv || !out_cell) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many samples");
+  GuideSpan s[5] = {{g1, nullptr, n * 4, nullptr}, {g2, nullptr, n * 4, nullptr}, {g3, nullptr, n * 4, nullptr},
+                    {nullptr, out_uv, n * 8, nullptr}, {nullptr, out_cell, n * 4, nullptr}};
+  return guide_hook(h, s, 5, [&]() {
+    hipLaunchKernelGGL(ptd::env_guide_sample_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, h->guide,
+                       reinterpret_cast<const uint32_t*>(s[0].dev), reinterpret_cast<const uint32_t*>(s[1].dev),
+                       reinterpret_cast<const uint32_t*>(s[2].dev), (uint32_t)n, reinterpret_cast<float*>(s[3].dev),
+                       reinterpret_cast<uint32_t*>(s[4].dev));
+  });
+}
+
+int pt_env_guide_eval(pt_handle h, const float* dir_world, size_t n, uint32_t* out_cell, float* out_g) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->guide_set) return fail(h, PT_ERR_NOT_READY, "pt_set_env_guide has not been called (or the guide has been cleared)");
+  if (n == 0) return PT_OK;
+  if (!dir_world || !out_cell || !out_g) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many directions");
+  GuideSpan s[3] = {{dir_world, nullptr, n * 12, nullptr}, {nullptr, out_cell, n * 4, nullptr}, {nullptr, out_g, n * 4, nullptr}};
+  return guide_hook(h, s, 3, [&]() {
+    hipLaunchKernelGGL(ptd::env_guide_eval_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, h->guide, h->azimuth,
+                       reinterpret_cast<const float*>(s[0].dev), (uint32_t)n, reinterpret_cast<uint32_t*>(s[1].dev),
+                       reinterpret_cast<float*>(s[2].dev));
+  });
+}
+
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!objects && n == 0) { h->scene_n = 0; h->feature_gen += 1; return PT_OK; }   // the built-in scene
@@ -1274,8 +1377,8 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   ptd::TraceParams P;
   fill_trace_params(h, P);
   P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
-  hipLaunchKernelGGL(ptd::trace_paths_kernel, dim3(((uint32_t)n + 127) / 128), dim3(128), ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s,
-                     (uint32_t)n, d_out);
+  hipLaunchKernelGGL(h->guide_set ? ptd::trace_paths_guide_kernel : ptd::trace_paths_kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
+                     ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_path_record), hipMemcpyDeviceToHost, h->stream));
   PT_HIP(hipStreamSynchronize(h->stream));

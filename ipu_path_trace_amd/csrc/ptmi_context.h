@@ -197,6 +197,11 @@ struct pt_context {
   DevBuf<float4> d_env_texels;       // [env_h][env_w] (B, G, R, 0), row-major
   uint32_t env_w = 0, env_h = 0;
   int32_t env_filter = 0;
+  // environment guide (pt_set_env_guide, pt_env_guide.h): sampling, not light -- it outlives every change of environment
+  bool guide_set = false;
+  ptd::GuideParams guide{};          // device-visible: raw pointers into the two owners below (all zero without a guide)
+  DevBuf<uint2> d_guide_alias;       // [rows * cols] {threshold, alias}
+  DevBuf<float> d_guide_q;           // [rows * cols]
   bool nif_valid = false;
   int nif_hidden = 0, nif_emb = 0;   // PADDED hidden width / embedding dimension the kernels are instantiated for
   bool nif_gemm = false;  // layer-by-layer path (pt_nif_gemm.h)
@@ -437,6 +442,7 @@ void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   P.pix = h->acc.pix;
   P.emitted = h->d_counters + 3;
   P.state_stride = h->queue_cap;
+  P.guide = h->guide;
   item_divider(h->n_items ? h->n_items : 1u, P.div_magic, P.div_shift);
 }
 

@@ -18,6 +18,7 @@
 #include "logging.hpp"
 #include "../csrc/ptmi_scene.h"
 #include "../csrc/ptmi_camera.h"
+#include "../csrc/ptmi_env_guide.h"
 #include "trace_ranges.hpp"
 
 /// Adjust samples per pixel to be a multiple of samples per step (PathTracerApp.cpp:19-27).
@@ -94,6 +95,9 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
       {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
+      {"env-guide", 0, "", false, false, "FILE | map: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
+      {"env-guide-size", 0, "", false, false, "RxC: grid of the guide, rows x columns, powers of two, at most 1024x2048 and the image size (default: the largest that fit)."},
+      {"env-guide-alpha", 0, "0.5", false, false, "Probability in [0, 0.9] that a diffuse bounce draws its direction from the guide."},
       {"denoise", 0, "false", false, true, "Also write <basename>_denoised.exr and _denoised.<ext> at every save: the film through the edge-avoiding A-trous filter (pt_denoise), guided by first-hit object id, normal, depth and albedo. The plain outputs are unchanged. One device with the film resident filters the resident film; --host-film, load balancing or several devices filter the host film on device 0."},
       {"denoise-iterations", 0, "5", false, false, "A-trous iterations, 1..6 (steps 1, 2, 4, ...)."},
       {"denoise-sigma-colour", 0, "4", false, false, "Colour stop of the denoiser (halved every iteration); <= 0 disables it."},
@@ -309,6 +313,47 @@ void PathTracerApp::init(const OptionMap& options) {
   } else if (!constantEnv) {
     if (!loadNifModels(args.u32("ipus"), args.str("assets"))) throw std::runtime_error("Could not load NIF model.");
   }
+  // --env-guide (an extension): read, checked and its tables built once here with the library's own code (ptmi_env_guide.h),
+  // before any device is attached (so --compile-only validates it); the image goes to every handle in execute()
+  if (args.has("env-guide") && !args.str("env-guide").empty()) {
+    const std::string file = args.str("env-guide");
+    envGuideFromMap = file == "map";
+    if (envGuideFromMap) {
+      if (envMap.bgr.empty()) throw std::runtime_error("--env-guide map needs --env-map: there is no map to reuse");
+    } else {
+      try {
+        envGuide = env_map::read(file);
+      } catch (const std::exception& e) {
+        throw std::runtime_error(std::string("--env-guide ") + e.what());
+      }
+    }
+    const pt_env_guide g = envGuideRequest(args.str("env-guide-size"), args.f32("env-guide-alpha"));
+    std::string bad = ptguide::check(&g);
+    ptguide::Table table;
+    if (bad.empty()) bad = ptguide::build(g, table);
+    if (!bad.empty()) throw std::runtime_error("--env-guide '" + file + "': " + bad);
+    pt_log::info_("Environment guide '{}': {} x {} image, {} x {} cells, alpha {}", file, g.width, g.height, g.rows, g.cols, table.alpha);
+  }
+}
+
+// The pt_env_guide of --env-guide / --env-guide-size / --env-guide-alpha over the image read in the constructor.
+pt_env_guide PathTracerApp::envGuideRequest(const std::string& size, float alpha) {
+  const env_map::Image& img = envGuideFromMap ? envMap : envGuide;
+  pt_env_guide g{};
+  g.struct_size = sizeof(pt_env_guide);
+  g.width = (std::uint32_t)img.width; g.height = (std::uint32_t)img.height;
+  g.bgr = img.bgr.data();
+  g.alpha = alpha;
+  if (size.empty()) {
+    ptguide::default_grid(g.width, g.height, g.rows, g.cols);
+  } else {
+    unsigned r = 0, c = 0;
+    char tail = 0;
+    if (std::sscanf(size.c_str(), "%ux%u%c", &r, &c, &tail) != 2) throw std::runtime_error("--env-guide-size expects RxC, e.g. 64x128; got '" + size + "'");
+    g.rows = r; g.cols = c;
+  }
+  envGuideRows = g.rows; envGuideCols = g.cols; envGuideAlpha = alpha;
+  return g;
 }
 
 bool PathTracerApp::loadNifModels(std::size_t numDevices, const std::string& assetPath) {
@@ -483,6 +528,10 @@ void PathTracerApp::execute() {
     }
     check(devices[d], pt_set_render_settings(devices[d], seed, antiAliasingScale, fieldOfView, radians, samplesPerIpuStep),
           "init_render_settings");
+    if (envGuideRows) {   // --env-guide: every handle samples by the same guide
+      const pt_env_guide g = envGuideRequest(std::to_string(envGuideRows) + "x" + std::to_string(envGuideCols), envGuideAlpha);
+      check(devices[d], pt_set_env_guide(devices[d], &g), "set_env_guide");
+    }
   }
   initialiseState(imageWidth, imageHeight);
   initialisation.reset();

@@ -40,6 +40,7 @@ struct PathTracerApp {
 
 private:
   bool loadNifModels(std::size_t numDevices, const std::string& assetPath);
+  pt_env_guide envGuideRequest(const std::string& size, float alpha);
   void initialiseState(std::uint32_t imageWidth, std::uint32_t imageHeight);
   /// One call on every device, each from its own thread (devices run concurrently and exchange no ray data,
   /// PathTracerApp.cpp:205-252); throws with the first device's message on failure.
@@ -89,6 +90,10 @@ private:
   pt_camera camera{};                   ///< --scene: the file's "camera", set on every handle when hasCamera
   env_map::Image envMap;                ///< --env-map: the image every handle takes as its environment (empty: NIF or constant)
   std::int32_t envMapFilterMode = 1;    ///< --env-map-filter (PT_ENV_FILTER_*)
+  env_map::Image envGuide;              ///< --env-guide: the image every handle's diffuse bounces are guided by (empty: unguided; "map": envMap is used)
+  bool envGuideFromMap = false;         ///< --env-guide map
+  std::uint32_t envGuideRows = 0, envGuideCols = 0;   ///< --env-guide-size (default: the largest powers of two that fit)
+  float envGuideAlpha = 0.5f;           ///< --env-guide-alpha
   bool hasCamera = false;
   bool denoise = false, saveFeatures = false;   ///< --denoise, --save-features
   pt_denoise_params denoiseParams{};            ///< --denoise-iterations / -sigma-colour / -sigma-normal / -sigma-depth over the library's defaults

@@ -42,11 +42,12 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_train_layer_shapes", "pt_nif_train_steps", "pt_nif_train_get_weights", "pt_nif_train_set_weights",
            "pt_nif_train_get_encode_params", "pt_nif_train_export", "pt_nif_train_install", "pt_nif_train_end",
            "pt_nif_train_batch", "pt_nif_train_gradients", "pt_nif_train_default_precision", "pt_nif_train_set_precision",
-           "pt_nif_train_get_precision_state"]
+           "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
 ENV_FILTERS = {"nearest": ENV_FILTER_NEAREST, "bilinear": ENV_FILTER_BILINEAR}
+ENV_GUIDE_MAX_ROWS, ENV_GUIDE_MAX_COLS, ENV_GUIDE_MAX_ALPHA = 1024, 2048, 0.9
 COMM_ID_BYTES = 128
 HDR_ACCUMULATORS, HDR_FILM = 0, 1
 DENOISE_HOST_IMAGE, DENOISE_ACCUMULATORS, DENOISE_FILM = 0, 1, 2
@@ -101,6 +102,25 @@ class Camera(C.Structure):
 
 
 assert C.sizeof(Camera) == 48   # pt_camera
+
+
+class EnvGuide(C.Structure):
+    """pt_env_guide (include/ptmi.h): the image, the grid and alpha of an environment guide."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("rows", C.c_uint32),
+                ("cols", C.c_uint32), ("alpha", C.c_float), ("bgr", C.c_void_p)]
+
+
+assert C.sizeof(EnvGuide) == 32   # pt_env_guide
+
+
+def default_env_guide_grid(width, height):
+    """(rows, cols): the largest powers of two not above the image size or the caps."""
+    rows = cols = 1
+    while rows * 2 <= min(height, ENV_GUIDE_MAX_ROWS):
+        rows *= 2
+    while cols * 2 <= min(width, ENV_GUIDE_MAX_COLS):
+        cols *= 2
+    return rows, cols
 
 
 def make_camera(position=(0.0, 0.0, 0.0), look_at=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), lens_radius=0.0, focus_distance=1.0):
@@ -338,6 +358,9 @@ def load_library(diag=False):
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
     L.pt_env_map_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pt_set_env_guide.argtypes = [C.c_void_p, C.POINTER(EnvGuide)]
+    L.pt_env_guide_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.pt_env_guide_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.pt_feature_buffers.argtypes = [C.c_void_p, C.POINTER(Features)]
     L.pt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
     L.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_int32, C.c_void_p, C.c_void_p]
@@ -466,6 +489,46 @@ class Renderer:
         out = np.empty((u.size, 3), dtype=np.float32)
         self._check(self._lib.pt_env_map_lookup(self.handle, u.ctypes.data, v.ctypes.data, u.size, out.ctypes.data))
         return out
+
+    def set_env_guide(self, bgr, rows=None, cols=None, alpha=0.5):
+        """Guide diffuse bounces by an equirectangular HDR image (include/ptmi.h, pt_set_env_guide): an (H, W, 3) array as
+        set_env_map takes it, a grid of rows x cols cells (powers of two; default: the largest not above the image or the caps)
+        and the probability alpha in [0, 0.9] of drawing from the guide.  None clears the guide.  It changes how directions are
+        sampled, not the light: any environment stays unbiased.  Takes effect at the next path_trace / trace_paths; a rejected
+        guide (PtError) leaves the previous one in force."""
+        if bgr is None:
+            self._check(self._lib.pt_set_env_guide(self.handle, None))
+            return
+        bgr = np.ascontiguousarray(bgr, dtype=np.float32)
+        if bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("env guide image must have shape (H, W, 3), got %r" % (bgr.shape,))
+        drows, dcols = default_env_guide_grid(bgr.shape[1], bgr.shape[0])
+        g = EnvGuide()
+        g.struct_size = C.sizeof(EnvGuide)
+        g.width, g.height = bgr.shape[1], bgr.shape[0]
+        g.rows, g.cols = int(drows if rows is None else rows), int(dcols if cols is None else cols)
+        g.alpha = float(alpha)
+        g.bgr = bgr.ctypes.data
+        self._check(self._lib.pt_set_env_guide(self.handle, C.byref(g)))
+
+    def env_guide_sample(self, g1, g2, g3):
+        """The kernels' own guide sampling over caller words (pt_env_guide_sample): (uv float32 [n, 2], cell uint32 [n])."""
+        w = [np.ascontiguousarray(x, dtype=np.uint32).ravel() for x in (g1, g2, g3)]
+        if not (w[0].size == w[1].size == w[2].size):
+            raise ValueError("g1, g2 and g3 must have the same size")
+        n = w[0].size
+        uv, cell = np.empty((n, 2), np.float32), np.empty(n, np.uint32)
+        self._check(self._lib.pt_env_guide_sample(self.handle, w[0].ctypes.data, w[1].ctypes.data, w[2].ctypes.data, n,
+                                                  uv.ctypes.data, cell.ctypes.data))
+        return uv, cell
+
+    def env_guide_eval(self, dir_world):
+        """The kernels' own guide density over caller world directions [n, 3] (pt_env_guide_eval): (cell uint32 [n],
+        g float32 [n]), g = 2 pi x the guide's solid-angle density."""
+        d = np.ascontiguousarray(dir_world, dtype=np.float32).reshape(-1, 3)
+        cell, g = np.empty(len(d), np.uint32), np.empty(len(d), np.float32)
+        self._check(self._lib.pt_env_guide_eval(self.handle, d.ctypes.data, len(d), cell.ctypes.data, g.ctypes.data))
+        return cell, g
 
     # ---- program "init_render_settings"
     def init_render_settings(self, seed=1, aa_noise_scale=0.3, fov_degrees=90.0, env_rotation_degrees=0.0,
