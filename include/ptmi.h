@@ -414,6 +414,80 @@ int pt_env_guide_sample(pt_handle h, const uint32_t* g1, const uint32_t* g2, con
                         uint32_t* out_cell);
 int pt_env_guide_eval(pt_handle h, const float* dir_world, size_t n, uint32_t* out_cell, float* out_g);
 
+/* Emitter-guided diffuse sampling -- an EXTENSION, opt-in: a diffuse bounce draws its next direction, with probability beta,
+ * towards an emissive sphere or disc of the scene (the visible cone of a sphere, a uniform point of a disc), and divides by the
+ * mixture density at the direction it took.  No shadow ray and no second contribution: an occluded lamp direction hits the
+ * occluder and the path goes on, so the estimator is unbiased for any scene and environment.  Additive: PTMI_ABI_VERSION stays 5
+ * and no existing struct moves; a process that never calls pt_set_light_guide launches the kernels it launched before and
+ * renders the same bits, and so does one whose guide is inert (below) or has beta = 0.
+ * Table (host, binary64; csrc/ptmi_light_guide.h): the emitters are the objects of the scene in force with
+ * PT_MATERIAL_EMISSIVE, in declaration order, rank k = 0 .. K - 1.  Mass m_k = Y(colour_k) a_k, Y = 0.2126 R + 0.7152 G + 0.0722 B,
+ * a_k = 4 r^2 (sphere) or 2 r^2 (disc).  Thresholds c_k = floor(2^32 sum_{j<=k} m_j / sum m) (uint32) before the last emitter of
+ * positive mass; that one takes the rest (from it on the reported threshold is 0xffffffff).  A 32-bit word g1 selects the first k
+ * with g1 < c_k, else that last emitter.  p_k = (c_k - c_{k-1}) / 2^32 from the integers (the last: (2^32 - c_{k-1}) / 2^32),
+ * rounded to float32 once: sum p_k = 1, and an emitter with p_k = 0 is never selected and adds nothing to the density.  If the
+ * scene has no emitter, or none of positive mass, the guide is accepted but INERT: the library launches what it would launch
+ * without it.  The table is rebuilt by pt_set_light_guide and by every pt_set_scene while a guide is set; the camera does not
+ * change it.  beta is used as beta_thr / 2^32, beta_thr = (uint32)(beta 2^32).
+ * Estimator (device, binary32, every operation rounded once, no contraction; csrc/pt_light_guide.h), in the kernel's frame, at
+ * the hit point x with the normal n as the bounce forms them (a disc's stored normal is not flipped):
+ *   eligible(k), sphere (c, r): v = c - x, D2 = v.v; D2 > r^2 and v.n + r > 0.
+ *   eligible(k), disc (c, m, R): v = c - x, hgt = v.m; |hgt| > 1e-5 and v.n + R sqrtf(fmaxf(0, 1 - (n.m)(n.m))) > 0.
+ *   P_E = sum of p_k over the eligible k, in declaration order.
+ *   x1 = ((float)(g2 >> 8) + 0.5f) 2^-24, x2 = (float)(g3 >> 8) 2^-24, (sn, cs) = sincos(2 pi x2).
+ *   sphere draw: s2 = r^2 / D2, cm = sqrtf(1 - s2), a = v (1 / sqrtf(D2)), (rx, ry) the hemisphere draw's basis about a,
+ *     ct = 1 - (x1 s2) / (1 + cm), st = sqrtf(fmaxf(0, 1 - ct ct)), w = rx (cs st) + ry (sn st) + a ct (per component the dot
+ *     product ((rx, ry, a) . (cs st, sn st, ct)) left to right); own term g_k = (1 + cm) / s2.
+ *   sphere density of any w: (1 + cm) / s2 if w.a >= cm, else 0.
+ *   disc draw: (t1, t2) that basis about m, rho = R sqrtf(x1), y = c + (t1 (rho cs) + t2 (rho sn)), e = y - x, l2 = e.e,
+ *     l = sqrtf(l2), w = e (1 / l); own term g_k = (2 (l2 l)) / (|hgt| R^2).
+ *   disc density of any w: dn = m.w; if dn != 0, t = hgt / dn > 1e-5 and not (|x + t w - c|^2 > R^2): (2 (t t)) / (|dn| R^2), else 0.
+ * THE RIM RULE: a direction drawn from emitter k takes k's own term by construction and does not run k's inside test; the test
+ * is used for every other emitter, and for all of them when the direction came from the hemisphere or the environment guide.
+ * A guided diffuse bounce at depth d draws Philox block 66 + d, words g0..g3 -- the environment guide's block: the branches are
+ * exclusive and share the words.  alpha_thr is the environment guide's (0 without one).  g0 < alpha_thr: the environment branch,
+ * exactly as pt_set_env_guide states it.  Else g0 < alpha_thr + beta_thr: the light branch; k selected by g1; if k is eligible
+ * w is drawn from it, else w is the hemisphere direction from words 1 and 2 of the bounce's own block (the fallback).  Else
+ * that hemisphere direction.  Whichever gave w: cos = w.n,
+ *   den = (one_minus + alpha g_env(w)) + beta ((1 - P_E) + sum over eligible k, in declaration order, of p_k g_k(w)),
+ *   T = T (.) colour x ((cos x rr) / den),
+ * one_minus = (float)(1 - (alpha_thr + beta_thr) / 2^32), the environment term present only with an environment guide.
+ * A direction drawn from an emitter (not a fallback) or from the environment guide with cos <= 0 ends the path with no
+ * contribution, under the environment guide's length rule: length d + 1, counted in paths, segments and pathLength, not in
+ * escaped; pt_trace_paths reports escaped = 0 and throughput 0.
+ * pt_set_light_guide takes effect at the next pt_path_trace / pt_trace_paths; it survives pt_upload_nif, pt_set_env_map,
+ * pt_set_constant_env and pt_set_camera, follows pt_set_scene, and touches neither the worklist, the film, the features, NIF
+ * sharing nor the memo.  g == NULL clears it.  PT_ERR_INVALID_ARGUMENT, pt_last_error naming the field, checked in this order
+ * before any device call: a wrong struct_size; beta not finite or outside [0, PT_LIGHT_GUIDE_MAX_BETA]; alpha + beta >
+ * PT_LIGHT_GUIDE_MAX_BETA (+ 1e-6 for the rounding of the two floats) against an environment guide already set (pt_set_env_guide checks the same sum from its side while a
+ * light guide is set); a NULL handle.  After a rejection the previous guide stays in force.
+ * pt_get_light_guide_info: set, active (set and not inert), beta as used, and the table over all K emitters.
+ * pt_light_guide_sample runs the kernels' own selection and draw over n caller items in WORLD space against the world-space
+ * scene table: origin, normal float32 [n][3], words g1, g2, g3; out_dir float32 [n][3] and out_light the rank drawn from, or -1
+ * (and direction 0) where the selected emitter is not eligible.  pt_light_guide_eval runs the kernels' own density over caller
+ * (origin, normal, unit direction) triples with the inside test for every emitter: out_sum = sum over eligible k of p_k g_k,
+ * out_pe = P_E.  Both: PT_ERR_NOT_READY without an active guide; n == 0 is a no-op. */
+#define PT_LIGHT_GUIDE_MAX_BETA 0.9f
+typedef struct pt_light_guide {
+  uint32_t struct_size;          /* = sizeof(pt_light_guide) */
+  float beta;                    /* probability of the light branch, 0 .. PT_LIGHT_GUIDE_MAX_BETA */
+} pt_light_guide;
+int pt_set_light_guide(pt_handle h, const pt_light_guide* g);   /* NULL clears the guide */
+typedef struct pt_light_guide_info {
+  uint32_t struct_size;          /* = sizeof(pt_light_guide_info), set by the caller */
+  int32_t set, active;
+  float beta;                    /* beta_thr / 2^32 */
+  uint32_t n_lights;             /* K */
+  uint32_t object_index[32];     /* rank -> index into the scene in force (pt_get_scene) */
+  uint32_t threshold[32];
+  float probability[32];
+} pt_light_guide_info;
+int pt_get_light_guide_info(pt_handle h, pt_light_guide_info* out);
+int pt_light_guide_sample(pt_handle h, const float* origin, const float* normal, const uint32_t* g1, const uint32_t* g2,
+                          const uint32_t* g3, size_t n, float* out_dir, int32_t* out_light);
+int pt_light_guide_eval(pt_handle h, const float* origin, const float* normal, const float* dir, size_t n, float* out_sum,
+                        float* out_pe);
+
 /* First-hit feature buffers -- an EXTENSION: what the centre ray of every pixel sees, noise free, for masks, compositing, the
  * debugging of runtime scenes and as the guide of pt_denoise.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves;
  * a process that never calls it runs exactly as before.

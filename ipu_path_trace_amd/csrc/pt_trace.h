@@ -53,6 +53,18 @@ struct SceneObject {
   int32_t same_centre;  // a sphere whose centre equals that of the sphere declared just before it
 };
 
+// The emitter guide's table (pt_set_light_guide; built by ptmi_light_guide.h, used by pt_light_guide.h): the emitters that can
+// be drawn, in declaration order, up to the last one of positive mass.  12 bytes per emitter.
+struct LightParams {
+  uint32_t n;                       // ranks in the table; 0: no light-guided instance is launched
+  uint32_t beta_thr;                // a word g0 with alpha_thr <= g0 < alpha_thr + beta_thr takes the light branch
+  float beta;                       // beta_thr / 2^32, rounded once on the host
+  float one_minus;                  // 1 - (alpha_thr + beta_thr) / 2^32, rounded once on the host
+  uint32_t index[kMaxObjects];      // rank -> object index
+  uint32_t threshold[kMaxObjects];  // rank k is selected by the first threshold a 32-bit word is below, the last rank otherwise
+  float probability[kMaxObjects];   // p_k, from the integer differences of the thresholds
+};
+
 struct TraceParams {
   SceneObject obj[kMaxObjects];   // obj[0 .. n_objects): the scene in declaration order
   uint32_t n_objects;        // 1 .. kMaxObjects; the launch's dynamic LDS holds one HitRow per object
@@ -94,6 +106,9 @@ struct TraceParams {
   // Environment guide (pt_set_env_guide, pt_env_guide.h): read by the guided instances alone, which are launched only while a
   // guide is set.  Last on purpose: no field the other instances read moves.
   GuideParams guide;
+  // Emitter guide (pt_set_light_guide, pt_light_guide.h): read by the light-guided instances alone.  After the guide: nothing
+  // the other instances read moves.
+  LightParams lights;
 };
 static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
 
@@ -373,7 +388,7 @@ __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab
 
 // GUIDE: the diffuse bounce mixes the hemisphere with the environment guide (pt_env_guide.h); CAM tells it whether directions
 // are rotated between camera and world space, as in emit_escaped (CAM_LENS: when P.cam_pose says so).
-template <bool GUIDE = false, int CAM = CAM_BUILTIN>
+template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length);
 
@@ -381,14 +396,14 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
 // AccumulateContributions fold (codelets.cpp:255-292) carried forward as throughput T.
 // Returns the path length (contribution-stack size, codelets.cpp:253) through `length` when the
 // path ends.
-template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN>
+template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length);
 #ifdef PTMI_DIAG_BUILD
 __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3 d, float& tbest);
 __device__ __forceinline__ int shade_hit_r3(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                             const uint32_t (&w)[4], float rr, uint32_t& length);
 #endif
-template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM>
+template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length) {
   uint32_t w[4];
   philox4x32_10(s.pixel, s.sample, 1u + s.depth, 0x5054u, P.seed_lo, P.seed_hi, w);
@@ -420,7 +435,18 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
 #ifdef PTMI_DIAG_BUILD
   if constexpr (LEGACY) return shade_hit_r3(P, tab, s, best, tbest, w, rr, length);
 #endif
-  return shade_hit<GUIDE, CAM>(P, tab, s, best, tbest, w, rr, length);
+  return shade_hit<GUIDE, CAM, LIGHTS>(P, tab, s, best, tbest, w, rr, length);
+}
+
+// The basis of light::diffuse (codelets.cpp:199-204) about a unit vector n: rx, ry with (rx, ry, n) orthonormal.  Its branch as
+// selects: one square root and one division per lane, not two of each per wave.
+__device__ __forceinline__ void basis_about(Vec3 n, Vec3& rx, Vec3& ry) {
+  const bool xmajor = fabsf(n.x) > fabsf(n.y);
+  const float m = xmajor ? n.x : n.y;
+  const float inv = 1.0f / sqrtf(m * m + n.z * n.z);
+  const float a = n.z * inv, b = m * inv;
+  rx = xmajor ? mk(-a, 0.0f, b) : mk(0.0f, a, -b);
+  ry = cross(n, rx);
 }
 
 // light::diffuse (codelets.cpp:199-204): a direction uniform over the hemisphere about n from words 1 and 2 of the bounce's block.
@@ -428,14 +454,7 @@ __device__ __forceinline__ Vec3 hemisphere_direction(const TraceParams& P, Vec3 
   float u1 = uniform01(w[1], P.samples_half);
   float u2 = uniform01(w[2], P.samples_half);
   Vec3 rx, ry;
-  {   // the branch of light::diffuse's basis as selects: one square root and one division per lane, not two of each per wave
-    const bool xmajor = fabsf(n.x) > fabsf(n.y);
-    const float m = xmajor ? n.x : n.y;
-    const float inv = 1.0f / sqrtf(m * m + n.z * n.z);
-    const float a = n.z * inv, b = m * inv;
-    rx = xmajor ? mk(-a, 0.0f, b) : mk(0.0f, a, -b);
-  }
-  ry = cross(n, rx);
+  basis_about(n, rx, ry);
   float r = sqrtf(1.0f - u1 * u1);
   float sn, cs;
   dm_sincos2pi(u2, sn, cs);
@@ -443,9 +462,13 @@ __device__ __forceinline__ Vec3 hemisphere_direction(const TraceParams& P, Vec3 
   return mk(dot(mk(rx.x, ry.x, n.x), h), dot(mk(rx.y, ry.y, n.y), h), dot(mk(rx.z, ry.z, n.z), h));
 }
 
+}  // namespace ptd
+#include "pt_light_guide.h"
+namespace ptd {
+
 // The second half of a loop trip of RayTraceKernel::compute (codelets.cpp:192-216): the ray has hit object `best` at
 // distance `tbest`; w = the bounce's Philox block, rr = its roulette weight.
-template <bool GUIDE, int CAM>
+template <bool GUIDE, int CAM, bool LIGHTS>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length) {
   // the hit object's row, by per-lane index
@@ -465,7 +488,46 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
   Vec3 hp = add(s.o, scale(s.d, tbest));
   s.o = hp;
   Vec3 n = is_disc ? mk(nx, ny, nz) : normalise(sub(hp, mk(cx, cy, cz)));
-  if (GUIDE && type == MAT_DIFFUSE) {
+  if (LIGHTS && type == MAT_DIFFUSE) {
+    // Emitter-guided diffuse bounce (include/ptmi.h, pt_set_light_guide): word g0 of the guide's block picks the environment
+    // guide (when one is set: a wave-uniform test), an emitter, or the hemisphere; whichever gave the direction, the weight
+    // divides by the mixture density there, one_minus + alpha g_env + beta ((1 - P_E) + sum of p_k g_k over the eligible emitters).
+    const GuideParams& G = P.guide;
+    const LightParams& L = P.lights;
+    const bool env = G.alpha_thr != 0u && G.alias != nullptr && G.q != nullptr;
+    const bool rotate = CAM == CAM_POSE || (CAM == CAM_LENS && P.cam_pose);
+    uint32_t gw[4];
+    philox4x32_10(s.pixel, s.sample, kGuideBlock + s.depth, 0x5054u, P.seed_lo, P.seed_hi, gw);
+    const uint32_t alpha_thr = env ? G.alpha_thr : 0u;
+    const bool env_branch = gw[0] < alpha_thr;
+    const bool light_branch = !env_branch && gw[0] < alpha_thr + L.beta_thr;
+    int drawn = -1;          // the rank the direction was drawn from
+    float g_drawn = 0.0f;
+    Vec3 d = mk(0.f, 0.f, 0.f);
+    if (env_branch) {
+      float gu, gv;
+      (void)guide_sample(G, gw[1], gw[2], gw[3], gu, gv);
+      const Vec3 dw = guide_direction(gu, gv, P.azimuth);
+      d = rotate ? to_camera(P, dw) : dw;
+    } else if (light_branch) {
+      drawn = light_draw(P, hp, n, gw[1], gw[2], gw[3], d, g_drawn);
+    }
+    if (!env_branch && drawn < 0) d = hemisphere_direction(P, n, w);   // the hemisphere branch, and the fallback of an ineligible emitter
+    s.d = d;
+    const float cost = dot(s.d, n);
+    if ((env_branch || drawn >= 0) && !(cost > 0.0f)) {       // a guide pointed below the surface: no contribution
+      length = s.depth + 1u;
+      return STEP_DEAD;
+    }
+    float ge = 0.0f;
+    if (env) {
+      uint32_t cell;
+      ge = G.alpha * guide_density(G, rotate ? to_world(P, s.d) : s.d, P.azimuth, cell);
+    }
+    float pe;
+    const float sum = light_mixture(P, hp, n, s.d, drawn, g_drawn, pe);
+    s.T = scale(cwise(s.T, mk(cr, cg, cb)), (cost * rr) / ((L.one_minus + ge) + L.beta * ((1.0f - pe) + sum)));
+  } else if (GUIDE && type == MAT_DIFFUSE) {
     // Guided diffuse bounce (include/ptmi.h, pt_set_env_guide): with probability alpha the direction comes from the guide's
     // alias table, otherwise from the hemisphere by the expressions of the branch below; either way the weight divides by the
     // mixture density at the direction actually taken, (1 - alpha) + alpha g, in units of the hemisphere's 1 / 2 pi.
@@ -611,7 +673,7 @@ namespace ptd {
 // workgroup barriers per 256 paths) and 2 % slower inside the C2 step -- its 16 KiB of LDS do not fit beside the NIF
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
-template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false>
+template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
@@ -731,7 +793,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if constexpr ((OPT & 64) != 0) res = shade_hit_r3(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       else
 #endif
-      res = shade_hit<GUIDE, CAM>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
+      res = shade_hit<GUIDE, CAM, LIGHTS>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       if (res == STEP_CONTINUE) alive = true;
       else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full (guided: or the guide pointed below the surface)
       // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
@@ -803,7 +865,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     int res = STEP_CONTINUE;
     uint32_t length = 0;
-    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM>(P, hit_table, st, length);
+    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS>(P, hit_table, st, length);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
     const bool emitted = active && res == STEP_EMITTED;
@@ -834,6 +896,14 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens(const TracePara
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true>(P); }
+// pt_set_light_guide: the same three with the emitter-guided diffuse bounce, launched only while an active light guide is set.
+// They handle an environment guide too, by a wave-uniform test at run time: three instances, not a cross product.
+// amdgpu_waves_per_eu(6, 6): the grid is six workgroups per CU (pt_context::kTraceBlocksPerCu), one wave of each per SIMD; left
+// alone the allocator takes 83-84 VGPRs, five waves, and the grid's last sixth runs late (measured: 9.6 % of a guided step).
+// Held to 80 it spills no VGPR and the code has no scratch access.
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true>(P); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -845,8 +915,8 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
 };
 
 // One thread per requested path; same device functions as trace_kernel.  GUIDE: the guided twin (the camera is read at run
-// time either way: CAM_LENS rotates when P.cam_pose says so).
-template <bool GUIDE>
+// time either way: CAM_LENS rotates when P.cam_pose says so).  LIGHTS: the emitter-guided twin.
+template <bool GUIDE, bool LIGHTS = false>
 __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                  uint32_t n, PathRecordOut* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -861,7 +931,7 @@ __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uin
   if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
-  do { res = bounce<false, false, false, GUIDE, CAM_LENS>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
+  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
@@ -878,5 +948,7 @@ __global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const
                                    uint32_t n, PathRecordOut* out) { trace_paths_body<false>(P, u, v, sample, n, out); }
 __global__ void trace_paths_guide_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                          uint32_t n, PathRecordOut* out) { trace_paths_body<true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_lights_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                          uint32_t n, PathRecordOut* out) { trace_paths_body<false, true>(P, u, v, sample, n, out); }
 
 }  // namespace ptd

@@ -46,6 +46,7 @@
 #include "ptmi_scene.h"
 #include "ptmi_camera.h"
 #include "ptmi_env_guide.h"
+#include "ptmi_light_guide.h"
 #include "ptmi_nif_train_check.h"
 #include "ptmi_step_plan.h"
 #include "ptmi_context.h"
@@ -671,6 +672,8 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
       auto kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens : (P.cam_pose ? ptd::trace_kernel_pose : ptd::trace_kernel);
       if (h->guide_set)
         kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide : (P.cam_pose ? ptd::trace_kernel_pose_guide : ptd::trace_kernel_guide);
+      if (P.lights.n)   // an active light guide: the emitter-guided twin, which handles an environment guide too
+        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights : (P.cam_pose ? ptd::trace_kernel_pose_lights : ptd::trace_kernel_lights);
       hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
     PT_HIP(hipGetLastError());
@@ -1248,10 +1251,15 @@ int pt_set_env_guide(pt_handle h, const pt_env_guide* g) {
     h->d_guide_alias.reset(); h->d_guide_q.reset();
     h->guide = ptd::GuideParams{};
     h->guide_set = false;
+    h->guide_alpha = 0.f;
     return PT_OK;
   }
   const std::string bad = ptguide::check(g);
   if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);
+  if (h->light_set) {   // the two guides share the hemisphere's probability
+    const std::string sum = ptlight::check_alpha((double)g->alpha, (double)h->light_beta);
+    if (!sum.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, sum);
+  }
   ptguide::Table T;
   const std::string why = ptguide::build(*g, T);
   if (!why.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, why);
@@ -1276,6 +1284,7 @@ int pt_set_env_guide(pt_handle h, const pt_env_guide* g) {
   G.inv_rows = 1.0f / (float)T.rows; G.inv_cols = 1.0f / (float)T.cols;
   h->guide = G;
   h->guide_set = true;
+  h->guide_alpha = g->alpha;
   return PT_OK;
 }
 
@@ -1310,15 +1319,109 @@ int pt_env_guide_eval(pt_handle h, const float* dir_world, size_t n, uint32_t* o
   });
 }
 
+// The emitter guide's table over the scene in force (ptmi_light_guide.h): host data alone, it travels in the kernel arguments.
+static void rebuild_light_guide(pt_handle h) {
+  if (!h->light_set) { h->light = ptlight::Table{}; return; }
+  pt_scene_object builtin[ptd::kBuiltinObjects];
+  builtin_scene(builtin);
+  if (h->scene_n) ptlight::build(h->light_beta, h->scene, h->scene_n, h->light);
+  else ptlight::build(h->light_beta, builtin, ptd::kBuiltinObjects, h->light);
+}
+
+int pt_set_light_guide(pt_handle h, const pt_light_guide* g) {
+  if (g) {
+    const double alpha = (h && h->guide_set) ? (double)h->guide_alpha : 0.0;
+    const std::string bad = ptlight::check(g, alpha);
+    if (!bad.empty()) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, bad) : PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  h->light_set = g != nullptr;
+  h->light_beta = g ? g->beta : 0.f;
+  rebuild_light_guide(h);
+  return PT_OK;
+}
+
+int pt_get_light_guide_info(pt_handle h, pt_light_guide_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_light_guide_info))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_light_guide_info: struct_size must be " + std::to_string(sizeof(pt_light_guide_info)));
+  const ptlight::Table& T = h->light;
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->set = h->light_set ? 1 : 0;
+  out->active = h->light_set && T.active() ? 1 : 0;
+  out->beta = (float)T.beta;
+  out->n_lights = T.n;
+  for (uint32_t k = 0; k < T.n; ++k) {
+    out->object_index[k] = T.object_index[k];
+    out->threshold[k] = T.threshold[k];
+    out->probability[k] = T.probability[k];
+  }
+  return PT_OK;
+}
+
+// The hooks' kernel arguments: the WORLD-space scene table (no camera) and the guide's table.
+static void light_hook_params(pt_handle h, ptd::TraceParams& P) {
+  memset(&P, 0, sizeof(P));
+  pt_scene_object builtin[ptd::kBuiltinObjects];
+  builtin_scene(builtin);
+  if (h->scene_n) fill_scene(P, h->scene, h->scene_n);
+  else fill_scene(P, builtin, ptd::kBuiltinObjects);
+  fill_light_params(h, P, true);
+}
+
+int pt_light_guide_sample(pt_handle h, const float* origin, const float* normal, const uint32_t* g1, const uint32_t* g2,
+                          const uint32_t* g3, size_t n, float* out_dir, int32_t* out_light) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->light_set || !h->light.active())
+    return fail(h, PT_ERR_NOT_READY, "no active light guide: pt_set_light_guide has not been called, or the scene has no emitter with mass");
+  if (n == 0) return PT_OK;
+  if (!origin || !normal || !g1 || !g2 || !g3 || !out_dir || !out_light) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many samples");
+  ptd::TraceParams P;
+  light_hook_params(h, P);
+  GuideSpan s[7] = {{origin, nullptr, n * 12, nullptr}, {normal, nullptr, n * 12, nullptr}, {g1, nullptr, n * 4, nullptr},
+                    {g2, nullptr, n * 4, nullptr},      {g3, nullptr, n * 4, nullptr},      {nullptr, out_dir, n * 12, nullptr},
+                    {nullptr, out_light, n * 4, nullptr}};
+  return guide_hook(h, s, 7, [&]() {
+    hipLaunchKernelGGL(ptd::light_guide_sample_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
+                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev),
+                       reinterpret_cast<const uint32_t*>(s[2].dev), reinterpret_cast<const uint32_t*>(s[3].dev),
+                       reinterpret_cast<const uint32_t*>(s[4].dev), (uint32_t)n, reinterpret_cast<float*>(s[5].dev),
+                       reinterpret_cast<int32_t*>(s[6].dev));
+  });
+}
+
+int pt_light_guide_eval(pt_handle h, const float* origin, const float* normal, const float* dir, size_t n, float* out_sum,
+                        float* out_pe) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->light_set || !h->light.active())
+    return fail(h, PT_ERR_NOT_READY, "no active light guide: pt_set_light_guide has not been called, or the scene has no emitter with mass");
+  if (n == 0) return PT_OK;
+  if (!origin || !normal || !dir || !out_sum || !out_pe) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many directions");
+  ptd::TraceParams P;
+  light_hook_params(h, P);
+  GuideSpan s[5] = {{origin, nullptr, n * 12, nullptr}, {normal, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr},
+                    {nullptr, out_sum, n * 4, nullptr}, {nullptr, out_pe, n * 4, nullptr}};
+  return guide_hook(h, s, 5, [&]() {
+    hipLaunchKernelGGL(ptd::light_guide_eval_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
+                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev),
+                       reinterpret_cast<const float*>(s[2].dev), (uint32_t)n, reinterpret_cast<float*>(s[3].dev),
+                       reinterpret_cast<float*>(s[4].dev));
+  });
+}
+
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!objects && n == 0) { h->scene_n = 0; h->feature_gen += 1; return PT_OK; }   // the built-in scene
+  if (!objects && n == 0) { h->scene_n = 0; h->feature_gen += 1; rebuild_light_guide(h); return PT_OK; }   // the built-in scene
   const std::string bad = ptscene::check(objects, n);
   if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the scene in force stays
   std::copy(objects, objects + n, h->scene);
   ptscene::normalise(h->scene, n);
   h->scene_n = n;
   h->feature_gen += 1;
+  rebuild_light_guide(h);   // a light guide follows the scene
   return PT_OK;
 }
 
@@ -1377,7 +1480,7 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   ptd::TraceParams P;
   fill_trace_params(h, P);
   P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
-  hipLaunchKernelGGL(h->guide_set ? ptd::trace_paths_guide_kernel : ptd::trace_paths_kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
+  hipLaunchKernelGGL(P.lights.n ? ptd::trace_paths_lights_kernel : (h->guide_set ? ptd::trace_paths_guide_kernel : ptd::trace_paths_kernel), dim3(((uint32_t)n + 127) / 128), dim3(128),
                      ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_path_record), hipMemcpyDeviceToHost, h->stream));

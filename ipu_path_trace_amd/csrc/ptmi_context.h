@@ -202,6 +202,11 @@ struct pt_context {
   ptd::GuideParams guide{};          // device-visible: raw pointers into the two owners below (all zero without a guide)
   DevBuf<uint2> d_guide_alias;       // [rows * cols] {threshold, alias}
   DevBuf<float> d_guide_q;           // [rows * cols]
+  float guide_alpha = 0.f;           // alpha as given (the sum check of pt_set_light_guide)
+  // emitter guide (pt_set_light_guide, pt_light_guide.h): host data alone, rebuilt with the scene; it travels in the kernel arguments
+  bool light_set = false;
+  float light_beta = 0.f;            // beta as given
+  ptlight::Table light{};
   bool nif_valid = false;
   int nif_hidden = 0, nif_emb = 0;   // PADDED hidden width / embedding dimension the kernels are instantiated for
   bool nif_gemm = false;  // layer-by-layer path (pt_nif_gemm.h)
@@ -402,6 +407,24 @@ void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, con
   }
 }
 
+// The emitter guide's table into the kernel arguments.  P.lights.n stays 0 -- no light-guided instance is launched -- unless a
+// guide is set, has an emitter with mass and beta > 0 (beta = 0 is the mixture without the light branch: the other instances'
+// arithmetic exactly).  The hooks (hook = true) take the table whatever beta is.
+void fill_light_params(pt_handle h, ptd::TraceParams& P, bool hook = false) {
+  const ptlight::Table& T = h->light;
+  if (!h->light_set || !T.active() || (!hook && T.beta_thr == 0u)) return;
+  ptd::LightParams& L = P.lights;
+  L.n = T.n_draw;
+  L.beta_thr = T.beta_thr;
+  L.beta = (float)T.beta;
+  L.one_minus = (float)(1.0 - ((double)P.guide.alpha_thr + (double)T.beta_thr) / ptlight::kTwo32);
+  for (uint32_t k = 0; k < T.n_draw; ++k) {
+    L.index[k] = T.object_index[k];
+    L.threshold[k] = T.threshold[k];
+    L.probability[k] = T.probability[k];
+  }
+}
+
 void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   memset(&P, 0, sizeof(P));
   const ptcamera::Basis& cb = h->camera_basis;
@@ -443,6 +466,7 @@ void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   P.emitted = h->d_counters + 3;
   P.state_stride = h->queue_cap;
   P.guide = h->guide;
+  fill_light_params(h, P);
   item_divider(h->n_items ? h->n_items : 1u, P.div_magic, P.div_shift);
 }
 

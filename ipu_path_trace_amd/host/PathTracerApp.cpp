@@ -19,6 +19,7 @@
 #include "../csrc/ptmi_scene.h"
 #include "../csrc/ptmi_camera.h"
 #include "../csrc/ptmi_env_guide.h"
+#include "../csrc/ptmi_light_guide.h"
 #include "trace_ranges.hpp"
 
 /// Adjust samples per pixel to be a multiple of samples per step (PathTracerApp.cpp:19-27).
@@ -98,6 +99,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"env-guide", 0, "", false, false, "FILE | map: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
       {"env-guide-size", 0, "", false, false, "RxC: grid of the guide, rows x columns, powers of two, at most 1024x2048 and the image size (default: the largest that fit)."},
       {"env-guide-alpha", 0, "0.5", false, false, "Probability in [0, 0.9] that a diffuse bounce draws its direction from the guide."},
+      {"light-guide-beta", 0, "0", false, false, "Probability in [0, 0.9] that a diffuse bounce draws its direction towards an emitter of the scene (0 = off); with --env-guide, alpha + beta must not exceed 0.9. Changes how directions are sampled, not the light."},
       {"denoise", 0, "false", false, true, "Also write <basename>_denoised.exr and _denoised.<ext> at every save: the film through the edge-avoiding A-trous filter (pt_denoise), guided by first-hit object id, normal, depth and albedo. The plain outputs are unchanged. One device with the film resident filters the resident film; --host-film, load balancing or several devices filter the host film on device 0."},
       {"denoise-iterations", 0, "5", false, false, "A-trous iterations, 1..6 (steps 1, 2, 4, ...)."},
       {"denoise-sigma-colour", 0, "4", false, false, "Colour stop of the denoiser (halved every iteration); <= 0 disables it."},
@@ -334,6 +336,20 @@ void PathTracerApp::init(const OptionMap& options) {
     if (!bad.empty()) throw std::runtime_error("--env-guide '" + file + "': " + bad);
     pt_log::info_("Environment guide '{}': {} x {} image, {} x {} cells, alpha {}", file, g.width, g.height, g.rows, g.cols, table.alpha);
   }
+  // --light-guide-beta (an extension): checked with the environment guide's alpha by the library's own code
+  // (ptmi_light_guide.h), before any device is attached; set on every handle in execute()
+  lightGuideBeta = args.f32("light-guide-beta");
+  {
+    const pt_light_guide g{(std::uint32_t)sizeof(pt_light_guide), lightGuideBeta};
+    const std::string bad = ptlight::check(&g, envGuideRows ? (double)envGuideAlpha : 0.0);
+    if (!bad.empty()) throw std::runtime_error("--light-guide-beta: " + bad);
+    if (lightGuideBeta > 0.f) {
+      ptlight::Table table;
+      ptlight::build(lightGuideBeta, scene.data(), (std::uint32_t)scene.size(), table);   // (no --scene: the built-in one, which has no emitter)
+      if (table.active()) pt_log::info_("light guide: beta {}, {} emitters", ptlight::num(lightGuideBeta), table.n);   // the value as given, %g
+      else pt_log::info_("light guide: inactive: the scene has no emitter");
+    }
+  }
 }
 
 // The pt_env_guide of --env-guide / --env-guide-size / --env-guide-alpha over the image read in the constructor.
@@ -531,6 +547,10 @@ void PathTracerApp::execute() {
     if (envGuideRows) {   // --env-guide: every handle samples by the same guide
       const pt_env_guide g = envGuideRequest(std::to_string(envGuideRows) + "x" + std::to_string(envGuideCols), envGuideAlpha);
       check(devices[d], pt_set_env_guide(devices[d], &g), "set_env_guide");
+    }
+    if (lightGuideBeta > 0.f) {   // --light-guide-beta: every handle samples its emitters alike
+      const pt_light_guide g{(std::uint32_t)sizeof(pt_light_guide), lightGuideBeta};
+      check(devices[d], pt_set_light_guide(devices[d], &g), "set_light_guide");
     }
   }
   initialiseState(imageWidth, imageHeight);

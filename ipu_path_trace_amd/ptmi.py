@@ -42,12 +42,14 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_train_layer_shapes", "pt_nif_train_steps", "pt_nif_train_get_weights", "pt_nif_train_set_weights",
            "pt_nif_train_get_encode_params", "pt_nif_train_export", "pt_nif_train_install", "pt_nif_train_end",
            "pt_nif_train_batch", "pt_nif_train_gradients", "pt_nif_train_default_precision", "pt_nif_train_set_precision",
-           "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval"]
+           "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval",
+           "pt_set_light_guide", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
 ENV_FILTERS = {"nearest": ENV_FILTER_NEAREST, "bilinear": ENV_FILTER_BILINEAR}
 ENV_GUIDE_MAX_ROWS, ENV_GUIDE_MAX_COLS, ENV_GUIDE_MAX_ALPHA = 1024, 2048, 0.9
+LIGHT_GUIDE_MAX_BETA = 0.9
 COMM_ID_BYTES = 128
 HDR_ACCUMULATORS, HDR_FILM = 0, 1
 DENOISE_HOST_IMAGE, DENOISE_ACCUMULATORS, DENOISE_FILM = 0, 1, 2
@@ -111,6 +113,21 @@ class EnvGuide(C.Structure):
 
 
 assert C.sizeof(EnvGuide) == 32   # pt_env_guide
+
+
+class LightGuide(C.Structure):
+    """pt_light_guide (include/ptmi.h): the probability beta of drawing a diffuse bounce towards an emitter."""
+    _fields_ = [("struct_size", C.c_uint32), ("beta", C.c_float)]
+
+
+class LightGuideInfo(C.Structure):
+    """pt_light_guide_info (include/ptmi.h): the emitter guide in force and its table."""
+    _fields_ = [("struct_size", C.c_uint32), ("set", C.c_int32), ("active", C.c_int32), ("beta", C.c_float),
+                ("n_lights", C.c_uint32), ("object_index", C.c_uint32 * 32), ("threshold", C.c_uint32 * 32),
+                ("probability", C.c_float * 32)]
+
+
+assert C.sizeof(LightGuide) == 8 and C.sizeof(LightGuideInfo) == 404   # pt_light_guide, pt_light_guide_info
 
 
 def default_env_guide_grid(width, height):
@@ -361,6 +378,11 @@ def load_library(diag=False):
     L.pt_set_env_guide.argtypes = [C.c_void_p, C.POINTER(EnvGuide)]
     L.pt_env_guide_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.pt_env_guide_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.pt_set_light_guide.argtypes = [C.c_void_p, C.POINTER(LightGuide)]
+    L.pt_get_light_guide_info.argtypes = [C.c_void_p, C.POINTER(LightGuideInfo)]
+    L.pt_light_guide_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_void_p]
+    L.pt_light_guide_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.pt_feature_buffers.argtypes = [C.c_void_p, C.POINTER(Features)]
     L.pt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
     L.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_int32, C.c_void_p, C.c_void_p]
@@ -529,6 +551,54 @@ class Renderer:
         cell, g = np.empty(len(d), np.uint32), np.empty(len(d), np.float32)
         self._check(self._lib.pt_env_guide_eval(self.handle, d.ctypes.data, len(d), cell.ctypes.data, g.ctypes.data))
         return cell, g
+
+    def set_light_guide(self, beta=0.5):
+        """Guide diffuse bounces towards the scene's emitters (include/ptmi.h, pt_set_light_guide): with probability beta in
+        [0, 0.9] a bounce draws its direction from an emissive sphere's visible cone or a point of an emissive disc.  None
+        clears the guide.  It changes how directions are sampled, not the light; a scene without emitters leaves it inert.  The
+        guide follows set_scene; a rejected one (PtError) leaves the previous one in force."""
+        if beta is None:
+            self._check(self._lib.pt_set_light_guide(self.handle, None))
+            return
+        g = LightGuide(C.sizeof(LightGuide), float(beta))
+        self._check(self._lib.pt_set_light_guide(self.handle, C.byref(g)))
+
+    def light_guide_info(self):
+        """pt_get_light_guide_info as a dict: set, active, beta, and per emitter object_index, threshold, probability."""
+        info = LightGuideInfo()
+        info.struct_size = C.sizeof(LightGuideInfo)
+        self._check(self._lib.pt_get_light_guide_info(self.handle, C.byref(info)))
+        k = info.n_lights
+        return {"set": bool(info.set), "active": bool(info.active), "beta": info.beta, "n_lights": k,
+                "object_index": np.array(info.object_index[:k], np.uint32), "threshold": np.array(info.threshold[:k], np.uint32),
+                "probability": np.array(info.probability[:k], np.float32)}
+
+    def light_guide_sample(self, origin, normal, g1, g2, g3):
+        """The kernels' own emitter selection and draw over caller data in world space (pt_light_guide_sample):
+        (dir float32 [n, 3], light int32 [n]: the rank drawn from, -1 where the selected emitter is not eligible)."""
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normal, dtype=np.float32).reshape(-1, 3)
+        w = [np.ascontiguousarray(x, dtype=np.uint32).ravel() for x in (g1, g2, g3)]
+        n = len(o)
+        if not (len(nn) == w[0].size == w[1].size == w[2].size == n):
+            raise ValueError("origin, normal, g1, g2 and g3 must have the same length")
+        d, light = np.zeros((n, 3), np.float32), np.full(n, -1, np.int32)
+        self._check(self._lib.pt_light_guide_sample(self.handle, o.ctypes.data, nn.ctypes.data, w[0].ctypes.data, w[1].ctypes.data,
+                                                    w[2].ctypes.data, n, d.ctypes.data, light.ctypes.data))
+        return d, light
+
+    def light_guide_eval(self, origin, normal, direction):
+        """The kernels' own emitter density over caller (origin, normal, unit direction) triples in world space
+        (pt_light_guide_eval): (sum over the eligible emitters of p_k g_k, float32 [n]; P_E, float32 [n])."""
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normal, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
+        if not (len(o) == len(nn) == len(d)):
+            raise ValueError("origin, normal and direction must have the same length")
+        total, pe = np.zeros(len(o), np.float32), np.zeros(len(o), np.float32)
+        self._check(self._lib.pt_light_guide_eval(self.handle, o.ctypes.data, nn.ctypes.data, d.ctypes.data, len(o),
+                                                  total.ctypes.data, pe.ctypes.data))
+        return total, pe
 
     # ---- program "init_render_settings"
     def init_render_settings(self, seed=1, aa_noise_scale=0.3, fov_degrees=90.0, env_rotation_degrees=0.0,
