@@ -414,6 +414,62 @@ int pt_env_guide_sample(pt_handle h, const uint32_t* g1, const uint32_t* g2, con
                         uint32_t* out_cell);
 int pt_env_guide_eval(pt_handle h, const float* dir_world, size_t n, uint32_t* out_cell, float* out_g);
 
+/* The environment guide built from the environment in force -- the NIF, the map or the constant -- with no image in host memory:
+ * a render from shipped NIF assets, from a NIF made by pt_nif_train_install or after a hot swap can be guided.  Additive:
+ * PTMI_ABI_VERSION stays 5, no existing struct moves, no trace, NIF or accumulate kernel changes and the tables keep their format.
+ * DEFINITION (the contract).  With S = supersample, the guide is pt_set_env_guide of the image I of height rows S and width
+ * cols S, same rows, cols and alpha, where
+ *   I[r][c] = the environment in force looked up at u = ((float)r + 0.5f) / (float)(rows S), v = ((float)c + 0.5f) / (float)(cols S)
+ * (both exact in binary32: the divisors are powers of two; the guide's cells live in the post-azimuth (u, v) square the
+ * environment is defined on, so the azimuth does not enter).  The lookup is the NIF stage's own: for a NIF the value
+ * pt_nif_infer gives, whichever kernel family the model dispatches to; for a map the value pt_env_map_lookup gives with the
+ * filter in force; for a constant the rgb of pt_set_constant_env as (B, G, R) = (rgb[2], rgb[1], rgb[0]).  Each channel x of the
+ * result is then clamped, x' = x >= 0 ? fminf(x, FLT_MAX) : 0 -- NaN and negative values become 0, +inf becomes FLT_MAX (a
+ * NIF's decode can give any of them) -- and `clamped` counts the channel values this replaced.
+ * Masses, the total, the alias table, P and q follow from I by the rules of pt_set_env_guide (csrc/ptmi_env_guide.h) in the same
+ * binary64 arithmetic in the same order: a sample adds ((0.0722 B + 0.7152 G) + 0.2126 R) sin(pi (r + 0.5) / (rows S)) -- the
+ * sine table comes from the host --, a cell adds its S^2 samples one after the other in row-major order, the total adds the
+ * cells in cell order.  Host and device are compiled without contraction, so the two routes agree BIT FOR BIT in threshold,
+ * alias and q.  The masses are summed on the device (csrc/pt_env_guide_build.h), one sub-sample plane at a time: S^2 launches of
+ * the NIF stage over dense queues of rows cols entries, device memory bounded by one plane.
+ * Validation: PT_ERR_INVALID_ARGUMENT, pt_last_error naming the field, checked in this order before any device call: a NULL
+ * struct, struct_size, rows, cols (powers of two within the caps), supersample (1, 2 or 4), alpha (0 .. PT_ENV_GUIDE_MAX_ALPHA),
+ * follow (0 or 1), a NULL handle (the message is then pt_last_error(NULL)'s), alpha + beta against a light guide already set.
+ * PT_ERR_NOT_READY: no environment has ever been set (none of pt_upload_nif, pt_set_env_map, pt_set_constant_env).
+ * PT_ERR_INVALID_ARGUMENT naming the total: the environment's total mass is 0.  After any failure, PT_ERR_OUT_OF_MEMORY
+ * included, the previous guide stays in force.
+ * The call changes nothing else: not the worklist, the film or the feature cache; it bypasses NIF sharing and the memo (their
+ * stats do not move, no new memo generation); pt_get_stats, pt_nif_kernel_name and the replay state of pt_calibrate_nif stay as
+ * they were.  pt_set_env_guide(image) replaces such a guide and turns follow off; pt_set_env_guide(NULL) clears it.
+ * follow = 1: every successful pt_upload_nif, pt_set_env_map, pt_set_constant_env and pt_nif_train_install rebuilds the tables
+ * from the new environment before it returns, with the same rows, cols, S and alpha; its own return value is unaffected.  If
+ * the rebuild fails (a black constant, out of memory) the old tables stay and `stale` is 1 -- a stale guide is still unbiased --
+ * until the next successful build.  With follow = 0, or a guide set from an image, those calls do what they always did.
+ * pt_get_env_guide_info reports the guide in force (struct_size set by the caller; supersample is 0 for a guide from an image).
+ * pt_get_env_guide_tables copies the tables the device holds: PT_ERR_NOT_READY without a guide, PT_ERR_INVALID_ARGUMENT unless
+ * n == rows cols. */
+typedef struct pt_env_guide_auto {
+  uint32_t struct_size;   /* sizeof(pt_env_guide_auto) */
+  uint32_t rows, cols;    /* powers of two, <= PT_ENV_GUIDE_MAX_ROWS / _COLS */
+  uint32_t supersample;   /* S: 1, 2 or 4 samples per cell edge */
+  float    alpha;         /* 0 .. PT_ENV_GUIDE_MAX_ALPHA */
+  int32_t  follow;        /* 0 | 1: rebuild when the environment is replaced */
+} pt_env_guide_auto;
+int pt_set_env_guide_from_environment(pt_handle h, const pt_env_guide_auto* a);
+
+typedef struct pt_env_guide_info {
+  uint32_t struct_size;          /* sizeof(pt_env_guide_info), set by the caller */
+  int32_t  set, source;          /* source: 0 = image (pt_set_env_guide), 1 = environment */
+  uint32_t rows, cols, supersample;
+  float    alpha;                /* alpha_thr / 2^32 */
+  int32_t  follow, stale;
+  uint64_t rebuilds, clamped;    /* builds from the environment so far; channel values replaced in the last one */
+  double   build_ms;             /* device time of the last build from the environment (HIP events) */
+} pt_env_guide_info;
+int pt_get_env_guide_info(pt_handle h, pt_env_guide_info* out);
+/* threshold, alias uint32 [n], q float32 [n], n = rows * cols; any pointer may be NULL */
+int pt_get_env_guide_tables(pt_handle h, uint32_t* threshold, uint32_t* alias, float* q, size_t n);
+
 /* Emitter-guided diffuse sampling -- an EXTENSION, opt-in: a diffuse bounce draws its next direction, with probability beta,
  * towards an emissive sphere or disc of the scene (the visible cone of a sphere, a uniform point of a disc), and divides by the
  * mixture density at the direction it took.  No shadow ray and no second contribution: an occluded lamp direction hits the

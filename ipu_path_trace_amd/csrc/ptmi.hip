@@ -38,6 +38,7 @@
 #include "pt_nif_memo.h"
 #include "pt_envmap.h"
 #include "pt_env_guide.h"
+#include "pt_env_guide_build.h"
 #include "pt_features.h"
 #include "pt_denoise.h"
 #include "pt_nif_train.h"
@@ -60,6 +61,7 @@ static void comm_release(pt_handle h);   // ptmi_film_comm.h: orderly end of the
 static void memo_new_generation(pt_handle h);
 static void drop_env_map(pt_handle h);
 static void forget_replay_state(pt_handle h);
+static void env_guide_follow(pt_handle h);
 
 extern "C" {
 
@@ -287,8 +289,8 @@ static int upload_nif_f32(pt_handle h, const pt_layer* layers, uint32_t n_layers
   return PT_OK;
 }
 
-int pt_upload_nif(pt_handle h, const pt_layer* layers, uint32_t n_layers, uint32_t embedding_dim, float max,
-                  const float mean[3], int32_t log_tonemap) {
+static int upload_nif(pt_handle h, const pt_layer* layers, uint32_t n_layers, uint32_t embedding_dim, float max,
+                      const float mean[3], int32_t log_tonemap) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!layers || !mean || n_layers == 0) return fail(h, PT_ERR_INVALID_ARGUMENT, "null NIF arguments");
   std::vector<HostLayer> L(n_layers);
@@ -373,6 +375,13 @@ int pt_upload_nif(pt_handle h, const pt_layer* layers, uint32_t n_layers, uint32
   return PT_OK;
 }
 
+int pt_upload_nif(pt_handle h, const pt_layer* layers, uint32_t n_layers, uint32_t embedding_dim, float max,
+                  const float mean[3], int32_t log_tonemap) {
+  const int rc = upload_nif(h, layers, n_layers, embedding_dim, max, mean, log_tonemap);
+  if (rc == PT_OK) env_guide_follow(h);   // a guide that follows the environment (pt_set_env_guide_from_environment)
+  return rc;
+}
+
 int pt_set_constant_env(pt_handle h, const float rgb[3]) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!rgb) return fail(h, PT_ERR_INVALID_ARGUMENT, "null rgb");
@@ -383,6 +392,7 @@ int pt_set_constant_env(pt_handle h, const float rgb[3]) {
   h->env_const = true;
   memcpy(h->env_rgb, rgb, 12);
   forget_replay_state(h);
+  env_guide_follow(h);
   return PT_OK;
 }
 
@@ -1228,6 +1238,7 @@ int pt_set_env_map(pt_handle h, const float* bgr, uint32_t width, uint32_t heigh
   h->env_const = false;
   memo_new_generation(h);   // the memo's values belong to the environment being replaced
   forget_replay_state(h);
+  env_guide_follow(h);
   return PT_OK;
 }
 
@@ -1243,26 +1254,7 @@ int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, flo
 // The guide's two tables are built on the host (ptmi_env_guide.h) and copied; the new copies are complete before the old ones
 // go, so a failure leaves the previous guide in force.  No kernel of the handle is running: every entry point that launches a
 // trace kernel waits for its streams before it returns.
-int pt_set_env_guide(pt_handle h, const pt_env_guide* g) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!g) {
-    PT_HIP(hipSetDevice(h->cfg.device));
-    PT_HIP(hipStreamSynchronize(h->stream));
-    h->d_guide_alias.reset(); h->d_guide_q.reset();
-    h->guide = ptd::GuideParams{};
-    h->guide_set = false;
-    h->guide_alpha = 0.f;
-    return PT_OK;
-  }
-  const std::string bad = ptguide::check(g);
-  if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);
-  if (h->light_set) {   // the two guides share the hemisphere's probability
-    const std::string sum = ptlight::check_alpha((double)g->alpha, (double)h->light_beta);
-    if (!sum.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, sum);
-  }
-  ptguide::Table T;
-  const std::string why = ptguide::build(*g, T);
-  if (!why.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, why);
+static int install_guide_tables(pt_handle h, const ptguide::Table& T, float alpha_given) {
   const size_t n = (size_t)T.rows * T.cols;
   std::vector<uint2> entries(n);
   for (size_t k = 0; k < n; ++k) entries[k] = make_uint2(T.threshold[k], T.alias[k]);
@@ -1284,7 +1276,209 @@ int pt_set_env_guide(pt_handle h, const pt_env_guide* g) {
   G.inv_rows = 1.0f / (float)T.rows; G.inv_cols = 1.0f / (float)T.cols;
   h->guide = G;
   h->guide_set = true;
-  h->guide_alpha = g->alpha;
+  h->guide_alpha = alpha_given;
+  return PT_OK;
+}
+
+// A guide from an image (or none) is not one from the environment: nothing follows, nothing is stale.
+static void guide_source_is_image(pt_handle h) {
+  h->guide_from_env = false;
+  h->guide_supersample = 0;
+  h->guide_follow = false;
+  h->guide_stale = false;
+  h->guide_clamped = 0;
+  h->guide_build_ms = 0;
+}
+
+int pt_set_env_guide(pt_handle h, const pt_env_guide* g) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!g) {
+    PT_HIP(hipSetDevice(h->cfg.device));
+    PT_HIP(hipStreamSynchronize(h->stream));
+    h->d_guide_alias.reset(); h->d_guide_q.reset();
+    h->guide = ptd::GuideParams{};
+    h->guide_set = false;
+    h->guide_alpha = 0.f;
+    guide_source_is_image(h);
+    return PT_OK;
+  }
+  const std::string bad = ptguide::check(g);
+  if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);
+  if (h->light_set) {   // the two guides share the hemisphere's probability
+    const std::string sum = ptlight::check_alpha((double)g->alpha, (double)h->light_beta);
+    if (!sum.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, sum);
+  }
+  ptguide::Table T;
+  const std::string why = ptguide::build(*g, T);
+  if (!why.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, why);
+  if (int rc = install_guide_tables(h, T, g->alpha)) return rc;
+  guide_source_is_image(h);
+  return PT_OK;
+}
+
+// ---- the guide built from the environment in force (pt_set_env_guide_from_environment; kernels: pt_env_guide_build.h)
+
+// The cell masses of a rows x cols grid with S x S samples per cell, summed on the device from the environment in force, then
+// the tables (ptguide::build_from_masses) into T.  Nothing of the handle changes but the scratch-free buffers made and freed
+// here: the dense queue has the layout pt_nif_infer gives it (u, v, bgr, count in one allocation) and goes through the same
+// launcher, which is why the image it stands for is pt_nif_infer's / pt_env_map_lookup's, value for value.  It bypasses NIF
+// sharing and the memo, and what pt_nif_kernel_name reports is put back.
+static int build_guide_from_environment(pt_handle h, uint32_t rows, uint32_t cols, uint32_t S, float alpha, ptguide::Table& T,
+                                        uint64_t& clamped, double& build_ms) {
+  const bool constant = h->env_const, map = !constant && h->env_map;
+  if (!constant && !map && !h->nif_valid)
+    return fail(h, PT_ERR_NOT_READY, std::string("pt_set_env_guide_from_environment: ") + ptguide::kNoEnvironment);
+  PT_HIP(hipSetDevice(h->cfg.device));
+  PT_HIP(hipStreamSynchronize(h->stream));
+  const uint32_t n = rows * cols;   // <= 2^21
+  const uint32_t blocks = (n + ptd::kGuideBuildBlock - 1u) / ptd::kGuideBuildBlock;
+  const std::vector<double> sines = ptguide::row_sines(rows * S);
+  DevBuf<char> d_queue;
+  DevBuf<double> d_mass, d_sn;
+  DevBuf<uint32_t> d_partial;
+  PT_HIP(dev_alloc(d_queue, (size_t)n * 4 * 2 + (size_t)n * 12 + 16));
+  PT_HIP(dev_alloc(d_mass, n));
+  PT_HIP(dev_alloc(d_sn, sines.size()));
+  PT_HIP(dev_alloc(d_partial, blocks));
+  float* q_u = reinterpret_cast<float*>(static_cast<char*>(d_queue));
+  float* q_v = q_u + n;
+  float* q_bgr = q_v + n;
+  uint32_t* q_count = reinterpret_cast<uint32_t*>(q_bgr + 3 * (size_t)n);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const std::string name = h->nif_kernel;
+  auto run = [&]() -> int {
+    PT_HIP(hipEventCreate(&e0));
+    PT_HIP(hipEventCreate(&e1));
+    PT_HIP(hipMemcpyAsync(d_sn, sines.data(), sines.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PT_HIP(hipMemsetAsync(d_mass, 0, (size_t)n * sizeof(double), h->stream));
+    PT_HIP(hipMemsetAsync(d_partial, 0, (size_t)blocks * sizeof(uint32_t), h->stream));
+    PT_HIP(hipEventRecord(e0, h->stream));
+    ptd::GuideBuildParams B{};
+    B.n = n; B.cols = cols; B.log2cols = ptguide::log2u(cols); B.S = S;
+    B.inv_h = 1.0f / (float)(rows * S); B.inv_w = 1.0f / (float)(cols * S);
+    const dim3 grid(blocks), block(ptd::kGuideBuildBlock);
+    for (uint32_t sr = 0; sr < S; ++sr)
+      for (uint32_t sc = 0; sc < S; ++sc) {
+        B.sr = sr; B.sc = sc;
+        if (constant) {   // (B, G, R) of the constant: pt_set_constant_env takes R, G, B
+          hipLaunchKernelGGL(ptd::env_guide_fill_kernel, grid, block, 0, h->stream, n, h->env_rgb[2], h->env_rgb[1], h->env_rgb[0], q_bgr);
+        } else {
+          hipLaunchKernelGGL(ptd::env_guide_grid_kernel, grid, block, 0, h->stream, B, q_u, q_v, q_count);
+          PT_HIP(hipGetLastError());
+          ptd::NifParams N = h->nif;   // (the map kernel reads the queue fields alone)
+          bind_dense_queue(N, q_u, q_v, q_count, n, q_bgr);
+          if (int rc = map ? launch_envmap(h, N) : launch_nif(h, N, h->n_cus)) return rc;
+        }
+        PT_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ptd::env_guide_mass_kernel, grid, block, 0, h->stream, B, q_bgr, d_sn, d_mass, d_partial);
+        PT_HIP(hipGetLastError());
+      }
+    PT_HIP(hipEventRecord(e1, h->stream));
+    PT_HIP(hipStreamSynchronize(h->stream));
+    return PT_OK;
+  };
+  int rc = run();
+  h->nif_kernel = name;
+  std::vector<double> mass(n);
+  std::vector<uint32_t> partial(blocks);
+  auto finish = [&]() -> int {
+    float ms = 0.f;
+    PT_HIP(hipEventElapsedTime(&ms, e0, e1));
+    build_ms = (double)ms;
+    PT_HIP(hipMemcpy(mass.data(), d_mass, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    PT_HIP(hipMemcpy(partial.data(), d_partial, (size_t)blocks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return PT_OK;
+  };
+  if (rc == PT_OK) rc = finish();
+  else (void)hipStreamSynchronize(h->stream);   // nothing is left running on the buffers that go now
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (rc) return rc;
+  clamped = 0;
+  for (uint32_t p : partial) clamped += p;
+  const std::string why = ptguide::build_from_masses(rows, cols, alpha, mass, T, "the environment");
+  if (!why.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, why);
+  return PT_OK;
+}
+
+// Build and install; on any failure the guide in force and everything the info reports about it stay.
+static int set_guide_from_environment(pt_handle h, uint32_t rows, uint32_t cols, uint32_t S, float alpha, bool follow) {
+  ptguide::Table T;
+  uint64_t clamped = 0;
+  double ms = 0;
+  if (int rc = build_guide_from_environment(h, rows, cols, S, alpha, T, clamped, ms)) return rc;
+  if (int rc = install_guide_tables(h, T, alpha)) return rc;
+  h->guide_from_env = true;
+  h->guide_supersample = S;
+  h->guide_follow = follow;
+  h->guide_stale = false;
+  h->guide_rebuilds += 1;
+  h->guide_clamped = clamped;
+  h->guide_build_ms = ms;
+  return PT_OK;
+}
+
+// After a successful change of environment: a guide that follows is rebuilt from the new one with its own grid, S and alpha.
+// The caller's return value does not depend on it: a failure (a black constant, out of memory) keeps the old tables -- still
+// an unbiased guide -- and marks them stale.
+static void env_guide_follow(pt_handle h) {
+  if (!h->guide_set || !h->guide_from_env || !h->guide_follow) return;
+  const int rc = set_guide_from_environment(h, h->guide.rows, h->guide.cols, h->guide_supersample, h->guide_alpha, true);
+  if (rc) { h->guide_stale = true; (void)hipGetLastError(); }
+}
+
+int pt_set_env_guide_from_environment(pt_handle h, const pt_env_guide_auto* a) {
+  // the checks that need no device come first; without a handle the message goes where pt_last_error(NULL) reads it
+  const std::string bad = ptguide::check_auto(a);
+  if (!bad.empty()) {
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) { g_create_error = "pt_set_env_guide_from_environment: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  if (h->light_set) {   // the two guides share the hemisphere's probability
+    const std::string sum = ptlight::check_alpha((double)a->alpha, (double)h->light_beta);
+    if (!sum.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, sum);
+  }
+  return set_guide_from_environment(h, a->rows, a->cols, a->supersample, a->alpha, a->follow != 0);
+}
+
+int pt_get_env_guide_info(pt_handle h, pt_env_guide_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_env_guide_info))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_env_guide_info: struct_size must be " + std::to_string(sizeof(pt_env_guide_info)));
+  pt_env_guide_info I{};
+  I.struct_size = sizeof(pt_env_guide_info);
+  I.set = h->guide_set ? 1 : 0;
+  I.source = h->guide_from_env ? 1 : 0;
+  I.rows = h->guide.rows; I.cols = h->guide.cols;
+  I.supersample = h->guide_supersample;
+  I.alpha = (float)((double)h->guide.alpha_thr / ptguide::kTwo32);
+  I.follow = h->guide_follow ? 1 : 0;
+  I.stale = h->guide_stale ? 1 : 0;
+  I.rebuilds = h->guide_rebuilds;
+  I.clamped = h->guide_clamped;
+  I.build_ms = h->guide_build_ms;
+  *out = I;
+  return PT_OK;
+}
+
+int pt_get_env_guide_tables(pt_handle h, uint32_t* threshold, uint32_t* alias, float* q, size_t n) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->guide_set) return fail(h, PT_ERR_NOT_READY, "pt_set_env_guide has not been called (or the guide has been cleared)");
+  const size_t cells = (size_t)h->guide.rows * h->guide.cols;
+  if (n != cells)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_env_guide_tables: n must be rows * cols = " + std::to_string(cells) + " (got " + std::to_string(n) + ")");
+  PT_HIP(hipSetDevice(h->cfg.device));
+  PT_HIP(hipStreamSynchronize(h->stream));
+  if (threshold || alias) {
+    std::vector<uint2> entries(n);
+    PT_HIP(hipMemcpy(entries.data(), h->d_guide_alias, n * sizeof(uint2), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n; ++k) {
+      if (threshold) threshold[k] = entries[k].x;
+      if (alias) alias[k] = entries[k].y;
+    }
+  }
+  if (q) PT_HIP(hipMemcpy(q, h->d_guide_q, n * sizeof(float), hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

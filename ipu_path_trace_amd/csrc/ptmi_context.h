@@ -203,6 +203,13 @@ struct pt_context {
   DevBuf<uint2> d_guide_alias;       // [rows * cols] {threshold, alias}
   DevBuf<float> d_guide_q;           // [rows * cols]
   float guide_alpha = 0.f;           // alpha as given (the sum check of pt_set_light_guide)
+  // ... built from the environment in force (pt_set_env_guide_from_environment, pt_env_guide_build.h) instead of an image
+  bool guide_from_env = false;       // the tables in force came from the environment
+  uint32_t guide_supersample = 0;    // S of that build (0: from an image)
+  bool guide_follow = false;         // rebuild when the environment is replaced
+  bool guide_stale = false;          // the last such rebuild failed: the tables follow an earlier environment
+  uint64_t guide_rebuilds = 0, guide_clamped = 0;
+  double guide_build_ms = 0;
   // emitter guide (pt_set_light_guide, pt_light_guide.h): host data alone, rebuilt with the scene; it travels in the kernel arguments
   bool light_set = false;
   float light_beta = 0.f;            // beta as given

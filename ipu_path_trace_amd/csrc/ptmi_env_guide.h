@@ -33,6 +33,10 @@ struct Table {
   std::vector<double> P;             // [n]: the probability the table really draws each cell with
 };
 
+// What a guide built from the environment answers when there is none (PT_ERR_NOT_READY; the CLI refuses with the same words).
+constexpr const char* kNoEnvironment =
+    "no environment has been set (none of pt_upload_nif, pt_set_env_map, pt_set_constant_env has been called)";
+
 inline bool pow2(uint32_t x) { return x != 0 && (x & (x - 1)) == 0; }
 inline uint32_t log2u(uint32_t x) { uint32_t l = 0; while ((1u << l) < x) ++l; return l; }
 inline std::string num(double v) { char b[40]; snprintf(b, sizeof(b), "%g", v); return b; }
@@ -110,29 +114,21 @@ inline void alias_table(const std::vector<double>& m, double total, std::vector<
   }
 }
 
-// The tables of a guide check() accepted.  "" on success, else the reason (an image without mass), naming the field.
-inline std::string build(const pt_env_guide& g, Table& T) {
-  const uint32_t rows = g.rows, cols = g.cols, W = g.width, H = g.height;
+// The tables from the cell masses (cell order, binary64): the total, the alias table, P and q.  Both routes to a guide end here --
+// build() below over an image in host memory, and pt_set_env_guide_from_environment over the masses its kernels summed on the
+// device (csrc/pt_env_guide_build.h) -- so one set of masses gives one set of tables.  "" on success, else the reason (no mass).
+inline std::string build_from_masses(uint32_t rows, uint32_t cols, float alpha, const std::vector<double>& mass, Table& T,
+                                     const char* what = "bgr") {
   const size_t n = (size_t)rows * cols;
   T.rows = rows; T.cols = cols;
   T.log2cols = log2u(cols);
   T.log2n = log2u(rows) + T.log2cols;
-  T.alpha_thr = (uint32_t)((double)g.alpha * kTwo32);
+  T.alpha_thr = (uint32_t)((double)alpha * kTwo32);
   T.alpha = (double)T.alpha_thr / kTwo32;
-  std::vector<double> mass(n, 0.0);
   double total = 0.0;
-  for (uint32_t r = 0; r < H; ++r) {
-    const size_t i = (size_t)((uint64_t)r * rows / H);
-    const double sn = std::sin(kPi * ((double)r + 0.5) / (double)H);
-    for (uint32_t c = 0; c < W; ++c) {
-      const size_t j = (size_t)((uint64_t)c * cols / W);
-      const float* t = g.bgr + 3 * ((size_t)r * W + c);
-      mass[i * cols + j] += (0.0722 * (double)t[0] + 0.7152 * (double)t[1] + 0.2126 * (double)t[2]) * sn;
-    }
-  }
   for (double m : mass) total += m;
   if (!(total > 0.0) || !std::isfinite(total))
-    return "env guide: bgr has a total mass (luminance x sin theta) of " + num(total) + ": the image must not be black";
+    return std::string("env guide: ") + what + " has a total mass (luminance x sin theta) of " + num(total) + ": the image must not be black";
   alias_table(mass, total, T.threshold, T.alias);
   std::vector<uint64_t> acc(n, 0);   // P(cell) n 2^32, an integer: at most n 2^32 <= 2^53
   for (size_t k = 0; k < n; ++k) {
@@ -145,6 +141,49 @@ inline std::string build(const pt_env_guide& g, Table& T) {
     T.q[k] = (float)((double)acc[k] / kTwo32 / kPi);
     T.ideal[k] = mass[k] / total;
   }
+  return "";
+}
+
+// sin(pi (r + 0.5) / height) for every image row, as build() weighs them: the device build takes this table from the host.
+inline std::vector<double> row_sines(uint32_t height) {
+  std::vector<double> sn(height);
+  for (uint32_t r = 0; r < height; ++r) sn[r] = std::sin(kPi * ((double)r + 0.5) / (double)height);
+  return sn;
+}
+
+// The tables of a guide check() accepted.  "" on success, else the reason (an image without mass), naming the field.
+inline std::string build(const pt_env_guide& g, Table& T) {
+  const uint32_t rows = g.rows, cols = g.cols, W = g.width, H = g.height;
+  const size_t n = (size_t)rows * cols;
+  std::vector<double> mass(n, 0.0);
+  for (uint32_t r = 0; r < H; ++r) {
+    const size_t i = (size_t)((uint64_t)r * rows / H);
+    const double sn = std::sin(kPi * ((double)r + 0.5) / (double)H);
+    for (uint32_t c = 0; c < W; ++c) {
+      const size_t j = (size_t)((uint64_t)c * cols / W);
+      const float* t = g.bgr + 3 * ((size_t)r * W + c);
+      mass[i * cols + j] += (0.0722 * (double)t[0] + 0.7152 * (double)t[1] + 0.2126 * (double)t[2]) * sn;
+    }
+  }
+  return build_from_masses(rows, cols, g.alpha, mass, T);
+}
+
+// "" if the fields of a guide built from the environment in force are valid, else what is wrong, naming the field; checked in
+// the order of the struct (pt_set_env_guide_from_environment, include/ptmi.h).
+inline std::string check_auto(const pt_env_guide_auto* a) {
+  if (!a) return "env guide: null pt_env_guide_auto";
+  if (a->struct_size != sizeof(pt_env_guide_auto))
+    return "env guide: struct_size must be " + std::to_string(sizeof(pt_env_guide_auto)) + " (got " + std::to_string(a->struct_size) + ")";
+  if (!pow2(a->rows) || a->rows > kMaxRows)
+    return "env guide: rows must be a power of two in 1.." + std::to_string(kMaxRows) + " (got " + std::to_string(a->rows) + ")";
+  if (!pow2(a->cols) || a->cols > kMaxCols)
+    return "env guide: cols must be a power of two in 1.." + std::to_string(kMaxCols) + " (got " + std::to_string(a->cols) + ")";
+  if (a->supersample != 1 && a->supersample != 2 && a->supersample != 4)
+    return "env guide: supersample must be 1, 2 or 4 (got " + std::to_string(a->supersample) + ")";
+  if (!(a->alpha >= 0.f && a->alpha <= PT_ENV_GUIDE_MAX_ALPHA))
+    return "env guide: alpha must be in [0, " + num(PT_ENV_GUIDE_MAX_ALPHA) + "] (got " + num(a->alpha) + ")";
+  if (a->follow != 0 && a->follow != 1)
+    return "env guide: follow must be 0 or 1 (got " + std::to_string(a->follow) + ")";
   return "";
 }
 

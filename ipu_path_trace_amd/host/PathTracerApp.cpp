@@ -96,8 +96,9 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
       {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
-      {"env-guide", 0, "", false, false, "FILE | map: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
-      {"env-guide-size", 0, "", false, false, "RxC: grid of the guide, rows x columns, powers of two, at most 1024x2048 and the image size (default: the largest that fit)."},
+      {"env-guide", 0, "", false, false, "FILE | map | env: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map; 'env' needs no file: the guide is built on the device from the environment in force -- the NIF of --assets, the map or the constant -- and follows a NIF loaded later). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
+      {"env-guide-size", 0, "", false, false, "RxC: grid of the guide, rows x columns, powers of two, at most 1024x2048 and the image size (default: the largest that fit; 256x512 for 'env')."},
+      {"env-guide-supersample", 0, "2", false, false, "S: 1, 2 or 4 lookups of the environment per cell edge of --env-guide env."},
       {"env-guide-alpha", 0, "0.5", false, false, "Probability in [0, 0.9] that a diffuse bounce draws its direction from the guide."},
       {"light-guide-beta", 0, "0", false, false, "Probability in [0, 0.9] that a diffuse bounce draws its direction towards an emitter of the scene (0 = off); with --env-guide, alpha + beta must not exceed 0.9. Changes how directions are sampled, not the light."},
       {"denoise", 0, "false", false, true, "Also write <basename>_denoised.exr and _denoised.<ext> at every save: the film through the edge-avoiding A-trous filter (pt_denoise), guided by first-hit object id, normal, depth and albedo. The plain outputs are unchanged. One device with the film resident filters the resident film; --host-film, load balancing or several devices filter the host film on device 0."},
@@ -299,6 +300,11 @@ void PathTracerApp::init(const OptionMap& options) {
   // --env-map (an extension): the image is read and checked here, before any device is attached (so --compile-only validates it)
   const bool constantEnv = args.has("constant-env") && !args.str("constant-env").empty();
   envMapFilterMode = envMapFilter(args.str("env-map-filter"));
+  // --env-guide env builds the guide from the environment: without one (no --assets, --env-map or --constant-env) the library
+  // would answer PT_ERR_NOT_READY, and the tool says so in the library's words before it looks for any asset
+  if (args.has("env-guide") && args.str("env-guide") == "env" && !constantEnv && (!args.has("env-map") || args.str("env-map").empty()) &&
+      (!args.has("assets") || args.str("assets").empty()))
+    throw std::runtime_error(std::string("--env-guide env: ") + ptguide::kNoEnvironment);
   if (args.has("env-map") && !args.str("env-map").empty()) {
     if (constantEnv) throw std::runtime_error("--env-map and --constant-env are both given: the environment is one or the other");
     try {
@@ -320,7 +326,15 @@ void PathTracerApp::init(const OptionMap& options) {
   if (args.has("env-guide") && !args.str("env-guide").empty()) {
     const std::string file = args.str("env-guide");
     envGuideFromMap = file == "map";
-    if (envGuideFromMap) {
+    envGuideFromEnv = file == "env";
+    if (envGuideFromEnv) {
+      // no image: the library builds the guide from the environment each handle holds (pt_set_env_guide_from_environment)
+      const pt_env_guide_auto a = envGuideAutoRequest(args.str("env-guide-size"), args.f32("env-guide-alpha"), args.u32("env-guide-supersample"));
+      const std::string bad = ptguide::check_auto(&a);
+      if (!bad.empty()) throw std::runtime_error("--env-guide env: " + bad);
+      pt_log::info_("Environment guide from the environment in force: {} x {} cells, {} x {} lookups per cell, alpha {}", a.rows, a.cols,
+                    a.supersample, a.supersample, ptguide::num(a.alpha));
+    } else if (envGuideFromMap) {
       if (envMap.bgr.empty()) throw std::runtime_error("--env-guide map needs --env-map: there is no map to reuse");
     } else {
       try {
@@ -329,12 +343,14 @@ void PathTracerApp::init(const OptionMap& options) {
         throw std::runtime_error(std::string("--env-guide ") + e.what());
       }
     }
-    const pt_env_guide g = envGuideRequest(args.str("env-guide-size"), args.f32("env-guide-alpha"));
-    std::string bad = ptguide::check(&g);
-    ptguide::Table table;
-    if (bad.empty()) bad = ptguide::build(g, table);
-    if (!bad.empty()) throw std::runtime_error("--env-guide '" + file + "': " + bad);
-    pt_log::info_("Environment guide '{}': {} x {} image, {} x {} cells, alpha {}", file, g.width, g.height, g.rows, g.cols, table.alpha);
+    if (!envGuideFromEnv) {
+      const pt_env_guide g = envGuideRequest(args.str("env-guide-size"), args.f32("env-guide-alpha"));
+      std::string bad = ptguide::check(&g);
+      ptguide::Table table;
+      if (bad.empty()) bad = ptguide::build(g, table);
+      if (!bad.empty()) throw std::runtime_error("--env-guide '" + file + "': " + bad);
+      pt_log::info_("Environment guide '{}': {} x {} image, {} x {} cells, alpha {}", file, g.width, g.height, g.rows, g.cols, table.alpha);
+    }
   }
   // --light-guide-beta (an extension): checked with the environment guide's alpha by the library's own code
   // (ptmi_light_guide.h), before any device is attached; set on every handle in execute()
@@ -370,6 +386,25 @@ pt_env_guide PathTracerApp::envGuideRequest(const std::string& size, float alpha
   }
   envGuideRows = g.rows; envGuideCols = g.cols; envGuideAlpha = alpha;
   return g;
+}
+
+// The pt_env_guide_auto of --env-guide env / --env-guide-size / --env-guide-alpha / --env-guide-supersample; follow is on, so
+// a NIF loaded later (the interactive load_nif) keeps the guide current.
+pt_env_guide_auto PathTracerApp::envGuideAutoRequest(const std::string& size, float alpha, std::uint32_t supersample) {
+  pt_env_guide_auto a{};
+  a.struct_size = sizeof(pt_env_guide_auto);
+  a.rows = 256; a.cols = 512;
+  if (!size.empty()) {
+    unsigned r = 0, c = 0;
+    char tail = 0;
+    if (std::sscanf(size.c_str(), "%ux%u%c", &r, &c, &tail) != 2) throw std::runtime_error("--env-guide-size expects RxC, e.g. 64x128; got '" + size + "'");
+    a.rows = r; a.cols = c;
+  }
+  a.supersample = supersample;
+  a.alpha = alpha;
+  a.follow = 1;
+  envGuideRows = a.rows; envGuideCols = a.cols; envGuideAlpha = alpha; envGuideSupersample = supersample;
+  return a;
 }
 
 bool PathTracerApp::loadNifModels(std::size_t numDevices, const std::string& assetPath) {
@@ -544,7 +579,15 @@ void PathTracerApp::execute() {
     }
     check(devices[d], pt_set_render_settings(devices[d], seed, antiAliasingScale, fieldOfView, radians, samplesPerIpuStep),
           "init_render_settings");
-    if (envGuideRows) {   // --env-guide: every handle samples by the same guide
+    if (envGuideRows && envGuideFromEnv) {   // --env-guide env: every handle derives the same tables from its own replica
+      const pt_env_guide_auto a = envGuideAutoRequest(std::to_string(envGuideRows) + "x" + std::to_string(envGuideCols), envGuideAlpha, envGuideSupersample);
+      check(devices[d], pt_set_env_guide_from_environment(devices[d], &a), "set_env_guide_from_environment");
+      pt_env_guide_info info{};
+      info.struct_size = sizeof(pt_env_guide_info);
+      check(devices[d], pt_get_env_guide_info(devices[d], &info), "get_env_guide_info");
+      pt_log::info_("Environment guide built on device {}: {} x {} cells, supersample {}, build_ms {}, {} values clamped", d, info.rows, info.cols,
+                    info.supersample, info.build_ms, info.clamped);
+    } else if (envGuideRows) {   // --env-guide: every handle samples by the same guide
       const pt_env_guide g = envGuideRequest(std::to_string(envGuideRows) + "x" + std::to_string(envGuideCols), envGuideAlpha);
       check(devices[d], pt_set_env_guide(devices[d], &g), "set_env_guide");
     }

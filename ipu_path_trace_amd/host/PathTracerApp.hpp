@@ -41,6 +41,7 @@ struct PathTracerApp {
 private:
   bool loadNifModels(std::size_t numDevices, const std::string& assetPath);
   pt_env_guide envGuideRequest(const std::string& size, float alpha);
+  pt_env_guide_auto envGuideAutoRequest(const std::string& size, float alpha, std::uint32_t supersample);
   void initialiseState(std::uint32_t imageWidth, std::uint32_t imageHeight);
   /// One call on every device, each from its own thread (devices run concurrently and exchange no ray data,
   /// PathTracerApp.cpp:205-252); throws with the first device's message on failure.
@@ -92,6 +93,8 @@ private:
   std::int32_t envMapFilterMode = 1;    ///< --env-map-filter (PT_ENV_FILTER_*)
   env_map::Image envGuide;              ///< --env-guide: the image every handle's diffuse bounces are guided by (empty: unguided; "map": envMap is used)
   bool envGuideFromMap = false;         ///< --env-guide map
+  bool envGuideFromEnv = false;         ///< --env-guide env: no image, the library builds the guide from the environment in force
+  std::uint32_t envGuideSupersample = 2; ///< --env-guide-supersample
   std::uint32_t envGuideRows = 0, envGuideCols = 0;   ///< --env-guide-size (default: the largest powers of two that fit)
   float envGuideAlpha = 0.5f;           ///< --env-guide-alpha
   float lightGuideBeta = 0.f;           ///< --light-guide-beta (0 = off)

@@ -42,7 +42,9 @@ static OptionMap parseOptions(int argc, char** argv, const std::vector<OptionSpe
     throw std::runtime_error("Show help");
   }
   // --train-nif trains instead of rendering: it needs neither --outfile nor --assets
-  for (auto& s : specs) if (s.required && !vm.has(s.name) && !nif_train::requested(vm)) throw std::runtime_error("the option '--" + s.name + "' is required but missing");
+  // ... and --env-guide env without any environment gets the library's own message from PathTracerApp::init, not this one
+  const bool guideFromEnv = vm.str("env-guide") == "env";
+  for (auto& s : specs) if (s.required && !vm.has(s.name) && !nif_train::requested(vm) && !(guideFromEnv && s.name == "assets")) throw std::runtime_error("the option '--" + s.name + "' is required but missing");
   if (!vm.str("save-exe").empty() && !vm.str("load-exe").empty())
     throw std::logic_error("You can not set both save-exe and load-exe.");   // main.cpp:63-66
   return vm;

@@ -43,7 +43,8 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_train_get_encode_params", "pt_nif_train_export", "pt_nif_train_install", "pt_nif_train_end",
            "pt_nif_train_batch", "pt_nif_train_gradients", "pt_nif_train_default_precision", "pt_nif_train_set_precision",
            "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval",
-           "pt_set_light_guide", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval"]
+           "pt_set_light_guide", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
+           "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
@@ -113,6 +114,27 @@ class EnvGuide(C.Structure):
 
 
 assert C.sizeof(EnvGuide) == 32   # pt_env_guide
+
+
+class EnvGuideAuto(C.Structure):
+    """pt_env_guide_auto (include/ptmi.h): grid, supersampling, alpha and follow of a guide built from the environment in force."""
+    _fields_ = [("struct_size", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32), ("supersample", C.c_uint32),
+                ("alpha", C.c_float), ("follow", C.c_int32)]
+
+
+class EnvGuideInfo(C.Structure):
+    """pt_env_guide_info (include/ptmi.h): the environment guide in force and how it was built."""
+    _fields_ = [("struct_size", C.c_uint32), ("set", C.c_int32), ("source", C.c_int32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+                ("supersample", C.c_uint32), ("alpha", C.c_float), ("follow", C.c_int32), ("stale", C.c_int32),
+                ("rebuilds", C.c_uint64), ("clamped", C.c_uint64), ("build_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+        d.update(set=bool(self.set), source="environment" if self.source else "image", follow=bool(self.follow), stale=bool(self.stale))
+        return d
+
+
+assert C.sizeof(EnvGuideAuto) == 24 and C.sizeof(EnvGuideInfo) == 64   # pt_env_guide_auto, pt_env_guide_info
 
 
 class LightGuide(C.Structure):
@@ -378,6 +400,9 @@ def load_library(diag=False):
     L.pt_set_env_guide.argtypes = [C.c_void_p, C.POINTER(EnvGuide)]
     L.pt_env_guide_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.pt_env_guide_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.pt_set_env_guide_from_environment.argtypes = [C.c_void_p, C.POINTER(EnvGuideAuto)]
+    L.pt_get_env_guide_info.argtypes = [C.c_void_p, C.POINTER(EnvGuideInfo)]
+    L.pt_get_env_guide_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.pt_set_light_guide.argtypes = [C.c_void_p, C.POINTER(LightGuide)]
     L.pt_get_light_guide_info.argtypes = [C.c_void_p, C.POINTER(LightGuideInfo)]
     L.pt_light_guide_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -532,6 +557,32 @@ class Renderer:
         g.alpha = float(alpha)
         g.bgr = bgr.ctypes.data
         self._check(self._lib.pt_set_env_guide(self.handle, C.byref(g)))
+
+    def set_env_guide_from_environment(self, rows=256, cols=512, alpha=0.5, supersample=2, follow=True):
+        """Guide diffuse bounces by the environment in force -- the NIF, the map or the constant -- with no image in host memory
+        (include/ptmi.h, pt_set_env_guide_from_environment): the guide of the image the environment gives at supersample x
+        supersample points per cell of a rows x cols grid, its masses summed on the device.  follow: every later
+        init_nif_weights, set_env_map, set_constant_env and trainer install rebuilds it from the new environment.  A rejected
+        call (PtError) leaves the previous guide in force."""
+        a = EnvGuideAuto(C.sizeof(EnvGuideAuto), int(rows), int(cols), int(supersample), float(alpha), int(follow))
+        self._check(self._lib.pt_set_env_guide_from_environment(self.handle, C.byref(a)))
+
+    def env_guide_info(self):
+        """pt_get_env_guide_info as a dict: set, source ("image" or "environment"), rows, cols, supersample, alpha as used,
+        follow, stale, rebuilds, clamped, build_ms."""
+        info = EnvGuideInfo()
+        info.struct_size = C.sizeof(EnvGuideInfo)
+        self._check(self._lib.pt_get_env_guide_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
+    def env_guide_tables(self):
+        """The tables the device holds (pt_get_env_guide_tables): (threshold uint32 [n], alias uint32 [n], q float32 [n]),
+        n = rows x cols in cell order."""
+        info = self.env_guide_info()
+        n = info["rows"] * info["cols"]
+        thr, alias, q = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.float32)
+        self._check(self._lib.pt_get_env_guide_tables(self.handle, thr.ctypes.data, alias.ctypes.data, q.ctypes.data, n))
+        return thr, alias, q
 
     def env_guide_sample(self, g1, g2, g3):
         """The kernels' own guide sampling over caller words (pt_env_guide_sample): (uv float32 [n, 2], cell uint32 [n])."""
