@@ -182,7 +182,8 @@ int pt_calibrate_nif(pt_handle h, uint32_t launches, double* ms_per_launch, uint
  * (PathTracerApp.cpp:147-198).  The NIF output of an escaped path depends on its (u, v) alone (the azimuth is folded in by
  * PreProcessEscapedRays, codelets.cpp:343-347; the path's throughput multiplies the decoded BGR afterwards, one fp32 multiply
  * per channel), and camera rays and primary samples are half, so many escaped paths carry bit-identical (u, v).
- *   PT_NIF_SHARE_OFF    every escaped path is one NIF row (the default; the library runs exactly as without this API).
+ *   PT_NIF_SHARE_OFF    every escaped path is one NIF row: the library runs exactly as without this API -- same kernels,
+ *                       launches, streams and events.
  *   PT_NIF_SHARE_BATCH  paths of one kernel batch whose queue entries have bit-identical (u, v) share one NIF evaluation.
  *   PT_NIF_SHARE_STEP   the same across all batches of one pt_path_trace.
  * Exact: the key is the 64 raw bits of (u, v), with no tolerance; each distinct key is evaluated once by the unchanged NIF
@@ -190,9 +191,22 @@ int pt_calibrate_nif(pt_handle h, uint32_t launches, double* ms_per_launch, uint
  * same single fp32 multiply the per-path NIF head does.  So every accumulator, record, resident-film value and HDR tile is
  * bit-identical to sharing off, for any option set and any table capacity.  A key that finds no table slot (full table, or
  * the key equals the table's empty marker) is evaluated on its own and counted in `overflowed`: never dropped.
+ * THE DEFAULT IS AUTOMATIC.  A handle on which neither pt_set_nif_sharing nor pt_set_nif_memo was ever called runs PT_NIF_SHARE_STEP in every
+ * pt_path_trace for which all of these hold, and PT_NIF_SHARE_OFF otherwise:
+ *   - the environment is a NIF model (pt_upload_nif), not a constant and not an environment map;
+ *   - the memo (pt_set_nif_memo) is off;
+ *   - the step's distinct-queue store has fewer than 2^31 entries, and what the step has to allocate -- the table (12 bytes per
+ *     slot), the store (20 bytes per queue slot of every batch) and the owner maps, less what the handle already holds -- is at
+ *     most a quarter of the free device memory at that moment.
+ * In automatic mode an allocation that fails all the same is no error: the buffers are given back and the handle runs off
+ * from then on.  The result is the same bytes either way; `mode` of pt_nif_sharing_stats says what really ran.  The first
+ * call of pt_set_nif_sharing, with any mode, ends the automatic choice for the handle: PT_NIF_SHARE_OFF then gives the
+ * unshared step whatever the environment, and a sharing mode reports its errors as described below.
+ * A valid pt_set_nif_memo call, with 0 too, ends it as well: a caller that manages the memo gets the sharing mode it set, which
+ * is PT_NIF_SHARE_OFF until it says otherwise, so turning the memo off again gives the unshared step as before.
  * No table survives a step: every pt_path_trace starts empty, so hot-swapping the NIF (pt_upload_nif), a new azimuth
  * (pt_set_render_settings) and a mode switch between steps need no invalidation.
- * pt_set_nif_sharing takes effect at the next pt_path_trace.  The first switch to a sharing mode allocates the device table
+ * pt_set_nif_sharing takes effect at the next pt_path_trace.  The first explicit switch to a sharing mode allocates the device table
  * (sized from the batch capacity and the free memory) and the distinct-queue store: PT_ERR_OUT_OF_MEMORY leaves the mode
  * off.  A step-scope step with more batches than the store holds grows it (pt_path_trace may then return
  * PT_ERR_OUT_OF_MEMORY).  A bad mode or a NULL handle is PT_ERR_INVALID_ARGUMENT.
@@ -202,7 +216,7 @@ int pt_calibrate_nif(pt_handle h, uint32_t launches, double* ms_per_launch, uint
 enum { PT_NIF_SHARE_OFF = 0, PT_NIF_SHARE_BATCH = 1, PT_NIF_SHARE_STEP = 2 };
 typedef struct pt_nif_sharing_stats {
   uint32_t struct_size;          /* sizeof(pt_nif_sharing_stats), set by the caller */
-  int32_t mode;                  /* mode the last path_trace ran with (PT_NIF_SHARE_OFF with a constant environment) */
+  int32_t mode;                  /* mode the last path_trace really ran with, chosen or automatic (PT_NIF_SHARE_OFF with a constant environment) */
   uint64_t escaped;              /* = pt_stats.escaped */
   uint64_t evaluations;          /* NIF rows executed by the last path_trace */
   uint64_t overflowed;           /* entries evaluated alone because no table slot was free */

@@ -50,6 +50,7 @@
 #include "ptmi_light_guide.h"
 #include "ptmi_nif_train_check.h"
 #include "ptmi_step_plan.h"
+#include "ptmi_share_plan.h"
 #include "ptmi_context.h"
 #include "ptmi_nif_pack.h"
 #include "ptmi_nif_launch.h"
@@ -477,17 +478,17 @@ static void forget_replay_state(pt_handle h) {   // pt_calibrate_nif may only re
 // ---- exact sharing of NIF evaluations: buffers (pt_set_nif_sharing allocates them, a step-scope step with more batches
 // than store regions grows the store) and the S / E launches of one batch (pt_nif_share.h)
 
-// Table capacity: twice the queue slots of the table's scope -- one batch, or every batch of a step -- so the load factor
-// stays <= 1/2 even if every entry is distinct; a power of two, at most 1/8 of the free device memory and 2^30 slots (owner[]
-// flags a slot with bit 31).  A full table is not an error: the keys that find no slot are evaluated alone.
+static uint64_t free_device_bytes() {
+  size_t free_b = 0, total_b = 0;
+  return hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (uint64_t)free_b : ptshare::kFreeUnknown;
+}
+
+// Table capacity: the worst case of the table's scope -- one batch, or every batch of a step (ptmi_share_plan.h: load factor
+// <= 1/2 even if every entry is distinct, at most 1/8 of the free device memory and 2^30 slots).  A full table is not an
+// error: the keys that find no slot are evaluated alone.
 static uint32_t share_table_slots(pt_handle h, uint64_t entries) {
   if (h->share_diag_slots) return h->share_diag_slots;
-  uint64_t want = 1024;
-  while (want < 2ull * entries && want < (1ull << 30)) want <<= 1;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-    while (want > 1024 && want * 12 > free_b / 8) want >>= 1;
-  return (uint32_t)want;
+  return ptshare::worst_case_slots(entries, free_device_bytes());
 }
 
 static int ensure_share_counts(pt_handle h, size_t batches) {
@@ -548,6 +549,45 @@ static int alloc_group_buffers(pt_handle h) {
 static int alloc_share_buffers(pt_handle h) {
   if (int rc = ensure_share_table(h, h->queue_cap)) return rc;
   return alloc_group_buffers(h);
+}
+
+static void free_share_buffers(pt_handle h) {   // (the counts and the overflow counter are a few bytes: they stay)
+  h->d_share_keys.reset(); h->d_share_vals.reset();
+  h->share_slots = 0;
+  h->d_share_u.reset(); h->d_share_v.reset(); h->d_share_bgr.reset();
+  h->share_regions = 0;
+  for (auto& o : h->d_share_owner) o.reset();
+}
+
+static int ensure_memo_slot_map(pt_handle h);
+
+// The buffers of a grouped step at the step's size (the table's only without the memo, which has its own).
+static int ensure_group_buffers(pt_handle h, bool memo, bool step_scope, size_t batches) {
+  if (int rc = ensure_share_counts(h, batches)) return rc;
+  if (int rc = ensure_share_store(h, step_scope ? batches : 2)) return rc;
+  if (memo) return ensure_memo_slot_map(h);
+  return ensure_share_table(h, (step_scope ? batches : 1) * (uint64_t)h->queue_cap);
+}
+
+// The mode of a handle on which neither pt_set_nif_sharing nor pt_set_nif_memo was ever called: step scope if the environment is a NIF, the memo is off
+// and what the step would allocate fits the budget of ptmi_share_plan.h (a quarter of the free device memory); otherwise, and
+// if an allocation fails all the same, off -- exactly the unshared step, and no error.  Buffers the handle already holds
+// (an earlier step, the test build's forced capacity) count as held.
+static int32_t auto_share_mode(pt_handle h, size_t batches) {
+  if (h->env_const || h->env_map || h->memo_slots || h->share_auto_failed) return PT_NIF_SHARE_OFF;   // (memo_slots: the test build's hook; pt_set_nif_memo ends the choice)
+  const uint64_t free_b = free_device_bytes();
+  const uint64_t slots = h->share_diag_slots ? h->share_diag_slots : ptshare::worst_case_slots(batches * (uint64_t)h->queue_cap, free_b);
+  ptshare::Held held;
+  held.table_slots = h->d_share_keys ? (h->share_diag_slots ? slots : h->share_slots) : 0;
+  held.store_regions = h->share_regions;
+  held.owner_maps = (h->d_share_owner[0] ? 1 : 0) + (h->d_share_owner[1] ? 1 : 0);
+  if (!ptshare::auto_fits(slots, batches, h->queue_cap, held, free_b)) return PT_NIF_SHARE_OFF;
+  if (ensure_group_buffers(h, false, true, batches) == PT_OK && alloc_group_buffers(h) == PT_OK) return PT_NIF_SHARE_STEP;   // (the step's sizes first: nothing is allocated twice)
+  (void)hipGetLastError();   // an allocation failed: give back what was taken and run unshared from now on
+  free_share_buffers(h);
+  h->share_auto_failed = true;
+  h->error.clear();
+  return PT_NIF_SHARE_OFF;
 }
 
 // ---- persistent memo of decoded NIF values (pt_set_nif_memo, pt_nif_memo.h): buffers, generations, the per-step passes
@@ -652,13 +692,7 @@ struct Batch {
 // Before the first batch of a grouped step: the buffers at the step's size, and the counts, the overflow counter and a
 // step-scope table cleared on the trace stream, where S runs (after e_begin: part of the step).
 static int prepare_group_store(pt_handle h, const StepMode& mode, size_t batches) {
-  if (int rc = ensure_share_counts(h, batches)) return rc;
-  if (int rc = ensure_share_store(h, mode.step_scope() ? batches : 2)) return rc;
-  if (mode.memo) {
-    if (int rc = ensure_memo_slot_map(h)) return rc;
-  } else if (int rc = ensure_share_table(h, (mode.share == PT_NIF_SHARE_STEP ? batches : 1) * (uint64_t)h->queue_cap)) {
-    return rc;
-  }
+  if (int rc = ensure_group_buffers(h, mode.memo, mode.step_scope(), batches)) return rc;
   PT_HIP(hipMemsetAsync(h->d_share_count, 0, batches * 4, h->trace_stream));
   PT_HIP(hipMemsetAsync(h->d_share_over, 0, 8, h->trace_stream));
   if (!mode.memo && mode.share == PT_NIF_SHARE_STEP)   // one table for the step
@@ -842,7 +876,8 @@ static int enqueue_path_trace(pt_handle h) {
   PT_HIP(hipStreamWaitEvent(h->trace_stream, e_begin, 0));   // counters memset and earlier work on `stream`
   const std::vector<uint32_t> deal = ptplan::batch_iterations(h->samples_per_step, h->iters_per_batch, h->first_batch_iters, h->env_const);
   const uint32_t batches = (uint32_t)deal.size();
-  const StepMode mode{h->env_const ? 0 : h->share_mode, !h->env_const && h->memo_slots != 0};
+  const int32_t share = h->share_mode_set ? h->share_mode : auto_share_mode(h, batches);   // (an explicit off: no look at the memory)
+  const StepMode mode{h->env_const ? 0 : share, !h->env_const && h->memo_slots != 0};
   h->share_mode_last = mode.share;
   h->memo_ran = mode.memo;
   if (mode.grouped())
@@ -986,9 +1021,10 @@ int pt_set_nif_sharing(pt_handle h, int32_t mode) {
     return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_nif_sharing: mode must be PT_NIF_SHARE_OFF, _BATCH or _STEP");
   if (mode != PT_NIF_SHARE_OFF) {
     PT_HIP(hipSetDevice(h->cfg.device));
-    if (int rc = alloc_share_buffers(h)) { h->share_mode = PT_NIF_SHARE_OFF; return rc; }
+    if (int rc = alloc_share_buffers(h)) { h->share_mode = PT_NIF_SHARE_OFF; h->share_mode_set = true; return rc; }
   }
   h->share_mode = mode;
+  h->share_mode_set = true;
   return PT_OK;
 }
 
@@ -1011,6 +1047,7 @@ int pt_set_nif_memo(pt_handle h, uint64_t max_bytes) {
   if (max_bytes == 0) {
     PT_HIP(hipStreamSynchronize(h->stream));
     free_memo_buffers(h);
+    h->share_mode_set = true;   // a caller that manages the memo has chosen: the sharing mode is what pt_set_nif_sharing said (off)
     return PT_OK;
   }
   // table + retain list = 48 bytes per slot; a power of two, at most 2^30 slots
@@ -1019,6 +1056,7 @@ int pt_set_nif_memo(pt_handle h, uint64_t max_bytes) {
   while (slots < (1ull << 30) && 2 * slots * per_slot <= max_bytes) slots <<= 1;
   if (slots * per_slot > max_bytes || slots < 1024)
     return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_nif_memo: max_bytes must be 0 or at least 48 KiB (1024 slots of 48 bytes)");
+  h->share_mode_set = true;   // as above: with or without the memo, this handle no longer chooses its sharing mode itself
   if (slots == h->memo_slots) return PT_OK;   // same capacity: the entries stay
   return alloc_memo(h, (uint32_t)slots);
 }

@@ -250,6 +250,8 @@ struct pt_context {
   // exact sharing of NIF evaluations (pt_set_nif_sharing, pt_nif_share.h).  Nothing here survives a step: the table is
   // cleared at the start of every batch (PT_NIF_SHARE_BATCH) or step (PT_NIF_SHARE_STEP), the counts at every step.
   int32_t share_mode = 0;                    // requested: taken up by the next pt_path_trace
+  bool share_mode_set = false;               // pt_set_nif_sharing or pt_set_nif_memo was called; until then the step chooses (auto_share_mode)
+  bool share_auto_failed = false;            // the automatic default could not allocate: off until pt_set_nif_sharing
   int32_t share_mode_last = 0;               // what the last pt_path_trace ran with (0 also for a constant environment)
   DevBuf<unsigned long long> d_share_keys;
   DevBuf<uint32_t> d_share_vals;

@@ -692,7 +692,9 @@ class Renderer:
 
     def set_nif_sharing(self, mode):
         """Exact sharing of NIF evaluations between paths with bit-identical (u, v): "off", "batch" or "step"
-        (include/ptmi.h, pt_set_nif_sharing).  Takes effect at the next path_trace."""
+        (include/ptmi.h, pt_set_nif_sharing).  Takes effect at the next path_trace.  A Renderer on which this is never called
+        chooses per step: "step" with a NIF environment, the memo off and room in device memory, otherwise "off"; the first
+        call, "off" included, ends that choice, and so does set_nif_memo.  nif_sharing_stats()["mode"] says what a step really ran."""
         if mode not in NIF_SHARE_MODES:
             raise ValueError("NIF sharing mode must be one of %s, got %r" % (sorted(NIF_SHARE_MODES), mode))
         self._check(self._lib.pt_set_nif_sharing(self.handle, NIF_SHARE_MODES[mode]))

@@ -1,11 +1,13 @@
 """NIF-evaluation sharing (pt_set_nif_sharing) against the headline workload, in ONE process, modes alternating.
 
 C2: 1104 x 1000, 300 spp per step, depth 8, synthetic 6 x 320 NIF with the urban_alley decode constants, tile-order worklist
-(bench.py's shape at one GPU).  Every round runs one step in each mode (off, batch, step) on its own handle, so a drifting
-clock touches all modes alike; after --warmup rounds, --steps timed rounds.  Prints one JSON line per mode: M path-samples/s,
-escaped / evaluations / overflowed per step, NIF and sharing device ms per step, and whether the film (pt_gather_hdr of the
-resident film after the last step) is bit-identical to off.  --configs c2,c3,c5 adds the 4K deep-path and wide-NIF shapes.
-Not bench.py: the headline keeps measuring the reference's amount of work (sharing off).
+(bench.py's shape at one GPU).  Every round runs one step in each mode on its own handle, so a drifting clock touches all
+modes alike; after --warmup rounds, --steps timed rounds.  Prints one JSON line per mode: M path-samples/s, escaped /
+evaluations / overflowed per step, NIF and sharing device ms per step, and whether the film (pt_gather_hdr of the resident
+film after the last step) is bit-identical to off.  --configs c2,c3,c5 adds the 4K deep-path and wide-NIF shapes.
+--modes picks among
+  off, batch, step   pt_set_nif_sharing with that mode;
+  default            a handle on which pt_set_nif_sharing is never called (bench.py's handle: the automatic default).
 """
 import argparse
 import hashlib
@@ -24,9 +26,10 @@ CONFIGS = {   # name: (width, height, spp, depth, hidden, layers) -- BASELINE.js
     "c5": (1104, 1000, 64, 8, 1024, 8),
 }
 MODES = ("off", "batch", "step")
+ALL_MODES = MODES + ("default",)
 
 
-def run(name, warmup, steps):
+def run(name, warmup, steps, MODES=MODES):
     import torch
     W, H, spp, depth, hidden, nlayers = CONFIGS[name]
     meta = nif_assets.URBAN_ALLEY_META
@@ -39,7 +42,8 @@ def run(name, warmup, steps):
         r = ptmi.Renderer(W, H, max_work_items=work.size, max_path_length=depth, stream=stream)
         r.init_nif_weights(layers, meta["embedding_dimension"], meta["max"], nif_assets.folded_mean())
         r.init_render_settings(seed=1, aa_noise_scale=0.3, fov_degrees=90.0, samples_per_step=spp)
-        r.set_nif_sharing(mode)
+        if mode != "default":
+            r.set_nif_sharing(mode)
         r.setup(work.copy())
         handles[mode] = r
     acc = {m: {"sec": 0.0, "paths": 0, "escaped": 0, "evaluations": 0, "overflowed": 0, "nif_ms": 0.0, "share_ms": 0.0,
@@ -61,6 +65,7 @@ def run(name, warmup, steps):
             for k in ("escaped", "evaluations", "overflowed", "share_ms"):
                 a[k] += sh[k]
             a["table_slots"] = sh["table_slots"]
+            a["ran"] = sh["mode"]
     films = {}
     for mode in MODES:
         r = handles[mode]
@@ -69,7 +74,7 @@ def run(name, warmup, steps):
     for mode in MODES:
         a = acc[mode]
         print(json.dumps({
-            "config": name, "mode": mode, "width": W, "height": H, "spp": spp, "depth": depth, "nif": "%dx%d" % (nlayers, hidden),
+            "config": name, "mode": mode, "ran": a.get("ran"), "width": W, "height": H, "spp": spp, "depth": depth, "nif": "%dx%d" % (nlayers, hidden),
             "timed_steps": steps, "Mpaths_per_s": round(a["paths"] / a["sec"] / 1e6, 1),
             "device_ms_per_step": round(a["total_ms"] / steps, 2),
             "escaped_per_step": a["escaped"] // steps, "evaluations_per_step": a["evaluations"] // steps,
@@ -86,10 +91,14 @@ def main():
     ap.add_argument("--configs", default="c2")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--modes", default=",".join(MODES), help="comma-separated, from %s; off is always run" % ", ".join(ALL_MODES))
     args = ap.parse_args()
+    modes = tuple(dict.fromkeys(["off"] + args.modes.split(",")))
+    if any(m not in ALL_MODES for m in modes):
+        raise SystemExit("--modes: choose from %s" % ", ".join(ALL_MODES))
     ok = True
     for name in args.configs.split(","):
-        ok = run(name, args.warmup, args.steps) and ok
+        ok = run(name, args.warmup, args.steps, modes) and ok
     if not ok:
         raise SystemExit("film differs between sharing modes")
 
