@@ -1,8 +1,10 @@
 // ptmi.hip -- implementation of include/ptmi.h.  One translation unit: this file holds the entry points (create / upload /
-// setup / path_trace / read_results ...) and the stages of a step; ptmi_step_plan.h the step's integer arithmetic (batch deal,
-// trace grid, index reciprocal: plain C++), ptmi_context.h the buffer owners and the per-handle state, ptmi_nif_pack.h the NIF
-// normalisation and weight packing, ptmi_nif_launch.h the queue bindings, the kernel launchers and the step's event allocator,
-// ptmi_film_comm.h the resident film, tile costs and the RCCL hand-off, ptmi_denoise.h the feature buffers and the denoiser.
+// setup / path_trace / read_results ...) and the stages T, N and A of a step; ptmi_step_plan.h the step's integer arithmetic
+// (batch deal, trace grid, index reciprocal: plain C++), ptmi_share_plan.h that of NIF sharing and the memo (owner word, table
+// sizes: plain C++), ptmi_context.h the buffer owners and the per-handle state, ptmi_nif_pack.h the NIF normalisation and weight
+// packing, ptmi_nif_launch.h the queue bindings, the kernel launchers and the step's event allocator, ptmi_nif_group.h NIF
+// sharing and the memo (buffers, the step's mode, the stages S and E, their entry points), ptmi_film_comm.h the resident film,
+// tile costs and the RCCL hand-off, ptmi_denoise.h the feature buffers and the denoiser, ptmi_nif_train.h the NIF trainer.
 //
 // Build (see __graft_entry__.build): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // -ffp-contract=off is part of the numerical contract (pt_device_math.h).
@@ -30,12 +32,12 @@
 #include <vector>
 
 #include "ptmi.h"
+#include "ptmi_share_plan.h"
 #include "pt_nif.h"
 #include "pt_nif_gemm.h"
 #include "pt_nif_f32.h"
 #include "pt_trace.h"
-#include "pt_nif_share.h"
-#include "pt_nif_memo.h"
+#include "pt_nif_group.h"
 #include "pt_envmap.h"
 #include "pt_env_guide.h"
 #include "pt_env_guide_build.h"
@@ -50,7 +52,6 @@
 #include "ptmi_light_guide.h"
 #include "ptmi_nif_train_check.h"
 #include "ptmi_step_plan.h"
-#include "ptmi_share_plan.h"
 #include "ptmi_context.h"
 #include "ptmi_nif_pack.h"
 #include "ptmi_nif_launch.h"
@@ -437,7 +438,7 @@ int pt_setup(pt_handle h, const pt_trace_record* work, size_t n) {
 
 }  // extern "C"
 
-// ---- what a step is made of: the buffers of the environment, of NIF sharing and of the memo, and the stages of pt_path_trace
+// ---- what a step is made of: the environment's map and the stages of pt_path_trace
 
 // The map stops being the environment (replaced by a NIF or a constant, or the handle goes): its device copy is freed.  No
 // kernel of the handle is running: every entry point that launches on the texels waits for its stream before it returns.
@@ -475,209 +476,11 @@ static void forget_replay_state(pt_handle h) {   // pt_calibrate_nif may only re
   for (auto& B : h->bb) { B.last_paths = 0; B.last_regions = 0; B.last_region_cap = 0; B.share_batch = -1; }
 }
 
-// ---- exact sharing of NIF evaluations: buffers (pt_set_nif_sharing allocates them, a step-scope step with more batches
-// than store regions grows the store) and the S / E launches of one batch (pt_nif_share.h)
-
-static uint64_t free_device_bytes() {
-  size_t free_b = 0, total_b = 0;
-  return hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (uint64_t)free_b : ptshare::kFreeUnknown;
-}
-
-// Table capacity: the worst case of the table's scope -- one batch, or every batch of a step (ptmi_share_plan.h: load factor
-// <= 1/2 even if every entry is distinct, at most 1/8 of the free device memory and 2^30 slots).  A full table is not an
-// error: the keys that find no slot are evaluated alone.
-static uint32_t share_table_slots(pt_handle h, uint64_t entries) {
-  if (h->share_diag_slots) return h->share_diag_slots;
-  return ptshare::worst_case_slots(entries, free_device_bytes());
-}
-
-static int ensure_share_counts(pt_handle h, size_t batches) {
-  if (batches <= h->share_count_cap) return PT_OK;
-  h->share_count_cap = 0;
-  PT_HIP(dev_alloc(h->d_share_count, batches));
-  PT_HIP(dev_alloc(h->h_share_count, batches));
-  h->share_count_cap = batches;
-  return PT_OK;
-}
-
-// store regions of queue_cap entries each: (u, v) of the distinct queue and its decoded BGR.  Store indices stay below 2^31.
-static int ensure_share_store(pt_handle h, size_t regions) {
-  if (regions <= h->share_regions) return PT_OK;
-  if (regions * h->queue_cap >= (size_t)ptd::kShareSlotFlag)
-    return fail(h, PT_ERR_OUT_OF_MEMORY, "NIF sharing: the step's distinct queues would exceed 2^31 entries (fewer samples per step)");
-  PT_HIP(hipStreamSynchronize(h->stream));
-  h->d_share_u.reset(); h->d_share_v.reset(); h->d_share_bgr.reset();   // all three go before the first comes back: they are large
-  h->share_regions = 0;
-  PT_HIP(dev_alloc(h->d_share_u, regions * h->queue_cap));
-  PT_HIP(dev_alloc(h->d_share_v, regions * h->queue_cap));
-  PT_HIP(dev_alloc(h->d_share_bgr, 3 * regions * h->queue_cap));
-  h->share_regions = regions;
-  return PT_OK;
-}
-
-// The table with exactly `slots` slots, the stream drained first.
-static int alloc_share_table(pt_handle h, uint32_t slots) {
-  PT_HIP(hipStreamSynchronize(h->stream));
-  h->d_share_keys.reset(); h->d_share_vals.reset();
-  h->share_slots = 0;
-  if (!slots) return PT_OK;
-  PT_HIP(dev_alloc(h->d_share_keys, slots));
-  PT_HIP(dev_alloc(h->d_share_vals, slots));
-  h->share_slots = slots;
-  return PT_OK;
-}
-
-// (re)allocates the table if its scope needs more slots than it has (never for a capacity forced by the test build)
-static int ensure_share_table(pt_handle h, uint64_t entries) {
-  const uint32_t slots = share_table_slots(h, entries);
-  if (h->d_share_keys && (slots <= h->share_slots || h->share_diag_slots)) return PT_OK;
-  return alloc_share_table(h, slots);
-}
-
-// What sharing and the memo both need besides their table: the owner maps, the overflow counter, counts and a store.
-static int alloc_group_buffers(pt_handle h) {
-  for (auto& o : h->d_share_owner)
-    if (!o) PT_HIP(dev_alloc(o, h->queue_cap));
-  if (!h->d_share_over) {
-    PT_HIP(dev_alloc(h->d_share_over, 1));
-    PT_HIP(dev_alloc(h->h_share_over, 1));
-  }
-  if (int rc = ensure_share_counts(h, 64)) return rc;
-  return ensure_share_store(h, 2);
-}
-
-static int alloc_share_buffers(pt_handle h) {
-  if (int rc = ensure_share_table(h, h->queue_cap)) return rc;
-  return alloc_group_buffers(h);
-}
-
-static void free_share_buffers(pt_handle h) {   // (the counts and the overflow counter are a few bytes: they stay)
-  h->d_share_keys.reset(); h->d_share_vals.reset();
-  h->share_slots = 0;
-  h->d_share_u.reset(); h->d_share_v.reset(); h->d_share_bgr.reset();
-  h->share_regions = 0;
-  for (auto& o : h->d_share_owner) o.reset();
-}
-
-static int ensure_memo_slot_map(pt_handle h);
-
-// The buffers of a grouped step at the step's size (the table's only without the memo, which has its own).
-static int ensure_group_buffers(pt_handle h, bool memo, bool step_scope, size_t batches) {
-  if (int rc = ensure_share_counts(h, batches)) return rc;
-  if (int rc = ensure_share_store(h, step_scope ? batches : 2)) return rc;
-  if (memo) return ensure_memo_slot_map(h);
-  return ensure_share_table(h, (step_scope ? batches : 1) * (uint64_t)h->queue_cap);
-}
-
-// The mode of a handle on which neither pt_set_nif_sharing nor pt_set_nif_memo was ever called: step scope if the environment is a NIF, the memo is off
-// and what the step would allocate fits the budget of ptmi_share_plan.h (a quarter of the free device memory); otherwise, and
-// if an allocation fails all the same, off -- exactly the unshared step, and no error.  Buffers the handle already holds
-// (an earlier step, the test build's forced capacity) count as held.
-static int32_t auto_share_mode(pt_handle h, size_t batches) {
-  if (h->env_const || h->env_map || h->memo_slots || h->share_auto_failed) return PT_NIF_SHARE_OFF;   // (memo_slots: the test build's hook; pt_set_nif_memo ends the choice)
-  const uint64_t free_b = free_device_bytes();
-  const uint64_t slots = h->share_diag_slots ? h->share_diag_slots : ptshare::worst_case_slots(batches * (uint64_t)h->queue_cap, free_b);
-  ptshare::Held held;
-  held.table_slots = h->d_share_keys ? (h->share_diag_slots ? slots : h->share_slots) : 0;
-  held.store_regions = h->share_regions;
-  held.owner_maps = (h->d_share_owner[0] ? 1 : 0) + (h->d_share_owner[1] ? 1 : 0);
-  if (!ptshare::auto_fits(slots, batches, h->queue_cap, held, free_b)) return PT_NIF_SHARE_OFF;
-  if (ensure_group_buffers(h, false, true, batches) == PT_OK && alloc_group_buffers(h) == PT_OK) return PT_NIF_SHARE_STEP;   // (the step's sizes first: nothing is allocated twice)
-  (void)hipGetLastError();   // an allocation failed: give back what was taken and run unshared from now on
-  free_share_buffers(h);
-  h->share_auto_failed = true;
-  h->error.clear();
-  return PT_NIF_SHARE_OFF;
-}
-
-// ---- persistent memo of decoded NIF values (pt_set_nif_memo, pt_nif_memo.h): buffers, generations, the per-step passes
-static void free_memo_buffers(pt_handle h) {
-  h->d_memo.reset(); h->d_memo_list.reset(); h->d_memo_slot.reset(); h->d_memo_ctr.reset(); h->h_memo_ctr.reset();
-  h->memo_slots = 0; h->memo_slot_regions = 0; h->memo_occupied = 0;
-}
-
-// every value in the memo is forgotten: the table is cleared before the next lookup
-static void memo_new_generation(pt_handle h) {
-  h->memo_generation += 1;
-  h->memo_clear = true;
-  h->memo_occupied = 0;
-}
-
-// the publish map follows the step store (one entry per store index)
-static int ensure_memo_slot_map(pt_handle h) {
-  if (h->memo_slot_regions >= h->share_regions) return PT_OK;
-  PT_HIP(hipStreamSynchronize(h->stream));
-  h->memo_slot_regions = 0;
-  PT_HIP(dev_alloc(h->d_memo_slot, h->share_regions * h->queue_cap));
-  h->memo_slot_regions = h->share_regions;
-  return PT_OK;
-}
-
-static int alloc_memo_buffers(pt_handle h, uint32_t slots) {
-  PT_HIP(dev_alloc(h->d_memo, slots));
-  PT_HIP(dev_alloc(h->d_memo_list, std::max<size_t>(1, slots / 2)));
-  PT_HIP(dev_alloc(h->d_memo_ctr, ptd::kMemoCounters));
-  PT_HIP(dev_alloc(h->h_memo_ctr, ptd::kMemoCounters));
-  if (int rc = alloc_group_buffers(h)) return rc;
-  return ensure_memo_slot_map(h);
-}
-
-// A memo of `slots` slots (a power of two <= 2^30), its retain list and what the step-scope path needs besides the sharing
-// table; a failure leaves the memo off (h->error names the failing call).
-static int alloc_memo(pt_handle h, uint32_t slots) {
-  PT_HIP(hipStreamSynchronize(h->stream));
-  free_memo_buffers(h);
-  if (int rc = alloc_memo_buffers(h, slots)) { free_memo_buffers(h); return rc; }
-  h->memo_slots = slots;
-  h->memo_clear = true;   // cleared on the stream ahead of the first lookup
-  return PT_OK;
-}
-
-// Memo prologue of a step, on the trace stream ahead of the first lookup: the step's counters, and the table cleared (new
-// generation) or thinned out (retain pass: occupancy above 1/2 of the slots after the last step).
-static int enqueue_memo_prologue(pt_handle h) {
-  hipStream_t s = h->trace_stream;
-  PT_HIP(hipMemsetAsync(h->d_memo_ctr + ptd::kMemoServedCount, 0, (ptd::kMemoCounters - 1) * 8, s));
-  const uint32_t last = h->memo_step;
-  h->memo_step = h->memo_step >= ptd::kMemoMaxStamp ? 1u : h->memo_step + 1u;
-  const size_t table_bytes = (size_t)h->memo_slots * sizeof(ptd::MemoSlot);
-  if (h->memo_clear) {
-    PT_HIP(hipMemsetAsync(h->d_memo, 0xff, table_bytes, s));
-    PT_HIP(hipMemsetAsync(h->d_memo_ctr + ptd::kMemoOccupied, 0, 8, s));
-    h->memo_clear = false;
-  } else if (2 * h->memo_occupied > h->memo_slots) {
-    const uint32_t list_cap = std::max<uint32_t>(1, h->memo_slots / 2);
-    const uint32_t grid = std::min<uint32_t>(ptd::kMemoGrid, (h->memo_slots + ptd::kShareBlock - 1) / ptd::kShareBlock);
-    hipLaunchKernelGGL(ptd::memo_compact_kernel, dim3(grid), dim3(ptd::kShareBlock), 0, s, h->d_memo, h->memo_slots, last,
-                       h->d_memo_list, list_cap, h->d_memo_ctr);
-    PT_HIP(hipGetLastError());
-    PT_HIP(hipMemsetAsync(h->d_memo, 0xff, table_bytes, s));
-    PT_HIP(hipMemsetAsync(h->d_memo_ctr + ptd::kMemoOccupied, 0, 8, s));
-    const uint32_t rgrid = std::min<uint32_t>(ptd::kMemoGrid, (list_cap + ptd::kShareBlock - 1) / ptd::kShareBlock);
-    hipLaunchKernelGGL(ptd::memo_reinsert_kernel, dim3(rgrid), dim3(ptd::kShareBlock), 0, s, h->d_memo, h->memo_slots - 1u,
-                       h->d_memo_list, list_cap, h->d_memo_ctr);
-    PT_HIP(hipGetLastError());
-    h->memo_retains += 1;
-  }
-  return PT_OK;
-}
-
 // ---- one step: pt_path_trace's program on the three streams, stage by stage
 // Schedule: T(b) on trace_stream, N(b) on stream, A(b) on acc_stream.  T(b+1) overlaps N(b) (VALU under MFMA), A(b) overlaps
 // N(b+1) (a short HBM-bound pass), so the NIF launches follow each other without a gap; buffer set b&1 is reused by T(b+2) once
 // A(b) has consumed it.  The A(b) are ordered among themselves (one stream), which keeps every pixel's fp32 sum in iteration
-// order.
-// NIF sharing (off: S and E do not run, and the step is exactly the unshared one) puts S(b) behind T(b) and E(b) ahead of
-// A(b).  Batch scope: distinct queues in store regions b & 1 (N(b + 2) writes region b & 1 only after A(b), hence E(b), has
-// read it: T(b + 2) waits for B.accumulated); step scope: region b, every batch's results live until the step ends.  The memo
-// (pt_set_nif_memo) replaces the sharing table whatever the sharing mode: keys it does not hold are shared at step scope,
-// through the same store.
-struct StepMode {
-  int32_t share;   // sharing mode in force (off for a constant environment)
-  bool memo;
-  bool grouped() const { return share || memo; }   // N runs over distinct queues in the step store
-  bool step_scope() const { return memo || share == PT_NIF_SHARE_STEP; }
-};
+// order.  With NIF sharing or the memo (ptmi_nif_group.h), S(b) runs behind T(b) and E(b) ahead of A(b).
 
 // One batch: its sample iterations, trace grid and buffer set, and (grouped) where its distinct queue lies in the store.
 struct Batch {
@@ -689,16 +492,7 @@ struct Batch {
   dim3 group_grid() const { return dim3((g.region_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock, g.blocks); }
 };
 
-// Before the first batch of a grouped step: the buffers at the step's size, and the counts, the overflow counter and a
-// step-scope table cleared on the trace stream, where S runs (after e_begin: part of the step).
-static int prepare_group_store(pt_handle h, const StepMode& mode, size_t batches) {
-  if (int rc = ensure_group_buffers(h, mode.memo, mode.step_scope(), batches)) return rc;
-  PT_HIP(hipMemsetAsync(h->d_share_count, 0, batches * 4, h->trace_stream));
-  PT_HIP(hipMemsetAsync(h->d_share_over, 0, 8, h->trace_stream));
-  if (!mode.memo && mode.share == PT_NIF_SHARE_STEP)   // one table for the step
-    PT_HIP(hipMemsetAsync(h->d_share_keys, 0xff, (size_t)h->share_slots * 8, h->trace_stream));
-  return PT_OK;
-}
+#include "ptmi_nif_group.h"   // StepMode, S(b), E(b) and the memo's passes; pt_set_nif_sharing, pt_set_nif_memo and their stats
 
 // T(b): the persistent trace kernel, once A(b - 2) has consumed the buffer set.
 static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const Batch& b) {
@@ -722,49 +516,6 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
     }
     PT_HIP(hipGetLastError());
     return PT_OK;
-  });
-}
-
-// What ShareParams and MemoParams have in common: the batch's queue, its owner map and its distinct queue in the store.
-template <class Params>
-static Params group_params(pt_handle h, const Batch& b) {
-  Params S;
-  S.q_u = b.B->q_u; S.q_v = b.B->q_v;
-  S.region_count = b.B->region_count;
-  S.region_cap = b.g.region_cap;
-  S.owner = h->d_share_owner[b.set()];
-  S.d_u = h->d_share_u + b.store_base; S.d_v = h->d_share_v + b.store_base;
-  S.d_count = h->d_share_count + b.index;
-  S.base = b.store_base;
-  S.overflowed = h->d_share_over;
-  return S;
-}
-
-template <class Params>
-static int launch_group(pt_handle h, const Batch& b, void (*claim)(Params), void (*resolve)(Params), const Params& S) {
-  hipLaunchKernelGGL(claim, b.group_grid(), dim3(ptd::kShareBlock), 0, h->trace_stream, S);
-  PT_HIP(hipGetLastError());
-  hipLaunchKernelGGL(resolve, b.group_grid(), dim3(ptd::kShareBlock), 0, h->trace_stream, S);
-  PT_HIP(hipGetLastError());
-  return PT_OK;
-}
-
-// S(b), right behind T(b) (it hides under N(b - 1) as T(b) does): claim a slot per key -- in the sharing table, or with the
-// memo look the key up -- then resolve the owners claimed in this step.
-static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b) {
-  return ev.timed(h->trace_stream, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
-    if (mode.memo) {
-      ptd::MemoParams M = group_params<ptd::MemoParams>(h, b);
-      M.slots = h->d_memo; M.slot_mask = h->memo_slots - 1u;
-      M.step = h->memo_step;
-      M.d_slot = h->d_memo_slot;
-      M.counters = h->d_memo_ctr;
-      return launch_group(h, b, ptd::memo_lookup_kernel, ptd::memo_resolve_kernel, M);
-    }
-    if (mode.share == PT_NIF_SHARE_BATCH) PT_HIP(hipMemsetAsync(h->d_share_keys, 0xff, (size_t)h->share_slots * 8, h->trace_stream));
-    ptd::ShareParams S = group_params<ptd::ShareParams>(h, b);
-    S.keys = h->d_share_keys; S.vals = h->d_share_vals; S.slot_mask = h->share_slots - 1u;
-    return launch_group(h, b, ptd::share_claim_kernel, ptd::share_resolve_kernel, S);
   });
 }
 
@@ -796,36 +547,6 @@ static int stage_nif(pt_handle h, StepEvents& ev, const StepMode& mode, const Ba
   return PT_OK;
 }
 
-// E(b), ahead of A(b) (it overlaps N(b + 1) as A(b) does): per-path radiance from the owners' BGR in the step store, or with
-// the memo from the memo slot.
-template <class Params>
-static Params expand_params(pt_handle h, const Batch& b) {
-  const pt_context::BatchBuffers& B = *b.B;
-  Params X;
-  X.region_count = B.region_count;
-  X.region_cap = b.g.region_cap;
-  X.owner = h->d_share_owner[b.set()];
-  X.bgr = h->d_share_bgr;
-  X.q_tr = B.q_tr; X.q_tg = B.q_tg; X.q_tb = B.q_tb; X.q_path = B.q_path;
-  X.rad_r = B.rad_r; X.rad_g = B.rad_g; X.rad_b = B.rad_b;
-  return X;
-}
-
-static int stage_expand(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b) {
-  return ev.timed(h->acc_stream, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
-    if (mode.memo) {
-      ptd::MemoExpandParams X = expand_params<ptd::MemoExpandParams>(h, b);
-      X.slots = h->d_memo;
-      hipLaunchKernelGGL(ptd::memo_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X);
-    } else {
-      hipLaunchKernelGGL(ptd::share_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream,
-                         expand_params<ptd::ExpandParams>(h, b));
-    }
-    PT_HIP(hipGetLastError());
-    return PT_OK;
-  });
-}
-
 // A(b): AccumulateContributions, four consecutive items per thread where the worklist's size allows it; the buffer set is
 // free for T(b + 2) after it.
 static int stage_accumulate(pt_handle h, StepEvents& ev, const Batch& b) {
@@ -847,18 +568,6 @@ static int stage_accumulate(pt_handle h, StepEvents& ev, const Batch& b) {
   return PT_OK;
 }
 
-// The memo's publish pass on `stream`: after every N(b) (same stream) and every E(b) (the caller has made `stream` wait for
-// the accumulate stream), so no lookup or expand reads what it writes.  store_cap: the largest distinct-queue bound of the step.
-static int stage_memo_publish(pt_handle h, StepEvents& ev, uint32_t store_cap, uint32_t batches) {
-  return ev.timed(h->stream, pt_context::kSpanMemo, [&]() -> int {
-    const dim3 grid(std::min<uint32_t>(ptd::kMemoGrid, (store_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock), batches);
-    hipLaunchKernelGGL(ptd::memo_publish_kernel, grid, dim3(ptd::kShareBlock), 0, h->stream, h->d_memo, h->d_memo_slot,
-                       h->d_share_bgr, h->d_share_count, (uint32_t)h->queue_cap, h->memo_step);
-    PT_HIP(hipGetLastError());
-    return PT_OK;
-  });
-}
-
 // Enqueue the whole path_trace program on the three streams: prologue, per batch T / S / N / E / A, epilogue.  Returns at
 // the first failing call; the caller drains the streams either way, so a failure in the middle of the batch loop never
 // leaves kernels running on buffers the host is about to reuse or free.
@@ -876,10 +585,10 @@ static int enqueue_path_trace(pt_handle h) {
   PT_HIP(hipStreamWaitEvent(h->trace_stream, e_begin, 0));   // counters memset and earlier work on `stream`
   const std::vector<uint32_t> deal = ptplan::batch_iterations(h->samples_per_step, h->iters_per_batch, h->first_batch_iters, h->env_const);
   const uint32_t batches = (uint32_t)deal.size();
-  const int32_t share = h->share_mode_set ? h->share_mode : auto_share_mode(h, batches);   // (an explicit off: no look at the memory)
-  const StepMode mode{h->env_const ? 0 : share, !h->env_const && h->memo_slots != 0};
-  h->share_mode_last = mode.share;
-  h->memo_ran = mode.memo;
+  const int32_t share = h->group.share_mode_set ? h->group.share_mode : auto_share_mode(h, batches);   // (an explicit off: no look at the memory)
+  const StepMode mode{h->env_const ? 0 : share, !h->env_const && h->group.memo_slots != 0};
+  h->group.share_mode_last = mode.share;
+  h->group.memo_ran = mode.memo;
   if (mode.grouped())
     if (int rc = prepare_group_store(h, mode, batches)) return rc;
   if (mode.memo)   // counters, and a clear or a retain pass if one is due
@@ -907,10 +616,10 @@ static int enqueue_path_trace(pt_handle h) {
   // the counters travel to pinned host memory on the stream itself: the host waits once, for e_end
   PT_HIP(hipMemcpyAsync(h->h_counters, h->d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   if (mode.grouped()) {   // the distinct-queue lengths and the overflow count travel with them: still one wait
-    PT_HIP(hipMemcpyAsync(h->h_share_count, h->d_share_count, (size_t)batches * 4, hipMemcpyDeviceToHost, h->stream));
-    PT_HIP(hipMemcpyAsync(h->h_share_over, h->d_share_over, 8, hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(hipMemcpyAsync(h->group.h_share_count, h->group.d_share_count, (size_t)batches * 4, hipMemcpyDeviceToHost, h->stream));
+    PT_HIP(hipMemcpyAsync(h->group.h_share_over, h->group.d_share_over, 8, hipMemcpyDeviceToHost, h->stream));
   }
-  if (mode.memo) PT_HIP(hipMemcpyAsync(h->h_memo_ctr, h->d_memo_ctr, ptd::kMemoCounters * 8, hipMemcpyDeviceToHost, h->stream));
+  if (mode.memo) PT_HIP(hipMemcpyAsync(h->group.h_memo_ctr, h->group.d_memo_ctr, ptd::kMemoCounters * 8, hipMemcpyDeviceToHost, h->stream));
   return ev.record(h->stream, e_end, h->e_end_i);
 }
 
@@ -926,8 +635,8 @@ static int resolve_stage_times(pt_handle h) {
     if (s.kind == pt_context::kSpanTrace) h->stats.path_trace_ms += ms;
     else if (s.kind == pt_context::kSpanNif) h->stats.nif_ms += ms;
     else if (s.kind == pt_context::kSpanAccumulate) h->stats.accumulate_ms += ms;
-    else if (s.kind == pt_context::kSpanShare) h->share_ms += ms;
-    else h->memo_ms += ms;
+    else if (s.kind == pt_context::kSpanShare) h->group.share_ms += ms;
+    else h->group.memo_ms += ms;
   }
   float total_ms = 0.f;
   PT_HIP(hipEventElapsedTime(&total_ms, h->events[h->e_begin_i], h->events[h->e_end_i]));
@@ -970,8 +679,8 @@ int pt_path_trace(pt_handle h) {
     return fail(h, PT_ERR_NOT_READY, "no environment: call pt_upload_nif, pt_set_env_map or pt_set_constant_env");
   PT_HIP(hipSetDevice(h->cfg.device));
   memset(&h->stats, 0, sizeof(h->stats));
-  h->share_mode_last = 0; h->share_evals = 0; h->share_overflowed = 0; h->share_ms = 0;
-  h->memo_ran = false; h->memo_served = 0; h->memo_inserted = 0; h->memo_ms = 0;
+  h->group.share_mode_last = 0; h->group.share_evals = 0; h->group.share_overflowed = 0; h->group.share_ms = 0;
+  h->group.memo_ran = false; h->group.memo_served = 0; h->group.memo_inserted = 0; h->group.memo_ms = 0;
   h->spans_pending = false;
   h->stats.nif_flops_per_sample = (h->env_const || h->env_map) ? 0 : h->nif_flops;
   h->stats.first_sample = h->sample_cursor;
@@ -1000,88 +709,18 @@ int pt_path_trace(pt_handle h) {
   h->stats.paths = (uint64_t)h->n_real * h->samples_per_step;   // padding items are not traced (pt_setup)
   h->stats.segments = h->h_counters[0];
   h->stats.escaped = h->h_counters[1] - h->h_counters[3];   // the accumulate pass counts every contributing path, emitters too
-  if (h->share_mode_last || h->memo_ran) {
-    for (uint32_t b = 0; b < h->stats.trace_launches; ++b) h->share_evals += h->h_share_count[b];
-    h->share_overflowed = *h->h_share_over;
+  if (h->group.share_mode_last || h->group.memo_ran) {
+    for (uint32_t b = 0; b < h->stats.trace_launches; ++b) h->group.share_evals += h->group.h_share_count[b];
+    h->group.share_overflowed = *h->group.h_share_over;
   } else {
-    h->share_evals = h->env_const ? 0 : h->stats.escaped;
+    h->group.share_evals = h->env_const ? 0 : h->stats.escaped;
   }
-  if (h->memo_ran) {
-    h->memo_occupied = h->h_memo_ctr[ptd::kMemoOccupied];
-    h->memo_served = h->h_memo_ctr[ptd::kMemoServedCount];
-    h->memo_inserted = h->h_memo_ctr[ptd::kMemoInserted];
+  if (h->group.memo_ran) {
+    h->group.memo_occupied = h->group.h_memo_ctr[ptd::kMemoOccupied];
+    h->group.memo_served = h->group.h_memo_ctr[ptd::kMemoServedCount];
+    h->group.memo_inserted = h->group.h_memo_ctr[ptd::kMemoInserted];
   }
   h->spans_pending = true;
-  return PT_OK;
-}
-
-int pt_set_nif_sharing(pt_handle h, int32_t mode) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (mode != PT_NIF_SHARE_OFF && mode != PT_NIF_SHARE_BATCH && mode != PT_NIF_SHARE_STEP)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_nif_sharing: mode must be PT_NIF_SHARE_OFF, _BATCH or _STEP");
-  if (mode != PT_NIF_SHARE_OFF) {
-    PT_HIP(hipSetDevice(h->cfg.device));
-    if (int rc = alloc_share_buffers(h)) { h->share_mode = PT_NIF_SHARE_OFF; h->share_mode_set = true; return rc; }
-  }
-  h->share_mode = mode;
-  h->share_mode_set = true;
-  return PT_OK;
-}
-
-int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_nif_sharing_stats)) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_nif_sharing_stats.struct_size mismatch");
-  if (int rc = resolve_stage_times(h)) return rc;
-  out->mode = h->share_mode_last;
-  out->escaped = h->stats.escaped;
-  out->evaluations = h->share_evals;
-  out->overflowed = h->share_overflowed;
-  out->table_slots = h->share_mode_last && !h->memo_ran ? h->share_slots : 0;
-  out->share_ms = h->share_ms;
-  return PT_OK;
-}
-
-int pt_set_nif_memo(pt_handle h, uint64_t max_bytes) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  PT_HIP(hipSetDevice(h->cfg.device));
-  if (max_bytes == 0) {
-    PT_HIP(hipStreamSynchronize(h->stream));
-    free_memo_buffers(h);
-    h->share_mode_set = true;   // a caller that manages the memo has chosen: the sharing mode is what pt_set_nif_sharing said (off)
-    return PT_OK;
-  }
-  // table + retain list = 48 bytes per slot; a power of two, at most 2^30 slots
-  const uint64_t per_slot = sizeof(ptd::MemoSlot) + sizeof(ptd::MemoSlot) / 2;
-  uint64_t slots = 1;
-  while (slots < (1ull << 30) && 2 * slots * per_slot <= max_bytes) slots <<= 1;
-  if (slots * per_slot > max_bytes || slots < 1024)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_nif_memo: max_bytes must be 0 or at least 48 KiB (1024 slots of 48 bytes)");
-  h->share_mode_set = true;   // as above: with or without the memo, this handle no longer chooses its sharing mode itself
-  if (slots == h->memo_slots) return PT_OK;   // same capacity: the entries stay
-  return alloc_memo(h, (uint32_t)slots);
-}
-
-int pt_clear_nif_memo(pt_handle h) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  memo_new_generation(h);
-  return PT_OK;
-}
-
-int pt_get_nif_memo_stats(pt_handle h, pt_nif_memo_stats* out) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_nif_memo_stats)) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_nif_memo_stats.struct_size mismatch");
-  if (int rc = resolve_stage_times(h)) return rc;
-  out->enabled = h->memo_slots != 0;
-  out->slots = h->memo_slots;
-  out->occupied = h->memo_slots ? h->memo_occupied : 0;
-  out->escaped = h->stats.escaped;
-  out->served = h->memo_ran ? h->memo_served : 0;
-  out->evaluations = h->share_evals;
-  out->inserted = h->memo_ran ? h->memo_inserted : 0;
-  out->overflowed = h->memo_ran ? h->share_overflowed : 0;
-  out->generation = h->memo_generation;
-  out->retains = h->memo_retains;
-  out->memo_ms = h->memo_ms;
   return PT_OK;
 }
 
@@ -1108,7 +747,7 @@ int pt_calibrate_nif(pt_handle h, uint32_t launches, double* ms_per_launch, uint
   uint64_t evals = 0;
   if (B.share_batch >= 0) {   // the step shared NIF evaluations: its NIF stage ran over the distinct queue, and so does this
     uint32_t c = 0;
-    PT_HIP(hipMemcpy(&c, h->d_share_count + B.share_batch, 4, hipMemcpyDeviceToHost));
+    PT_HIP(hipMemcpy(&c, h->group.d_share_count + B.share_batch, 4, hipMemcpyDeviceToHost));
     evals = c;
     bind_store_queue(h, N, (uint32_t)B.share_batch, B.share_base, B.share_region_cap);
   } else {
@@ -1734,31 +1373,6 @@ int pt_diag_inject_fault(pt_handle h, int32_t batch) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   h->diag_fault_batch = batch;
   return PT_OK;
-}
-
-// test build only: the NIF-sharing table gets `slots` slots (rounded up to a power of two; 0 = sized from memory again), so that
-// a test reaches the overflow path with a small image
-int pt_diag_set_nif_share_capacity(pt_handle h, uint32_t slots) {
-  if (!h || slots > (1u << 30)) return PT_ERR_INVALID_ARGUMENT;
-  PT_HIP(hipSetDevice(h->cfg.device));
-  h->share_diag_slots = 0;
-  uint32_t p = slots ? 1 : 0;   // exactly the forced size (the sizing rule's minimum and memory bound do not apply)
-  while (p < slots) p <<= 1;
-  if (int rc = alloc_share_table(h, p)) return rc;
-  h->share_diag_slots = p;
-  if (int rc = alloc_share_buffers(h)) { h->share_mode = PT_NIF_SHARE_OFF; return rc; }
-  return PT_OK;
-}
-
-// test build only: the NIF memo gets exactly `slots` slots (rounded up to a power of two, at least 2), whatever pt_set_nif_memo
-// would size, so that a test reaches the overflow and retain paths with a small image; 0 turns the memo off
-int pt_diag_set_nif_memo_slots(pt_handle h, uint32_t slots) {
-  if (!h || slots > (1u << 30)) return PT_ERR_INVALID_ARGUMENT;
-  PT_HIP(hipSetDevice(h->cfg.device));
-  if (slots == 0) return pt_set_nif_memo(h, 0);
-  uint32_t p = 2;
-  while (p < slots) p <<= 1;
-  return alloc_memo(h, p);
 }
 
 // test build only: the point-to-point half of pt_gather_hdr on a communicator of ONE rank -- a grouped ncclSend / ncclRecv of

@@ -1,7 +1,7 @@
 // ptmi_context.h -- the owners of device and pinned memory, per-handle state (pt_context), error helpers, trace parameters
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h,
-// ptmi_denoise.h, ptmi_nif_train.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with ptmi_nif_group.h
+// among the stages of a step], ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
 #pragma once
 
 using ptplan::TraceGrid;
@@ -247,43 +247,46 @@ struct pt_context {
   DevBuf<unsigned long long> d_stamps;      // profiling build: 256 phase stamps of the wide-NIF layer kernel
   int diag_fault_batch = -1;                // test build: batch whose NIF launch fails (pt_diag_inject_fault), -1 = none
 
-  // exact sharing of NIF evaluations (pt_set_nif_sharing, pt_nif_share.h).  Nothing here survives a step: the table is
-  // cleared at the start of every batch (PT_NIF_SHARE_BATCH) or step (PT_NIF_SHARE_STEP), the counts at every step.
-  int32_t share_mode = 0;                    // requested: taken up by the next pt_path_trace
-  bool share_mode_set = false;               // pt_set_nif_sharing or pt_set_nif_memo was called; until then the step chooses (auto_share_mode)
-  bool share_auto_failed = false;            // the automatic default could not allocate: off until pt_set_nif_sharing
-  int32_t share_mode_last = 0;               // what the last pt_path_trace ran with (0 also for a constant environment)
-  DevBuf<unsigned long long> d_share_keys;
-  DevBuf<uint32_t> d_share_vals;
-  uint32_t share_slots = 0;                  // table capacity, a power of two
-  uint32_t share_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_share_capacity), 0 = sized from memory
-  DevBuf<uint32_t> d_share_owner[2];                 // per batch-buffer set: [queue_cap] store index of every entry's owner
-  // the step's distinct queues and their decoded BGR, region-structured: batch b's at store index (b or b & 1) x queue_cap
-  DevBuf<float> d_share_u, d_share_v, d_share_bgr;
-  size_t share_regions = 0;
-  DevBuf<uint32_t> d_share_count;            // [batch] distinct-queue length
-  DevBuf<unsigned long long> d_share_over;
-  PinnedBuf<uint32_t> h_share_count;         // pinned copies, written at the end of the step on `stream`
-  PinnedBuf<unsigned long long> h_share_over;
-  size_t share_count_cap = 0;
-  uint64_t share_evals = 0, share_overflowed = 0;
-  double share_ms = 0;
+  // NIF sharing and the memo (ptmi_nif_group.h; kernels: pt_nif_group.h, pt_nif_memo.h)
+  struct NifGroup {
+    // exact sharing of NIF evaluations (pt_set_nif_sharing).  Nothing here survives a step: the table is
+    // cleared at the start of every batch (PT_NIF_SHARE_BATCH) or step (PT_NIF_SHARE_STEP), the counts at every step.
+    int32_t share_mode = 0;                    // requested: taken up by the next pt_path_trace
+    bool share_mode_set = false;               // pt_set_nif_sharing or pt_set_nif_memo was called; until then the step chooses (auto_share_mode)
+    bool share_auto_failed = false;            // the automatic default could not allocate: off until pt_set_nif_sharing
+    int32_t share_mode_last = 0;               // what the last pt_path_trace ran with (0 also for a constant environment)
+    DevBuf<unsigned long long> d_share_keys;
+    DevBuf<uint32_t> d_share_vals;
+    uint32_t share_slots = 0;                  // table capacity, a power of two
+    uint32_t share_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_share_capacity), 0 = sized from memory
+    DevBuf<uint32_t> d_share_owner[2];                 // per batch-buffer set: [queue_cap] owner word of every entry (ptmi_share_plan.h)
+    // the step's distinct queues and their decoded BGR, region-structured: batch b's at store index (b or b & 1) x queue_cap
+    DevBuf<float> d_share_u, d_share_v, d_share_bgr;
+    size_t share_regions = 0;
+    DevBuf<uint32_t> d_share_count;            // [batch] distinct-queue length
+    DevBuf<unsigned long long> d_share_over;
+    PinnedBuf<uint32_t> h_share_count;         // pinned copies, written at the end of the step on `stream`
+    PinnedBuf<unsigned long long> h_share_over;
+    size_t share_count_cap = 0;
+    uint64_t share_evals = 0, share_overflowed = 0;
+    double share_ms = 0;
 
-  // persistent memo of decoded NIF values (pt_set_nif_memo, pt_nif_memo.h).  Unlike the sharing table it outlives the step:
-  // it is cleared at allocation, on a new generation (pt_upload_nif, pt_clear_nif_memo, a failed pt_path_trace) and by the
-  // retain pass.  With the memo on, every step uses the step-scope store above (d_share_u / _v / _bgr, d_share_count).
-  DevBuf<ptd::MemoSlot> d_memo;
-  uint32_t memo_slots = 0;                   // table capacity, a power of two; 0 = memo off
-  DevBuf<ptd::MemoSlot> d_memo_list;         // retain list, memo_slots / 2 entries
-  DevBuf<uint32_t> d_memo_slot;              // [store index]: slot the entry is published into (memo_slot_regions x queue_cap)
-  size_t memo_slot_regions = 0;
-  DevBuf<unsigned long long> d_memo_ctr;     // ptd::kMemoCounters counters of the memo passes
-  PinnedBuf<unsigned long long> h_memo_ctr;  // pinned copy, written at the end of the step on `stream` (the step's one wait)
-  bool memo_clear = false;                   // clear the table before the next lookup
-  uint32_t memo_step = 0;                    // stamp of the last step that ran the memo passes
-  bool memo_ran = false;                     // the last pt_path_trace ran them
-  uint64_t memo_occupied = 0, memo_served = 0, memo_inserted = 0, memo_generation = 0, memo_retains = 0;
-  double memo_ms = 0;
+    // persistent memo of decoded NIF values (pt_set_nif_memo).  Unlike the sharing table it outlives the step:
+    // it is cleared at allocation, on a new generation (pt_upload_nif, pt_clear_nif_memo, a failed pt_path_trace) and by the
+    // retain pass.  With the memo on, every step uses the step-scope store above (d_share_u / _v / _bgr, d_share_count).
+    DevBuf<ptd::MemoSlot> d_memo;
+    uint32_t memo_slots = 0;                   // table capacity, a power of two; 0 = memo off
+    DevBuf<ptd::MemoSlot> d_memo_list;         // retain list, memo_slots / 2 entries
+    DevBuf<uint32_t> d_memo_slot;              // [store index]: slot the entry is published into (memo_slot_regions x queue_cap)
+    size_t memo_slot_regions = 0;
+    DevBuf<unsigned long long> d_memo_ctr;     // ptd::kMemoCounters counters of the memo passes
+    PinnedBuf<unsigned long long> h_memo_ctr;  // pinned copy, written at the end of the step on `stream` (the step's one wait)
+    bool memo_clear = false;                   // clear the table before the next lookup
+    uint32_t memo_step = 0;                    // stamp of the last step that ran the memo passes
+    bool memo_ran = false;                     // the last pt_path_trace ran them
+    uint64_t memo_occupied = 0, memo_served = 0, memo_inserted = 0, memo_generation = 0, memo_retains = 0;
+    double memo_ms = 0;
+  } group;
 
   // stats.  The per-stage times are read lazily (pt_get_stats / pt_read_results): 3 hipEventElapsedTime calls per batch are
   // host time a step of a small image should not pay (BASELINE configs[0] is one millisecond of device work per step).

@@ -1,0 +1,382 @@
+// ptmi_nif_group.h -- host side of NIF sharing and the memo (pt_set_nif_sharing, pt_set_nif_memo; kernels: pt_nif_group.h,
+// pt_nif_memo.h; arithmetic: ptmi_share_plan.h): the buffers of pt_context::group, the mode a step runs in, the stages S(b) and
+// E(b) and the memo's publish pass, the entry points and the test build's hooks.  Part of the one translation unit ptmi.hip,
+// included there behind `Batch` and ahead of the other stages of a step, which take the StepMode.
+#pragma once
+
+static int resolve_stage_times(pt_handle h);   // ptmi.hip
+
+// ---- exact sharing of NIF evaluations: buffers (pt_set_nif_sharing allocates them, a step-scope step with more batches
+// than store regions grows the store) and the S / E launches of one batch (pt_nif_group.h)
+
+static uint64_t free_device_bytes() {
+  size_t free_b = 0, total_b = 0;
+  return hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (uint64_t)free_b : ptshare::kFreeUnknown;
+}
+
+// Table capacity: the worst case of the table's scope -- one batch, or every batch of a step (ptmi_share_plan.h: load factor
+// <= 1/2 even if every entry is distinct, at most 1/8 of the free device memory and 2^30 slots).  A full table is not an
+// error: the keys that find no slot are evaluated alone.
+static uint32_t share_table_slots(pt_handle h, uint64_t entries, uint64_t free_b) {
+  if (h->group.share_diag_slots) return h->group.share_diag_slots;   // test build: exactly the forced size
+  return ptshare::worst_case_slots(entries, free_b);
+}
+
+static int ensure_share_counts(pt_handle h, size_t batches) {
+  if (batches <= h->group.share_count_cap) return PT_OK;
+  h->group.share_count_cap = 0;
+  PT_HIP(dev_alloc(h->group.d_share_count, batches));
+  PT_HIP(dev_alloc(h->group.h_share_count, batches));
+  h->group.share_count_cap = batches;
+  return PT_OK;
+}
+
+// store regions of queue_cap entries each: (u, v) of the distinct queue and its decoded BGR.  Store indices stay below 2^31.
+static int ensure_share_store(pt_handle h, size_t regions) {
+  if (regions <= h->group.share_regions) return PT_OK;
+  if (regions * h->queue_cap >= ptshare::kMaxStoreEntries)
+    return fail(h, PT_ERR_OUT_OF_MEMORY, "NIF sharing: the step's distinct queues would exceed 2^31 entries (fewer samples per step)");
+  PT_HIP(hipStreamSynchronize(h->stream));
+  h->group.d_share_u.reset(); h->group.d_share_v.reset(); h->group.d_share_bgr.reset();   // all three go before the first comes back: they are large
+  h->group.share_regions = 0;
+  PT_HIP(dev_alloc(h->group.d_share_u, regions * h->queue_cap));
+  PT_HIP(dev_alloc(h->group.d_share_v, regions * h->queue_cap));
+  PT_HIP(dev_alloc(h->group.d_share_bgr, 3 * regions * h->queue_cap));
+  h->group.share_regions = regions;
+  return PT_OK;
+}
+
+// The table with exactly `slots` slots, the stream drained first.
+static int alloc_share_table(pt_handle h, uint32_t slots) {
+  PT_HIP(hipStreamSynchronize(h->stream));
+  h->group.d_share_keys.reset(); h->group.d_share_vals.reset();
+  h->group.share_slots = 0;
+  if (!slots) return PT_OK;
+  PT_HIP(dev_alloc(h->group.d_share_keys, slots));
+  PT_HIP(dev_alloc(h->group.d_share_vals, slots));
+  h->group.share_slots = slots;
+  return PT_OK;
+}
+
+// (re)allocates the table if its scope needs more slots than it has (never for a capacity forced by the test build)
+static int ensure_share_table(pt_handle h, uint64_t entries) {
+  const uint32_t slots = share_table_slots(h, entries, free_device_bytes());
+  if (h->group.d_share_keys && (slots <= h->group.share_slots || h->group.share_diag_slots)) return PT_OK;
+  return alloc_share_table(h, slots);
+}
+
+// What sharing and the memo both need besides their table: the owner maps, the overflow counter, counts and a store.
+static int alloc_group_buffers(pt_handle h) {
+  for (auto& o : h->group.d_share_owner)
+    if (!o) PT_HIP(dev_alloc(o, h->queue_cap));
+  if (!h->group.d_share_over) {
+    PT_HIP(dev_alloc(h->group.d_share_over, 1));
+    PT_HIP(dev_alloc(h->group.h_share_over, 1));
+  }
+  if (int rc = ensure_share_counts(h, 64)) return rc;
+  return ensure_share_store(h, 2);
+}
+
+static int alloc_share_buffers(pt_handle h) {
+  if (int rc = ensure_share_table(h, h->queue_cap)) return rc;
+  return alloc_group_buffers(h);
+}
+
+static void free_share_buffers(pt_handle h) {   // (the counts and the overflow counter are a few bytes: they stay)
+  h->group.d_share_keys.reset(); h->group.d_share_vals.reset();
+  h->group.share_slots = 0;
+  h->group.d_share_u.reset(); h->group.d_share_v.reset(); h->group.d_share_bgr.reset();
+  h->group.share_regions = 0;
+  for (auto& o : h->group.d_share_owner) o.reset();
+}
+
+static int ensure_memo_slot_map(pt_handle h);
+
+// The buffers of a grouped step at the step's size (the table's only without the memo, which has its own).
+static int ensure_group_buffers(pt_handle h, bool memo, bool step_scope, size_t batches) {
+  if (int rc = ensure_share_counts(h, batches)) return rc;
+  if (int rc = ensure_share_store(h, step_scope ? batches : 2)) return rc;
+  if (memo) return ensure_memo_slot_map(h);
+  return ensure_share_table(h, (step_scope ? batches : 1) * (uint64_t)h->queue_cap);
+}
+
+// ---- persistent memo of decoded NIF values (pt_set_nif_memo, pt_nif_memo.h): buffers, generations, the per-step passes
+static void free_memo_buffers(pt_handle h) {
+  h->group.d_memo.reset(); h->group.d_memo_list.reset(); h->group.d_memo_slot.reset(); h->group.d_memo_ctr.reset(); h->group.h_memo_ctr.reset();
+  h->group.memo_slots = 0; h->group.memo_slot_regions = 0; h->group.memo_occupied = 0;
+}
+
+// every value in the memo is forgotten: the table is cleared before the next lookup
+static void memo_new_generation(pt_handle h) {
+  h->group.memo_generation += 1;
+  h->group.memo_clear = true;
+  h->group.memo_occupied = 0;
+}
+
+// the publish map follows the step store (one entry per store index)
+static int ensure_memo_slot_map(pt_handle h) {
+  if (h->group.memo_slot_regions >= h->group.share_regions) return PT_OK;
+  PT_HIP(hipStreamSynchronize(h->stream));
+  h->group.memo_slot_regions = 0;
+  PT_HIP(dev_alloc(h->group.d_memo_slot, h->group.share_regions * h->queue_cap));
+  h->group.memo_slot_regions = h->group.share_regions;
+  return PT_OK;
+}
+
+static int alloc_memo_buffers(pt_handle h, uint32_t slots) {
+  PT_HIP(dev_alloc(h->group.d_memo, slots));
+  PT_HIP(dev_alloc(h->group.d_memo_list, std::max<size_t>(1, slots / 2)));
+  PT_HIP(dev_alloc(h->group.d_memo_ctr, ptd::kMemoCounters));
+  PT_HIP(dev_alloc(h->group.h_memo_ctr, ptd::kMemoCounters));
+  if (int rc = alloc_group_buffers(h)) return rc;
+  return ensure_memo_slot_map(h);
+}
+
+// A memo of `slots` slots (a power of two <= 2^30), its retain list and what the step-scope path needs besides the sharing
+// table; a failure leaves the memo off (h->error names the failing call).
+static int alloc_memo(pt_handle h, uint32_t slots) {
+  PT_HIP(hipStreamSynchronize(h->stream));
+  free_memo_buffers(h);
+  if (int rc = alloc_memo_buffers(h, slots)) { free_memo_buffers(h); return rc; }
+  h->group.memo_slots = slots;
+  h->group.memo_clear = true;   // cleared on the stream ahead of the first lookup
+  return PT_OK;
+}
+
+// Memo prologue of a step, on the trace stream ahead of the first lookup: the step's counters, and the table cleared (new
+// generation) or thinned out (retain pass: occupancy above 1/2 of the slots after the last step).
+static int enqueue_memo_prologue(pt_handle h) {
+  hipStream_t s = h->trace_stream;
+  PT_HIP(hipMemsetAsync(h->group.d_memo_ctr + ptd::kMemoServedCount, 0, (ptd::kMemoCounters - 1) * 8, s));
+  const uint32_t last = h->group.memo_step;
+  h->group.memo_step = h->group.memo_step >= ptd::kMemoMaxStamp ? 1u : h->group.memo_step + 1u;
+  const size_t table_bytes = (size_t)h->group.memo_slots * sizeof(ptd::MemoSlot);
+  if (h->group.memo_clear) {
+    PT_HIP(hipMemsetAsync(h->group.d_memo, 0xff, table_bytes, s));
+    PT_HIP(hipMemsetAsync(h->group.d_memo_ctr + ptd::kMemoOccupied, 0, 8, s));
+    h->group.memo_clear = false;
+  } else if (2 * h->group.memo_occupied > h->group.memo_slots) {
+    const uint32_t list_cap = std::max<uint32_t>(1, h->group.memo_slots / 2);
+    const uint32_t grid = std::min<uint32_t>(ptd::kMemoGrid, (h->group.memo_slots + ptd::kShareBlock - 1) / ptd::kShareBlock);
+    hipLaunchKernelGGL(ptd::memo_compact_kernel, dim3(grid), dim3(ptd::kShareBlock), 0, s, h->group.d_memo, h->group.memo_slots, last,
+                       h->group.d_memo_list, list_cap, h->group.d_memo_ctr);
+    PT_HIP(hipGetLastError());
+    PT_HIP(hipMemsetAsync(h->group.d_memo, 0xff, table_bytes, s));
+    PT_HIP(hipMemsetAsync(h->group.d_memo_ctr + ptd::kMemoOccupied, 0, 8, s));
+    const uint32_t rgrid = std::min<uint32_t>(ptd::kMemoGrid, (list_cap + ptd::kShareBlock - 1) / ptd::kShareBlock);
+    hipLaunchKernelGGL(ptd::memo_reinsert_kernel, dim3(rgrid), dim3(ptd::kShareBlock), 0, s, h->group.d_memo, h->group.memo_slots - 1u,
+                       h->group.d_memo_list, list_cap, h->group.d_memo_ctr);
+    PT_HIP(hipGetLastError());
+    h->group.memo_retains += 1;
+  }
+  return PT_OK;
+}
+
+// ---- the mode of a step and its stages S(b), E(b) and the memo's publish pass (schedule: ptmi.hip, "one step")
+// NIF sharing (off: S and E do not run, and the step is exactly the unshared one) puts S(b) behind T(b) and E(b) ahead of
+// A(b).  Batch scope: distinct queues in store regions b & 1 (N(b + 2) writes region b & 1 only after A(b), hence E(b), has
+// read it: T(b + 2) waits for B.accumulated); step scope: region b, every batch's results live until the step ends.  The memo
+// (pt_set_nif_memo) replaces the sharing table whatever the sharing mode: keys it does not hold are shared at step scope,
+// through the same store.
+struct StepMode {
+  int32_t share;   // sharing mode in force (off for a constant environment)
+  bool memo;
+  bool grouped() const { return share || memo; }   // N runs over distinct queues in the step store
+  bool step_scope() const { return memo || share == PT_NIF_SHARE_STEP; }
+};
+
+// The mode of a handle on which neither pt_set_nif_sharing nor pt_set_nif_memo was ever called: step scope if the environment
+// is a NIF, the memo is off and what the step would allocate fits the budget of ptmi_share_plan.h (a quarter of the free
+// device memory); otherwise, and if an allocation fails all the same, off -- exactly the unshared step, and no error.
+// Buffers the handle already holds (an earlier step, the test build's forced capacity) count as held.
+static int32_t auto_share_mode(pt_handle h, size_t batches) {
+  if (h->env_const || h->env_map || h->group.memo_slots || h->group.share_auto_failed) return PT_NIF_SHARE_OFF;   // (memo_slots: the test build's hook; pt_set_nif_memo ends the choice)
+  const uint64_t free_b = free_device_bytes();
+  const uint64_t slots = share_table_slots(h, batches * (uint64_t)h->queue_cap, free_b);
+  ptshare::Held held;
+  held.table_slots = h->group.d_share_keys ? (h->group.share_diag_slots ? slots : h->group.share_slots) : 0;
+  held.store_regions = h->group.share_regions;
+  held.owner_maps = (h->group.d_share_owner[0] ? 1 : 0) + (h->group.d_share_owner[1] ? 1 : 0);
+  if (!ptshare::auto_fits(slots, batches, h->queue_cap, held, free_b)) return PT_NIF_SHARE_OFF;
+  if (ensure_group_buffers(h, false, true, batches) == PT_OK && alloc_group_buffers(h) == PT_OK) return PT_NIF_SHARE_STEP;   // (the step's sizes first: nothing is allocated twice)
+  (void)hipGetLastError();   // an allocation failed: give back what was taken and run unshared from now on
+  free_share_buffers(h);
+  h->group.share_auto_failed = true;
+  h->error.clear();
+  return PT_NIF_SHARE_OFF;
+}
+
+// Before the first batch of a grouped step: the buffers at the step's size, and the counts, the overflow counter and a
+// step-scope table cleared on the trace stream, where S runs (after e_begin: part of the step).
+static int prepare_group_store(pt_handle h, const StepMode& mode, size_t batches) {
+  if (int rc = ensure_group_buffers(h, mode.memo, mode.step_scope(), batches)) return rc;
+  PT_HIP(hipMemsetAsync(h->group.d_share_count, 0, batches * 4, h->trace_stream));
+  PT_HIP(hipMemsetAsync(h->group.d_share_over, 0, 8, h->trace_stream));
+  if (!mode.memo && mode.share == PT_NIF_SHARE_STEP)   // one table for the step
+    PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
+  return PT_OK;
+}
+
+static ptd::ShareTable share_table(pt_handle h) { return {h->group.d_share_keys, h->group.d_share_vals, h->group.share_slots - 1u}; }
+static ptd::MemoTable memo_table(pt_handle h) {
+  return {h->group.d_memo, h->group.memo_slots - 1u, h->group.memo_step, h->group.d_memo_slot, h->group.d_memo_ctr};
+}
+
+// S(b), right behind T(b) (it hides under N(b - 1) as T(b) does): claim a slot per key -- in the sharing table, or with the
+// memo look the key up -- then resolve the owners claimed in this step.
+static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b) {
+  return ev.timed(h->trace_stream, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
+    ptd::GroupQueue Q;   // the batch's queue, its owner map and its distinct queue in the store
+    Q.q_u = b.B->q_u; Q.q_v = b.B->q_v;
+    Q.region_count = b.B->region_count;
+    Q.region_cap = b.g.region_cap;
+    Q.owner = h->group.d_share_owner[b.set()];
+    Q.d_u = h->group.d_share_u + b.store_base; Q.d_v = h->group.d_share_v + b.store_base;
+    Q.d_count = h->group.d_share_count + b.index;
+    Q.base = b.store_base;
+    Q.overflowed = h->group.d_share_over;
+    const dim3 grid = b.group_grid(), block(ptd::kShareBlock);
+    if (mode.memo) {
+      hipLaunchKernelGGL(ptd::memo_lookup_kernel, grid, block, 0, h->trace_stream, Q, memo_table(h));
+      PT_HIP(hipGetLastError());
+      hipLaunchKernelGGL(ptd::memo_resolve_kernel, grid, block, 0, h->trace_stream, Q, memo_table(h));
+    } else {
+      if (mode.share == PT_NIF_SHARE_BATCH)   // one table per batch
+        PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
+      hipLaunchKernelGGL(ptd::share_claim_kernel, grid, block, 0, h->trace_stream, Q, share_table(h));
+      PT_HIP(hipGetLastError());
+      hipLaunchKernelGGL(ptd::share_resolve_kernel, grid, block, 0, h->trace_stream, Q, share_table(h));
+    }
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+  });
+}
+
+// E(b), ahead of A(b) (it overlaps N(b + 1) as A(b) does): per-path radiance from the owners' BGR in the step store, or with
+// the memo from the memo slot.
+static int stage_expand(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b) {
+  return ev.timed(h->acc_stream, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
+    const pt_context::BatchBuffers& B = *b.B;
+    ptd::GroupExpand X;
+    X.region_count = B.region_count;
+    X.region_cap = b.g.region_cap;
+    X.owner = h->group.d_share_owner[b.set()];
+    X.bgr = h->group.d_share_bgr;
+    X.q_tr = B.q_tr; X.q_tg = B.q_tg; X.q_tb = B.q_tb; X.q_path = B.q_path;
+    X.rad_r = B.rad_r; X.rad_g = B.rad_g; X.rad_b = B.rad_b;
+    if (mode.memo) hipLaunchKernelGGL(ptd::memo_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, memo_table(h));
+    else hipLaunchKernelGGL(ptd::share_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, share_table(h));
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+  });
+}
+
+// The memo's publish pass on `stream`: after every N(b) (same stream) and every E(b) (the caller has made `stream` wait for
+// the accumulate stream), so no lookup or expand reads what it writes.  store_cap: the largest distinct-queue bound of the step.
+static int stage_memo_publish(pt_handle h, StepEvents& ev, uint32_t store_cap, uint32_t batches) {
+  return ev.timed(h->stream, pt_context::kSpanMemo, [&]() -> int {
+    const dim3 grid(std::min<uint32_t>(ptd::kMemoGrid, (store_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock), batches);
+    hipLaunchKernelGGL(ptd::memo_publish_kernel, grid, dim3(ptd::kShareBlock), 0, h->stream, h->group.d_memo, h->group.d_memo_slot,
+                       h->group.d_share_bgr, h->group.d_share_count, (uint32_t)h->queue_cap, h->group.memo_step);
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+  });
+}
+
+extern "C" {
+
+int pt_set_nif_sharing(pt_handle h, int32_t mode) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (mode != PT_NIF_SHARE_OFF && mode != PT_NIF_SHARE_BATCH && mode != PT_NIF_SHARE_STEP)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_nif_sharing: mode must be PT_NIF_SHARE_OFF, _BATCH or _STEP");
+  if (mode != PT_NIF_SHARE_OFF) {
+    PT_HIP(hipSetDevice(h->cfg.device));
+    if (int rc = alloc_share_buffers(h)) { h->group.share_mode = PT_NIF_SHARE_OFF; h->group.share_mode_set = true; return rc; }
+  }
+  h->group.share_mode = mode;
+  h->group.share_mode_set = true;
+  return PT_OK;
+}
+
+int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_nif_sharing_stats)) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_nif_sharing_stats.struct_size mismatch");
+  if (int rc = resolve_stage_times(h)) return rc;
+  out->mode = h->group.share_mode_last;
+  out->escaped = h->stats.escaped;
+  out->evaluations = h->group.share_evals;
+  out->overflowed = h->group.share_overflowed;
+  out->table_slots = h->group.share_mode_last && !h->group.memo_ran ? h->group.share_slots : 0;
+  out->share_ms = h->group.share_ms;
+  return PT_OK;
+}
+
+int pt_set_nif_memo(pt_handle h, uint64_t max_bytes) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  if (max_bytes == 0) {
+    PT_HIP(hipStreamSynchronize(h->stream));
+    free_memo_buffers(h);
+    h->group.share_mode_set = true;   // a caller that manages the memo has chosen: the sharing mode is what pt_set_nif_sharing said (off)
+    return PT_OK;
+  }
+  const uint64_t slots = ptshare::memo_slots_for(max_bytes);   // table + retain list = 48 bytes per slot
+  if (!slots)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_nif_memo: max_bytes must be 0 or at least 48 KiB (1024 slots of 48 bytes)");
+  h->group.share_mode_set = true;   // as above: with or without the memo, this handle no longer chooses its sharing mode itself
+  if (slots == h->group.memo_slots) return PT_OK;   // same capacity: the entries stay
+  return alloc_memo(h, (uint32_t)slots);
+}
+
+int pt_clear_nif_memo(pt_handle h) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  memo_new_generation(h);
+  return PT_OK;
+}
+
+int pt_get_nif_memo_stats(pt_handle h, pt_nif_memo_stats* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_nif_memo_stats)) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_nif_memo_stats.struct_size mismatch");
+  if (int rc = resolve_stage_times(h)) return rc;
+  out->enabled = h->group.memo_slots != 0;
+  out->slots = h->group.memo_slots;
+  out->occupied = h->group.memo_slots ? h->group.memo_occupied : 0;
+  out->escaped = h->stats.escaped;
+  out->served = h->group.memo_ran ? h->group.memo_served : 0;
+  out->evaluations = h->group.share_evals;
+  out->inserted = h->group.memo_ran ? h->group.memo_inserted : 0;
+  out->overflowed = h->group.memo_ran ? h->group.share_overflowed : 0;
+  out->generation = h->group.memo_generation;
+  out->retains = h->group.memo_retains;
+  out->memo_ms = h->group.memo_ms;
+  return PT_OK;
+}
+
+#ifdef PTMI_DIAG_BUILD
+// test build only: the NIF-sharing table gets `slots` slots (rounded up to a power of two; 0 = sized from memory again), so that
+// a test reaches the overflow path with a small image
+int pt_diag_set_nif_share_capacity(pt_handle h, uint32_t slots) {
+  if (!h || slots > ptshare::kMaxSlots) return PT_ERR_INVALID_ARGUMENT;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  h->group.share_diag_slots = 0;
+  uint32_t p = slots ? 1 : 0;   // exactly the forced size (the sizing rule's minimum and memory bound do not apply)
+  while (p < slots) p <<= 1;
+  if (int rc = alloc_share_table(h, p)) return rc;
+  h->group.share_diag_slots = p;
+  if (int rc = alloc_share_buffers(h)) { h->group.share_mode = PT_NIF_SHARE_OFF; return rc; }
+  return PT_OK;
+}
+
+// test build only: the NIF memo gets exactly `slots` slots (rounded up to a power of two, at least 2), whatever pt_set_nif_memo
+// would size, so that a test reaches the overflow and retain paths with a small image; 0 turns the memo off
+int pt_diag_set_nif_memo_slots(pt_handle h, uint32_t slots) {
+  if (!h || slots > ptshare::kMaxSlots) return PT_ERR_INVALID_ARGUMENT;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  if (slots == 0) return pt_set_nif_memo(h, 0);
+  uint32_t p = 2;
+  while (p < slots) p <<= 1;
+  return alloc_memo(h, p);
+}
+#endif
+
+}  // extern "C"

@@ -1,8 +1,8 @@
 // ptmi_nif_launch.h -- the two bindings of a NIF queue, the launchers of the NIF kernels: fused (pt_nif.h), layer by layer
 // (pt_nif_gemm.h), float32 (pt_nif_f32.h), and the event allocator of a step
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [the entry points in ptmi.hip], ptmi_film_comm.h,
-// ptmi_denoise.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with ptmi_nif_group.h
+// among the stages of a step], ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
 #pragma once
 
 namespace {
@@ -29,7 +29,7 @@ void bind_dense_queue(ptd::NifParams& N, const float* u, const float* v, const u
 }
 // ... the distinct queue of batch `batch` in the step store of NIF sharing and the memo, at store index `base`
 void bind_store_queue(pt_handle h, ptd::NifParams& N, uint32_t batch, uint32_t base, uint32_t cap) {
-  bind_dense_queue(N, h->d_share_u + base, h->d_share_v + base, h->d_share_count + batch, cap, h->d_share_bgr + 3 * (size_t)base);
+  bind_dense_queue(N, h->group.d_share_u + base, h->group.d_share_v + base, h->group.d_share_count + batch, cap, h->group.d_share_bgr + 3 * (size_t)base);
 }
 
 // Dynamic-LDS opt-in of a kernel, once per device (one bit per device: the host app drives devices from threads).

@@ -1,18 +1,32 @@
-// ptmi_share_plan.h -- the sizing arithmetic of NIF sharing (pt_set_nif_sharing, pt_nif_share.h): how many slots the table of
-// a batch or a step gets, and whether the automatic default may take the memory it needs.  Plain C++ (nothing from HIP), so that
-// tests/share_plan_main.cpp checks it on a CPU; ptmi.hip includes it ahead of ptmi_context.h.
+// ptmi_share_plan.h -- the arithmetic of NIF sharing and the memo (pt_set_nif_sharing, pt_set_nif_memo; pt_nif_group.h): the
+// format of an owner word, how many slots the table of a batch or a step gets, whether the automatic default may take the
+// memory it needs, and how many slots a memo of a given size has.  Plain C++ (nothing from HIP), so that
+// tests/share_plan_main.cpp checks it on a CPU; ptmi.hip includes it ahead of the device headers.
 #pragma once
 
 #include <cstdint>
 
 namespace ptshare {
 
+// The owner word of a queue entry (owner[q], written by the claim pass of either table): the store index of the entry's owner
+// (bit 31 clear), a SERVED slot (10: the value is read from the table itself; the memo alone produces it), or a PENDING slot
+// (11: claimed in this step by another entry, whose store index the resolve pass puts in its place).
+constexpr uint32_t kOwnerTagged = 0x80000000u;    // not a store index
+constexpr uint32_t kOwnerPending = 0xc0000000u;
+constexpr uint32_t kOwnerSlotBits = 0x3fffffffu;
+constexpr uint32_t owner_served(uint32_t slot) { return kOwnerTagged | slot; }
+constexpr uint32_t owner_pending(uint32_t slot) { return kOwnerPending | slot; }
+constexpr bool owner_is_store(uint32_t o) { return !(o & kOwnerTagged); }
+constexpr bool owner_is_pending(uint32_t o) { return (o & kOwnerPending) == kOwnerPending; }
+constexpr bool owner_is_served(uint32_t o) { return (o & kOwnerPending) == kOwnerTagged; }
+constexpr uint32_t owner_slot(uint32_t o) { return o & kOwnerSlotBits; }
+
 constexpr uint64_t kMinSlots = 1024;            // smallest table the sizing rules give
-constexpr uint64_t kMaxSlots = 1ull << 30;      // owner[] flags a slot with bit 31
+constexpr uint64_t kMaxSlots = (uint64_t)kOwnerSlotBits + 1;   // a tagged owner word holds the slot
 constexpr uint64_t kSlotBytes = 12;             // 64-bit key + 32-bit store index of its owner
 constexpr uint64_t kStoreEntryBytes = 20;       // (u, v) of a distinct-queue entry and its decoded BGR
 constexpr uint64_t kOwnerEntryBytes = 4;        // store index of a queue entry's owner
-constexpr uint64_t kMaxStoreEntries = 1ull << 31;   // store indices stay below the slot flag
+constexpr uint64_t kMaxStoreEntries = kOwnerTagged;   // store indices stay below the tag
 constexpr uint64_t kTableMemoryDivisor = 8;     // a table takes at most 1/8 of the free device memory
 constexpr uint64_t kAutoMemoryDivisor = 4;      // what the automatic default allocates: at most 1/4 of the free device memory
 constexpr uint64_t kFreeUnknown = ~0ull;        // free_bytes when the device did not say: no memory bound
@@ -49,6 +63,17 @@ inline bool auto_fits(uint64_t table_slots, uint64_t batches, uint64_t queue_cap
   if (need == 0) return true;
   if (free_bytes == kFreeUnknown) return false;
   return need <= free_bytes / kAutoMemoryDivisor;
+}
+
+// Slots of a memo that may take max_bytes (pt_set_nif_memo): the largest power of two, at most kMaxSlots, whose table and
+// retain list (half as many entries) fit; 0 -- refused -- below kMinSlots.
+constexpr uint64_t kMemoSlotBytes = 32;                                   // sizeof(ptd::MemoSlot)
+constexpr uint64_t kMemoBytesPerSlot = kMemoSlotBytes + kMemoSlotBytes / 2;
+inline uint64_t memo_slots_for(uint64_t max_bytes) {
+  uint64_t slots = kMinSlots;
+  if (max_bytes / kMemoBytesPerSlot < slots) return 0;
+  while (slots < kMaxSlots && 2 * slots <= max_bytes / kMemoBytesPerSlot) slots <<= 1;
+  return slots;
 }
 
 }  // namespace ptshare

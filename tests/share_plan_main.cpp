@@ -1,4 +1,4 @@
-// The sizing arithmetic of NIF sharing (ipu_path_trace_amd/csrc/ptmi_share_plan.h) on the CPU: tests/test_share_plan.py
+// The arithmetic of NIF sharing and the memo (ipu_path_trace_amd/csrc/ptmi_share_plan.h) on the CPU: tests/test_share_plan.py
 // builds this with -fsanitize=address,undefined and runs it.
 #include <cstdio>
 #include <cstdlib>
@@ -65,6 +65,41 @@ int main() {
   CHECK(auto_fits(1024, 1, kBig, nothing, ~0ull - 1) && !auto_fits(1024, 1, kBig + 1, nothing, ~0ull - 1));
   CHECK(!auto_fits(kMaxSlots, 251, 33177600ull, nothing, 288ull << 30));      // 4K, 1000 samples per step: declined
   CHECK(!auto_fits(1024, kBig, kBig, nothing, ~0ull - 1));
+
+  // the owner word: a store index, a served slot or a pending slot -- exactly one of the three, and the payload comes back
+  const uint32_t kLastStore = 0x7fffffffu, kLastSlot = 0x3fffffffu;
+  for (uint32_t g : {0u, 1u, kLastSlot, kLastSlot + 1u, kLastStore}) {
+    CHECK(owner_is_store(g) && !owner_is_served(g) && !owner_is_pending(g));
+  }
+  for (uint32_t s : {0u, 1u, kLastSlot - 1u, kLastSlot}) {
+    const uint32_t sv = owner_served(s), pd = owner_pending(s);
+    CHECK(!owner_is_store(sv) && owner_is_served(sv) && !owner_is_pending(sv) && owner_slot(sv) == s);
+    CHECK(!owner_is_store(pd) && !owner_is_served(pd) && owner_is_pending(pd) && owner_slot(pd) == s);
+    CHECK(sv != pd);
+  }
+  CHECK(kMaxSlots == (uint64_t)kLastSlot + 1 && kMaxStoreEntries == (uint64_t)kLastStore + 1);
+  CHECK(!owner_is_store((uint32_t)kMaxStoreEntries));   // the first index that is none
+
+  // memo_slots_for: 48 bytes per slot (table + retain list), a power of two in kMinSlots .. kMaxSlots or 0 (refused), within
+  // max_bytes, monotone
+  CHECK(kMemoBytesPerSlot == 48);
+  const unsigned long long k48 = 48 * 1024;
+  CHECK(memo_slots_for(0) == 0 && memo_slots_for(k48 - 1) == 0 && memo_slots_for(k48) == 1024 && memo_slots_for(k48 + 1) == 1024);
+  CHECK(memo_slots_for(2 * k48 - 1) == 1024 && memo_slots_for(2 * k48) == 2048 && memo_slots_for(2 * k48 + 1) == 2048);
+  CHECK(memo_slots_for((48ull << 30) - 1) == (1ull << 29) && memo_slots_for(48ull << 30) == kMaxSlots);
+  CHECK(memo_slots_for((48ull << 30) + 1) == kMaxSlots && memo_slots_for((48ull << 31) + 1) == kMaxSlots);
+  CHECK(memo_slots_for(~0ull) == kMaxSlots);
+  uint64_t prev_slots = 0;
+  for (uint64_t bytes : {0ull, 1ull, 47ull, 48ull, k48 - 1, k48, k48 + 1, 2 * k48 - 1, 2 * k48, 2 * k48 + 1, 1ull << 20, (1ull << 30) - 1,
+                         1ull << 30, (1ull << 30) + 1, 6ull << 30, (48ull << 30) - 1, 48ull << 30, (48ull << 30) + 1, 1ull << 40, ~0ull - 1,
+                         ~0ull}) {
+    const uint64_t m = memo_slots_for(bytes);
+    CHECK(m == 0 || (pow2(m) && m >= kMinSlots && m <= kMaxSlots));
+    CHECK(m * kMemoBytesPerSlot <= bytes);
+    CHECK(m == kMaxSlots || 2 * m * kMemoBytesPerSlot > bytes || m == 0);   // the largest that fits
+    CHECK(m >= prev_slots);
+    prev_slots = m;
+  }
 
   std::printf("SHARE_PLAN_OK\n");
   return 0;

@@ -1,6 +1,7 @@
-"""The sizing arithmetic of NIF sharing (ipu_path_trace_amd/csrc/ptmi_share_plan.h) on the CPU, under AddressSanitizer and
+"""The arithmetic of NIF sharing and the memo (ipu_path_trace_amd/csrc/ptmi_share_plan.h) on the CPU, under AddressSanitizer and
 UndefinedBehaviorSanitizer: the worst-case table of a batch or a step (powers of two, monotone in the entries and in the free
-memory, entry counts of 0, 1 and 2^31 - 1) and the memory budget under which the automatic default declines.  The header
+memory, entry counts of 0, 1 and 2^31 - 1), the memory budget under which the automatic default declines, the owner word of
+both tables (round trips, the three kinds exclusive, its limits) and the slots of a memo of a given size.  The header
 includes nothing from HIP, so the stand-alone program tests/share_plan_main.cpp compiles with g++ alone."""
 import os
 import subprocess
