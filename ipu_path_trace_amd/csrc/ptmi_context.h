@@ -139,8 +139,9 @@ struct pt_context {
   DevBuf<unsigned long long> d_counters;     // [0] segments, [1] escaped or emitter paths, [2] real items (pt_setup), [3] emitter paths
   PinnedBuf<unsigned long long> h_counters;  // the same in pinned host memory: copied on the stream at the end of a step (no blocking hipMemcpy)
 
-  // batch buffers, double-buffered: the trace kernel of batch b+1 runs on `trace_stream` while the NIF
-  // kernel of batch b (MFMA-bound) runs on `stream`
+  // batch buffers, a ring of kBatchSets sets (ptmi_step_plan.h: ring_slot): the trace kernel of batch b+1 runs on
+  // `trace_stream` while the NIF kernel of batch b (MFMA-bound) runs on `stream`, and a third set keeps a batch's trip
+  // N -> E -> A -> T -> S -> N from setting the pace of the step
   uint32_t iters_per_batch = 1;
   uint32_t first_batch_iters = 1;   // iterations of a step's first batch (see enqueue_path_trace)
   size_t batch_paths_cap = 0;
@@ -150,15 +151,19 @@ struct pt_context {
   // unchanged -- the 60-VGPR / 106-SGPR kernel is resident six-fold per CU, not eight-fold as
   // hipOccupancyMaxActiveBlocksPerMultiprocessor reports, so a larger grid runs its last workgroups on part of the chip.
   static constexpr int kTraceBlocksPerCu = 6;
-  // Bytes of batch buffers per path of batch capacity, both sets: per path plen 1 + rad 12; per queue slot (one per path,
-  // rounded up per region) q_* 24 + survivor note 16 + path state 48.
-  static constexpr uint64_t kBatchBytesPerPath = 2 * (1 + 12 + 24 + 16 + 48);
+  static constexpr uint32_t kBatchSets = 3;
+  // Bytes of batch buffers per path of batch capacity: in every set, per path plen 1 + rad 12 and per queue slot (one per
+  // path, rounded up per region) q_* 24; once per handle, per queue slot, survivor note 16 + path state 48.
+  static constexpr uint64_t kBatchBytesPerPath = kBatchSets * (1 + 12 + 24) + 16 + 48;
   uint32_t trace_blocks = 1536;
+  uint32_t ring_depth = kBatchSets;    // sets a step cycles through; the profiling build can lower it (PTMI_BATCH_SETS)
+  // Scratch of the trace kernel, written and read inside one launch (pt_trace.h).  The trace launches of a handle follow each
+  // other on one stream, so one copy serves every set.
+  DevBuf<uint4> d_survivors;           // primary-phase notes of the trace kernel, one region per trace workgroup
+  DevBuf<float4> d_states;             // path states after the first shading, three planes of queue_cap float4
   struct BatchBuffers {
     DevBuf<float> q_u, q_v, q_tr, q_tg, q_tb;
     DevBuf<uint32_t> q_path;
-    DevBuf<uint4> survivors;           // primary-phase notes of the trace kernel, one region per trace workgroup
-    DevBuf<float4> states;             // path states after the first shading, three planes of queue_cap float4
     DevBuf<uint32_t> region_count;
     DevBuf<uint8_t> plen;
     DevBuf<float> rad_r, rad_g, rad_b;
@@ -169,7 +174,7 @@ struct pt_context {
     // ... and, if that batch ran with sharing on, where its distinct queue lies: count index (-1 = not shared), store base
     int32_t share_batch = -1;
     uint32_t share_base = 0, share_region_cap = 0;
-  } bb[2];
+  } bb[kBatchSets];
   hipStream_t trace_stream = nullptr;
   hipStream_t acc_stream = nullptr;   // accumulate(b) runs here, so NIF(b+1) follows NIF(b) back to back on `stream`
   bool serial = false;   // profiling build only: trace kernels share the NIF stream
@@ -259,8 +264,8 @@ struct pt_context {
     DevBuf<uint32_t> d_share_vals;
     uint32_t share_slots = 0;                  // table capacity, a power of two
     uint32_t share_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_share_capacity), 0 = sized from memory
-    DevBuf<uint32_t> d_share_owner[2];                 // per batch-buffer set: [queue_cap] owner word of every entry (ptmi_share_plan.h)
-    // the step's distinct queues and their decoded BGR, region-structured: batch b's at store index (b or b & 1) x queue_cap
+    DevBuf<uint32_t> d_share_owner[kBatchSets];        // per batch-buffer set: [queue_cap] owner word of every entry (ptmi_share_plan.h)
+    // the step's distinct queues and their decoded BGR, region-structured: batch b's at store region (b, or at batch scope its set) x queue_cap
     DevBuf<float> d_share_u, d_share_v, d_share_bgr;
     size_t share_regions = 0;
     DevBuf<uint32_t> d_share_count;            // [batch] distinct-queue length
@@ -482,11 +487,11 @@ void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   item_divider(h->n_items ? h->n_items : 1u, P.div_magic, P.div_shift);
 }
 
-void bind_batch(ptd::TraceParams& P, const pt_context::BatchBuffers& B) {
+void bind_batch(pt_handle h, ptd::TraceParams& P, const pt_context::BatchBuffers& B) {
   P.q_u = B.q_u; P.q_v = B.q_v; P.q_tr = B.q_tr; P.q_tg = B.q_tg; P.q_tb = B.q_tb; P.q_path = B.q_path;
   P.region_count = B.region_count;
-  P.survivors = B.survivors;
-  P.states = B.states;
+  P.survivors = h->d_survivors;
+  P.states = h->d_states;
   P.plen = B.plen;
   P.rad_r = B.rad_r; P.rad_g = B.rad_g; P.rad_b = B.rad_b;
 }

@@ -74,7 +74,7 @@ static int alloc_group_buffers(pt_handle h) {
     PT_HIP(dev_alloc(h->group.h_share_over, 1));
   }
   if (int rc = ensure_share_counts(h, 64)) return rc;
-  return ensure_share_store(h, 2);
+  return ensure_share_store(h, pt_context::kBatchSets);   // what batch scope needs: a region per set
 }
 
 static int alloc_share_buffers(pt_handle h) {
@@ -95,7 +95,7 @@ static int ensure_memo_slot_map(pt_handle h);
 // The buffers of a grouped step at the step's size (the table's only without the memo, which has its own).
 static int ensure_group_buffers(pt_handle h, bool memo, bool step_scope, size_t batches) {
   if (int rc = ensure_share_counts(h, batches)) return rc;
-  if (int rc = ensure_share_store(h, step_scope ? batches : 2)) return rc;
+  if (int rc = ensure_share_store(h, step_scope ? batches : pt_context::kBatchSets)) return rc;
   if (memo) return ensure_memo_slot_map(h);
   return ensure_share_table(h, (step_scope ? batches : 1) * (uint64_t)h->queue_cap);
 }
@@ -174,8 +174,11 @@ static int enqueue_memo_prologue(pt_handle h) {
 
 // ---- the mode of a step and its stages S(b), E(b) and the memo's publish pass (schedule: ptmi.hip, "one step")
 // NIF sharing (off: S and E do not run, and the step is exactly the unshared one) puts S(b) behind T(b) and E(b) ahead of
-// A(b).  Batch scope: distinct queues in store regions b & 1 (N(b + 2) writes region b & 1 only after A(b), hence E(b), has
-// read it: T(b + 2) waits for B.accumulated); step scope: region b, every batch's results live until the step ends.  The memo
+// A(b).  Batch scope: the distinct queue of batch b in the store region of its buffer set, b mod depth
+// (ptmi_step_plan.h: store_region).  N(b + depth) writes region b mod depth only after A(b), hence E(b), has read it: N(b + depth)
+// is behind S(b + depth), that behind T(b + depth), and T(b + depth) waits for the set's B.accumulated, which A(b) recorded.
+// The same chain keeps the set's owner map, which S(b + depth) rewrites, for E(b).  Step scope: region b, every batch's
+// results live until the step ends.  The memo
 // (pt_set_nif_memo) replaces the sharing table whatever the sharing mode: keys it does not hold are shared at step scope,
 // through the same store.
 struct StepMode {
@@ -196,8 +199,8 @@ static int32_t auto_share_mode(pt_handle h, size_t batches) {
   ptshare::Held held;
   held.table_slots = h->group.d_share_keys ? (h->group.share_diag_slots ? slots : h->group.share_slots) : 0;
   held.store_regions = h->group.share_regions;
-  held.owner_maps = (h->group.d_share_owner[0] ? 1 : 0) + (h->group.d_share_owner[1] ? 1 : 0);
-  if (!ptshare::auto_fits(slots, batches, h->queue_cap, held, free_b)) return PT_NIF_SHARE_OFF;
+  for (const auto& o : h->group.d_share_owner) held.owner_maps += o ? 1 : 0;
+  if (!ptshare::auto_fits(slots, batches, h->queue_cap, held, free_b, pt_context::kBatchSets)) return PT_NIF_SHARE_OFF;
   if (ensure_group_buffers(h, false, true, batches) == PT_OK && alloc_group_buffers(h) == PT_OK) return PT_NIF_SHARE_STEP;   // (the step's sizes first: nothing is allocated twice)
   (void)hipGetLastError();   // an allocation failed: give back what was taken and run unshared from now on
   free_share_buffers(h);

@@ -56,4 +56,14 @@ inline std::vector<uint32_t> batch_iterations(uint32_t samples_per_step, uint32_
   return iters;
 }
 
+// The ring of batch-buffer sets.  Batch b of a step uses set b mod depth; before it may overwrite the set, the batch that used
+// the set last -- b - depth -- must have been accumulated.  With `depth` sets, `depth` batches travel the dependency cycle
+// N -> E -> A -> T -> S -> N at once.
+constexpr uint32_t kNoBatch = ~0u;
+inline uint32_t ring_slot(uint32_t batch, uint32_t depth) { return batch % depth; }
+// The batch whose `accumulated` event T(batch) waits for, or kNoBatch: the first `depth` batches of a step find their set free.
+inline uint32_t ring_predecessor(uint32_t batch, uint32_t depth) { return batch >= depth ? batch - depth : kNoBatch; }
+// Store region of a batch's distinct queue (NIF sharing): its own at step scope, the one that goes with its set at batch scope.
+inline uint32_t store_region(uint32_t batch, uint32_t depth, bool step_scope) { return step_scope ? batch : ring_slot(batch, depth); }
+
 }  // namespace ptplan
