@@ -300,6 +300,56 @@ typedef struct pt_scene_object {     /* 48 bytes */
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n);
 int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t* n);
 
+/* Polygons in a runtime scene -- an EXTENSION, opt-in and additive: PTMI_ABI_VERSION stays 5 and no existing struct moves; a
+ * process that never calls pt_set_scene_ex launches the kernels it launched before and renders the same bits.  pt_set_scene_ex
+ * takes the same table as pt_set_scene with nine more floats per object, and two more shapes, traced by the same object loop in
+ * declaration order under the same cap of PT_MAX_SCENE_OBJECTS.
+ * Geometry: e1 = v1 - v0, e2 = v2 - v0, both in binary32.  PT_SHAPE_TRIANGLE is the set v0 + a e1 + b e2 with a, b >= 0 and
+ * a + b <= 1; PT_SHAPE_PARALLELOGRAM the same with a <= 1 and b <= 1 (its fourth corner is v1 + v2 - v0).  The stored normal is
+ * n = c / sqrtf(dot(c, c)), c = cross(e1, e2), formed once on the host by the same volatile, left-to-right binary32 expressions
+ * as a disc's normal.  pt_get_scene_ex returns a polygon with centre = v0, radius = 0 and normal = n, and a sphere or disc with
+ * vertex = 0.
+ * Intersection (device, every operation one rounded binary32, no contraction), in the kernel's frame, for a ray (o, d):
+ *   pv = cross(d, e2); det = dot(e1, pv); det == 0 -> miss
+ *   inv = 1 / det; tv = sub(o, v0)
+ *   a = dot(tv, pv) * inv;  !(a >= 0) or a > 1 -> miss
+ *   qv = cross(tv, e1); b = dot(d, qv) * inv;  !(b >= 0) -> miss
+ *   triangle: a + b > 1 -> miss;  parallelogram: b > 1 -> miss
+ *   t = dot(e2, qv) * inv;  t > 1e-5 else miss
+ * and then the scene's own t > eps && t < tbest in declaration order, as for every object.  Polygons are two-sided: for a
+ * diffuse or specular polygon the shading normal is dot(n, d) > 0 ? -n : n; the refractive branch flips the normal itself, as
+ * it does for every object; an emissive polygon emits from both faces (the material is not consulted, as for every emitter).
+ * Shared edges are NOT watertight in binary32: a ray can pass between two walls of a box that share an edge.
+ * Camera: under a pose v0 enters the kernels as a point, R^T (v0 - position), and e1, e2 and the stored world n each as a
+ * direction, R^T x, as centres and disc normals do; the built-in camera applies nothing.
+ * Validation: PT_ERR_INVALID_ARGUMENT, pt_last_error naming the object's index and the field, checked in this order before any
+ * device call: stride != sizeof(pt_scene_object_ex); n outside 1..32; a NULL table; then per object: a shape outside 0..3; a
+ * material outside 0..3; a used field that is not finite (polygon: vertex and colour -- centre, radius and normal are ignored;
+ * sphere, disc: centre, radius, normal, colour -- vertex is ignored); a negative colour component; a sphere's or disc's radius
+ * <= 0 and a disc normal of length zero; a polygon whose e1, e2 or cross(e1, e2) is not finite or whose dot(c, c) is not > 0
+ * ("vertices are collinear"); last, a NULL handle, whose message is pt_last_error(NULL)'s.  After a rejection the previous
+ * scene stays in force.  (NULL, 0, stride) restores the built-in scene.  pt_get_scene_ex(NULL, ...) gives the built-in table and
+ * needs no device; out may be NULL with capacity 0 to ask for the size.
+ * Coexistence: pt_set_scene is unchanged and still refuses shapes above 1.  A table of spheres and discs given through
+ * pt_set_scene_ex is the same scene bit for bit and runs the same kernels.  While a scene with a polygon is in force
+ * pt_get_scene still reports the count in *n and answers PT_ERR_INVALID_ARGUMENT ("use pt_get_scene_ex") when asked to copy.
+ * pt_stats, the escaped = 2 convention of pt_trace_paths, NIF sharing, the memo, the film and tile costs behave as for any
+ * scene.  Feature buffers: object_id is the index, depth is t, normal is the stored normal flipped to face the ray and then
+ * rotated to world space (the disc rule), albedo follows the material rule.  The environment guide applies to a diffuse hit on
+ * a polygon as to any diffuse hit; eligibility and densities of the emitter guide at a polygon hit use n as the bounce forms
+ * it, that is, flipped. */
+enum { PT_SHAPE_TRIANGLE = 2, PT_SHAPE_PARALLELOGRAM = 3 };
+typedef struct pt_scene_object_ex {   /* 84 bytes; the first 48 are pt_scene_object, field for field */
+  int32_t shape, material;
+  float centre[3];
+  float radius;
+  float normal[3];
+  float colour[3];
+  float vertex[3][3];                 /* polygons: v0, v1, v2 in world space */
+} pt_scene_object_ex;
+int pt_set_scene_ex(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, uint32_t stride /* = sizeof(pt_scene_object_ex) */);
+int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uint32_t* n);
+
 /* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
  * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an
  * optional thin lens.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves.
@@ -499,6 +549,8 @@ int pt_get_env_guide_tables(pt_handle h, uint32_t* threshold, uint32_t* alias, f
  * scene has no emitter, or none of positive mass, the guide is accepted but INERT: the library launches what it would launch
  * without it.  The table is rebuilt by pt_set_light_guide and by every pt_set_scene while a guide is set; the camera does not
  * change it.  beta is used as beta_thr / 2^32, beta_thr = (uint32)(beta 2^32).
+ * An emissive polygon (pt_set_scene_ex) is skipped by the table (n_lights and object_index say so): it is still reached by the
+ * hemisphere and environment branches, and the estimator stays unbiased because the guide is only a density mixed with the hemisphere's.
  * Estimator (device, binary32, every operation rounded once, no contraction; csrc/pt_light_guide.h), in the kernel's frame, at
  * the hit point x with the normal n as the bounce forms them (a disc's stored normal is not flipped):
  *   eligible(k), sphere (c, r): v = c - x, D2 = v.v; D2 > r^2 and v.n + r > 0.

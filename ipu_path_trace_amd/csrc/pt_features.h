@@ -19,21 +19,22 @@ namespace ptd {
 
 constexpr int kFeatureBlock = 256;
 
-__global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
+template <bool POLY>
+__device__ __forceinline__ void features_body(const TraceParams& P, float4* __restrict__ f0, float4* __restrict__ f1) {
   const uint32_t i = blockIdx.x * kFeatureBlock + threadIdx.x;
   if (i >= P.width * P.height) return;   // width, height <= 65535: the product fits 32 bits
   const uint32_t v = i / P.width, u = i - v * P.width;
   PathState st;
   float camx, camy, tbest;
   start_path(P, u | (v << 16), 0u, st, camx, camy);   // P.aa_scale == 0 (the host's copy): the noise-free ray
-  const int best = nearest_hit_primary(P, st.d, tbest);
+  const int best = nearest_hit_primary<false, POLY>(P, st.d, tbest);
   Vec3 n = mk(0.f, 0.f, 0.f), alb = mk(1.f, 1.f, 1.f);
   float depth = 0.f;
   if (best >= 0) {
     const SceneObject ob = P.obj[best];
     depth = tbest;
     // sphere: (hit - centre) / |hit - centre| -- (hit - centre) / radius but for the rounding of the hit point, and unit to
-    // rounding as the production shading forms it (shade_hit); disc: its stored normal
+    // rounding as the production shading forms it (shade_hit); disc or polygon (shape code >= 1): its stored normal
     n = ob.is_disc ? mk(ob.nx, ob.ny, ob.nz) : normalise(sub(scale(st.d, tbest), mk(ob.cx, ob.cy, ob.cz)));
     if (dot(n, st.d) > 0.0f) n = scale(n, -1.0f);                     // faces the ray
     if (P.cam_pose) n = normalise(to_world(P, n));                    // reported in world space; unit again after the rotation's roundings
@@ -41,6 +42,14 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
   }
   f0[i] = make_float4(n.x, n.y, n.z, depth);
   f1[i] = make_float4(alb.z, alb.y, alb.x, __int_as_float(best));     // B, G, R like every image of the ABI
+}
+
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
+  features_body<false>(P, f0, f1);
+}
+// pt_set_scene_ex: launched only while the scene in force holds a polygon
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel_poly(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
+  features_body<true>(P, f0, f1);
 }
 
 }  // namespace ptd

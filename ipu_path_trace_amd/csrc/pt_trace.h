@@ -44,7 +44,7 @@ struct SceneObject {
   float nx, ny, nz;     // disc normal
   float colr, colg, colb;
   int32_t type;         // MAT_* (MAT_EMISSIVE: col = emitted radiance)
-  int32_t is_disc;
+  int32_t is_disc;      // the shape code: 0 sphere, 1 disc; 2 triangle, 3 parallelogram (pt_set_scene_ex: the POLY instances alone meet these)
   // Camera rays start at the origin (codelets.cpp:162): what Sphere / Disc::intersect compute from (origin, object) alone
   // is a constant of the object, formed on the host by the SAME binary32 expressions in the same order (fill_scene):
   float ocx, ocy, ocz;  // sub(o, c) at o = 0
@@ -64,6 +64,13 @@ struct LightParams {
   uint32_t threshold[kMaxObjects];  // rank k is selected by the first threshold a 32-bit word is below, the last rank otherwise
   float probability[kMaxObjects];   // p_k, from the integer differences of the thresholds
 };
+
+// A polygon's edges (pt_set_scene_ex): e1 = v1 - v0, e2 = v2 - v0 in the kernel's frame; v0 and the stored normal travel in
+// the object's cx..cz and nx..nz.  24 bytes per object, zero for a sphere or disc.
+struct PolyEdges {
+  float e1x, e1y, e1z, e2x, e2y, e2z;
+};
+enum { SHAPE_TRIANGLE = 2, SHAPE_PARALLELOGRAM = 3 };   // = PT_SHAPE_* (include/ptmi.h)
 
 struct TraceParams {
   SceneObject obj[kMaxObjects];   // obj[0 .. n_objects): the scene in declaration order
@@ -109,6 +116,9 @@ struct TraceParams {
   // Emitter guide (pt_set_light_guide, pt_light_guide.h): read by the light-guided instances alone.  After the guide: nothing
   // the other instances read moves.
   LightParams lights;
+  // Polygon edges (pt_set_scene_ex): read by the POLY instances alone, which are launched only while the scene in force holds a
+  // polygon.  Last again: nothing any other instance reads moves.
+  PolyEdges poly[kMaxObjects];
 };
 static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
 
@@ -244,12 +254,32 @@ __device__ __forceinline__ float disc_intersect(Vec3 o, Vec3 d, const SceneObjec
   return t;
 }
 
+// A triangle or parallelogram v0 + a e1 + b e2 (include/ptmi.h, pt_set_scene_ex): Moeller-Trumbore, two-sided, every operation
+// one rounded binary32 in this order.  0 for a miss.
+__device__ __forceinline__ float poly_intersect(Vec3 o, Vec3 d, const SceneObject& ob, const PolyEdges& pe) {
+  const Vec3 e1 = mk(pe.e1x, pe.e1y, pe.e1z), e2 = mk(pe.e2x, pe.e2y, pe.e2z);
+  const Vec3 pv = cross(d, e2);
+  const float det = dot(e1, pv);
+  if (det == 0.0f) return 0.0f;   // (real branches on purpose, as in sphere_intersect)
+  const float inv = 1.0f / det;
+  const Vec3 tv = sub(o, mk(ob.cx, ob.cy, ob.cz));
+  const float a = dot(tv, pv) * inv;
+  if (!(a >= 0.0f) || a > 1.0f) return 0.0f;
+  const Vec3 qv = cross(tv, e1);
+  const float b = dot(d, qv) * inv;
+  if (!(b >= 0.0f)) return 0.0f;
+  if (ob.is_disc == SHAPE_TRIANGLE ? a + b > 1.0f : b > 1.0f) return 0.0f;
+  const float t = dot(e2, qv) * inv;
+  return t > kEps ? t : 0.0f;
+}
+
 // Scene::intersect (codelets.cpp:183): nearest hit in declaration order, -1 for none.
 // The loop stays rolled: one object's constants at a time are fetched from the kernel-argument segment (scalar
 // loads, wave-uniform), instead of all of them living in SGPRs.
 // A sphere that shares its centre with the object declared before it (the clear-coat pair, codelets.cpp:115-116) reuses that
 // object's sub(o, c), dot(oc, d) and dot(oc, oc): the same expressions on the same values (wave-uniform flag from the host).
-template <bool PIPE = false>   // PIPE: the next object's constants are requested before this object's arithmetic, awaited after it
+// POLY: the scene may hold polygons (shape codes 2, 3); every other instance compiles none of that.
+template <bool PIPE = false, bool POLY = false>   // PIPE: the next object's constants are requested before this object's arithmetic, awaited after it
 __device__ __forceinline__ int nearest_hit(const TraceParams& P, Vec3 o, Vec3 d, float& tbest) {
   int best = -1;
   tbest = kInf;
@@ -262,7 +292,9 @@ __device__ __forceinline__ int nearest_hit(const TraceParams& P, Vec3 o, Vec3 d,
     if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < n ? i + 1 : n - 1]; }
     else ob = P.obj[i];
     float t;
-    if (ob.is_disc) {
+    if (POLY && ob.is_disc >= SHAPE_TRIANGLE) {
+      if constexpr (POLY) t = poly_intersect(o, d, ob, P.poly[i]);
+    } else if (ob.is_disc) {
       t = disc_intersect(o, d, ob);
     } else {
       if (!ob.same_centre) {
@@ -288,7 +320,7 @@ __device__ __forceinline__ int nearest_hit(const TraceParams& P, Vec3 o, Vec3 d,
 // constants, everything that depends on the direction is the expression of sphere_intersect / disc_intersect unchanged, so
 // the result is the same float.  (Disc: the hit point add(o, scale(d, t)) is scale(d, t) but for the sign of a zero, which
 // sub(p, c) and the squares that follow erase.)
-template <bool PIPE = false>
+template <bool PIPE = false, bool POLY = false>
 __device__ __forceinline__ int nearest_hit_primary(const TraceParams& P, Vec3 d, float& tbest) {
   int best = -1;
   tbest = kInf;
@@ -301,7 +333,9 @@ __device__ __forceinline__ int nearest_hit_primary(const TraceParams& P, Vec3 d,
     if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < n ? i + 1 : n - 1]; }
     else ob = P.obj[i];
     float t;
-    if (ob.is_disc) {
+    if (POLY && ob.is_disc >= SHAPE_TRIANGLE) {   // the general function at o = (0, 0, 0): sub(o, v0) is formed here, the same float
+      if constexpr (POLY) t = poly_intersect(mk(0.f, 0.f, 0.f), d, ob, P.poly[i]);
+    } else if (ob.is_disc) {
       const Vec3 n = mk(ob.nx, ob.ny, ob.nz), c = mk(ob.cx, ob.cy, ob.cz);
       const float denom = dot(n, d);
       t = 0.0f;
@@ -388,7 +422,7 @@ __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab
 
 // GUIDE: the diffuse bounce mixes the hemisphere with the environment guide (pt_env_guide.h); CAM tells it whether directions
 // are rotated between camera and world space, as in emit_escaped (CAM_LENS: when P.cam_pose says so).
-template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false>
+template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length);
 
@@ -396,14 +430,15 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
 // AccumulateContributions fold (codelets.cpp:255-292) carried forward as throughput T.
 // Returns the path length (contribution-stack size, codelets.cpp:253) through `length` when the
 // path ends.
-template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false>
+template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false,
+          bool POLY = false>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length);
 #ifdef PTMI_DIAG_BUILD
 __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3 d, float& tbest);
 __device__ __forceinline__ int shade_hit_r3(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                             const uint32_t (&w)[4], float rr, uint32_t& length);
 #endif
-template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS>
+template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length) {
   uint32_t w[4];
   philox4x32_10(s.pixel, s.sample, 1u + s.depth, 0x5054u, P.seed_lo, P.seed_hi, w);
@@ -426,7 +461,7 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
   if constexpr (SCENE_C) best = nearest_hit_c(s.o, s.d, tbest, SceneIndices{});
   else
 #endif
-  best = nearest_hit<PIPE>(P, s.o, s.d, tbest);               // Scene::intersect (:183)
+  best = nearest_hit<PIPE, POLY>(P, s.o, s.d, tbest);         // Scene::intersect (:183)
   if (best < 0) {                                             // :184-190 ESCAPED
     s.T = scale(s.T, rr);
     length = s.depth + 1u;
@@ -435,7 +470,7 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
 #ifdef PTMI_DIAG_BUILD
   if constexpr (LEGACY) return shade_hit_r3(P, tab, s, best, tbest, w, rr, length);
 #endif
-  return shade_hit<GUIDE, CAM, LIGHTS>(P, tab, s, best, tbest, w, rr, length);
+  return shade_hit<GUIDE, CAM, LIGHTS, POLY>(P, tab, s, best, tbest, w, rr, length);
 }
 
 // The basis of light::diffuse (codelets.cpp:199-204) about a unit vector n: rx, ry with (rx, ry, n) orthonormal.  Its branch as
@@ -468,7 +503,7 @@ namespace ptd {
 
 // The second half of a loop trip of RayTraceKernel::compute (codelets.cpp:192-216): the ray has hit object `best` at
 // distance `tbest`; w = the bounce's Philox block, rr = its roulette weight.
-template <bool GUIDE, int CAM, bool LIGHTS>
+template <bool GUIDE, int CAM, bool LIGHTS, bool POLY>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length) {
   // the hit object's row, by per-lane index
@@ -488,6 +523,9 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
   Vec3 hp = add(s.o, scale(s.d, tbest));
   s.o = hp;
   Vec3 n = is_disc ? mk(nx, ny, nz) : normalise(sub(hp, mk(cx, cy, cz)));
+  if constexpr (POLY) {   // a polygon is two-sided: its stored normal faces the ray (the refractive branch flips the normal itself)
+    if (is_disc >= SHAPE_TRIANGLE && type != MAT_REFRACTIVE && dot(n, s.d) > 0.0f) n = scale(n, -1.0f);
+  }
   if (LIGHTS && type == MAT_DIFFUSE) {
     // Emitter-guided diffuse bounce (include/ptmi.h, pt_set_light_guide): word g0 of the guide's block picks the environment
     // guide (when one is set: a wave-uniform test), an emitter, or the hemisphere; whichever gave the direction, the weight
@@ -673,7 +711,7 @@ namespace ptd {
 // workgroup barriers per 256 paths) and 2 % slower inside the C2 step -- its 16 KiB of LDS do not fit beside the NIF
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
-template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false>
+template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false, bool POLY = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
@@ -720,9 +758,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
 #endif
         if constexpr (CAM == CAM_LENS) {   // the ray starts on the lens, not at the origin: no origin-folded constants
           lens_ray(P, pixel, st.sample, camx, camy, st.o, st.d);
-          best = nearest_hit<PIPE>(P, st.o, st.d, tbest);
+          best = nearest_hit<PIPE, POLY>(P, st.o, st.d, tbest);
         } else
-        best = PRIMARY ? nearest_hit_primary<PIPE>(P, st.d, tbest) : nearest_hit<PIPE>(P, st.o, st.d, tbest);
+        best = PRIMARY ? nearest_hit_primary<PIPE, POLY>(P, st.d, tbest) : nearest_hit<PIPE, POLY>(P, st.o, st.d, tbest);
       }
     }
     const bool hit = best >= 0;
@@ -793,7 +831,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if constexpr ((OPT & 64) != 0) res = shade_hit_r3(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       else
 #endif
-      res = shade_hit<GUIDE, CAM, LIGHTS>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
+      res = shade_hit<GUIDE, CAM, LIGHTS, POLY>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       if (res == STEP_CONTINUE) alive = true;
       else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full (guided: or the guide pointed below the surface)
       // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
@@ -865,7 +903,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     int res = STEP_CONTINUE;
     uint32_t length = 0;
-    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS>(P, hit_table, st, length);
+    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY>(P, hit_table, st, length);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
     const bool emitted = active && res == STEP_EMITTED;
@@ -904,6 +942,17 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide(const Tra
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true>(P); }
+// pt_set_scene_ex: the same nine with the polygon test in the object loop and the two-sided normal, launched only while the scene
+// in force holds a triangle or a parallelogram (resource rows: profiles/r20_polygons.txt)
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true>(P); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -916,7 +965,7 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
 
 // One thread per requested path; same device functions as trace_kernel.  GUIDE: the guided twin (the camera is read at run
 // time either way: CAM_LENS rotates when P.cam_pose says so).  LIGHTS: the emitter-guided twin.
-template <bool GUIDE, bool LIGHTS = false>
+template <bool GUIDE, bool LIGHTS = false, bool POLY = false>
 __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                  uint32_t n, PathRecordOut* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -931,7 +980,7 @@ __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uin
   if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
-  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
+  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
@@ -950,5 +999,11 @@ __global__ void trace_paths_guide_kernel(const TraceParams P, const uint16_t* u,
                                          uint32_t n, PathRecordOut* out) { trace_paths_body<true>(P, u, v, sample, n, out); }
 __global__ void trace_paths_lights_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                           uint32_t n, PathRecordOut* out) { trace_paths_body<false, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_poly_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                        uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_guide_poly_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                              uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_lights_poly_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                               uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true>(P, u, v, sample, n, out); }
 
 }  // namespace ptd

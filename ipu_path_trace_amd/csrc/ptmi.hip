@@ -517,6 +517,13 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
         kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide : (P.cam_pose ? ptd::trace_kernel_pose_guide : ptd::trace_kernel_guide);
       if (P.lights.n)   // an active light guide: the emitter-guided twin, which handles an environment guide too
         kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights : (P.cam_pose ? ptd::trace_kernel_pose_lights : ptd::trace_kernel_lights);
+      if (h->scene_n && h->scene_poly) {   // a polygon in the scene in force (pt_set_scene_ex): the polygon twin of each of the nine
+        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_poly : (P.cam_pose ? ptd::trace_kernel_pose_poly : ptd::trace_kernel_poly);
+        if (h->guide_set)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_poly : (P.cam_pose ? ptd::trace_kernel_pose_guide_poly : ptd::trace_kernel_guide_poly);
+        if (P.lights.n)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_poly : (P.cam_pose ? ptd::trace_kernel_pose_lights_poly : ptd::trace_kernel_lights_poly);
+      }
       hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
     PT_HIP(hipGetLastError());
@@ -1202,7 +1209,7 @@ static void rebuild_light_guide(pt_handle h) {
   if (!h->light_set) { h->light = ptlight::Table{}; return; }
   pt_scene_object builtin[ptd::kBuiltinObjects];
   builtin_scene(builtin);
-  if (h->scene_n) ptlight::build(h->light_beta, h->scene, h->scene_n, h->light);
+  if (h->scene_n) ptlight::build(h->light_beta, h->scene, h->scene_n, h->light);   // (it skips polygons)
   else ptlight::build(h->light_beta, builtin, ptd::kBuiltinObjects, h->light);
 }
 
@@ -1243,7 +1250,7 @@ static void light_hook_params(pt_handle h, ptd::TraceParams& P) {
   memset(&P, 0, sizeof(P));
   pt_scene_object builtin[ptd::kBuiltinObjects];
   builtin_scene(builtin);
-  if (h->scene_n) fill_scene(P, h->scene, h->scene_n);
+  if (h->scene_n) fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr);
   else fill_scene(P, builtin, ptd::kBuiltinObjects);
   fill_light_params(h, P, true);
 }
@@ -1292,12 +1299,13 @@ int pt_light_guide_eval(pt_handle h, const float* origin, const float* normal, c
 
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!objects && n == 0) { h->scene_n = 0; h->feature_gen += 1; rebuild_light_guide(h); return PT_OK; }   // the built-in scene
+  if (!objects && n == 0) { h->scene_n = 0; h->scene_poly = false; h->feature_gen += 1; rebuild_light_guide(h); return PT_OK; }   // the built-in scene
   const std::string bad = ptscene::check(objects, n);
   if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the scene in force stays
   std::copy(objects, objects + n, h->scene);
   ptscene::normalise(h->scene, n);
   h->scene_n = n;
+  h->scene_poly = false;
   h->feature_gen += 1;
   rebuild_light_guide(h);   // a light guide follows the scene
   return PT_OK;
@@ -1312,10 +1320,61 @@ int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t*
   const uint32_t count = custom ? h->scene_n : (uint32_t)ptd::kBuiltinObjects;
   *n = count;
   if (!out && capacity == 0) return PT_OK;   // size query
+  if (custom && h->scene_poly)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_scene: the scene in force holds a polygon: use pt_get_scene_ex");
   if (!out || capacity < count)
     return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_scene: capacity " + std::to_string(capacity) + " < " + std::to_string(count) + " objects")
              : PT_ERR_INVALID_ARGUMENT;
   std::copy(src, src + count, out);
+  return PT_OK;
+}
+
+// pt_set_scene with triangles and parallelograms.  Every hook of pt_set_scene applies: the feature cache is made dirty and the
+// light guide rebuilt (its table skips polygons); the hooks pt_light_guide_sample / _eval read spheres and discs alone.
+int pt_set_scene_ex(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, uint32_t stride) {
+  if (!objects && n == 0 && stride == sizeof(pt_scene_object_ex)) {   // the built-in scene
+    if (!h) { g_create_error = "pt_set_scene_ex: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+    return pt_set_scene(h, nullptr, 0);
+  }
+  const std::string bad = ptscene::check_ex(objects, n, stride);
+  if (!bad.empty()) {   // the scene in force stays
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) { g_create_error = "pt_set_scene_ex: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  pt_scene_object_ex stored[PT_MAX_SCENE_OBJECTS];
+  std::copy(objects, objects + n, stored);
+  ptscene::normalise_ex(stored, n);
+  bool poly = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    memcpy(&h->scene[i], &stored[i], sizeof(pt_scene_object));   // the first 48 bytes, field for field
+    memcpy(h->scene_vertex[i], stored[i].vertex, sizeof(stored[i].vertex));
+    poly = poly || ptscene::is_polygon(stored[i].shape);
+  }
+  h->scene_n = n;
+  h->scene_poly = poly;   // a table of spheres and discs is pt_set_scene's scene, and runs its kernels
+  h->feature_gen += 1;
+  rebuild_light_guide(h);
+  return PT_OK;
+}
+
+int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uint32_t* n) {
+  if (!n) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "null count") : PT_ERR_INVALID_ARGUMENT;
+  pt_scene_object builtin[ptd::kBuiltinObjects];
+  builtin_scene(builtin);
+  const bool custom = h && h->scene_n;
+  const pt_scene_object* src = custom ? h->scene : builtin;
+  const uint32_t count = custom ? h->scene_n : (uint32_t)ptd::kBuiltinObjects;
+  *n = count;
+  if (!out && capacity == 0) return PT_OK;   // size query
+  if (!out || capacity < count)
+    return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_scene_ex: capacity " + std::to_string(capacity) + " < " + std::to_string(count) + " objects")
+             : PT_ERR_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < count; ++i) {
+    memset(&out[i], 0, sizeof(out[i]));
+    memcpy(&out[i], &src[i], sizeof(pt_scene_object));
+    if (custom && h->scene_poly) memcpy(out[i].vertex, h->scene_vertex[i], sizeof(out[i].vertex));
+  }
   return PT_OK;
 }
 
@@ -1358,7 +1417,10 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   ptd::TraceParams P;
   fill_trace_params(h, P);
   P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
-  hipLaunchKernelGGL(P.lights.n ? ptd::trace_paths_lights_kernel : (h->guide_set ? ptd::trace_paths_guide_kernel : ptd::trace_paths_kernel), dim3(((uint32_t)n + 127) / 128), dim3(128),
+  auto kernel = P.lights.n ? ptd::trace_paths_lights_kernel : (h->guide_set ? ptd::trace_paths_guide_kernel : ptd::trace_paths_kernel);
+  if (h->scene_n && h->scene_poly)   // the polygon twins (pt_set_scene_ex)
+    kernel = P.lights.n ? ptd::trace_paths_lights_poly_kernel : (h->guide_set ? ptd::trace_paths_guide_poly_kernel : ptd::trace_paths_poly_kernel);
+  hipLaunchKernelGGL(kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
                      ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_path_record), hipMemcpyDeviceToHost, h->stream));

@@ -189,6 +189,10 @@ struct pt_context {
   // scene (pt_set_scene): the table in force, stored normalised; scene_n = 0: the built-in scene (pt_trace.h::scene_const)
   pt_scene_object scene[PT_MAX_SCENE_OBJECTS] = {};
   uint32_t scene_n = 0;
+  // ... and, for a table given through pt_set_scene_ex, the polygons' vertices (a polygon's row above holds centre = v0,
+  // radius = 0 and its normal); scene_poly: the table holds a polygon, the POLY kernel instances run
+  float scene_vertex[PT_MAX_SCENE_OBJECTS][3][3] = {};
+  bool scene_poly = false;
 
   // camera (pt_set_camera): the values as given, and the frame made from them once (ptmi_camera.h)
   pt_camera camera = ptcamera::default_camera();
@@ -377,6 +381,8 @@ T* scratch_as(pt_handle h) { return reinterpret_cast<T*>(static_cast<char*>(h->d
 // table pt_trace.h::scene_const.  A disc's normal (0, 1, 0) is already normalised (n / sqrtf(dot(n, n)) leaves it as it is).
 static_assert(ptd::kMaxObjects == PT_MAX_SCENE_OBJECTS && ptd::MAT_EMISSIVE == PT_MATERIAL_EMISSIVE, "scene capacity / materials");
 static_assert(sizeof(pt_scene_object) == 48, "pt_scene_object layout");
+static_assert(sizeof(pt_scene_object_ex) == 84 && sizeof(ptd::PolyEdges) == 24 && ptd::SHAPE_TRIANGLE == PT_SHAPE_TRIANGLE &&
+              ptd::SHAPE_PARALLELOGRAM == PT_SHAPE_PARALLELOGRAM, "pt_scene_object_ex layout / shape codes");
 void builtin_scene(pt_scene_object (&out)[ptd::kBuiltinObjects]) {
   for (int i = 0; i < ptd::kBuiltinObjects; ++i) {
     const ptd::SceneConst S = ptd::scene_const(i);
@@ -390,16 +396,29 @@ void builtin_scene(pt_scene_object (&out)[ptd::kBuiltinObjects]) {
 // The kernels trace in camera space: with a camera other than the built-in one (cam != nullptr) a centre enters as
 // R^T (c - position) and a disc normal as R^T n, and the expressions below run on those values.  The built-in camera applies
 // no transform at all (not a multiplication by the identity), so "no camera set" is the same bits by construction.
-void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, const ptcamera::Basis* cam = nullptr) {
+// A polygon (vertex != nullptr: the vertices of pt_set_scene_ex's table) enters with v0 as its centre, a point, and its edges
+// e1, e2 (formed in world space in binary32, as the validation forms them) and stored normal as directions.
+void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, const ptcamera::Basis* cam = nullptr,
+                const float (*vertex)[3][3] = nullptr) {
   P.n_objects = n;
   for (uint32_t i = 0; i < n; ++i) {
     ptd::SceneObject& o = P.obj[i];
     const bool disc = src[i].shape == PT_SHAPE_DISC;
+    const bool poly = vertex && ptscene::is_polygon(src[i].shape);
     float centre[3] = {src[i].centre[0], src[i].centre[1], src[i].centre[2]};
     float normal[3] = {src[i].normal[0], src[i].normal[1], src[i].normal[2]};
     if (cam) {
       ptcamera::to_camera_point(*cam, src[i].centre, centre);
-      if (disc) ptcamera::to_camera_direction(*cam, src[i].normal, normal);
+      if (disc || poly) ptcamera::to_camera_direction(*cam, src[i].normal, normal);
+    }
+    if (poly) {
+      const ptscene::PolyFrame f = ptscene::poly_frame(vertex[i]);
+      float e1[3] = {f.e1[0], f.e1[1], f.e1[2]}, e2[3] = {f.e2[0], f.e2[1], f.e2[2]};
+      if (cam) {
+        ptcamera::to_camera_direction(*cam, f.e1, e1);
+        ptcamera::to_camera_direction(*cam, f.e2, e2);
+      }
+      P.poly[i] = ptd::PolyEdges{e1[0], e1[1], e1[2], e2[0], e2[1], e2[2]};
     }
     o.cx = centre[0]; o.cy = centre[1]; o.cz = centre[2];
     o.radius = src[i].radius;
@@ -407,7 +426,7 @@ void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, con
     o.nx = normal[0]; o.ny = normal[1]; o.nz = normal[2];
     o.colr = src[i].colour[0]; o.colg = src[i].colour[1]; o.colb = src[i].colour[2];
     o.type = src[i].material;
-    o.is_disc = disc ? 1 : 0;
+    o.is_disc = poly ? src[i].shape : (disc ? 1 : 0);   // the shape code
     // constants of a ray that starts at the origin, by the device's own expressions (this file is compiled with
     // -ffp-contract=off like the kernels; volatile keeps every intermediate a rounded binary32 whatever the host's FLT_EVAL_METHOD)
     volatile float ox = 0.f - o.cx, oy = 0.f - o.cy, oz = 0.f - o.cz;          // sub(o, c)
@@ -419,7 +438,7 @@ void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, con
     volatile float kx = (o.cx - 0.f) * o.nx, ky = (o.cy - 0.f) * o.ny, kz = (o.cz - 0.f) * o.nz;   // dot(sub(c, o), n)
     volatile float k0 = kx + ky, k1 = k0 + kz;
     o.kdisc = k1;
-    o.same_centre = (i > 0 && !disc && src[i - 1].shape != PT_SHAPE_DISC && src[i].centre[0] == src[i - 1].centre[0] &&
+    o.same_centre = (i > 0 && !disc && !poly && src[i - 1].shape == PT_SHAPE_SPHERE && src[i].centre[0] == src[i - 1].centre[0] &&
                      src[i].centre[1] == src[i - 1].centre[1] && src[i].centre[2] == src[i - 1].centre[2]) ? 1 : 0;
   }
 }
@@ -447,7 +466,7 @@ void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   const ptcamera::Basis& cb = h->camera_basis;
   const ptcamera::Basis* cam = cb.identity ? nullptr : &cb;
   if (h->scene_n) {
-    fill_scene(P, h->scene, h->scene_n, cam);
+    fill_scene(P, h->scene, h->scene_n, cam, h->scene_poly ? h->scene_vertex : nullptr);
   } else {
     pt_scene_object builtin[ptd::kBuiltinObjects];
     builtin_scene(builtin);

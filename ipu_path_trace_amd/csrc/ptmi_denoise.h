@@ -32,7 +32,7 @@ int ensure_features(pt_handle h) {
   P.lens_a = 0.f;        // ... through a pinhole
   P.emitted = nullptr;
   const uint32_t px = h->cfg.width * h->cfg.height;
-  hipLaunchKernelGGL(ptd::features_kernel, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0, h->stream, P,
+  hipLaunchKernelGGL(h->scene_n && h->scene_poly ? ptd::features_kernel_poly : ptd::features_kernel, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0, h->stream, P,
                      h->d_feat[0], h->d_feat[1]);
   PT_HIP(hipGetLastError());
   h->feature_cached_gen = h->feature_gen;

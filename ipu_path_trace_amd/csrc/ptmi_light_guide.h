@@ -67,6 +67,7 @@ inline void build(float beta, const pt_scene_object* scene, uint32_t n_objects, 
   int last = -1;
   for (uint32_t i = 0; i < n_objects && T.n < PT_MAX_SCENE_OBJECTS; ++i) {
     if (scene[i].material != PT_MATERIAL_EMISSIVE) continue;
+    if (scene[i].shape != PT_SHAPE_SPHERE && scene[i].shape != PT_SHAPE_DISC) continue;   // an emissive polygon (pt_set_scene_ex) is not drawn from
     const float* c = scene[i].colour;
     const double y = 0.2126 * (double)c[0] + 0.7152 * (double)c[1] + 0.0722 * (double)c[2];
     const double r = (double)scene[i].radius;

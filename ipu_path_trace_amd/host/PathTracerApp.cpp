@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <algorithm>
 #include <fstream>
 #include <limits>
@@ -93,7 +94,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
-      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
+      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}; a \"triangle\" or \"parallelogram\" takes \"vertices\": [[x, y, z], [x, y, z], [x, y, z]] (v0, v1, v2; the parallelogram's fourth corner is v1 + v2 - v0) instead of centre, radius and normal.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
       {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
       {"env-guide", 0, "", false, false, "FILE | map | env: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map; 'env' needs no file: the guide is built on the device from the environment in force -- the NIF of --assets, the map or the constant -- and follows a NIF loaded later). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
@@ -156,7 +157,10 @@ std::uint64_t nifMemoBytes(const std::string& text) {
 // --scene (an extension: the reference's scene is compile-time, codelets.cpp:90,110-144).  Read and checked before any device is
 // attached, with the library's own checks (ptmi_scene.h) and messages; the table goes to every handle in attach().
 // `camera` receives the file's optional top-level "camera" (every key optional, defaults of pt_camera), checked like the table.
-std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& camera, bool& hasCamera) {
+// A "triangle" or "parallelogram" takes "vertices": [[..], [..], [..]] instead of centre / radius / normal; a file that holds one is
+// checked as pt_set_scene_ex checks it and leaves its table in `ex` (empty otherwise: the file goes through pt_set_scene as ever).
+std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& camera, bool& hasCamera,
+                                           std::vector<pt_scene_object_ex>& ex) {
   const std::string at = "--scene '" + path + "': ";
   std::ifstream in(path, std::ios::binary);
   if (!in) throw std::runtime_error(at + "cannot open the file");
@@ -170,6 +174,8 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
   if (list.empty() || list.size() > PT_MAX_SCENE_OBJECTS)
     throw std::runtime_error(at + "scene: object count must be 1.." + std::to_string(PT_MAX_SCENE_OBJECTS) + " (got " + std::to_string(list.size()) + ")");
   std::vector<pt_scene_object> objs(list.size());
+  std::vector<pt_scene_object_ex> objsEx(list.size());
+  bool anyPolygon = false;
   for (std::size_t i = 0; i < list.size(); ++i) {
     const json::Value& v = list[i];
     const std::string obj = "scene object " + std::to_string(i) + ": ";
@@ -191,23 +197,46 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     };
     for (const auto& kv : v.obj)
       if (kv.first != "shape" && kv.first != "material" && kv.first != "centre" && kv.first != "radius" && kv.first != "normal" &&
-          kv.first != "colour" && kv.first != "emission")
+          kv.first != "colour" && kv.first != "emission" && kv.first != "vertices")
         throw std::runtime_error(at + obj + "unknown key \"" + kv.first + "\"");
     pt_scene_object& o = objs[i];
     o = pt_scene_object{};
     const std::string shape = name("shape"), material = name("material");
     if (shape == "sphere") o.shape = PT_SHAPE_SPHERE;
     else if (shape == "disc") o.shape = PT_SHAPE_DISC;
-    else throw std::runtime_error(at + obj + "unknown shape '" + shape + "' (sphere, disc)");
+    else if (shape == "triangle") o.shape = PT_SHAPE_TRIANGLE;
+    else if (shape == "parallelogram") o.shape = PT_SHAPE_PARALLELOGRAM;
+    else throw std::runtime_error(at + obj + "unknown shape '" + shape + "' (sphere, disc, triangle, parallelogram)");
     if (material == "diffuse") o.material = PT_MATERIAL_DIFFUSE;
     else if (material == "specular") o.material = PT_MATERIAL_SPECULAR;
     else if (material == "refractive") o.material = PT_MATERIAL_REFRACTIVE;
     else if (material == "emissive") o.material = PT_MATERIAL_EMISSIVE;
     else throw std::runtime_error(at + obj + "unknown material '" + material + "' (diffuse, specular, refractive, emissive)");
+    const bool polygon = ptscene::is_polygon(o.shape);
+    anyPolygon = anyPolygon || polygon;
+    pt_scene_object_ex& x = objsEx[i];
+    x = pt_scene_object_ex{};
+    if (polygon) {
+      for (const char* key : {"centre", "radius", "normal"})
+        if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a " + shape + " (it takes \"vertices\")");
+      if (!v.has("vertices")) throw std::runtime_error(at + obj + "\"vertices\" is missing (a " + shape + " needs three)");
+      const json::Value& a = v.at("vertices");
+      if (a.type != json::Value::Array || a.arr.size() != 3) throw std::runtime_error(at + obj + "\"vertices\" must be an array of 3 points");
+      for (std::size_t p = 0; p < 3; ++p) {
+        if (a.arr[p].type != json::Value::Array || a.arr[p].arr.size() != 3)
+          throw std::runtime_error(at + obj + "\"vertices\" must hold arrays of 3 numbers");
+        for (std::size_t c = 0; c < 3; ++c) {
+          if (a.arr[p].arr[c].type != json::Value::Number) throw std::runtime_error(at + obj + "\"vertices\" must hold numbers");
+          x.vertex[p][c] = (float)a.arr[p].arr[c].num;
+        }
+      }
+    } else {
+    if (v.has("vertices")) throw std::runtime_error(at + obj + "\"vertices\" does not apply to a " + shape);
     for (const char* key : {"centre", "radius"})
       if (!v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" is missing");
     numbers("centre", o.centre, 3);
     numbers("radius", &o.radius, 1);
+    }
     if (o.shape == PT_SHAPE_DISC) {
       if (!v.has("normal")) throw std::runtime_error(at + obj + "\"normal\" is missing (a disc needs one)");
       numbers("normal", o.normal, 3);
@@ -216,9 +245,13 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     o.colour[0] = o.colour[1] = o.colour[2] = 1.f;
     if (v.has("colour")) numbers("colour", o.colour, 3);
     if (v.has("emission")) numbers("emission", o.colour, 3);
+    std::memcpy(&x, &o, sizeof(o));   // the first 48 bytes of pt_scene_object_ex are pt_scene_object
   }
-  const std::string bad = ptscene::check(objs.data(), (std::uint32_t)objs.size());
+  const std::string bad = anyPolygon ? ptscene::check_ex(objsEx.data(), (std::uint32_t)objsEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex))
+                                     : ptscene::check(objs.data(), (std::uint32_t)objs.size());
   if (!bad.empty()) throw std::runtime_error(at + bad);
+  ex.clear();
+  if (anyPolygon) ex = objsEx;
   camera = ptcamera::default_camera();
   hasCamera = root.has("camera");
   if (hasCamera) {
@@ -291,7 +324,7 @@ void PathTracerApp::init(const OptionMap& options) {
     throw std::runtime_error("--denoise-iterations must be 1..6; got " + args.str("denoise-iterations"));
   for (const char* name : {"denoise-sigma-colour", "denoise-sigma-normal", "denoise-sigma-depth"})
     if (!std::isfinite(args.f32(name))) throw std::runtime_error(std::string("--") + name + " must be finite; got " + args.str(name));
-  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera);
+  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera, sceneEx);
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
   if (!image_io::ldrWriterFor(args.str("outfile")))
@@ -490,7 +523,10 @@ void PathTracerApp::attach() {
     devices.push_back(h);
     if (pt_set_nif_sharing(h, nifSharing))
       throw std::runtime_error(std::string("--share-nif-evaluations: ") + pt_last_error(h));
-    if (!scene.empty() && pt_set_scene(h, scene.data(), (std::uint32_t)scene.size()))
+    if (!sceneEx.empty()) {   // the file holds a polygon
+      if (pt_set_scene_ex(h, sceneEx.data(), (std::uint32_t)sceneEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex)))
+        throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
+    } else if (!scene.empty() && pt_set_scene(h, scene.data(), (std::uint32_t)scene.size()))
       throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
     if (hasCamera && pt_set_camera(h, &camera))
       throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));

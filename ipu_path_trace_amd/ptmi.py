@@ -18,8 +18,12 @@ assert PATH_DTYPE.itemsize == 48
 SCENE_DTYPE = np.dtype([("shape", "<i4"), ("material", "<i4"), ("centre", "<f4", 3), ("radius", "<f4"),
                         ("normal", "<f4", 3), ("colour", "<f4", 3)])
 assert SCENE_DTYPE.itemsize == 48   # pt_scene_object
+SCENE_EX_DTYPE = np.dtype(SCENE_DTYPE.descr + [("vertex", "<f4", (3, 3))])
+assert SCENE_EX_DTYPE.itemsize == 84   # pt_scene_object_ex
 MAX_SCENE_OBJECTS = 32
 SHAPE_SPHERE, SHAPE_DISC = 0, 1
+SHAPE_TRIANGLE, SHAPE_PARALLELOGRAM = 2, 3
+SHAPES_EX = {"sphere": SHAPE_SPHERE, "disc": SHAPE_DISC, "triangle": SHAPE_TRIANGLE, "parallelogram": SHAPE_PARALLELOGRAM}
 MATERIAL_DIFFUSE, MATERIAL_SPECULAR, MATERIAL_REFRACTIVE, MATERIAL_EMISSIVE = 0, 1, 2, 3
 SHAPES = {"sphere": SHAPE_SPHERE, "disc": SHAPE_DISC}
 MATERIALS = {"diffuse": MATERIAL_DIFFUSE, "specular": MATERIAL_SPECULAR, "refractive": MATERIAL_REFRACTIVE,
@@ -44,7 +48,8 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_train_batch", "pt_nif_train_gradients", "pt_nif_train_default_precision", "pt_nif_train_set_precision",
            "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval",
            "pt_set_light_guide", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
-           "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables"]
+           "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
+           "pt_get_scene_ex"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
@@ -202,6 +207,63 @@ def scene_array(objects):
         out[i]["normal"] = o.get("normal", (0.0, 0.0, 0.0))
         out[i]["colour"] = o.get("colour", o.get("emission", (1.0, 1.0, 1.0)))
     return out
+
+
+def _is_polygon_shape(shape):
+    return shape in ("triangle", "parallelogram") or (not isinstance(shape, str) and int(shape) in (SHAPE_TRIANGLE, SHAPE_PARALLELOGRAM))
+
+
+def has_polygon(objects):
+    """Does a scene (a SCENE_DTYPE / SCENE_EX_DTYPE array or a list of dicts) hold a triangle or a parallelogram?"""
+    if isinstance(objects, np.ndarray):
+        return bool(np.any(objects["shape"] >= SHAPE_TRIANGLE))
+    return any(_is_polygon_shape(o["shape"]) for o in objects)
+
+
+def scene_array_ex(objects):
+    """A SCENE_EX_DTYPE array (pt_scene_object_ex) from a SCENE_EX_DTYPE or SCENE_DTYPE array or a list of dicts: the keys of
+    scene_array, the shape names "triangle" and "parallelogram", and for those "vertices", three points v0, v1, v2 (a polygon
+    takes no centre, radius or normal)."""
+    if isinstance(objects, np.ndarray) and objects.dtype == SCENE_EX_DTYPE:
+        return np.ascontiguousarray(objects)
+    if isinstance(objects, np.ndarray) and objects.dtype == SCENE_DTYPE:
+        out = np.zeros(len(objects), dtype=SCENE_EX_DTYPE)
+        for name in SCENE_DTYPE.names:
+            out[name] = objects[name]
+        return out
+    out = np.zeros(len(objects), dtype=SCENE_EX_DTYPE)
+    for i, o in enumerate(objects):
+        poly = _is_polygon_shape(o["shape"])
+        allowed = {"shape", "material", "vertices", "colour", "emission"} if poly else \
+            {"shape", "material", "centre", "radius", "normal", "colour", "emission"}
+        unknown = set(o) - allowed
+        if unknown:
+            raise ValueError("scene object %d: unknown key(s) %s" % (i, sorted(unknown)))
+        shape, mat = o["shape"], o["material"]
+        out[i]["shape"] = SHAPES_EX[shape] if isinstance(shape, str) else int(shape)
+        out[i]["material"] = MATERIALS[mat] if isinstance(mat, str) else int(mat)
+        if poly:
+            vertices = np.asarray(o["vertices"], dtype=np.float32)
+            if vertices.shape != (3, 3):
+                raise ValueError("scene object %d: vertices must be three points of three coordinates" % i)
+            out[i]["vertex"] = vertices
+        else:
+            out[i]["centre"] = o["centre"]
+            out[i]["radius"] = o["radius"]
+            out[i]["normal"] = o.get("normal", (0.0, 0.0, 0.0))
+        out[i]["colour"] = o.get("colour", o.get("emission", (1.0, 1.0, 1.0)))
+    return out
+
+
+def builtin_scene_ex():
+    """The built-in scene as a SCENE_EX_DTYPE array (pt_get_scene_ex with no handle: vertices 0); needs no GPU."""
+    lib = load_library()
+    n = C.c_uint32()
+    out = np.zeros(MAX_SCENE_OBJECTS, dtype=SCENE_EX_DTYPE)
+    rc = lib.pt_get_scene_ex(None, out.ctypes.data, MAX_SCENE_OBJECTS, C.byref(n))
+    if rc:
+        raise PtError(rc, "pt_get_scene_ex failed")
+    return out[:n.value].copy()
 
 
 def builtin_scene():
@@ -393,6 +455,8 @@ def load_library(diag=False):
     L.pt_get_nif_memo_stats.argtypes = [C.c_void_p, C.POINTER(NifMemoStats)]
     L.pt_set_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.pt_get_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.pt_set_scene_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.pt_get_scene_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
@@ -728,15 +792,31 @@ class Renderer:
 
     def set_scene(self, objects):
         """Render a scene of 1..32 spheres and discs instead of the built-in one (include/ptmi.h, pt_set_scene): a SCENE_DTYPE
-        array or a list of dicts (scene_array).  None restores the built-in scene.  Takes effect at the next path_trace."""
+        array or a list of dicts (scene_array).  A list that holds a "triangle" or a "parallelogram" (scene_array_ex), or a
+        SCENE_EX_DTYPE array, goes through pt_set_scene_ex.  None restores the built-in scene.  Takes effect at the next
+        path_trace."""
         if objects is None:
             self._check(self._lib.pt_set_scene(self.handle, None, 0))
+            return
+        if (isinstance(objects, np.ndarray) and objects.dtype == SCENE_EX_DTYPE) or has_polygon(objects):
+            # a triangle or a parallelogram (or an ex table as it is): pt_set_scene_ex, keys of scene_array_ex
+            arr = scene_array_ex(objects)
+            self._check(self._lib.pt_set_scene_ex(self.handle, arr.ctypes.data, arr.size, SCENE_EX_DTYPE.itemsize))
             return
         arr = scene_array(objects)
         self._check(self._lib.pt_set_scene(self.handle, arr.ctypes.data, arr.size))   # (an empty table is refused)
 
+    def scene_ex(self):
+        """The scene in force as a SCENE_EX_DTYPE array (pt_get_scene_ex): a polygon with centre = v0, radius 0 and its stored
+        normal, a sphere or disc with vertex 0."""
+        n = C.c_uint32()
+        out = np.zeros(MAX_SCENE_OBJECTS, dtype=SCENE_EX_DTYPE)
+        self._check(self._lib.pt_get_scene_ex(self.handle, out.ctypes.data, MAX_SCENE_OBJECTS, C.byref(n)))
+        return out[:n.value].copy()
+
     def scene(self):
-        """The scene in force as a SCENE_DTYPE array (disc normals as the library normalised them)."""
+        """The scene in force as a SCENE_DTYPE array (disc normals as the library normalised them).  A scene that holds a
+        polygon raises PtError: scene_ex() reports it."""
         n = C.c_uint32()
         out = np.zeros(MAX_SCENE_OBJECTS, dtype=SCENE_DTYPE)
         self._check(self._lib.pt_get_scene(self.handle, out.ctypes.data, MAX_SCENE_OBJECTS, C.byref(n)))
