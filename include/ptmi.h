@@ -549,8 +549,9 @@ int pt_get_env_guide_tables(pt_handle h, uint32_t* threshold, uint32_t* alias, f
  * scene has no emitter, or none of positive mass, the guide is accepted but INERT: the library launches what it would launch
  * without it.  The table is rebuilt by pt_set_light_guide and by every pt_set_scene while a guide is set; the camera does not
  * change it.  beta is used as beta_thr / 2^32, beta_thr = (uint32)(beta 2^32).
- * An emissive polygon (pt_set_scene_ex) is skipped by the table (n_lights and object_index say so): it is still reached by the
- * hemisphere and environment branches, and the estimator stays unbiased because the guide is only a density mixed with the hemisphere's.
+ * An emissive polygon (pt_set_scene_ex) is skipped by the table unless pt_set_light_guide_ex asks for polygons (n_lights and
+ * object_index say so): it is still reached by the hemisphere and environment branches, and the estimator stays unbiased because
+ * the guide is only a density mixed with the hemisphere's.
  * Estimator (device, binary32, every operation rounded once, no contraction; csrc/pt_light_guide.h), in the kernel's frame, at
  * the hit point x with the normal n as the bounce forms them (a disc's stored normal is not flipped):
  *   eligible(k), sphere (c, r): v = c - x, D2 = v.v; D2 > r^2 and v.n + r > 0.
@@ -595,6 +596,38 @@ typedef struct pt_light_guide {
   float beta;                    /* probability of the light branch, 0 .. PT_LIGHT_GUIDE_MAX_BETA */
 } pt_light_guide;
 int pt_set_light_guide(pt_handle h, const pt_light_guide* g);   /* NULL clears the guide */
+/* Polygon lamps -- an EXTENSION of the emitter guide, opt-in: pt_set_light_guide_ex with PT_LIGHT_GUIDE_POLYGONS lists emissive
+ * triangles and parallelograms (pt_set_scene_ex) in the table too, in declaration order together with spheres and discs, and
+ * guided bounces draw a uniform point of their area.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves;
+ * pt_set_light_guide(h, g) is pt_set_light_guide_ex with flags = 0, an emissive polygon is then still skipped, and a process
+ * that never sets the flag launches the kernels it launched before and renders the same bits.  So does one that sets it over a
+ * scene whose emitters are all spheres and discs (the flag survives such a scene and applies again when polygons return).
+ * Table: a polygon v0 + a e1 + b e2, e1 = v1 - v0, e2 = v2 - v0, has S = sqrtf(dot(c, c)), c = cross(e1, e2), the binary32
+ * value its stored normal was divided by (world space), area A_p = S (parallelogram) or 0.5 S (triangle) and the binary64 mass
+ * m_k = Y(colour_k) 2 A_p / pi: two faces, and the pi the masses 4 r^2 and 2 r^2 dropped.  Thresholds and p_k follow as above.
+ * Estimator, with m the stored normal, kTwoPi = 2 kPi in binary32, every operation one rounded binary32, left to right:
+ *   eligible(k), polygon: v = v0 - x, hgt = v.m, d0 = v.n, d1 = e1.n, d2 = e2.n; reach = fmaxf(0, fmaxf(d1, d2)) (triangle) or
+ *     fmaxf(0, d1) + fmaxf(0, d2) (parallelogram); |hgt| > 1e-5 and d0 + reach > 0: some corner is above the horizon.
+ *   polygon draw: a = x1, b = x2; triangle only: if a + b > 1 then a = 1 - a, b = 1 - b; y = v0 + (e1 a + e2 b), e = y - x,
+ *     l2 = e.e, l = sqrtf(l2), w = e (1 / l); own term g_k = (kTwoPi (l2 l)) / (|hgt| A_p).
+ *   polygon density of any w: t = the tracer's own polygon intersection of the ray (x, w), epsilon included; t == 0 -> 0;
+ *     dn = m.w; dn == 0 -> 0; else (kTwoPi (t t)) / (|dn| A_p): positive exactly where a ray would hit.
+ * The rim rule, the denominator, the cos <= 0 rule and its length rule, the fallback of an ineligible selection and the
+ * combination with the environment guide are those of pt_set_light_guide; at a diffuse polygon hit n is the flipped normal.
+ * S is not recomputed under a camera (a rotation would change its bits): the kernels receive the world-space value.
+ * PT_ERR_INVALID_ARGUMENT, pt_last_error naming the field, checked in this order before any device call: a wrong struct_size;
+ * beta not finite or outside [0, PT_LIGHT_GUIDE_MAX_BETA]; a flags bit other than PT_LIGHT_GUIDE_POLYGONS; alpha + beta against
+ * an environment guide already set (the rule and slack above); a NULL handle.  After a rejection the previous guide and its
+ * flags stay in force.  pt_get_light_guide_info, pt_light_guide_sample and pt_light_guide_eval cover the polygon ranks while
+ * the flag is set.  pt_get_light_guide_flags: the flags of the guide in force, 0 without one. */
+enum { PT_LIGHT_GUIDE_POLYGONS = 1 };          /* flags of pt_light_guide_ex */
+typedef struct pt_light_guide_ex {             /* 12 bytes */
+  uint32_t struct_size;                        /* = sizeof(pt_light_guide_ex) */
+  float    beta;                               /* as pt_light_guide.beta */
+  uint32_t flags;                              /* 0 or PT_LIGHT_GUIDE_POLYGONS */
+} pt_light_guide_ex;
+int pt_set_light_guide_ex(pt_handle h, const pt_light_guide_ex* g);   /* NULL clears the guide */
+int pt_get_light_guide_flags(pt_handle h, uint32_t* flags);           /* flags of the guide in force, 0 without one */
 typedef struct pt_light_guide_info {
   uint32_t struct_size;          /* = sizeof(pt_light_guide_info), set by the caller */
   int32_t set, active;

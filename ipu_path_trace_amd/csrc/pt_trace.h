@@ -422,7 +422,8 @@ __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab
 
 // GUIDE: the diffuse bounce mixes the hemisphere with the environment guide (pt_env_guide.h); CAM tells it whether directions
 // are rotated between camera and world space, as in emit_escaped (CAM_LENS: when P.cam_pose says so).
-template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false>
+// PLAMPS: the emitter guide's table may list polygons (pt_set_light_guide_ex; with LIGHTS and POLY alone).
+template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length);
 
@@ -431,14 +432,14 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
 // Returns the path length (contribution-stack size, codelets.cpp:253) through `length` when the
 // path ends.
 template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false,
-          bool POLY = false>
+          bool POLY = false, bool PLAMPS = false>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length);
 #ifdef PTMI_DIAG_BUILD
 __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3 d, float& tbest);
 __device__ __forceinline__ int shade_hit_r3(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                             const uint32_t (&w)[4], float rr, uint32_t& length);
 #endif
-template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY>
+template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length) {
   uint32_t w[4];
   philox4x32_10(s.pixel, s.sample, 1u + s.depth, 0x5054u, P.seed_lo, P.seed_hi, w);
@@ -470,7 +471,7 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
 #ifdef PTMI_DIAG_BUILD
   if constexpr (LEGACY) return shade_hit_r3(P, tab, s, best, tbest, w, rr, length);
 #endif
-  return shade_hit<GUIDE, CAM, LIGHTS, POLY>(P, tab, s, best, tbest, w, rr, length);
+  return shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS>(P, tab, s, best, tbest, w, rr, length);
 }
 
 // The basis of light::diffuse (codelets.cpp:199-204) about a unit vector n: rx, ry with (rx, ry, n) orthonormal.  Its branch as
@@ -503,7 +504,7 @@ namespace ptd {
 
 // The second half of a loop trip of RayTraceKernel::compute (codelets.cpp:192-216): the ray has hit object `best` at
 // distance `tbest`; w = the bounce's Philox block, rr = its roulette weight.
-template <bool GUIDE, int CAM, bool LIGHTS, bool POLY>
+template <bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length) {
   // the hit object's row, by per-lane index
@@ -548,7 +549,7 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
       const Vec3 dw = guide_direction(gu, gv, P.azimuth);
       d = rotate ? to_camera(P, dw) : dw;
     } else if (light_branch) {
-      drawn = light_draw(P, hp, n, gw[1], gw[2], gw[3], d, g_drawn);
+      drawn = light_draw<PLAMPS>(P, hp, n, gw[1], gw[2], gw[3], d, g_drawn);
     }
     if (!env_branch && drawn < 0) d = hemisphere_direction(P, n, w);   // the hemisphere branch, and the fallback of an ineligible emitter
     s.d = d;
@@ -563,7 +564,7 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
       ge = G.alpha * guide_density(G, rotate ? to_world(P, s.d) : s.d, P.azimuth, cell);
     }
     float pe;
-    const float sum = light_mixture(P, hp, n, s.d, drawn, g_drawn, pe);
+    const float sum = light_mixture<PLAMPS>(P, hp, n, s.d, drawn, g_drawn, pe);
     s.T = scale(cwise(s.T, mk(cr, cg, cb)), (cost * rr) / ((L.one_minus + ge) + L.beta * ((1.0f - pe) + sum)));
   } else if (GUIDE && type == MAT_DIFFUSE) {
     // Guided diffuse bounce (include/ptmi.h, pt_set_env_guide): with probability alpha the direction comes from the guide's
@@ -711,7 +712,8 @@ namespace ptd {
 // workgroup barriers per 256 paths) and 2 % slower inside the C2 step -- its 16 KiB of LDS do not fit beside the NIF
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
-template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false, bool POLY = false>
+template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false, bool POLY = false,
+          bool PLAMPS = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
@@ -831,7 +833,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if constexpr ((OPT & 64) != 0) res = shade_hit_r3(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       else
 #endif
-      res = shade_hit<GUIDE, CAM, LIGHTS, POLY>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
+      res = shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       if (res == STEP_CONTINUE) alive = true;
       else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full (guided: or the guide pointed below the surface)
       // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
@@ -903,7 +905,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     int res = STEP_CONTINUE;
     uint32_t length = 0;
-    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY>(P, hit_table, st, length);
+    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY, PLAMPS>(P, hit_table, st, length);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
     const bool emitted = active && res == STEP_EMITTED;
@@ -953,6 +955,14 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_poly(cons
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true>(P); }
+// pt_set_light_guide_ex with PT_LIGHT_GUIDE_POLYGONS: the last three with the polygon branch of the emitter guide, launched only
+// while the table in force lists a polygon.  Instances of their own: the three above sit at 80 VGPRs and compile none of this.
+// Pinned to six waves like them and for their reason: left alone the allocator takes 87-88 VGPRs, five waves; held to 80 the
+// scratch goes from 52 to 64-68 bytes per lane, 8-14 VGPRs spilled, and the trace stage of a Cornell box is still 6 % shorter
+// (8.6 against 9.2 ms; resource rows and the A/B: profiles/r21_light_guide_polygons.txt).
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true>(P); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -965,7 +975,7 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
 
 // One thread per requested path; same device functions as trace_kernel.  GUIDE: the guided twin (the camera is read at run
 // time either way: CAM_LENS rotates when P.cam_pose says so).  LIGHTS: the emitter-guided twin.
-template <bool GUIDE, bool LIGHTS = false, bool POLY = false>
+template <bool GUIDE, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false>
 __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                  uint32_t n, PathRecordOut* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -980,7 +990,7 @@ __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uin
   if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
-  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
+  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY, PLAMPS>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
@@ -1005,5 +1015,7 @@ __global__ void trace_paths_guide_poly_kernel(const TraceParams P, const uint16_
                                               uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true>(P, u, v, sample, n, out); }
 __global__ void trace_paths_lights_poly_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_lights_plamps_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                                 uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true>(P, u, v, sample, n, out); }
 
 }  // namespace ptd

@@ -523,6 +523,8 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
           kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_poly : (P.cam_pose ? ptd::trace_kernel_pose_guide_poly : ptd::trace_kernel_guide_poly);
         if (P.lights.n)
           kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_poly : (P.cam_pose ? ptd::trace_kernel_pose_lights_poly : ptd::trace_kernel_lights_poly);
+        if (P.lights.n && h->light.polygons)   // the table lists a polygon lamp (pt_set_light_guide_ex)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps : ptd::trace_kernel_lights_plamps);
       }
       hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
@@ -1209,7 +1211,8 @@ static void rebuild_light_guide(pt_handle h) {
   if (!h->light_set) { h->light = ptlight::Table{}; return; }
   pt_scene_object builtin[ptd::kBuiltinObjects];
   builtin_scene(builtin);
-  if (h->scene_n) ptlight::build(h->light_beta, h->scene, h->scene_n, h->light);   // (it skips polygons)
+  const bool polygons = (h->light_flags & PT_LIGHT_GUIDE_POLYGONS) && h->scene_poly;   // else it skips polygons
+  if (h->scene_n) ptlight::build(h->light_beta, h->scene, h->scene_n, h->light, polygons ? h->scene_vertex : nullptr);
   else ptlight::build(h->light_beta, builtin, ptd::kBuiltinObjects, h->light);
 }
 
@@ -1222,8 +1225,33 @@ int pt_set_light_guide(pt_handle h, const pt_light_guide* g) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   h->light_set = g != nullptr;
   h->light_beta = g ? g->beta : 0.f;
+  h->light_flags = 0;
   rebuild_light_guide(h);
   return PT_OK;
+}
+
+// pt_set_light_guide with flags: PT_LIGHT_GUIDE_POLYGONS lists the scene's emissive polygons in the table too.
+int pt_set_light_guide_ex(pt_handle h, const pt_light_guide_ex* g) {
+  if (g) {
+    const double alpha = (h && h->guide_set) ? (double)h->guide_alpha : 0.0;
+    const std::string bad = ptlight::check_ex(g, alpha);
+    if (!bad.empty()) {   // the guide in force and its flags stay
+      if (h) h->error = bad; else g_create_error = bad;
+      return PT_ERR_INVALID_ARGUMENT;
+    }
+  }
+  if (!h) { g_create_error = "pt_set_light_guide_ex: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  h->light_set = g != nullptr;
+  h->light_beta = g ? g->beta : 0.f;
+  h->light_flags = g ? g->flags : 0u;
+  rebuild_light_guide(h);
+  return PT_OK;
+}
+
+int pt_get_light_guide_flags(pt_handle h, uint32_t* flags) {
+  if (!flags) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_light_guide_flags: null output") : PT_ERR_INVALID_ARGUMENT;
+  *flags = (h && h->light_set) ? h->light_flags : 0u;
+  return h ? PT_OK : PT_ERR_INVALID_ARGUMENT;
 }
 
 int pt_get_light_guide_info(pt_handle h, pt_light_guide_info* out) {
@@ -1269,7 +1297,7 @@ int pt_light_guide_sample(pt_handle h, const float* origin, const float* normal,
                     {g2, nullptr, n * 4, nullptr},      {g3, nullptr, n * 4, nullptr},      {nullptr, out_dir, n * 12, nullptr},
                     {nullptr, out_light, n * 4, nullptr}};
   return guide_hook(h, s, 7, [&]() {
-    hipLaunchKernelGGL(ptd::light_guide_sample_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
+    hipLaunchKernelGGL(h->light.polygons ? ptd::light_guide_sample_plamps_kernel : ptd::light_guide_sample_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
                        reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev),
                        reinterpret_cast<const uint32_t*>(s[2].dev), reinterpret_cast<const uint32_t*>(s[3].dev),
                        reinterpret_cast<const uint32_t*>(s[4].dev), (uint32_t)n, reinterpret_cast<float*>(s[5].dev),
@@ -1290,7 +1318,7 @@ int pt_light_guide_eval(pt_handle h, const float* origin, const float* normal, c
   GuideSpan s[5] = {{origin, nullptr, n * 12, nullptr}, {normal, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr},
                     {nullptr, out_sum, n * 4, nullptr}, {nullptr, out_pe, n * 4, nullptr}};
   return guide_hook(h, s, 5, [&]() {
-    hipLaunchKernelGGL(ptd::light_guide_eval_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
+    hipLaunchKernelGGL(h->light.polygons ? ptd::light_guide_eval_plamps_kernel : ptd::light_guide_eval_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
                        reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev),
                        reinterpret_cast<const float*>(s[2].dev), (uint32_t)n, reinterpret_cast<float*>(s[3].dev),
                        reinterpret_cast<float*>(s[4].dev));
@@ -1330,7 +1358,7 @@ int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t*
 }
 
 // pt_set_scene with triangles and parallelograms.  Every hook of pt_set_scene applies: the feature cache is made dirty and the
-// light guide rebuilt (its table skips polygons); the hooks pt_light_guide_sample / _eval read spheres and discs alone.
+// light guide rebuilt (its table skips polygons unless pt_set_light_guide_ex asked for them, and the hooks follow the table).
 int pt_set_scene_ex(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, uint32_t stride) {
   if (!objects && n == 0 && stride == sizeof(pt_scene_object_ex)) {   // the built-in scene
     if (!h) { g_create_error = "pt_set_scene_ex: null handle"; return PT_ERR_INVALID_ARGUMENT; }
@@ -1419,7 +1447,8 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
   auto kernel = P.lights.n ? ptd::trace_paths_lights_kernel : (h->guide_set ? ptd::trace_paths_guide_kernel : ptd::trace_paths_kernel);
   if (h->scene_n && h->scene_poly)   // the polygon twins (pt_set_scene_ex)
-    kernel = P.lights.n ? ptd::trace_paths_lights_poly_kernel : (h->guide_set ? ptd::trace_paths_guide_poly_kernel : ptd::trace_paths_poly_kernel);
+    kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_kernel : ptd::trace_paths_lights_poly_kernel)
+                        : (h->guide_set ? ptd::trace_paths_guide_poly_kernel : ptd::trace_paths_poly_kernel);
   hipLaunchKernelGGL(kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
                      ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());

@@ -222,6 +222,7 @@ struct pt_context {
   // emitter guide (pt_set_light_guide, pt_light_guide.h): host data alone, rebuilt with the scene; it travels in the kernel arguments
   bool light_set = false;
   float light_beta = 0.f;            // beta as given
+  uint32_t light_flags = 0;          // pt_set_light_guide_ex: PT_LIGHT_GUIDE_POLYGONS lists emissive polygons in the table
   ptlight::Table light{};
   bool nif_valid = false;
   int nif_hidden = 0, nif_emb = 0;   // PADDED hidden width / embedding dimension the kernels are instantiated for
@@ -421,7 +422,8 @@ void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, con
       P.poly[i] = ptd::PolyEdges{e1[0], e1[1], e1[2], e2[0], e2[1], e2[2]};
     }
     o.cx = centre[0]; o.cy = centre[1]; o.cz = centre[2];
-    o.radius = src[i].radius;
+    // (a polygon: S = |e1 x e2| as formed in world space, for the polygon-lamp instances alone; r2 and c4 stay those of radius 0)
+    o.radius = poly ? ptlight::poly_area_s(vertex[i]) : src[i].radius;
     o.r2 = src[i].radius * src[i].radius;
     o.nx = normal[0]; o.ny = normal[1]; o.nz = normal[2];
     o.colr = src[i].colour[0]; o.colg = src[i].colour[1]; o.colb = src[i].colour[2];

@@ -8,6 +8,12 @@
 // faces; the common pi is dropped).  A 32-bit word g1 selects the first k with g1 < c_k, c_k = floor(2^32 sum_{j<=k} m_j / sum m),
 // else the last emitter of positive mass, which takes the rest.  p_k is made from the QUANTISED thresholds, an integer
 // difference / 2^32: the density the kernel divides by is exactly the distribution it draws from, and the p_k sum to 1.
+//
+// Polygon lamps (pt_set_light_guide_ex, PT_LIGHT_GUIDE_POLYGONS): build() given the vertices of pt_set_scene_ex's table lists an
+// emissive triangle or parallelogram too, in declaration order with the spheres and discs, a_k = 2 A_p / pi (two faces; the pi
+// the others dropped), A_p = (double)S (parallelogram) or 0.5 (double)S (triangle), S = sqrtf(dot(c, c)), c = cross(e1, e2),
+// the binary32 value the stored normal was divided by (ptmi_scene.h, poly_frame; world space).  Without vertices -- the
+// four-argument call, pt_set_light_guide -- a polygon is skipped.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -15,6 +21,7 @@
 #include <string>
 
 #include "ptmi.h"
+#include "ptmi_scene.h"
 
 namespace ptlight {
 
@@ -31,6 +38,7 @@ struct Table {
   uint64_t weight[PT_MAX_SCENE_OBJECTS] = {};        // p_k 2^32, an integer; the weights sum to 2^32
   float probability[PT_MAX_SCENE_OBJECTS] = {};      // (float)(weight / 2^32)
   double mass[PT_MAX_SCENE_OBJECTS] = {};
+  bool polygons = false;                             // a polygon is listed: the polygon-lamp kernel instances run
   bool active() const { return n_draw != 0; }
 };
 
@@ -50,6 +58,26 @@ inline std::string check(const pt_light_guide* g, double alpha = 0.0) {
   return "";
 }
 
+// The same for pt_set_light_guide_ex, in the order include/ptmi.h states: struct_size, beta, flags, the sum.
+inline std::string check_ex(const pt_light_guide_ex* g, double alpha = 0.0) {
+  if (!g) return "light guide: null guide";
+  if (g->struct_size != sizeof(pt_light_guide_ex))
+    return "light guide: struct_size must be " + std::to_string(sizeof(pt_light_guide_ex)) + " (got " + std::to_string(g->struct_size) + ")";
+  const pt_light_guide plain{(uint32_t)sizeof(pt_light_guide), g->beta};
+  const std::string bad = check(&plain, 0.0);   // beta alone
+  if (!bad.empty()) return bad;
+  if (g->flags & ~(uint32_t)PT_LIGHT_GUIDE_POLYGONS)
+    return "light guide: flags must be 0 or PT_LIGHT_GUIDE_POLYGONS (1) (got " + std::to_string(g->flags) + ")";
+  return check(&plain, alpha);
+}
+
+// S of a polygon: sqrtf(dot(c, c)), c = cross(e1, e2), every operation one rounded binary32 -- the length normalise_ex divides by.
+inline float poly_area_s(const float (&vertex)[3][3]) {
+  const ptscene::PolyFrame f = ptscene::poly_frame(vertex);
+  volatile float len = sqrtf(f.cc);
+  return len;
+}
+
 // The same sum, seen from pt_set_env_guide while a light guide is set.
 inline std::string check_alpha(double alpha, double beta) {
   if (alpha + beta > (double)PT_LIGHT_GUIDE_MAX_BETA + kSumSlack)
@@ -58,8 +86,9 @@ inline std::string check_alpha(double alpha, double beta) {
   return "";
 }
 
-// The table of a guide check() accepted over a scene ptscene::check() accepted (n <= PT_MAX_SCENE_OBJECTS).
-inline void build(float beta, const pt_scene_object* scene, uint32_t n_objects, Table& T) {
+// The table of a guide check() accepted over a scene ptscene::check() accepted (n <= PT_MAX_SCENE_OBJECTS).  vertex: the
+// polygons' vertices (pt_set_scene_ex's table as stored) when polygon lamps are asked for, else nullptr: polygons are skipped.
+inline void build(float beta, const pt_scene_object* scene, uint32_t n_objects, Table& T, const float (*vertex)[3][3] = nullptr) {
   T = Table{};
   T.beta_thr = (uint32_t)((double)beta * kTwo32);
   T.beta = (double)T.beta_thr / kTwo32;
@@ -67,13 +96,20 @@ inline void build(float beta, const pt_scene_object* scene, uint32_t n_objects, 
   int last = -1;
   for (uint32_t i = 0; i < n_objects && T.n < PT_MAX_SCENE_OBJECTS; ++i) {
     if (scene[i].material != PT_MATERIAL_EMISSIVE) continue;
-    if (scene[i].shape != PT_SHAPE_SPHERE && scene[i].shape != PT_SHAPE_DISC) continue;   // an emissive polygon (pt_set_scene_ex) is not drawn from
+    const bool poly = ptscene::is_polygon(scene[i].shape);
+    if (poly && !vertex) continue;   // an emissive polygon (pt_set_scene_ex) is not drawn from unless pt_set_light_guide_ex asks
+    if (!poly && scene[i].shape != PT_SHAPE_SPHERE && scene[i].shape != PT_SHAPE_DISC) continue;
     const float* c = scene[i].colour;
     const double y = 0.2126 * (double)c[0] + 0.7152 * (double)c[1] + 0.0722 * (double)c[2];
     const double r = (double)scene[i].radius;
     double m = y * (scene[i].shape == PT_SHAPE_DISC ? 2.0 : 4.0) * r * r;
+    if (poly) {
+      const double S = (double)poly_area_s(vertex[i]);
+      m = y * 2.0 * (scene[i].shape == PT_SHAPE_TRIANGLE ? 0.5 * S : S) / 3.14159265358979323846;
+    }
     if (!(m > 0.0) || !std::isfinite(m)) m = 0.0;
     T.object_index[T.n] = i;
+    T.polygons = T.polygons || poly;
     T.mass[T.n] = m;
     if (m > 0.0) last = (int)T.n;
     total += m;

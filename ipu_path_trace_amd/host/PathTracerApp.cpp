@@ -102,6 +102,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"env-guide-supersample", 0, "2", false, false, "S: 1, 2 or 4 lookups of the environment per cell edge of --env-guide env."},
       {"env-guide-alpha", 0, "0.5", false, false, "Probability in [0, 0.9] that a diffuse bounce draws its direction from the guide."},
       {"light-guide-beta", 0, "0", false, false, "Probability in [0, 0.9] that a diffuse bounce draws its direction towards an emitter of the scene (0 = off); with --env-guide, alpha + beta must not exceed 0.9. Changes how directions are sampled, not the light."},
+      {"light-guide-polygons", 0, "false", false, true, "With --light-guide-beta > 0: guided bounces also draw from the emissive triangles and parallelograms of --scene, a uniform point of their area (without it an emissive polygon is reached by the hemisphere alone)."},
       {"denoise", 0, "false", false, true, "Also write <basename>_denoised.exr and _denoised.<ext> at every save: the film through the edge-avoiding A-trous filter (pt_denoise), guided by first-hit object id, normal, depth and albedo. The plain outputs are unchanged. One device with the film resident filters the resident film; --host-film, load balancing or several devices filter the host film on device 0."},
       {"denoise-iterations", 0, "5", false, false, "A-trous iterations, 1..6 (steps 1, 2, 4, ...)."},
       {"denoise-sigma-colour", 0, "4", false, false, "Colour stop of the denoiser (halved every iteration); <= 0 disables it."},
@@ -392,10 +393,25 @@ void PathTracerApp::init(const OptionMap& options) {
     const pt_light_guide g{(std::uint32_t)sizeof(pt_light_guide), lightGuideBeta};
     const std::string bad = ptlight::check(&g, envGuideRows ? (double)envGuideAlpha : 0.0);
     if (!bad.empty()) throw std::runtime_error("--light-guide-beta: " + bad);
+    lightGuidePolygons = args.flag("light-guide-polygons");
+    if (lightGuidePolygons && !(lightGuideBeta > 0.f))
+      throw std::runtime_error("--light-guide-polygons needs --light-guide-beta > 0: there is no emitter guide to extend");
     if (lightGuideBeta > 0.f) {
       ptlight::Table table;
+      if (lightGuidePolygons && !sceneEx.empty()) {   // the table as the library will build it: the stored vertices
+        std::vector<pt_scene_object_ex> stored(sceneEx);
+        ptscene::normalise_ex(stored.data(), (std::uint32_t)stored.size());
+        float vertex[PT_MAX_SCENE_OBJECTS][3][3] = {};
+        pt_scene_object head[PT_MAX_SCENE_OBJECTS] = {};
+        for (std::size_t i = 0; i < stored.size(); ++i) {
+          std::memcpy(&head[i], &stored[i], sizeof(pt_scene_object));
+          std::memcpy(vertex[i], stored[i].vertex, sizeof(vertex[i]));
+        }
+        ptlight::build(lightGuideBeta, head, (std::uint32_t)stored.size(), table, vertex);
+      } else
       ptlight::build(lightGuideBeta, scene.data(), (std::uint32_t)scene.size(), table);   // (no --scene: the built-in one, which has no emitter)
-      if (table.active()) pt_log::info_("light guide: beta {}, {} emitters", ptlight::num(lightGuideBeta), table.n);   // the value as given, %g
+      if (table.active() && table.polygons) pt_log::info_("light guide: beta {}, {} emitters, polygons included", ptlight::num(lightGuideBeta), table.n);
+      else if (table.active()) pt_log::info_("light guide: beta {}, {} emitters", ptlight::num(lightGuideBeta), table.n);   // the value as given, %g
       else pt_log::info_("light guide: inactive: the scene has no emitter");
     }
   }
@@ -629,7 +645,9 @@ void PathTracerApp::execute() {
     }
     if (lightGuideBeta > 0.f) {   // --light-guide-beta: every handle samples its emitters alike
       const pt_light_guide g{(std::uint32_t)sizeof(pt_light_guide), lightGuideBeta};
-      check(devices[d], pt_set_light_guide(devices[d], &g), "set_light_guide");
+      const pt_light_guide_ex gx{(std::uint32_t)sizeof(pt_light_guide_ex), lightGuideBeta, (std::uint32_t)PT_LIGHT_GUIDE_POLYGONS};
+      if (lightGuidePolygons) check(devices[d], pt_set_light_guide_ex(devices[d], &gx), "set_light_guide_ex");
+      else check(devices[d], pt_set_light_guide(devices[d], &g), "set_light_guide");
     }
   }
   initialiseState(imageWidth, imageHeight);

@@ -99,6 +99,7 @@ private:
   std::uint32_t envGuideRows = 0, envGuideCols = 0;   ///< --env-guide-size (default: the largest powers of two that fit)
   float envGuideAlpha = 0.5f;           ///< --env-guide-alpha
   float lightGuideBeta = 0.f;           ///< --light-guide-beta (0 = off)
+  bool lightGuidePolygons = false;      ///< --light-guide-polygons: draw from emissive triangles and parallelograms too
   bool hasCamera = false;
   bool denoise = false, saveFeatures = false;   ///< --denoise, --save-features
   pt_denoise_params denoiseParams{};            ///< --denoise-iterations / -sigma-colour / -sigma-normal / -sigma-depth over the library's defaults

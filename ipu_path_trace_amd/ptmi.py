@@ -47,7 +47,7 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_train_get_encode_params", "pt_nif_train_export", "pt_nif_train_install", "pt_nif_train_end",
            "pt_nif_train_batch", "pt_nif_train_gradients", "pt_nif_train_default_precision", "pt_nif_train_set_precision",
            "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval",
-           "pt_set_light_guide", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
+           "pt_set_light_guide", "pt_set_light_guide_ex", "pt_get_light_guide_flags", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
            "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
            "pt_get_scene_ex"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
@@ -56,6 +56,7 @@ ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
 ENV_FILTERS = {"nearest": ENV_FILTER_NEAREST, "bilinear": ENV_FILTER_BILINEAR}
 ENV_GUIDE_MAX_ROWS, ENV_GUIDE_MAX_COLS, ENV_GUIDE_MAX_ALPHA = 1024, 2048, 0.9
 LIGHT_GUIDE_MAX_BETA = 0.9
+LIGHT_GUIDE_POLYGONS = 1          # PT_LIGHT_GUIDE_POLYGONS: flags of pt_light_guide_ex
 COMM_ID_BYTES = 128
 HDR_ACCUMULATORS, HDR_FILM = 0, 1
 DENOISE_HOST_IMAGE, DENOISE_ACCUMULATORS, DENOISE_FILM = 0, 1, 2
@@ -147,6 +148,11 @@ class LightGuide(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("beta", C.c_float)]
 
 
+class LightGuideEx(C.Structure):
+    """pt_light_guide_ex (include/ptmi.h): pt_light_guide with flags (LIGHT_GUIDE_POLYGONS: draw from emissive polygons too)."""
+    _fields_ = [("struct_size", C.c_uint32), ("beta", C.c_float), ("flags", C.c_uint32)]
+
+
 class LightGuideInfo(C.Structure):
     """pt_light_guide_info (include/ptmi.h): the emitter guide in force and its table."""
     _fields_ = [("struct_size", C.c_uint32), ("set", C.c_int32), ("active", C.c_int32), ("beta", C.c_float),
@@ -154,6 +160,7 @@ class LightGuideInfo(C.Structure):
                 ("probability", C.c_float * 32)]
 
 
+assert C.sizeof(LightGuideEx) == 12
 assert C.sizeof(LightGuide) == 8 and C.sizeof(LightGuideInfo) == 404   # pt_light_guide, pt_light_guide_info
 
 
@@ -468,6 +475,8 @@ def load_library(diag=False):
     L.pt_get_env_guide_info.argtypes = [C.c_void_p, C.POINTER(EnvGuideInfo)]
     L.pt_get_env_guide_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.pt_set_light_guide.argtypes = [C.c_void_p, C.POINTER(LightGuide)]
+    L.pt_set_light_guide_ex.argtypes = [C.c_void_p, C.POINTER(LightGuideEx)]
+    L.pt_get_light_guide_flags.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.pt_get_light_guide_info.argtypes = [C.c_void_p, C.POINTER(LightGuideInfo)]
     L.pt_light_guide_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p, C.c_void_p]
@@ -667,16 +676,28 @@ class Renderer:
         self._check(self._lib.pt_env_guide_eval(self.handle, d.ctypes.data, len(d), cell.ctypes.data, g.ctypes.data))
         return cell, g
 
-    def set_light_guide(self, beta=0.5):
+    def set_light_guide(self, beta=0.5, polygons=False):
         """Guide diffuse bounces towards the scene's emitters (include/ptmi.h, pt_set_light_guide): with probability beta in
         [0, 0.9] a bounce draws its direction from an emissive sphere's visible cone or a point of an emissive disc.  None
         clears the guide.  It changes how directions are sampled, not the light; a scene without emitters leaves it inert.  The
-        guide follows set_scene; a rejected one (PtError) leaves the previous one in force."""
+        guide follows set_scene; a rejected one (PtError) leaves the previous one in force.  polygons=True
+        (pt_set_light_guide_ex, PT_LIGHT_GUIDE_POLYGONS) draws from emissive triangles and parallelograms too, a uniform point of
+        their area; polygons=False is pt_set_light_guide itself, which skips them."""
         if beta is None:
             self._check(self._lib.pt_set_light_guide(self.handle, None))
             return
+        if polygons:
+            gx = LightGuideEx(C.sizeof(LightGuideEx), float(beta), LIGHT_GUIDE_POLYGONS)
+            self._check(self._lib.pt_set_light_guide_ex(self.handle, C.byref(gx)))
+            return
         g = LightGuide(C.sizeof(LightGuide), float(beta))
         self._check(self._lib.pt_set_light_guide(self.handle, C.byref(g)))
+
+    def light_guide_flags(self):
+        """pt_get_light_guide_flags: the flags of the emitter guide in force (LIGHT_GUIDE_POLYGONS), 0 without one."""
+        flags = C.c_uint32(0)
+        self._check(self._lib.pt_get_light_guide_flags(self.handle, C.byref(flags)))
+        return flags.value
 
     def light_guide_info(self):
         """pt_get_light_guide_info as a dict: set, active, beta, and per emitter object_index, threshold, probability."""
