@@ -350,6 +350,102 @@ typedef struct pt_scene_object_ex {   /* 84 bytes; the first 48 are pt_scene_obj
 int pt_set_scene_ex(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, uint32_t stride /* = sizeof(pt_scene_object_ex) */);
 int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uint32_t* n);
 
+/* Triangle meshes in a runtime scene -- an EXTENSION, opt-in and additive: PTMI_ABI_VERSION stays 5 and no existing struct moves; a
+ * process that never calls pt_set_scene_meshes launches the kernels it launched before and renders the same bits.
+ *
+ * Rows and meshes.  The table is pt_set_scene_ex's with one more shape, PT_SHAPE_MESH.  The k-th row of that shape, in declaration
+ * order, takes meshes[k]; the number of such rows must equal n_meshes.  A mesh is ONE row of the table, whatever its size: n stays
+ * 1..32.  Material and colour come from the row -- all four materials, one per mesh -- and a mesh row ignores centre, radius,
+ * normal and vertex.  A table without a mesh row (n_meshes == 0) IS pt_set_scene_ex's scene, bit for bit, on the kernels that ran
+ * before.  pt_set_scene and pt_set_scene_ex are unchanged and still refuse shape 4.  (NULL, 0, stride, NULL, 0) restores the
+ * built-in scene.
+ *
+ * Copies.  The library copies everything and retains no host pointer.  It keeps a host copy of the triangles' world-space frames
+ * (48 bytes per triangle), because a new camera needs them (below); the trees and the triangles the kernels read live in device
+ * memory (pt_mesh_info.device_bytes), owned by the handle and freed by pt_destroy or by the next scene.
+ *
+ * Triangle j of a mesh.  v0, v1, v2 are vertices[indices[3 j + 0 .. 2]]; e1 = v1 - v0 and e2 = v2 - v0 in binary32, and the
+ * stored normal is n = c / sqrtf(dot(c, c)), c = cross(e1, e2), exactly as for a PT_SHAPE_TRIANGLE object.  Shading is FLAT:
+ * there are no vertex normals and no texture coordinates.
+ *
+ * Intersection.  A triangle is tested by the expression sequence of a PT_SHAPE_TRIANGLE object, unchanged, then by the scene's
+ * t > eps and t < tbest in declaration order, as every object is.  Ties inside one mesh: the smallest t wins and, among equal
+ * t, the lowest triangle index, so the result does not depend on the tree and equals what the same triangles would give as
+ * consecutive PT_SHAPE_TRIANGLE rows.  Across objects the rule stays declaration order, strict <.
+ * NOT WATERTIGHT: the triangle test decides every triangle on its own, and its t > eps starts a bounce a little off the surface, so
+ * a ray that meets the shared edge of two triangles, or leaves a hit point within about eps of such an edge, can pass between
+ * them.  A closed unit box about the camera lets 8 of 6144 mirror paths and 22 of 6144 diffuse paths of six bounces out.  The
+ * same triangles as PT_SHAPE_TRIANGLE rows let the identical paths out: it is the polygon test's property, and the tree adds none.
+ *
+ * The tree.  Each mesh gets a binary bounding-volume hierarchy, built on the host by binned SAH with at most four triangles per
+ * leaf and walked by the kernels without a stack (depth-first node order with skip links).  Node boxes are padded outward by one
+ * value per mesh, pad = 2^-16 x the largest absolute coordinate of the mesh's box (pt_mesh_info.pad).  The pad is a safety margin,
+ * not a proof: the triangle test's rounding grows at grazing incidence and with the distance of the ray's origin (from thousands
+ * of box sizes away, where an ulp of t reaches the pad, ties between neighbouring triangles can fall the other way).  What is
+ * promised is that the library's tests find no difference between the tree walk and a loop over all triangles
+ * (PT_MESH_INTERSECT_BRUTE below is that loop).  The box test drops an axis whose slab products are NaN (0 x inf: the origin in a
+ * slab plane, the direction parallel to it) and visits a node whose near distance EQUALS the best t so far.  With a positive pad
+ * neither rule can change a result for rays from nearby -- a ray in a padded box's face is a pad away from that box's triangles
+ * -- so nothing that runs the shipped pad, on the device or the host, can tell a wrong NaN rule from a right one: it is pinned on
+ * the host alone, by a tree built with pad 0 (tests/mesh_bvh_main.cpp); the equality is also met on the device, by rays from far
+ * above a flat mesh, where rounding absorbs the pad.
+ *
+ * Shading and other passes.  A mesh triangle is two-sided and follows the polygon rules word for word: the stored normal is
+ * flipped to face the ray for diffuse and specular, glass flips its own normal, an emitter emits from both faces.  Feature
+ * buffers: object_id is the ROW index; depth and normal are the hit triangle's (the disc / polygon rule); albedo follows the
+ * material rule.  Emitter guide: an emissive mesh is SKIPPED by the table, whether or not polygon lamps are asked for; it is reached
+ * by the hemisphere and environment branches, so the estimator stays unbiased (n_lights and object_index say what is listed).
+ * The environment guide applies at a diffuse mesh hit as at any diffuse hit.
+ *
+ * Camera.  Under a pose v0 enters the kernels as a point and e1, e2 and n as directions through the camera's transform, from
+ * the world values -- exactly what polygons do -- and the tree is built over the triangles as the kernel sees them.  A
+ * pt_set_camera that changes the pose makes the meshes stale: they are transformed and rebuilt before the next pt_path_trace,
+ * pt_trace_paths, pt_feature_buffers or pt_mesh_intersect.  Device buffers are sized once, at pt_set_scene_meshes (a tree of T
+ * triangles has at most 2 T - 1 nodes): a rebuild allocates no device memory and cannot run out of it.  pt_mesh_info.build_ms
+ * reports the last build.
+ *
+ * Validation returns PT_ERR_INVALID_ARGUMENT, and pt_last_error names the object, the mesh, the triangle and the field.  The
+ * checks run in this order, before any device call: stride; n outside 1..32; a NULL table; per row the checks of
+ * pt_set_scene_ex (a mesh row: material and colour only); the number of mesh rows against n_meshes (and a NULL mesh table); per
+ * mesh struct_size, NULL vertices or indices, n_triangles == 0; the scene's total above PT_MAX_MESH_TRIANGLES; then per mesh
+ * and triangle an index >= n_vertices, a referenced vertex that is not finite, and e1, e2 or their cross product not finite or
+ * dot(c, c) not > 0 ("vertices are collinear"); last, a NULL handle (pt_last_error(NULL) then reports it).  After a rejection
+ * or PT_ERR_OUT_OF_MEMORY the previous scene stays in force.
+ *
+ * Getters.  pt_get_scene_ex reports a mesh row with shape 4 and its geometric fields 0.  pt_get_scene answers as it does for a
+ * polygon: the count, and PT_ERR_INVALID_ARGUMENT when asked to copy.  pt_get_mesh_info describes mesh k of the scene in force
+ * (PT_ERR_INVALID_ARGUMENT when there is none). */
+enum { PT_SHAPE_MESH = 4 };
+#define PT_MAX_MESH_TRIANGLES (1u << 22)      /* per scene, all meshes together */
+typedef struct pt_mesh {              /* 32 bytes */
+  uint32_t struct_size;               /* sizeof(pt_mesh) */
+  uint32_t n_vertices, n_triangles;
+  const float* vertices;              /* [n_vertices][3], world space, host memory */
+  const uint32_t* indices;            /* [n_triangles][3] */
+} pt_mesh;
+int pt_set_scene_meshes(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, uint32_t stride /* = sizeof(pt_scene_object_ex) */,
+                        const pt_mesh* meshes, uint32_t n_meshes);
+typedef struct pt_mesh_info {         /* 48 bytes */
+  uint32_t struct_size;               /* in: sizeof(pt_mesh_info) */
+  uint32_t object_index;              /* the mesh's row in the table */
+  uint32_t n_triangles, n_nodes;
+  uint32_t max_leaf, depth;           /* most triangles in a leaf (<= 4); levels of the tree */
+  uint64_t device_bytes;              /* this mesh's share of the device buffers, sized for 2 T - 1 nodes */
+  double build_ms;                    /* host time of the last transform + build of this mesh */
+  float pad;                          /* the outward pad of its node boxes, in the kernel's frame */
+} pt_mesh_info;
+int pt_get_mesh_info(pt_handle h, uint32_t mesh, pt_mesh_info* out);
+/* Kernel-level hook, like pt_light_guide_sample and pt_env_map_lookup: the kernels' own mesh-aware nearest hit over n caller
+ * rays, origin[n][3] and dir[n][3].  Origins and directions are WORLD space and the camera in force is IGNORED: the rays meet
+ * the scene as the built-in camera sees it (under a pose the trees are rebuilt for this call and again for the next render).
+ * out_t[i] is the hit distance (0 for a miss), out_object[i] the row index (-1 for a miss) and out_triangle[i] the triangle's
+ * index in its mesh (-1 unless a mesh was hit).  PT_MESH_INTERSECT_BRUTE replaces the tree walk by a loop over all triangles
+ * of each mesh with the same triangle function and the same tie rule: the yardstick for the tree.  PT_ERR_NOT_READY without a
+ * mesh in force; n == 0 is a no-op. */
+enum { PT_MESH_INTERSECT_BVH = 0, PT_MESH_INTERSECT_BRUTE = 1 };
+int pt_mesh_intersect(pt_handle h, const float* origin, const float* dir, size_t n, int32_t mode,
+                      float* out_t, int32_t* out_object, int32_t* out_triangle);
+
 /* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
  * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an
  * optional thin lens.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves.

@@ -19,7 +19,7 @@ namespace ptd {
 
 constexpr int kFeatureBlock = 256;
 
-template <bool POLY>
+template <bool POLY, bool MESH = false>
 __device__ __forceinline__ void features_body(const TraceParams& P, float4* __restrict__ f0, float4* __restrict__ f1) {
   const uint32_t i = blockIdx.x * kFeatureBlock + threadIdx.x;
   if (i >= P.width * P.height) return;   // width, height <= 65535: the product fits 32 bits
@@ -27,7 +27,15 @@ __device__ __forceinline__ void features_body(const TraceParams& P, float4* __re
   PathState st;
   float camx, camy, tbest;
   start_path(P, u | (v << 16), 0u, st, camx, camy);   // P.aa_scale == 0 (the host's copy): the noise-free ray
-  const int best = nearest_hit_primary<false, POLY>(P, st.d, tbest);
+  if constexpr (MESH) {
+    // On the image's middle row py = -(+0 x ty) = -0, so camy and d.y are -0.  In this instance the compiler folds the rounding to
+    // half into a fused multiply-add with a +0 addend, which turns that -0 into +0; the other instances keep it.  The sign is put
+    // back, so that a sphere centred on the camera's horizontal plane gets the normal.y = -0 there that the other instances report.
+    if (camy == 0.0f) st.d.y = -0.0f;
+  }
+  int best = nearest_hit_primary<false, POLY, MESH>(P, st.d, tbest);
+  [[maybe_unused]] const int packed = best;   // a MESH instance's hit is packed: `best` becomes the object's row, what the buffer reports
+  if constexpr (MESH) best = packed < 0 ? -1 : hit_object<true>(packed);
   Vec3 n = mk(0.f, 0.f, 0.f), alb = mk(1.f, 1.f, 1.f);
   float depth = 0.f;
   if (best >= 0) {
@@ -36,6 +44,9 @@ __device__ __forceinline__ void features_body(const TraceParams& P, float4* __re
     // sphere: (hit - centre) / |hit - centre| -- (hit - centre) / radius but for the rounding of the hit point, and unit to
     // rounding as the production shading forms it (shade_hit); disc or polygon (shape code >= 1): its stored normal
     n = ob.is_disc ? mk(ob.nx, ob.ny, ob.nz) : normalise(sub(scale(st.d, tbest), mk(ob.cx, ob.cy, ob.cz)));
+    if constexpr (MESH) {   // a mesh: the hit triangle's stored normal
+      if (ob.is_disc == SHAPE_MESH) { const ptmesh::F4 tn = P.mesh_tris[3u * (size_t)hit_slot(packed) + 2u]; n = mk(tn.y, tn.z, tn.w); }
+    }
     if (dot(n, st.d) > 0.0f) n = scale(n, -1.0f);                     // faces the ray
     if (P.cam_pose) n = normalise(to_world(P, n));                    // reported in world space; unit again after the rotation's roundings
     if (ob.type == MAT_DIFFUSE || ob.type == MAT_REFRACTIVE) alb = mk(ob.colr, ob.colg, ob.colb);   // mirrors, emitters and misses demodulate by 1
@@ -50,6 +61,10 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
 // pt_set_scene_ex: launched only while the scene in force holds a polygon
 __global__ __launch_bounds__(kFeatureBlock) void features_kernel_poly(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
   features_body<true>(P, f0, f1);
+}
+// pt_set_scene_meshes: launched only while the scene in force holds a mesh
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel_mesh(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
+  features_body<true, true>(P, f0, f1);
 }
 
 }  // namespace ptd

@@ -1,0 +1,127 @@
+// pt_mesh.h -- the walk of a mesh's stackless BVH and its box test (pt_set_scene_meshes, include/ptmi.h), written ONCE for the
+// kernels and for the host: no HIP intrinsic, no HIP type, so tests/mesh_bvh_main.cpp compiles it with g++ alone.  Compile
+// with -ffp-contract=off like everything else here: every operation below is one rounded binary32.
+//
+// Layout (built by ptmi_mesh.h).  Nodes lie in depth-first order, the left child of an inner node at node + 1; `skip` is the
+// node to continue at when a node's box is missed and also what follows a leaf; skip == n_nodes ends the walk, so the walk
+// keeps no stack.  Triangles lie in leaf order ("slots"), three 16-byte vectors each holding v0, e1, e2, n as twelve floats;
+// orig[slot] is the triangle's index in the caller's mesh.
+//
+// Ties.  The smallest t wins and, among equal t INSIDE one mesh, the lowest original index, so the result does not depend on
+// the tree: the node test uses <= against the best t so far, and the triangle loop accepts t == tbest from a lower index.
+// Against a hit of an earlier object the rule stays the scene's strict < (best_orig starts at 0: no index is lower).
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PT_MESH_HD __host__ __device__ __forceinline__
+#else
+#define PT_MESH_HD inline
+#endif
+
+namespace ptmesh {
+
+constexpr float kEps = 1e-5f;              // = ptd::kEps: the scene's intersection epsilon
+constexpr float kFarWiden = 1.0000004f;    // tfar is widened by a few ulps before it is compared
+constexpr uint32_t kMaxLeaf = 4;           // triangles per leaf at most
+constexpr uint32_t kLeafCountBits = 3;     // leaf word: first slot << 3 | count; 0 = an inner node
+
+struct alignas(16) F4 { float x, y, z, w; };
+struct alignas(16) Node {                  // 32 bytes
+  float lo[3], hi[3];
+  uint32_t skip;
+  uint32_t leaf;
+};
+static_assert(sizeof(F4) == 16 && sizeof(Node) == 32, "mesh node / vector layout");
+
+// A triangle's twelve floats from its three vectors.
+struct Tri { float v0[3], e1[3], e2[3]; };
+PT_MESH_HD Tri load_tri(const F4* t) {
+  const F4 a = t[0], b = t[1];
+  const float e2z = t[2].x;
+  return Tri{{a.x, a.y, a.z}, {a.w, b.x, b.y}, {b.z, b.w, e2z}};
+}
+
+// poly_intersect (pt_trace.h) for SHAPE_TRIANGLE, expression for expression: Moeller-Trumbore, two-sided.  0 for a miss.
+PT_MESH_HD float tri_intersect(const float* o, const float* d, const Tri& T) {
+  const float* e1 = T.e1;
+  const float* e2 = T.e2;
+  const float pvx = d[1] * e2[2] - d[2] * e2[1], pvy = d[2] * e2[0] - d[0] * e2[2], pvz = d[0] * e2[1] - d[1] * e2[0];   // cross(d, e2)
+  const float det = e1[0] * pvx + e1[1] * pvy + e1[2] * pvz;
+  if (det == 0.0f) return 0.0f;
+  const float inv = 1.0f / det;
+  const float tvx = o[0] - T.v0[0], tvy = o[1] - T.v0[1], tvz = o[2] - T.v0[2];
+  const float a = (tvx * pvx + tvy * pvy + tvz * pvz) * inv;
+  if (!(a >= 0.0f) || a > 1.0f) return 0.0f;
+  const float qvx = tvy * e1[2] - tvz * e1[1], qvy = tvz * e1[0] - tvx * e1[2], qvz = tvx * e1[1] - tvy * e1[0];         // cross(tv, e1)
+  const float b = (d[0] * qvx + d[1] * qvy + d[2] * qvz) * inv;
+  if (!(b >= 0.0f)) return 0.0f;
+  if (a + b > 1.0f) return 0.0f;
+  const float t = (e2[0] * qvx + e2[1] * qvy + e2[2] * qvz) * inv;
+  return t > kEps ? t : 0.0f;
+}
+
+// 1 / d per component; a zero component gives +-inf.
+PT_MESH_HD void ray_inverse(const float* d, float* inv) {
+  inv[0] = 1.0f / d[0]; inv[1] = 1.0f / d[1]; inv[2] = 1.0f / d[2];
+}
+
+// The slab test.  Two products per axis.  A NaN among them is 0 x inf: the origin lies ON a slab plane and the direction is
+// parallel to it, so the ray runs inside the closed slab -- a triangle with an edge in that plane is hit -- and the axis is
+// DROPPED: it constrains nothing, instead of rejecting the node.  (The other product of that axis is then +-inf or NaN too;
+// taking it as the axis' near and far value would reject as well, so the whole axis goes.)  Visit when tnear <= tfar, tfar > 0
+// and tnear <= tbest (<=: an equal-t triangle of a lower index is still reached).
+PT_MESH_HD bool box_hit(const Node& N, const float* o, const float* inv, float tbest) {
+  float tnear = -INFINITY, tfar = INFINITY;
+  for (int k = 0; k < 3; ++k) {
+    const float t0 = (N.lo[k] - o[k]) * inv[k], t1 = (N.hi[k] - o[k]) * inv[k];
+#ifdef PT_MESH_MUTATE_NAN   // (tests/mesh_bvh_main.cpp: the mutation must fail the test)
+    if (t0 != t0 || t1 != t1) return false;
+#endif
+    const bool on_plane = t0 != t0 || t1 != t1;
+    tnear = on_plane ? tnear : fmaxf(tnear, fminf(t0, t1));
+    tfar = on_plane ? tfar : fminf(tfar, fmaxf(t0, t1));
+  }
+  tfar = tfar * kFarWiden;
+#ifdef PT_MESH_MUTATE_CULL
+  return tnear <= tfar && tfar > 0.0f && tnear < tbest;
+#else
+  return tnear <= tfar && tfar > 0.0f && tnear <= tbest;
+#endif
+}
+
+// One candidate against the best so far.
+PT_MESH_HD void consider(float t, uint32_t slot, uint32_t index, float& tbest, int& best_slot, uint32_t& best_orig) {
+  if (t > kEps && (t < tbest || (t == tbest && index < best_orig))) { tbest = t; best_slot = (int)slot; best_orig = index; }
+}
+
+// The nearest triangle of one mesh in front of tbest: its slot, or -1 when the best so far stands.  tbest is carried in and out,
+// so the walk culls against the best hit of the objects before it.
+PT_MESH_HD int walk(const Node* nodes, uint32_t n_nodes, const F4* tris, const uint32_t* orig, const float* o, const float* d,
+                    const float* inv, float& tbest) {
+  int best_slot = -1;
+  uint32_t best_orig = 0;
+  uint32_t node = 0;
+  while (node < n_nodes) {
+    const Node N = nodes[node];
+    if (!box_hit(N, o, inv, tbest)) { node = N.skip; continue; }
+    if (N.leaf == 0u) { node += 1u; continue; }
+    const uint32_t first = N.leaf >> kLeafCountBits, count = N.leaf & ((1u << kLeafCountBits) - 1u);
+    for (uint32_t s = first; s < first + count; ++s)
+      consider(tri_intersect(o, d, load_tri(tris + 3u * s)), s, orig[s], tbest, best_slot, best_orig);
+    node = N.skip;
+  }
+  return best_slot;
+}
+
+// The yardstick: the same triangle function and the same tie rule over every triangle of the mesh, no tree.
+PT_MESH_HD int brute(const F4* tris, const uint32_t* orig, uint32_t n_triangles, const float* o, const float* d, float& tbest) {
+  int best_slot = -1;
+  uint32_t best_orig = 0;
+  for (uint32_t s = 0; s < n_triangles; ++s)
+    consider(tri_intersect(o, d, load_tri(tris + 3u * s)), s, orig[s], tbest, best_slot, best_orig);
+  return best_slot;
+}
+
+}  // namespace ptmesh

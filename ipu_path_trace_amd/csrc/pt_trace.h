@@ -24,6 +24,7 @@
 #pragma once
 #include "pt_device_math.h"
 #include "pt_env_guide.h"
+#include "pt_mesh.h"
 
 #include <utility>
 
@@ -70,7 +71,17 @@ struct LightParams {
 struct PolyEdges {
   float e1x, e1y, e1z, e2x, e2y, e2z;
 };
-enum { SHAPE_TRIANGLE = 2, SHAPE_PARALLELOGRAM = 3 };   // = PT_SHAPE_* (include/ptmi.h)
+enum { SHAPE_TRIANGLE = 2, SHAPE_PARALLELOGRAM = 3, SHAPE_MESH = 4 };   // = PT_SHAPE_* (include/ptmi.h)
+static_assert(ptmesh::kEps == kEps, "one intersection epsilon");
+
+// A mesh row (pt_set_scene_meshes) has no edges of its own: its PolyEdges slot carries, as bit patterns, where its tree and its
+// triangles lie in the arrays below the scene (mesh_nodes, mesh_tris / mesh_orig).  The MESH instances alone read it.
+struct MeshRow {
+  uint32_t node_base, tri_base, n_nodes, n_triangles, unused[2];
+};
+static_assert(sizeof(MeshRow) == sizeof(PolyEdges), "a mesh row travels in its PolyEdges slot");
+constexpr int kHitObjectBits = 5;   // a MESH instance's hit: object | slot << 5 (the slot counts over all meshes: < 2^22)
+static_assert((1 << kHitObjectBits) == kMaxObjects, "5 bits of object in a packed hit");
 
 struct TraceParams {
   SceneObject obj[kMaxObjects];   // obj[0 .. n_objects): the scene in declaration order
@@ -119,6 +130,12 @@ struct TraceParams {
   // Polygon edges (pt_set_scene_ex): read by the POLY instances alone, which are launched only while the scene in force holds a
   // polygon.  Last again: nothing any other instance reads moves.
   PolyEdges poly[kMaxObjects];
+  // Meshes (pt_set_scene_meshes): the trees, the triangles in leaf order (three vectors each: v0, e1, e2, n) and slot -> triangle
+  // index, in device memory; read by the MESH instances alone, which are launched only while the scene in force holds a mesh.
+  // (Three pointers, not two: the twelve floats of a triangle and the 32 bytes of a node leave no room for the index.)
+  const ptmesh::Node* mesh_nodes;
+  const ptmesh::F4* mesh_tris;
+  const uint32_t* mesh_orig;
 };
 static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
 
@@ -279,19 +296,47 @@ __device__ __forceinline__ float poly_intersect(Vec3 o, Vec3 d, const SceneObjec
 // A sphere that shares its centre with the object declared before it (the clear-coat pair, codelets.cpp:115-116) reuses that
 // object's sub(o, c), dot(oc, d) and dot(oc, oc): the same expressions on the same values (wave-uniform flag from the host).
 // POLY: the scene may hold polygons (shape codes 2, 3); every other instance compiles none of that.
-template <bool PIPE = false, bool POLY = false>   // PIPE: the next object's constants are requested before this object's arithmetic, awaited after it
+// MESH (implies POLY): the scene may hold meshes (shape code 4).  The object loop stays rolled and wave-uniform; at a mesh row each
+// lane walks that mesh's tree (pt_mesh.h: lane-divergent by nature) with the tbest it has so far, so the walk culls against the
+// best hit of the objects before it.  The hit comes back PACKED, object | slot << 5 (hit_object / hit_slot below); the other
+// instances return the object index as before.  BRUTE (pt_mesh_intersect's yardstick): a loop over the mesh's triangles instead.
+template <bool MESH>
+__device__ __forceinline__ int hit_object(int best) { return MESH ? (best & (kMaxObjects - 1)) : best; }
+__device__ __forceinline__ uint32_t hit_slot(int best) { return (uint32_t)best >> kHitObjectBits; }
+template <bool BRUTE>
+__device__ __forceinline__ int mesh_hit(const TraceParams& P, int i, Vec3 o, Vec3 d, const float (&inv)[3], float& tbest) {
+  const PolyEdges pe = P.poly[i];
+  const uint32_t node_base = __float_as_uint(pe.e1x), tri_base = __float_as_uint(pe.e1y);
+  const float ov[3] = {o.x, o.y, o.z}, dv[3] = {d.x, d.y, d.z};
+  const int slot = BRUTE ? ptmesh::brute(P.mesh_tris + 3u * (size_t)tri_base, P.mesh_orig + tri_base, __float_as_uint(pe.e2x), ov, dv, tbest)
+                         : ptmesh::walk(P.mesh_nodes + node_base, __float_as_uint(pe.e1z), P.mesh_tris + 3u * (size_t)tri_base,
+                                        P.mesh_orig + tri_base, ov, dv, inv, tbest);
+  return slot < 0 ? -1 : (i | (int)((tri_base + (uint32_t)slot) << kHitObjectBits));
+}
+
+template <bool PIPE = false, bool POLY = false, bool MESH = false, bool BRUTE = false>   // PIPE: the next object's constants are requested before this object's arithmetic, awaited after it
 __device__ __forceinline__ int nearest_hit(const TraceParams& P, Vec3 o, Vec3 d, float& tbest) {
+  static_assert(POLY || !MESH, "MESH implies POLY");
   int best = -1;
   tbest = kInf;
   float b = 0.f, oc2 = 0.f;
   const int n = (int)P.n_objects;
   SceneObject nxt = P.obj[0];
+  float inv[3] = {0.f, 0.f, 0.f};
+  if constexpr (MESH) { const float dv[3] = {d.x, d.y, d.z}; ptmesh::ray_inverse(dv, inv); }
 #pragma unroll 1
   for (int i = 0; i < n; ++i) {
     SceneObject ob;
     if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < n ? i + 1 : n - 1]; }
     else ob = P.obj[i];
     float t;
+    if constexpr (MESH) {
+      if (ob.is_disc == SHAPE_MESH) {
+        const int h = mesh_hit<BRUTE>(P, i, o, d, inv, tbest);   // tbest moves with it
+        if (h >= 0) best = h;
+        continue;
+      }
+    }
     if (POLY && ob.is_disc >= SHAPE_TRIANGLE) {
       if constexpr (POLY) t = poly_intersect(o, d, ob, P.poly[i]);
     } else if (ob.is_disc) {
@@ -320,19 +365,28 @@ __device__ __forceinline__ int nearest_hit(const TraceParams& P, Vec3 o, Vec3 d,
 // constants, everything that depends on the direction is the expression of sphere_intersect / disc_intersect unchanged, so
 // the result is the same float.  (Disc: the hit point add(o, scale(d, t)) is scale(d, t) but for the sign of a zero, which
 // sub(p, c) and the squares that follow erase.)
-template <bool PIPE = false, bool POLY = false>
+template <bool PIPE = false, bool POLY = false, bool MESH = false>
 __device__ __forceinline__ int nearest_hit_primary(const TraceParams& P, Vec3 d, float& tbest) {
   int best = -1;
   tbest = kInf;
   float b = 0.f;
   const int n = (int)P.n_objects;
   SceneObject nxt = P.obj[0];
+  float inv[3] = {0.f, 0.f, 0.f};
+  if constexpr (MESH) { const float dv[3] = {d.x, d.y, d.z}; ptmesh::ray_inverse(dv, inv); }
 #pragma unroll 1
   for (int i = 0; i < n; ++i) {
     SceneObject ob;
     if constexpr (PIPE) { ob = nxt; nxt = P.obj[i + 1 < n ? i + 1 : n - 1]; }
     else ob = P.obj[i];
     float t;
+    if constexpr (MESH) {   // the general walk at o = (0, 0, 0), as a polygon below
+      if (ob.is_disc == SHAPE_MESH) {
+        const int h = mesh_hit<false>(P, i, mk(0.f, 0.f, 0.f), d, inv, tbest);
+        if (h >= 0) best = h;
+        continue;
+      }
+    }
     if (POLY && ob.is_disc >= SHAPE_TRIANGLE) {   // the general function at o = (0, 0, 0): sub(o, v0) is formed here, the same float
       if constexpr (POLY) t = poly_intersect(mk(0.f, 0.f, 0.f), d, ob, P.poly[i]);
     } else if (ob.is_disc) {
@@ -423,7 +477,8 @@ __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab
 // GUIDE: the diffuse bounce mixes the hemisphere with the environment guide (pt_env_guide.h); CAM tells it whether directions
 // are rotated between camera and world space, as in emit_escaped (CAM_LENS: when P.cam_pose says so).
 // PLAMPS: the emitter guide's table may list polygons (pt_set_light_guide_ex; with LIGHTS and POLY alone).
-template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false>
+// MESH: `best` is a packed hit (nearest_hit), and a mesh triangle's normal comes from global memory.
+template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length);
 
@@ -432,14 +487,14 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
 // Returns the path length (contribution-stack size, codelets.cpp:253) through `length` when the
 // path ends.
 template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false,
-          bool POLY = false, bool PLAMPS = false>
+          bool POLY = false, bool PLAMPS = false, bool MESH = false>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length);
 #ifdef PTMI_DIAG_BUILD
 __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3 d, float& tbest);
 __device__ __forceinline__ int shade_hit_r3(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                             const uint32_t (&w)[4], float rr, uint32_t& length);
 #endif
-template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS>
+template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length) {
   uint32_t w[4];
   philox4x32_10(s.pixel, s.sample, 1u + s.depth, 0x5054u, P.seed_lo, P.seed_hi, w);
@@ -462,7 +517,7 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
   if constexpr (SCENE_C) best = nearest_hit_c(s.o, s.d, tbest, SceneIndices{});
   else
 #endif
-  best = nearest_hit<PIPE, POLY>(P, s.o, s.d, tbest);         // Scene::intersect (:183)
+  best = nearest_hit<PIPE, POLY, MESH>(P, s.o, s.d, tbest);   // Scene::intersect (:183)
   if (best < 0) {                                             // :184-190 ESCAPED
     s.T = scale(s.T, rr);
     length = s.depth + 1u;
@@ -471,7 +526,7 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
 #ifdef PTMI_DIAG_BUILD
   if constexpr (LEGACY) return shade_hit_r3(P, tab, s, best, tbest, w, rr, length);
 #endif
-  return shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS>(P, tab, s, best, tbest, w, rr, length);
+  return shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH>(P, tab, s, best, tbest, w, rr, length);
 }
 
 // The basis of light::diffuse (codelets.cpp:199-204) about a unit vector n: rx, ry with (rx, ry, n) orthonormal.  Its branch as
@@ -504,10 +559,11 @@ namespace ptd {
 
 // The second half of a loop trip of RayTraceKernel::compute (codelets.cpp:192-216): the ray has hit object `best` at
 // distance `tbest`; w = the bounce's Philox block, rr = its roulette weight.
-template <bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS>
-__device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
+template <bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH>
+__device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int packed, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length) {
   // the hit object's row, by per-lane index
+  const int best = hit_object<MESH>(packed);
   const float4 hc = tab[best].centre, hn = tab[best].normal, hcol = tab[best].colour;
   const float cx = hc.x, cy = hc.y, cz = hc.z, nx = hn.x, ny = hn.y, nz = hn.z, cr = hcol.x, cg = hcol.y, cb = hcol.z;
   const uint32_t bits = __float_as_uint(hcol.w);
@@ -524,6 +580,9 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
   Vec3 hp = add(s.o, scale(s.d, tbest));
   s.o = hp;
   Vec3 n = is_disc ? mk(nx, ny, nz) : normalise(sub(hp, mk(cx, cy, cz)));
+  if constexpr (MESH) {   // a mesh triangle's stored normal: the last three floats of its third vector, one 16-byte load per mesh hit
+    if (is_disc == SHAPE_MESH) { const ptmesh::F4 tn = P.mesh_tris[3u * (size_t)hit_slot(packed) + 2u]; n = mk(tn.y, tn.z, tn.w); }
+  }
   if constexpr (POLY) {   // a polygon is two-sided: its stored normal faces the ray (the refractive branch flips the normal itself)
     if (is_disc >= SHAPE_TRIANGLE && type != MAT_REFRACTIVE && dot(n, s.d) > 0.0f) n = scale(n, -1.0f);
   }
@@ -713,7 +772,7 @@ namespace ptd {
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
 template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false, bool POLY = false,
-          bool PLAMPS = false>
+          bool PLAMPS = false, bool MESH = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
@@ -760,9 +819,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
 #endif
         if constexpr (CAM == CAM_LENS) {   // the ray starts on the lens, not at the origin: no origin-folded constants
           lens_ray(P, pixel, st.sample, camx, camy, st.o, st.d);
-          best = nearest_hit<PIPE, POLY>(P, st.o, st.d, tbest);
+          best = nearest_hit<PIPE, POLY, MESH>(P, st.o, st.d, tbest);
         } else
-        best = PRIMARY ? nearest_hit_primary<PIPE, POLY>(P, st.d, tbest) : nearest_hit<PIPE, POLY>(P, st.o, st.d, tbest);
+        best = PRIMARY ? nearest_hit_primary<PIPE, POLY, MESH>(P, st.d, tbest) : nearest_hit<PIPE, POLY, MESH>(P, st.o, st.d, tbest);
       }
     }
     const bool hit = best >= 0;
@@ -773,13 +832,14 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     emit_escaped<CAM>(P, escaped, st, idx, lane, region_base, &wg_count);
     // survivors: diffuse hits fill the list from the front, mirror / glass hits from the back; an emitter hit is final
     // (codelets.cpp:192-196 at depth 0: no roulette, T = (1, 1, 1) x 1 as shade_hit would leave it) and queues nothing
-    const uint32_t mat = __float_as_uint(hit_table[hit ? best : 0].colour.w) & 0xffu;
+    // (a MESH instance's `best` is packed: hit_object is its row, and the note below carries it whole)
+    const uint32_t mat = __float_as_uint(hit_table[hit ? hit_object<MESH>(best) : 0].colour.w) & 0xffu;
     const bool diffuse = hit && mat == (uint32_t)MAT_DIFFUSE;
     const bool emitted = hit && mat == (uint32_t)MAT_EMISSIVE;
     const bool other = hit && !diffuse && !emitted;
     Vec3 erad = mk(0.f, 0.f, 0.f);
     if (emitted) {
-      const float4 e = hit_table[best].colour;
+      const float4 e = hit_table[hit_object<MESH>(best)].colour;
       erad = mk(e.x * st.T.x, e.y * st.T.y, e.z * st.T.z);
       P.plen[idx] = (uint8_t)(1u | 0x80u);
     }
@@ -833,7 +893,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if constexpr ((OPT & 64) != 0) res = shade_hit_r3(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       else
 #endif
-      res = shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
+      res = shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       if (res == STEP_CONTINUE) alive = true;
       else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full (guided: or the guide pointed below the surface)
       // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
@@ -905,7 +965,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     int res = STEP_CONTINUE;
     uint32_t length = 0;
-    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY, PLAMPS>(P, hit_table, st, length);
+    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH>(P, hit_table, st, length);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
     const bool emitted = active && res == STEP_EMITTED;
@@ -963,6 +1023,21 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true>(P); }
+// pt_set_scene_meshes: twelve more with the mesh walk in the object loop, launched only while the scene in force holds a mesh.
+// They carry the polygon code too (MESH implies POLY), and the emitter-guided ones come with and without polygon lamps, as
+// above: a mesh is never listed in the emitter guide's table.  Resource rows: profiles/r22_meshes.txt.
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, false, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true>(P); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -975,7 +1050,7 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
 
 // One thread per requested path; same device functions as trace_kernel.  GUIDE: the guided twin (the camera is read at run
 // time either way: CAM_LENS rotates when P.cam_pose says so).  LIGHTS: the emitter-guided twin.
-template <bool GUIDE, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false>
+template <bool GUIDE, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false>
 __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                  uint32_t n, PathRecordOut* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -990,7 +1065,7 @@ __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uin
   if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
-  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY, PLAMPS>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
+  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY, PLAMPS, MESH>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
@@ -1017,5 +1092,34 @@ __global__ void trace_paths_lights_poly_kernel(const TraceParams P, const uint16
                                                uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true>(P, u, v, sample, n, out); }
 __global__ void trace_paths_lights_plamps_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                  uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true>(P, u, v, sample, n, out); }
+// pt_set_scene_meshes: the mesh twins
+__global__ void trace_paths_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                        uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true, false, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_guide_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                              uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true, false, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_lights_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                               uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, false, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_lights_plamps_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                                      uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true>(P, u, v, sample, n, out); }
+
+// pt_mesh_intersect: the MESH instances' own nearest hit over caller rays, one thread per ray (the scene in the kernel arguments
+// is the world table).  BRUTE: a loop over all triangles of each mesh in place of the walk.
+template <bool BRUTE>
+__device__ __forceinline__ void mesh_intersect_body(const TraceParams& P, const float* origin, const float* dir, uint32_t n, float* out_t,
+                                                    int32_t* out_object, int32_t* out_triangle) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float tbest;
+  const int best = nearest_hit<false, true, true, BRUTE>(P, mk(origin[3 * i], origin[3 * i + 1], origin[3 * i + 2]),
+                                                         mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), tbest);
+  const int obj = best < 0 ? -1 : hit_object<true>(best);
+  out_t[i] = best < 0 ? 0.f : tbest;
+  out_object[i] = obj;
+  out_triangle[i] = (obj >= 0 && P.obj[obj].is_disc == SHAPE_MESH) ? (int32_t)P.mesh_orig[hit_slot(best)] : -1;
+}
+__global__ void mesh_intersect_kernel(const TraceParams P, const float* origin, const float* dir, uint32_t n, float* out_t,
+                                      int32_t* out_object, int32_t* out_triangle) { mesh_intersect_body<false>(P, origin, dir, n, out_t, out_object, out_triangle); }
+__global__ void mesh_intersect_brute_kernel(const TraceParams P, const float* origin, const float* dir, uint32_t n, float* out_t,
+                                            int32_t* out_object, int32_t* out_triangle) { mesh_intersect_body<true>(P, origin, dir, n, out_t, out_object, out_triangle); }
 
 }  // namespace ptd

@@ -48,6 +48,7 @@
 #include "ptmi_comm_worker.h"
 #include "ptmi_scene.h"
 #include "ptmi_camera.h"
+#include "ptmi_mesh.h"
 #include "ptmi_env_guide.h"
 #include "ptmi_light_guide.h"
 #include "ptmi_nif_train_check.h"
@@ -526,6 +527,15 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
         if (P.lights.n && h->light.polygons)   // the table lists a polygon lamp (pt_set_light_guide_ex)
           kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps : ptd::trace_kernel_lights_plamps);
       }
+      if (h->scene_n && h->scene_mesh) {   // a mesh in the scene in force (pt_set_scene_meshes): the mesh twin, which handles polygons too
+        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_mesh : (P.cam_pose ? ptd::trace_kernel_pose_mesh : ptd::trace_kernel_mesh);
+        if (h->guide_set)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_mesh : (P.cam_pose ? ptd::trace_kernel_pose_guide_mesh : ptd::trace_kernel_guide_mesh);
+        if (P.lights.n)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_mesh : (P.cam_pose ? ptd::trace_kernel_pose_lights_mesh : ptd::trace_kernel_lights_mesh);
+        if (P.lights.n && h->light.polygons)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_mesh : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_mesh : ptd::trace_kernel_lights_plamps_mesh);
+      }
       hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
     PT_HIP(hipGetLastError());
@@ -587,6 +597,7 @@ static int stage_accumulate(pt_handle h, StepEvents& ev, const Batch& b) {
 // leaves kernels running on buffers the host is about to reuse or free.
 static int enqueue_path_trace(pt_handle h) {
   const uint32_t n = h->n_items;
+  if (int rc = ensure_meshes(h)) return rc;   // a mesh scene under a new camera pose: the trees follow (a no-op otherwise)
   forget_replay_state(h);
   PT_HIP(hipMemsetAsync(h->d_counters, 0, 4 * sizeof(unsigned long long), h->stream));   // ([2] was consumed by pt_setup)
   ptd::TraceParams P;
@@ -1278,7 +1289,7 @@ static void light_hook_params(pt_handle h, ptd::TraceParams& P) {
   memset(&P, 0, sizeof(P));
   pt_scene_object builtin[ptd::kBuiltinObjects];
   builtin_scene(builtin);
-  if (h->scene_n) fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr);
+  if (h->scene_n) fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->scene_mesh ? h->mesh.row : nullptr);
   else fill_scene(P, builtin, ptd::kBuiltinObjects);
   fill_light_params(h, P, true);
 }
@@ -1325,15 +1336,24 @@ int pt_light_guide_eval(pt_handle h, const float* origin, const float* normal, c
   });
 }
 
+// A scene without a mesh takes over: the MESH instances stop running and the meshes' memory goes back (hipFree waits for the device).
+static void drop_meshes(pt_handle h) {
+  if (!h->scene_mesh && h->mesh.mesh.empty()) return;
+  h->scene_mesh = false;
+  (void)hipSetDevice(h->cfg.device);
+  h->mesh = pt_context::MeshSet{};
+}
+
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!objects && n == 0) { h->scene_n = 0; h->scene_poly = false; h->feature_gen += 1; rebuild_light_guide(h); return PT_OK; }   // the built-in scene
+  if (!objects && n == 0) { h->scene_n = 0; h->scene_poly = false; drop_meshes(h); h->feature_gen += 1; rebuild_light_guide(h); return PT_OK; }   // the built-in scene
   const std::string bad = ptscene::check(objects, n);
   if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the scene in force stays
   std::copy(objects, objects + n, h->scene);
   ptscene::normalise(h->scene, n);
   h->scene_n = n;
   h->scene_poly = false;
+  drop_meshes(h);
   h->feature_gen += 1;
   rebuild_light_guide(h);   // a light guide follows the scene
   return PT_OK;
@@ -1348,6 +1368,8 @@ int pt_get_scene(pt_handle h, pt_scene_object* out, uint32_t capacity, uint32_t*
   const uint32_t count = custom ? h->scene_n : (uint32_t)ptd::kBuiltinObjects;
   *n = count;
   if (!out && capacity == 0) return PT_OK;   // size query
+  if (custom && h->scene_mesh)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_scene: the scene in force holds a mesh: use pt_get_scene_ex");
   if (custom && h->scene_poly)
     return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_scene: the scene in force holds a polygon: use pt_get_scene_ex");
   if (!out || capacity < count)
@@ -1381,9 +1403,116 @@ int pt_set_scene_ex(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, 
   }
   h->scene_n = n;
   h->scene_poly = poly;   // a table of spheres and discs is pt_set_scene's scene, and runs its kernels
+  drop_meshes(h);
   h->feature_gen += 1;
   rebuild_light_guide(h);
   return PT_OK;
+}
+
+// pt_set_scene_ex with meshes.  Everything is checked, copied, built and on the device before the scene in force changes: a
+// rejection or a failed allocation leaves it as it was.
+int pt_set_scene_meshes(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, uint32_t stride, const pt_mesh* meshes,
+                        uint32_t n_meshes) {
+  if (!objects && n == 0 && stride == sizeof(pt_scene_object_ex) && !meshes && n_meshes == 0) {   // the built-in scene
+    if (!h) { g_create_error = "pt_set_scene_meshes: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+    return pt_set_scene(h, nullptr, 0);
+  }
+  const std::string bad = ptmesh::check(objects, n, stride, meshes, n_meshes);
+  if (!bad.empty()) {   // the scene in force stays
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) { g_create_error = "pt_set_scene_meshes: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  if (n_meshes == 0) return pt_set_scene_ex(h, objects, n, stride);   // no mesh row: pt_set_scene_ex's scene, on its kernels
+  PT_HIP(hipSetDevice(h->cfg.device));
+  try {   // (the host copies are large -- 48 bytes per triangle and the builder's arrays: no exception crosses the C boundary)
+  pt_context::MeshSet M;
+  size_t triangles = 0, nodes = 0;
+  for (uint32_t i = 0, m = 0; i < n; ++i) {
+    if (objects[i].shape != PT_SHAPE_MESH) continue;
+    pt_context::MeshSet::One one{};
+    one.object_index = i;
+    one.n_triangles = meshes[m].n_triangles;
+    one.tri_base = (uint32_t)triangles;
+    one.node_base = (uint32_t)nodes;
+    ptmesh::world_frames(meshes[m], M.world);
+    M.mesh.push_back(one);
+    triangles += one.n_triangles;
+    nodes += 2 * (size_t)one.n_triangles - 1;
+    m += 1;
+  }
+  PT_HIP(dev_alloc(M.d_nodes, nodes));
+  PT_HIP(dev_alloc(M.d_tris, 3 * triangles));
+  PT_HIP(dev_alloc(M.d_orig, triangles));
+  const ptcamera::Basis& cb = h->camera_basis;
+  if (int rc = build_meshes(h, M, cb.identity ? nullptr : &cb)) return rc;
+  // commit: the table as stored -- a mesh row with shape 4, its material and colour, and zeros
+  pt_scene_object_ex stored[PT_MAX_SCENE_OBJECTS];
+  std::copy(objects, objects + n, stored);
+  for (uint32_t i = 0; i < n; ++i)
+    if (stored[i].shape == PT_SHAPE_MESH) { stored[i].radius = 0.f; for (int k = 0; k < 3; ++k) stored[i].centre[k] = 0.f; }
+  ptscene::normalise_ex(stored, n);   // (a mesh row: normal and vertex 0, as a sphere's)
+  bool poly = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    memcpy(&h->scene[i], &stored[i], sizeof(pt_scene_object));
+    memcpy(h->scene_vertex[i], stored[i].vertex, sizeof(stored[i].vertex));
+    poly = poly || ptscene::is_polygon(stored[i].shape);
+  }
+  h->scene_n = n;
+  h->scene_poly = poly;   // (which rows are polygons: the light guide's polygon lamps and pt_get_scene_ex ask; the MESH instances run)
+  h->mesh = std::move(M);
+  h->scene_mesh = true;
+  h->feature_gen += 1;
+  rebuild_light_guide(h);
+  return PT_OK;
+  } catch (const std::bad_alloc&) {   // nothing of the scene in force has changed yet
+    return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_scene_meshes: out of host memory for the meshes' copies");
+  }
+}
+
+int pt_get_mesh_info(pt_handle h, uint32_t mesh, pt_mesh_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_mesh_info))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_info: struct_size must be " + std::to_string(sizeof(pt_mesh_info)));
+  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
+  if (mesh >= count)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_info: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
+  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->object_index = m.object_index;
+  out->n_triangles = m.n_triangles;
+  out->n_nodes = m.n_nodes;
+  out->max_leaf = m.max_leaf;
+  out->depth = m.depth;
+  out->device_bytes = (2 * (uint64_t)m.n_triangles - 1) * sizeof(ptmesh::Node) + (uint64_t)m.n_triangles * (3 * sizeof(ptmesh::F4) + sizeof(uint32_t));
+  out->build_ms = m.build_ms;
+  out->pad = m.pad;
+  return PT_OK;
+}
+
+int pt_mesh_intersect(pt_handle h, const float* origin, const float* dir, size_t n, int32_t mode, float* out_t, int32_t* out_object,
+                      int32_t* out_triangle) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_intersect: the scene in force holds no mesh (pt_set_scene_meshes)");
+  if (mode != PT_MESH_INTERSECT_BVH && mode != PT_MESH_INTERSECT_BRUTE)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_intersect: mode must be 0 (BVH) or 1 (brute force) (got " + std::to_string(mode) + ")");
+  if (n == 0) return PT_OK;
+  if (!origin || !dir || !out_t || !out_object || !out_triangle) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31) / 3) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many rays");
+  if (int rc = ensure_meshes(h, true)) return rc;   // the world frame, whatever the camera
+  ptd::TraceParams P;
+  memset(&P, 0, sizeof(P));
+  fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->mesh.row);
+  bind_meshes(h, P);
+  GuideSpan s[5] = {{origin, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr}, {nullptr, out_t, n * 4, nullptr},
+                    {nullptr, out_object, n * 4, nullptr}, {nullptr, out_triangle, n * 4, nullptr}};
+  return guide_hook(h, s, 5, [&]() {
+    hipLaunchKernelGGL(mode == PT_MESH_INTERSECT_BRUTE ? ptd::mesh_intersect_brute_kernel : ptd::mesh_intersect_kernel,
+                       dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P, reinterpret_cast<const float*>(s[0].dev),
+                       reinterpret_cast<const float*>(s[1].dev), (uint32_t)n, reinterpret_cast<float*>(s[2].dev),
+                       reinterpret_cast<int32_t*>(s[3].dev), reinterpret_cast<int32_t*>(s[4].dev));
+  });
 }
 
 int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uint32_t* n) {
@@ -1442,6 +1571,7 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   PT_HIP(hipMemcpyAsync(d_s, sample_index, n * 4, hipMemcpyHostToDevice, h->stream));
   PT_HIP(hipMemcpyAsync(d_u, u, n * 2, hipMemcpyHostToDevice, h->stream));
   PT_HIP(hipMemcpyAsync(d_v, v, n * 2, hipMemcpyHostToDevice, h->stream));
+  if (int rc = ensure_meshes(h)) return rc;
   ptd::TraceParams P;
   fill_trace_params(h, P);
   P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
@@ -1449,6 +1579,9 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   if (h->scene_n && h->scene_poly)   // the polygon twins (pt_set_scene_ex)
     kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_kernel : ptd::trace_paths_lights_poly_kernel)
                         : (h->guide_set ? ptd::trace_paths_guide_poly_kernel : ptd::trace_paths_poly_kernel);
+  if (h->scene_n && h->scene_mesh)   // the mesh twins (pt_set_scene_meshes)
+    kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_mesh_kernel : ptd::trace_paths_lights_mesh_kernel)
+                        : (h->guide_set ? ptd::trace_paths_guide_mesh_kernel : ptd::trace_paths_mesh_kernel);
   hipLaunchKernelGGL(kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
                      ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());

@@ -193,6 +193,25 @@ struct pt_context {
   // radius = 0 and its normal); scene_poly: the table holds a polygon, the POLY kernel instances run
   float scene_vertex[PT_MAX_SCENE_OBJECTS][3][3] = {};
   bool scene_poly = false;
+  // ... and, for a table given through pt_set_scene_meshes, the meshes (ptmi_mesh.h; a mesh's row above holds shape 4 and zeros).
+  // scene_mesh: the table holds a mesh, the MESH kernel instances run.  The device buffers are sized once, for 2 T - 1 nodes per
+  // mesh; a new camera pose rebuilds the trees into them from the host copy of the world-space frames (ensure_meshes).
+  bool scene_mesh = false;
+  struct MeshSet {
+    struct One {
+      uint32_t object_index, n_triangles, tri_base, node_base, n_nodes, max_leaf, depth;
+      float pad;
+      double build_ms;
+    };
+    std::vector<One> mesh;                 // in declaration order
+    std::vector<float> world;              // twelve floats per triangle (v0, e1, e2, n), the meshes one after the other
+    DevBuf<ptmesh::Node> d_nodes;          // mesh m at node_base = sum over the meshes before it of 2 T - 1
+    DevBuf<ptmesh::F4> d_tris;             // three per slot, mesh m's slots from tri_base
+    DevBuf<uint32_t> d_orig;               // slot -> triangle index in its mesh
+    ptd::PolyEdges row[PT_MAX_SCENE_OBJECTS] = {};   // what a mesh's row carries in the kernel arguments (ptd::MeshRow)
+    bool built = false, built_world = false;         // the trees on the device are valid / were built in the world frame ...
+    ptcamera::Basis built_for{};                     // ... or for this camera
+  } mesh;
 
   // camera (pt_set_camera): the values as given, and the frame made from them once (ptmi_camera.h)
   pt_camera camera = ptcamera::default_camera();
@@ -399,13 +418,16 @@ void builtin_scene(pt_scene_object (&out)[ptd::kBuiltinObjects]) {
 // no transform at all (not a multiplication by the identity), so "no camera set" is the same bits by construction.
 // A polygon (vertex != nullptr: the vertices of pt_set_scene_ex's table) enters with v0 as its centre, a point, and its edges
 // e1, e2 (formed in world space in binary32, as the validation forms them) and stored normal as directions.
+// A mesh row (mesh_row != nullptr: pt_set_scene_meshes) carries its shape code and, in its edges' slot, where its tree lies.
 void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, const ptcamera::Basis* cam = nullptr,
-                const float (*vertex)[3][3] = nullptr) {
+                const float (*vertex)[3][3] = nullptr, const ptd::PolyEdges* mesh_row = nullptr) {
   P.n_objects = n;
   for (uint32_t i = 0; i < n; ++i) {
     ptd::SceneObject& o = P.obj[i];
     const bool disc = src[i].shape == PT_SHAPE_DISC;
     const bool poly = vertex && ptscene::is_polygon(src[i].shape);
+    const bool mesh = mesh_row && src[i].shape == PT_SHAPE_MESH;
+    if (mesh) P.poly[i] = mesh_row[i];
     float centre[3] = {src[i].centre[0], src[i].centre[1], src[i].centre[2]};
     float normal[3] = {src[i].normal[0], src[i].normal[1], src[i].normal[2]};
     if (cam) {
@@ -428,7 +450,7 @@ void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, con
     o.nx = normal[0]; o.ny = normal[1]; o.nz = normal[2];
     o.colr = src[i].colour[0]; o.colg = src[i].colour[1]; o.colb = src[i].colour[2];
     o.type = src[i].material;
-    o.is_disc = poly ? src[i].shape : (disc ? 1 : 0);   // the shape code
+    o.is_disc = (poly || mesh) ? src[i].shape : (disc ? 1 : 0);   // the shape code
     // constants of a ray that starts at the origin, by the device's own expressions (this file is compiled with
     // -ffp-contract=off like the kernels; volatile keeps every intermediate a rounded binary32 whatever the host's FLT_EVAL_METHOD)
     volatile float ox = 0.f - o.cx, oy = 0.f - o.cy, oz = 0.f - o.cz;          // sub(o, c)
@@ -440,9 +462,66 @@ void fill_scene(ptd::TraceParams& P, const pt_scene_object* src, uint32_t n, con
     volatile float kx = (o.cx - 0.f) * o.nx, ky = (o.cy - 0.f) * o.ny, kz = (o.cz - 0.f) * o.nz;   // dot(sub(c, o), n)
     volatile float k0 = kx + ky, k1 = k0 + kz;
     o.kdisc = k1;
-    o.same_centre = (i > 0 && !disc && !poly && src[i - 1].shape == PT_SHAPE_SPHERE && src[i].centre[0] == src[i - 1].centre[0] &&
+    o.same_centre = (i > 0 && !disc && !poly && !mesh && src[i - 1].shape == PT_SHAPE_SPHERE && src[i].centre[0] == src[i - 1].centre[0] &&
                      src[i].centre[1] == src[i - 1].centre[1] && src[i].centre[2] == src[i - 1].centre[2]) ? 1 : 0;
   }
+}
+
+// ---- meshes (pt_set_scene_meshes): the trees on the device
+
+void bind_meshes(pt_handle h, ptd::TraceParams& P) {
+  P.mesh_nodes = h->mesh.d_nodes;
+  P.mesh_tris = h->mesh.d_tris;
+  P.mesh_orig = h->mesh.d_orig;
+}
+
+// Transforms every mesh of M into the frame of `cam` (nullptr: the world frame, which is the built-in camera's), builds its tree
+// and copies trees and triangles into M's device buffers, which hold any tree of these triangles (2 T - 1 nodes): no allocation on
+// the device.  The handle's streams are drained first: a step in flight may still read the buffers.
+int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam) try {
+  PT_HIP(hipSetDevice(h->cfg.device));
+  if (&M == &h->mesh)   // (a set that is not in force yet has no reader)
+    for (hipStream_t s : {h->stream, h->trace_stream, h->acc_stream})
+      if (s) PT_HIP(hipStreamSynchronize(s));
+  M.built = false;
+  std::vector<float> frames;
+  ptmesh::Built B;
+  for (pt_context::MeshSet::One& m : M.mesh) {
+    const auto t0 = std::chrono::steady_clock::now();
+    frames.resize(ptmesh::kFrameFloats * (size_t)m.n_triangles);
+    ptmesh::kernel_frames(M.world.data() + ptmesh::kFrameFloats * (size_t)m.tri_base, m.n_triangles, cam, frames.data());
+    ptmesh::build(frames.data(), m.n_triangles, B);
+    m.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    m.n_nodes = (uint32_t)B.nodes.size();
+    m.max_leaf = B.max_leaf; m.depth = B.depth; m.pad = B.pad;
+    if (B.nodes.size() > 2 * (size_t)m.n_triangles - 1 || B.orig.size() != m.n_triangles)
+      return fail(h, PT_ERR_HIP, "mesh builder: a tree larger than its buffer");   // (cannot happen: a binary tree with non-empty leaves)
+    PT_HIP(hipMemcpy(M.d_nodes + m.node_base, B.nodes.data(), B.nodes.size() * sizeof(ptmesh::Node), hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(M.d_tris + 3 * (size_t)m.tri_base, B.tris.data(), B.tris.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
+    PT_HIP(hipMemcpy(M.d_orig + m.tri_base, B.orig.data(), B.orig.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const ptd::MeshRow row{m.node_base, m.tri_base, m.n_nodes, m.n_triangles, {0u, 0u}};
+    memcpy(&M.row[m.object_index], &row, sizeof(row));
+  }
+  M.built = true;
+  M.built_world = cam == nullptr;
+  if (cam) M.built_for = *cam;
+  return PT_OK;
+} catch (const std::bad_alloc&) {   // the builder's host arrays: the trees stay marked stale, the next call tries again
+  return fail(h, PT_ERR_OUT_OF_MEMORY, "meshes: out of host memory while building the trees");
+}
+
+// Before anything traces a mesh scene: the trees follow the camera in force (world = true, pt_mesh_intersect: the world frame).
+int ensure_meshes(pt_handle h, bool world = false) {
+  if (!h->scene_n || !h->scene_mesh) return PT_OK;
+  const ptcamera::Basis& cb = h->camera_basis;
+  const ptcamera::Basis* cam = (world || cb.identity) ? nullptr : &cb;
+  pt_context::MeshSet& M = h->mesh;
+  const auto same = [](const ptcamera::Basis& a, const ptcamera::Basis& b) {
+    return !memcmp(a.r, b.r, sizeof a.r) && !memcmp(a.u, b.u, sizeof a.u) && !memcmp(a.f, b.f, sizeof a.f) &&
+           !memcmp(a.position, b.position, sizeof a.position);
+  };
+  if (M.built && (cam ? (!M.built_world && same(M.built_for, *cam)) : M.built_world)) return PT_OK;
+  return build_meshes(h, M, cam);
 }
 
 // The emitter guide's table into the kernel arguments.  P.lights.n stays 0 -- no light-guided instance is launched -- unless a
@@ -468,7 +547,8 @@ void fill_trace_params(pt_handle h, ptd::TraceParams& P) {
   const ptcamera::Basis& cb = h->camera_basis;
   const ptcamera::Basis* cam = cb.identity ? nullptr : &cb;
   if (h->scene_n) {
-    fill_scene(P, h->scene, h->scene_n, cam, h->scene_poly ? h->scene_vertex : nullptr);
+    fill_scene(P, h->scene, h->scene_n, cam, h->scene_poly ? h->scene_vertex : nullptr, h->scene_mesh ? h->mesh.row : nullptr);
+    if (h->scene_mesh) bind_meshes(h, P);
   } else {
     pt_scene_object builtin[ptd::kBuiltinObjects];
     builtin_scene(builtin);

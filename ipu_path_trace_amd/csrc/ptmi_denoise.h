@@ -26,13 +26,16 @@ int ensure_features(pt_handle h) {
     h->feature_cached_gen = 0;
   }
   if (h->feature_cached_gen == h->feature_gen) return PT_OK;
+  if (int rc = ensure_meshes(h)) return rc;
   ptd::TraceParams P;
   fill_trace_params(h, P);
   P.aa_scale = 0.f;      // the noise-free centre ray (pt_features.h)
   P.lens_a = 0.f;        // ... through a pinhole
   P.emitted = nullptr;
   const uint32_t px = h->cfg.width * h->cfg.height;
-  hipLaunchKernelGGL(h->scene_n && h->scene_poly ? ptd::features_kernel_poly : ptd::features_kernel, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0, h->stream, P,
+  auto kernel = h->scene_n && h->scene_poly ? ptd::features_kernel_poly : ptd::features_kernel;
+  if (h->scene_n && h->scene_mesh) kernel = ptd::features_kernel_mesh;
+  hipLaunchKernelGGL(kernel, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0, h->stream, P,
                      h->d_feat[0], h->d_feat[1]);
   PT_HIP(hipGetLastError());
   h->feature_cached_gen = h->feature_gen;

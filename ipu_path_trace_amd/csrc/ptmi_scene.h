@@ -87,8 +87,9 @@ inline PolyFrame poly_frame(const float (&v)[3][3]) {
   return f;
 }
 
-// "" if the ex table is valid, else what is wrong, in the order include/ptmi.h states.
-inline std::string check_ex(const pt_scene_object_ex* objs, uint32_t n, uint32_t stride) {
+// "" if the ex table is valid, else what is wrong, in the order include/ptmi.h states.  max_shape = PT_SHAPE_MESH
+// (pt_set_scene_meshes alone): a row of shape 4 passes, checked for its material and colour only.
+inline std::string check_ex(const pt_scene_object_ex* objs, uint32_t n, uint32_t stride, int32_t max_shape = PT_SHAPE_PARALLELOGRAM) {
   if (stride != sizeof(pt_scene_object_ex))
     return "scene: stride must be " + std::to_string(sizeof(pt_scene_object_ex)) + " (sizeof(pt_scene_object_ex)) (got " + std::to_string(stride) + ")";
   if (n < 1 || n > PT_MAX_SCENE_OBJECTS)
@@ -97,19 +98,22 @@ inline std::string check_ex(const pt_scene_object_ex* objs, uint32_t n, uint32_t
   for (uint32_t i = 0; i < n; ++i) {
     const pt_scene_object_ex& o = objs[i];
     const std::string at = "scene object " + std::to_string(i) + ": ";
-    if (o.shape < PT_SHAPE_SPHERE || o.shape > PT_SHAPE_PARALLELOGRAM)
-      return at + "shape must be 0 (sphere), 1 (disc), 2 (triangle) or 3 (parallelogram) (got " + std::to_string(o.shape) + ")";
+    if (o.shape < PT_SHAPE_SPHERE || o.shape > max_shape)
+      return at + (max_shape == PT_SHAPE_MESH ? "shape must be 0 (sphere), 1 (disc), 2 (triangle), 3 (parallelogram) or 4 (mesh) (got "
+                                              : "shape must be 0 (sphere), 1 (disc), 2 (triangle) or 3 (parallelogram) (got ") + std::to_string(o.shape) + ")";
     if (o.material < PT_MATERIAL_DIFFUSE || o.material > PT_MATERIAL_EMISSIVE)
       return at + "material must be 0 (diffuse), 1 (specular), 2 (refractive) or 3 (emissive) (got " + std::to_string(o.material) + ")";
-    const bool poly = is_polygon(o.shape);
+    const bool poly = is_polygon(o.shape), mesh = o.shape == PT_SHAPE_MESH;
+    const bool round = !poly && !mesh;   // a sphere or a disc
     const struct { const char* name; const float* v; int k; bool used; } fields[] = {
-        {"centre", o.centre, 3, !poly}, {"radius", &o.radius, 1, !poly}, {"normal", o.normal, 3, !poly},
+        {"centre", o.centre, 3, round}, {"radius", &o.radius, 1, round}, {"normal", o.normal, 3, round},
         {"vertex", &o.vertex[0][0], 9, poly}, {"colour", o.colour, 3, true}};
     for (const auto& f : fields)
       for (int k = 0; f.used && k < f.k; ++k)
         if (!std::isfinite(f.v[k])) return at + f.name + " must be finite (got " + num(f.v[k]) + ")";
     for (int k = 0; k < 3; ++k)
       if (o.colour[k] < 0.f) return at + "colour components must be >= 0 (got " + num(o.colour[k]) + ")";
+    if (mesh) continue;   // its triangles are checked with the mesh table (ptmi_mesh.h)
     if (!poly) {
       if (!(o.radius > 0.f)) return at + "radius must be > 0 (got " + num(o.radius) + ")";
       if (o.shape == PT_SHAPE_DISC) {

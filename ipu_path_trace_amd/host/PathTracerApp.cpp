@@ -21,6 +21,8 @@
 #include "../csrc/ptmi_camera.h"
 #include "../csrc/ptmi_env_guide.h"
 #include "../csrc/ptmi_light_guide.h"
+#include "../csrc/ptmi_mesh.h"
+#include "ObjReader.hpp"
 #include "trace_ranges.hpp"
 
 /// Adjust samples per pixel to be a multiple of samples per step (PathTracerApp.cpp:19-27).
@@ -94,7 +96,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
-      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}; a \"triangle\" or \"parallelogram\" takes \"vertices\": [[x, y, z], [x, y, z], [x, y, z]] (v0, v1, v2; the parallelogram's fourth corner is v1 + v2 - v0) instead of centre, radius and normal.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
+      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}; a \"triangle\" or \"parallelogram\" takes \"vertices\": [[x, y, z], [x, y, z], [x, y, z]] (v0, v1, v2; the parallelogram's fourth corner is v1 + v2 - v0) instead of centre, radius and normal; a \"mesh\" (one object of the table, one material, flat shading) takes either \"vertices\": [[x, y, z], ...] and \"triangles\": [[a, b, c], ...] (indices from 0) or \"file\": \"x.obj\" (relative to the scene file; v and f lines, faces triangulated as fans), and optionally \"scale\": s or [sx, sy, sz] and \"translate\": [x, y, z], applied in binary32 on the host as v * scale + translate before anything else.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
       {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
       {"env-guide", 0, "", false, false, "FILE | map | env: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map; 'env' needs no file: the guide is built on the device from the environment in force -- the NIF of --assets, the map or the constant -- and follows a NIF loaded later). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
@@ -160,8 +162,11 @@ std::uint64_t nifMemoBytes(const std::string& text) {
 // `camera` receives the file's optional top-level "camera" (every key optional, defaults of pt_camera), checked like the table.
 // A "triangle" or "parallelogram" takes "vertices": [[..], [..], [..]] instead of centre / radius / normal; a file that holds one is
 // checked as pt_set_scene_ex checks it and leaves its table in `ex` (empty otherwise: the file goes through pt_set_scene as ever).
+// A "mesh" takes inline "vertices" / "triangles" or "file": "x.obj" (relative to the scene file), and optionally "scale" and
+// "translate", applied here in binary32 -- v * scale, then + translate, one rounded operation each -- before anything else; a
+// file that holds one is checked as pt_set_scene_meshes checks it and leaves its geometry in `meshes`, in the order of its rows.
 std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& camera, bool& hasCamera,
-                                           std::vector<pt_scene_object_ex>& ex) {
+                                           std::vector<pt_scene_object_ex>& ex, std::vector<objreader::Mesh>& meshes) {
   const std::string at = "--scene '" + path + "': ";
   std::ifstream in(path, std::ios::binary);
   if (!in) throw std::runtime_error(at + "cannot open the file");
@@ -198,7 +203,8 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     };
     for (const auto& kv : v.obj)
       if (kv.first != "shape" && kv.first != "material" && kv.first != "centre" && kv.first != "radius" && kv.first != "normal" &&
-          kv.first != "colour" && kv.first != "emission" && kv.first != "vertices")
+          kv.first != "colour" && kv.first != "emission" && kv.first != "vertices" && kv.first != "triangles" && kv.first != "file" &&
+          kv.first != "scale" && kv.first != "translate")
         throw std::runtime_error(at + obj + "unknown key \"" + kv.first + "\"");
     pt_scene_object& o = objs[i];
     o = pt_scene_object{};
@@ -207,17 +213,67 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     else if (shape == "disc") o.shape = PT_SHAPE_DISC;
     else if (shape == "triangle") o.shape = PT_SHAPE_TRIANGLE;
     else if (shape == "parallelogram") o.shape = PT_SHAPE_PARALLELOGRAM;
-    else throw std::runtime_error(at + obj + "unknown shape '" + shape + "' (sphere, disc, triangle, parallelogram)");
+    else if (shape == "mesh") o.shape = PT_SHAPE_MESH;
+    else throw std::runtime_error(at + obj + "unknown shape '" + shape + "' (sphere, disc, triangle, parallelogram), or mesh");
     if (material == "diffuse") o.material = PT_MATERIAL_DIFFUSE;
     else if (material == "specular") o.material = PT_MATERIAL_SPECULAR;
     else if (material == "refractive") o.material = PT_MATERIAL_REFRACTIVE;
     else if (material == "emissive") o.material = PT_MATERIAL_EMISSIVE;
     else throw std::runtime_error(at + obj + "unknown material '" + material + "' (diffuse, specular, refractive, emissive)");
-    const bool polygon = ptscene::is_polygon(o.shape);
-    anyPolygon = anyPolygon || polygon;
+    const bool polygon = ptscene::is_polygon(o.shape), mesh = o.shape == PT_SHAPE_MESH;
+    anyPolygon = anyPolygon || polygon || mesh;   // (a mesh needs the ex table too)
     pt_scene_object_ex& x = objsEx[i];
     x = pt_scene_object_ex{};
-    if (polygon) {
+    if (!mesh)
+      for (const char* key : {"triangles", "file", "scale", "translate"})
+        if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a " + shape);
+    if (mesh) {
+      for (const char* key : {"centre", "radius", "normal"})
+        if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a mesh");
+      objreader::Mesh m;
+      if (v.has("file")) {
+        if (v.has("vertices") || v.has("triangles")) throw std::runtime_error(at + obj + "give \"file\" or \"vertices\" and \"triangles\", not both");
+        if (v.at("file").type != json::Value::String) throw std::runtime_error(at + obj + "\"file\" must be a string");
+        const std::string& name = v.at("file").str;
+        const std::size_t slash = path.find_last_of('/');
+        const std::string full = (!name.empty() && name[0] == '/') || slash == std::string::npos ? name : path.substr(0, slash + 1) + name;
+        try { m = objreader::read(full); } catch (const std::exception& e) { throw std::runtime_error(at + obj + e.what()); }
+      } else {
+        if (!v.has("vertices") || !v.has("triangles")) throw std::runtime_error(at + obj + "a mesh needs \"file\", or \"vertices\" and \"triangles\"");
+        const json::Value& vs = v.at("vertices");
+        const json::Value& ts = v.at("triangles");
+        if (vs.type != json::Value::Array || vs.arr.empty()) throw std::runtime_error(at + obj + "\"vertices\" must be a non-empty array of points");
+        if (ts.type != json::Value::Array || ts.arr.empty()) throw std::runtime_error(at + obj + "\"triangles\" must be a non-empty array of index triples");
+        for (const json::Value& q : vs.arr) {
+          if (q.type != json::Value::Array || q.arr.size() != 3) throw std::runtime_error(at + obj + "\"vertices\" must hold arrays of 3 numbers");
+          for (const json::Value& c : q.arr) {
+            if (c.type != json::Value::Number) throw std::runtime_error(at + obj + "\"vertices\" must hold numbers");
+            m.vertices.push_back((float)c.num);
+          }
+        }
+        for (const json::Value& q : ts.arr) {
+          if (q.type != json::Value::Array || q.arr.size() != 3) throw std::runtime_error(at + obj + "\"triangles\" must hold arrays of 3 indices");
+          for (const json::Value& c : q.arr) {
+            if (c.type != json::Value::Number || !(c.num >= 0.0) || c.num > 4294967295.0 || c.num != std::floor(c.num))
+              throw std::runtime_error(at + obj + "\"triangles\" must hold non-negative integers");
+            m.indices.push_back((std::uint32_t)c.num);
+          }
+        }
+      }
+      float scale[3] = {1.f, 1.f, 1.f}, translate[3] = {0.f, 0.f, 0.f};
+      if (v.has("scale")) {
+        if (v.at("scale").type == json::Value::Number) scale[0] = scale[1] = scale[2] = (float)v.at("scale").num;
+        else numbers("scale", scale, 3);
+      }
+      if (v.has("translate")) numbers("translate", translate, 3);
+      if (v.has("scale") || v.has("translate"))
+        for (std::size_t k = 0; k < m.vertices.size(); ++k) {
+          volatile float scaled = m.vertices[k] * scale[k % 3];
+          volatile float moved = scaled + translate[k % 3];
+          m.vertices[k] = moved;
+        }
+      meshes.push_back(std::move(m));
+    } else if (polygon) {
       for (const char* key : {"centre", "radius", "normal"})
         if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a " + shape + " (it takes \"vertices\")");
       if (!v.has("vertices")) throw std::runtime_error(at + obj + "\"vertices\" is missing (a " + shape + " needs three)");
@@ -248,7 +304,13 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     if (v.has("emission")) numbers("emission", o.colour, 3);
     std::memcpy(&x, &o, sizeof(o));   // the first 48 bytes of pt_scene_object_ex are pt_scene_object
   }
-  const std::string bad = anyPolygon ? ptscene::check_ex(objsEx.data(), (std::uint32_t)objsEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex))
+  std::vector<pt_mesh> views;
+  for (const objreader::Mesh& m : meshes)
+    views.push_back(pt_mesh{(std::uint32_t)sizeof(pt_mesh), (std::uint32_t)(m.vertices.size() / 3), (std::uint32_t)(m.indices.size() / 3),
+                            m.vertices.data(), m.indices.data()});
+  const std::string bad = !meshes.empty() ? ptmesh::check(objsEx.data(), (std::uint32_t)objsEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex),
+                                                          views.data(), (std::uint32_t)views.size())
+                          : anyPolygon ? ptscene::check_ex(objsEx.data(), (std::uint32_t)objsEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex))
                                      : ptscene::check(objs.data(), (std::uint32_t)objs.size());
   if (!bad.empty()) throw std::runtime_error(at + bad);
   ex.clear();
@@ -325,7 +387,7 @@ void PathTracerApp::init(const OptionMap& options) {
     throw std::runtime_error("--denoise-iterations must be 1..6; got " + args.str("denoise-iterations"));
   for (const char* name : {"denoise-sigma-colour", "denoise-sigma-normal", "denoise-sigma-depth"})
     if (!std::isfinite(args.f32(name))) throw std::runtime_error(std::string("--") + name + " must be finite; got " + args.str(name));
-  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera, sceneEx);
+  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera, sceneEx, sceneMeshes);
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
   if (!image_io::ldrWriterFor(args.str("outfile")))
@@ -539,7 +601,15 @@ void PathTracerApp::attach() {
     devices.push_back(h);
     if (pt_set_nif_sharing(h, nifSharing))
       throw std::runtime_error(std::string("--share-nif-evaluations: ") + pt_last_error(h));
-    if (!sceneEx.empty()) {   // the file holds a polygon
+    if (!sceneMeshes.empty()) {   // the file holds a mesh
+      std::vector<pt_mesh> views;
+      for (const objreader::Mesh& m : sceneMeshes)
+        views.push_back(pt_mesh{(std::uint32_t)sizeof(pt_mesh), (std::uint32_t)(m.vertices.size() / 3), (std::uint32_t)(m.indices.size() / 3),
+                                m.vertices.data(), m.indices.data()});
+      if (pt_set_scene_meshes(h, sceneEx.data(), (std::uint32_t)sceneEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex), views.data(),
+                              (std::uint32_t)views.size()))
+        throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
+    } else if (!sceneEx.empty()) {   // the file holds a polygon
       if (pt_set_scene_ex(h, sceneEx.data(), (std::uint32_t)sceneEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex)))
         throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
     } else if (!scene.empty() && pt_set_scene(h, scene.data(), (std::uint32_t)scene.size()))

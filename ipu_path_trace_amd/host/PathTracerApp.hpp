@@ -9,6 +9,7 @@
 
 #include "AccumulatedImage.hpp"
 #include "EnvMapReader.hpp"
+#include "ObjReader.hpp"
 #include "InterfaceServer.hpp"
 #include "IpuPathTraceJob.hpp"
 #include "LoadBalancer.hpp"
@@ -89,6 +90,7 @@ private:
   std::uint64_t memoServed = 0, memoEscaped = 0, memoRows = 0;
   std::vector<pt_scene_object> scene;   ///< --scene: the table every handle renders (empty: the built-in scene)
   std::vector<pt_scene_object_ex> sceneEx;   ///< --scene: the same with vertices, when the file holds a polygon (else empty)
+  std::vector<objreader::Mesh> sceneMeshes;   ///< --scene: the meshes of the file's "mesh" objects, in the order of their rows
   pt_camera camera{};                   ///< --scene: the file's "camera", set on every handle when hasCamera
   env_map::Image envMap;                ///< --env-map: the image every handle takes as its environment (empty: NIF or constant)
   std::int32_t envMapFilterMode = 1;    ///< --env-map-filter (PT_ENV_FILTER_*)

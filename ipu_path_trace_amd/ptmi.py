@@ -23,6 +23,9 @@ assert SCENE_EX_DTYPE.itemsize == 84   # pt_scene_object_ex
 MAX_SCENE_OBJECTS = 32
 SHAPE_SPHERE, SHAPE_DISC = 0, 1
 SHAPE_TRIANGLE, SHAPE_PARALLELOGRAM = 2, 3
+SHAPE_MESH = 4
+MAX_MESH_TRIANGLES = 1 << 22      # PT_MAX_MESH_TRIANGLES: per scene, all meshes together
+MESH_INTERSECT_BVH, MESH_INTERSECT_BRUTE = 0, 1
 SHAPES_EX = {"sphere": SHAPE_SPHERE, "disc": SHAPE_DISC, "triangle": SHAPE_TRIANGLE, "parallelogram": SHAPE_PARALLELOGRAM}
 MATERIAL_DIFFUSE, MATERIAL_SPECULAR, MATERIAL_REFRACTIVE, MATERIAL_EMISSIVE = 0, 1, 2, 3
 SHAPES = {"sphere": SHAPE_SPHERE, "disc": SHAPE_DISC}
@@ -49,7 +52,7 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval",
            "pt_set_light_guide", "pt_set_light_guide_ex", "pt_get_light_guide_flags", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
            "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
-           "pt_get_scene_ex"]
+           "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
@@ -262,6 +265,47 @@ def scene_array_ex(objects):
     return out
 
 
+def _is_mesh_shape(shape):
+    return shape == "mesh" or (not isinstance(shape, str) and int(shape) == SHAPE_MESH)
+
+
+def has_mesh(objects):
+    """Does a scene given as a list of dicts hold a mesh?  (An array cannot: a mesh's vertices and triangles travel beside it.)"""
+    return not isinstance(objects, np.ndarray) and any(_is_mesh_shape(o["shape"]) for o in objects)
+
+
+def scene_meshes(objects):
+    """(table, meshes) for pt_set_scene_meshes from a list of dicts: the keys of scene_array_ex, and for a mesh
+    {"shape": "mesh", "material": ..., "colour": ..., "vertices": (V, 3), "triangles": (T, 3)} -- world-space points and, per
+    triangle, three indices into them.  table is a SCENE_EX_DTYPE array whose mesh rows hold shape 4, material and colour;
+    meshes is the list of (vertices float32 (V, 3), triangles uint32 (T, 3)) in the order of those rows.  Shapes and index range
+    are checked here, everything else by the library."""
+    rows, meshes = [], []
+    for i, o in enumerate(objects):
+        if not _is_mesh_shape(o["shape"]):
+            rows.append(o)
+            continue
+        unknown = set(o) - {"shape", "material", "vertices", "triangles", "colour", "emission"}
+        if unknown:
+            raise ValueError("scene object %d: unknown key(s) %s" % (i, sorted(unknown)))
+        vertices = np.ascontiguousarray(o["vertices"], dtype=np.float32)
+        if vertices.ndim != 2 or vertices.shape[1] != 3 or len(vertices) == 0:
+            raise ValueError("scene object %d: vertices must be an array of shape (V, 3), V >= 1" % i)
+        tri = np.asarray(o["triangles"])
+        if tri.ndim != 2 or tri.shape[1] != 3 or len(tri) == 0:
+            raise ValueError("scene object %d: triangles must be an array of shape (T, 3), T >= 1" % i)
+        if not np.issubdtype(tri.dtype, np.integer) or tri.min() < 0 or tri.max() > 0xffffffff:
+            raise ValueError("scene object %d: triangles must hold unsigned 32-bit indices" % i)
+        meshes.append((vertices, np.ascontiguousarray(tri, dtype=np.uint32)))
+        rows.append({"shape": SHAPE_SPHERE, "material": o["material"], "centre": (0.0, 0.0, 0.0), "radius": 0.0,
+                     "colour": o.get("colour", o.get("emission", (1.0, 1.0, 1.0)))})
+    table = scene_array_ex(rows)
+    for i, o in enumerate(objects):
+        if _is_mesh_shape(o["shape"]):
+            table[i]["shape"] = SHAPE_MESH
+    return table, meshes
+
+
 def builtin_scene_ex():
     """The built-in scene as a SCENE_EX_DTYPE array (pt_get_scene_ex with no handle: vertices 0); needs no GPU."""
     lib = load_library()
@@ -282,6 +326,25 @@ def builtin_scene():
     if rc:
         raise PtError(rc, "pt_get_scene failed")
     return out[:n.value].copy()
+
+
+class Mesh(C.Structure):
+    """pt_mesh"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32),
+                ("vertices", C.c_void_p), ("indices", C.c_void_p)]
+
+
+class MeshInfo(C.Structure):
+    """pt_mesh_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("object_index", C.c_uint32), ("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32),
+                ("max_leaf", C.c_uint32), ("depth", C.c_uint32), ("device_bytes", C.c_uint64), ("build_ms", C.c_double),
+                ("pad", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
+assert C.sizeof(Mesh) == 32 and C.sizeof(MeshInfo) == 48
 
 
 class Features(C.Structure):
@@ -464,6 +527,9 @@ def load_library(diag=False):
     L.pt_get_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     L.pt_set_scene_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.pt_get_scene_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.pt_set_scene_meshes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Mesh), C.c_uint32]
+    L.pt_get_mesh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshInfo)]
+    L.pt_mesh_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
@@ -814,10 +880,14 @@ class Renderer:
     def set_scene(self, objects):
         """Render a scene of 1..32 spheres and discs instead of the built-in one (include/ptmi.h, pt_set_scene): a SCENE_DTYPE
         array or a list of dicts (scene_array).  A list that holds a "triangle" or a "parallelogram" (scene_array_ex), or a
-        SCENE_EX_DTYPE array, goes through pt_set_scene_ex.  None restores the built-in scene.  Takes effect at the next
-        path_trace."""
+        SCENE_EX_DTYPE array, goes through pt_set_scene_ex, and a list that holds a "mesh" (scene_meshes) through
+        pt_set_scene_meshes.  None restores the built-in scene.  Takes effect at the next path_trace."""
         if objects is None:
             self._check(self._lib.pt_set_scene(self.handle, None, 0))
+            return
+        if has_mesh(objects):
+            table, meshes = scene_meshes(objects)
+            self.set_scene_meshes(table, meshes)
             return
         if (isinstance(objects, np.ndarray) and objects.dtype == SCENE_EX_DTYPE) or has_polygon(objects):
             # a triangle or a parallelogram (or an ex table as it is): pt_set_scene_ex, keys of scene_array_ex
@@ -826,6 +896,43 @@ class Renderer:
             return
         arr = scene_array(objects)
         self._check(self._lib.pt_set_scene(self.handle, arr.ctypes.data, arr.size))   # (an empty table is refused)
+
+    def set_scene_meshes(self, table, meshes):
+        """pt_set_scene_meshes as it is: a SCENE_EX_DTYPE table and, for its rows of shape 4 in order, (vertices, triangles)
+        pairs.  The library copies everything; with no mesh this is pt_set_scene_ex."""
+        table = scene_array_ex(table)
+        keep = [(np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(t, dtype=np.uint32)) for v, t in meshes]
+        arr = (Mesh * max(len(keep), 1))()
+        for k, (v, t) in enumerate(keep):
+            if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+                raise ValueError("mesh %d: vertices must have shape (V, 3) and triangles (T, 3)" % k)
+            arr[k] = Mesh(C.sizeof(Mesh), len(v), len(t), v.ctypes.data, t.ctypes.data)
+        self._check(self._lib.pt_set_scene_meshes(self.handle, table.ctypes.data, table.size, SCENE_EX_DTYPE.itemsize,
+                                                  arr if keep else None, len(keep)))
+
+    def mesh_info(self, k):
+        """pt_get_mesh_info of mesh k of the scene in force as a dict: object_index, n_triangles, n_nodes, max_leaf, depth,
+        device_bytes, build_ms, pad."""
+        info = MeshInfo(struct_size=C.sizeof(MeshInfo))
+        self._check(self._lib.pt_get_mesh_info(self.handle, int(k), C.byref(info)))
+        return info.as_dict()
+
+    def mesh_intersect(self, origin, direction, brute=False):
+        """pt_mesh_intersect: the kernels' nearest hit over world-space rays origin (n, 3), direction (n, 3), the camera ignored.
+        Returns (t, object, triangle): t 0 for a miss, object -1 for a miss, triangle -1 unless a mesh was hit.  brute=True
+        loops over all triangles of each mesh instead of walking its tree."""
+        o = np.ascontiguousarray(origin, dtype=np.float32)
+        d = np.ascontiguousarray(direction, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("origin and direction must both have shape (n, 3)")
+        n = len(o)
+        t = np.zeros(n, np.float32)
+        obj = np.full(n, -1, np.int32)
+        tri = np.full(n, -1, np.int32)
+        self._check(self._lib.pt_mesh_intersect(self.handle, o.ctypes.data, d.ctypes.data, n,
+                                                MESH_INTERSECT_BRUTE if brute else MESH_INTERSECT_BVH,
+                                                t.ctypes.data, obj.ctypes.data, tri.ctypes.data))
+        return t, obj, tri
 
     def scene_ex(self):
         """The scene in force as a SCENE_EX_DTYPE array (pt_get_scene_ex): a polygon with centre = v0, radius 0 and its stored
