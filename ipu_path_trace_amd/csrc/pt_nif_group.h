@@ -27,7 +27,7 @@
 //   stamp(s)             what a served hit stamps
 //   store_index(s)       the owner's store index of a slot claimed in this step, for resolve
 //   served_bgr(s)        the BGR of a served slot, for expand
-//   count(...)           the table's own counters
+//   count(served, fresh) the table's own counters, a claim tile's sums at a time (only a table that serves has any)
 #pragma once
 
 #include "ptmi_share_plan.h"
@@ -37,6 +37,7 @@ namespace ptd {
 constexpr unsigned long long kShareEmpty = ~0ull;     // empty slot: u and v both the all-ones NaN pattern
 constexpr uint32_t kShareMaxProbes = 32;              // linear probes before a key is evaluated alone
 constexpr int kShareBlock = 256;
+static_assert(kShareBlock == (int)ptshare::kClaimBlock, "the claim tiles of ptmi_share_plan.h are for this workgroup");
 
 // 64-bit finaliser of MurmurHash3: neighbouring (u, v) bit patterns land on unrelated slots
 __device__ __forceinline__ uint32_t share_hash(unsigned long long k) {
@@ -96,7 +97,6 @@ struct ShareTable {
   __device__ __forceinline__ void claim(uint32_t s, uint32_t g) const { vals[s] = g; }
   __device__ __forceinline__ void stamp(uint32_t) const {}
   __device__ __forceinline__ uint32_t store_index(uint32_t s) const { return vals[s]; }
-  __device__ __forceinline__ void count(bool, bool) const {}
 };
 
 // slot_mask + 1 slots of pt_nif_memo.h
@@ -118,67 +118,127 @@ struct MemoTable {
   __device__ __forceinline__ void stamp(uint32_t s) const { if (slots[s].last_hit != step) slots[s].last_hit = step; }
   __device__ __forceinline__ uint32_t store_index(uint32_t s) const { return slots[s].idx; }
   __device__ __forceinline__ const float* served_bgr(uint32_t s) const { return &slots[s].b; }
-  __device__ __forceinline__ void count(bool served, bool fresh) const {
-    wave_count(served, counters + kMemoServedCount);
-    wave_count(fresh, counters + kMemoInserted);
-    wave_count(fresh, counters + kMemoOccupied);
+  // a claim tile's sums, by one thread of its workgroup
+  __device__ __forceinline__ void count(uint32_t served, uint32_t fresh) const {
+    if (served) atomicAdd(counters + kMemoServedCount, (unsigned long long)served);
+    if (fresh) {
+      atomicAdd(counters + kMemoInserted, (unsigned long long)fresh);
+      atomicAdd(counters + kMemoOccupied, (unsigned long long)fresh);
+    }
   }
 };
 static_assert(offsetof(MemoSlot, g) == offsetof(MemoSlot, b) + 4 && offsetof(MemoSlot, r) == offsetof(MemoSlot, b) + 8,
               "a memo slot holds its BGR as the store does");
 
-// grid (ceil(region_cap / 256), n_regions): x = 256 entries of one region, y = region
+// grid (claim_tiles(region_cap), n_regions): x = one tile of kClaimTile entries of one region, y = region.  A thread takes
+// kClaimK entries of the tile (ptmi_share_plan.h: claim_entry) and looks all of them up before anything is appended, so
+// kClaimK table loads are in flight per lane; then the workgroup reserves the tile's places in the distinct queue with ONE
+// returning atomic on d_count (the waves' append counts meet in LDS, each wave starts behind the waves before it), and the
+// tile's overflow and table counters go out once each, non-returning, where they are not zero.  One word takes about 88
+// returning atomics per microsecond; a reservation per wave of 64 entries made that rate the cost of the whole pass
+// (profiles/r20_claim_counter.txt).
 template <class Table>
 __device__ __forceinline__ void group_claim(const GroupQueue& Q, const Table& T) {
-  const uint32_t r = blockIdx.y, local = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x;
+  constexpr uint32_t K = ptshare::kClaimK, W = ptshare::kClaimWaves;
+  __shared__ uint32_t s_appends[W], s_alone[W], s_served[W], s_fresh[W];
+  __shared__ uint32_t s_first;
+  const uint32_t r = blockIdx.y, tile = blockIdx.x;
   const uint32_t count = Q.region_count[r];
-  if (blockIdx.x * (uint32_t)kShareBlock >= count) return;   // uniform over the workgroup
-  const bool valid = local < count;
-  const uint32_t q = r * Q.region_cap + local;
-  // fresh: claimed a new key; alone: no slot (evaluated on its own); served: the table holds the key's value
-  bool fresh = false, alone = false, served = false;
-  uint32_t slot = 0;
-  float u = 0.f, v = 0.f;
-  if (valid) {
-    u = Q.q_u[q]; v = Q.q_v[q];
-    const unsigned long long key = ((unsigned long long)__float_as_uint(u) << 32) | (unsigned long long)__float_as_uint(v);
-    alone = true;
+  if (ptshare::claim_tile_idle(tile, count)) return;   // uniform over the workgroup
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const size_t q0 = (size_t)r * Q.region_cap;
+  // bit k of each: entry k is below the count / fresh: claimed a new key / alone: no slot (evaluated on its own) / served:
+  // the table holds the key's value
+  uint32_t valid = 0, fresh = 0, alone = 0, served = 0;
+  float u[K], v[K];
+  uint32_t slot[K];
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    const uint32_t local = ptshare::claim_entry(tile, threadIdx.x, k);
+    // no branch around the loads, so that they go out together: an entry at or above the count reads the region's last
+    // live one (the tile is not idle, so there is one) and is not looked at again
+    const uint32_t at = local < count ? local : count - 1u;
+    u[k] = Q.q_u[q0 + at]; v[k] = Q.q_v[q0 + at];
+    valid |= (local < count ? 1u : 0u) << k;
+  }
+  // a plain look at every key's first slot, all of them in flight together: most entries find their key already there and
+  // need no atomic (a stale EMPTY only costs the CAS, and a slot that holds a key keeps it)
+  unsigned long long cur[K];
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    const unsigned long long key = ((unsigned long long)__float_as_uint(u[k]) << 32) | (unsigned long long)__float_as_uint(v[k]);
+    slot[k] = share_hash(key) & T.slot_mask;
+    cur[k] = __hip_atomic_load(T.key(slot[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (no branch, as above)
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    if (!((valid >> k) & 1u)) continue;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(u[k]) << 32) | (unsigned long long)__float_as_uint(v[k]);
+    bool none = true;
     if (key != kShareEmpty) {
-      uint32_t s = share_hash(key) & T.slot_mask;
-      for (uint32_t p = 0; p < kShareMaxProbes; ++p, s = (s + 1u) & T.slot_mask) {
-        // a plain look first: most entries find their key already there and need no atomic (a stale EMPTY only costs the CAS)
-        unsigned long long cur = __hip_atomic_load(T.key(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == kShareEmpty) cur = atomicCAS(T.key(s), kShareEmpty, key);
-        if (cur == kShareEmpty) { fresh = true; alone = false; slot = s; break; }
-        if (cur == key) { if constexpr (Table::kServes) served = T.served(s); alone = false; slot = s; break; }
+      uint32_t s = slot[k];
+      unsigned long long c = cur[k];
+#pragma unroll 1
+      for (uint32_t p = 0;;) {
+        if (c == kShareEmpty) c = atomicCAS(T.key(s), kShareEmpty, key);
+        if (c == kShareEmpty) { fresh |= 1u << k; none = false; slot[k] = s; break; }
+        if (c == key) {
+          if constexpr (Table::kServes) { if (T.served(s)) served |= 1u << k; }
+          none = false; slot[k] = s; break;
+        }
+        if (++p == kShareMaxProbes) break;
+        s = (s + 1u) & T.slot_mask;
+        c = __hip_atomic_load(T.key(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
+    if (none) alone |= 1u << k;
   }
-  const bool append = fresh || alone;
-  // one atomic per wave for the distinct-queue entries it appends (wave ballot + prefix count, as the trace kernel's queue)
-  const uint64_t m = __ballot(append);
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t first = 0;
-  if (m) {
-    const int leader = __ffsll((long long)m) - 1;
-    if (lane == (uint32_t)leader) first = atomicAdd(Q.d_count, (uint32_t)__popcll(m));
-    first = __shfl(first, leader, 64);
+  const uint32_t append = fresh | alone;
+  // the wave's counts (wave ballots: scalar work), then the workgroup's through LDS
+  uint32_t n_append = 0, n_alone = 0, n_served = 0, n_fresh = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    n_append += (uint32_t)__popcll(__ballot((append >> k) & 1u));
+    n_alone += (uint32_t)__popcll(__ballot((alone >> k) & 1u));
+    if constexpr (Table::kServes) {
+      n_served += (uint32_t)__popcll(__ballot((served >> k) & 1u));
+      n_fresh += (uint32_t)__popcll(__ballot((fresh >> k) & 1u));
+    }
   }
-  if (append) {
-    const uint32_t i = first + lane_rank(m);
-    Q.d_u[i] = u; Q.d_v[i] = v;
-    const uint32_t g = Q.base + i;
-    T.append(g, fresh, slot);
-    if (fresh) T.claim(slot, g);
-    Q.owner[q] = g;
-  } else if (served) {
-    T.stamp(slot);
-    Q.owner[q] = ptshare::owner_served(slot);
-  } else if (valid) {
-    Q.owner[q] = ptshare::owner_pending(slot);   // the key's owner may not have written its store index yet: resolved by the next pass
+  if (lane == 0) {
+    s_appends[wave] = n_append; s_alone[wave] = n_alone;
+    if constexpr (Table::kServes) { s_served[wave] = n_served; s_fresh[wave] = n_fresh; }
   }
-  wave_count(alone, Q.overflowed);
-  T.count(served, fresh);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t total = ptshare::claim_wave_offset(s_appends, W);
+    s_first = total ? atomicAdd(Q.d_count, total) : 0u;
+    const uint32_t over = ptshare::claim_wave_offset(s_alone, W);
+    if (over) atomicAdd(Q.overflowed, (unsigned long long)over);
+    if constexpr (Table::kServes) T.count(ptshare::claim_wave_offset(s_served, W), ptshare::claim_wave_offset(s_fresh, W));
+  }
+  __syncthreads();
+  uint32_t next = s_first + ptshare::claim_wave_offset(s_appends, wave);   // the wave's next place in the distinct queue
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    const uint32_t bit = 1u << k;
+    const size_t q = q0 + ptshare::claim_entry(tile, threadIdx.x, k);
+    const uint64_t m = __ballot((append & bit) != 0);
+    if (append & bit) {
+      const uint32_t i = next + lane_rank(m);
+      Q.d_u[i] = u[k]; Q.d_v[i] = v[k];
+      const uint32_t g = Q.base + i;
+      T.append(g, (fresh & bit) != 0, slot[k]);
+      if (fresh & bit) T.claim(slot[k], g);
+      Q.owner[q] = g;
+    } else if (served & bit) {
+      T.stamp(slot[k]);
+      Q.owner[q] = ptshare::owner_served(slot[k]);
+    } else if (valid & bit) {
+      Q.owner[q] = ptshare::owner_pending(slot[k]);   // the key's owner may not have written its store index yet: resolved by the next pass
+    }
+    next += (uint32_t)__popcll(m);
+  }
 }
 
 // owner[q] = the store index of the slot's owner, for the entries that found their key claimed by another in this step (every

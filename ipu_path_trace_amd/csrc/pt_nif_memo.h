@@ -35,6 +35,7 @@ struct alignas(32) MemoSlot {
   uint32_t idx;             // step-store index of the owner (claimed slots)
 };
 static_assert(sizeof(MemoSlot) == ptshare::kMemoSlotBytes, "one memo slot = 32 bytes, as pt_set_nif_memo counts them");
+static_assert(offsetof(MemoSlot, state) == 8 && offsetof(MemoSlot, last_hit) == 12, "memo_compact_kernel reads them as words 2 and 3");
 
 // counters of the memo passes, cleared at the start of every step (occupied only when the table is cleared)
 enum { kMemoOccupied = 0, kMemoServedCount = 1, kMemoInserted = 2, kMemoRetained = 3, kMemoCounters = 4 };
@@ -58,28 +59,49 @@ __global__ __launch_bounds__(kShareBlock) void memo_publish_kernel(MemoSlot* slo
   }
 }
 
-// retain pass, 1 of 2: the valid entries hit in step `last` into list[0 .. list_cap); the rest are dropped (a memo may forget)
+// retain pass, 1 of 2: the valid entries hit in step `last` into list[0 .. list_cap); the rest are dropped (a memo may forget).
+// A workgroup holds kCompactTrips trips of its grid-stride loop in registers and reserves their places in the list with one
+// atomic: with one per wave and trip, the single counter was the pass's time (profiles/r07_nif_memo.txt).  The list stays
+// dense (memo_reinsert_kernel reads list[0 .. retained)); the LDS words alternate between two sets, so a wave that is a
+// round ahead writes beside what a slower wave still reads.
+constexpr uint32_t kCompactTrips = 8;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(kShareBlock) void memo_compact_kernel(const MemoSlot* slots, uint32_t n_slots, uint32_t last,
                                                                    MemoSlot* list, uint32_t list_cap, unsigned long long* counters) {
-  const uint32_t lane = threadIdx.x & 63u;
-  for (uint32_t s0 = blockIdx.x * (uint32_t)kShareBlock; s0 < n_slots; s0 += gridDim.x * (uint32_t)kShareBlock) {
-    const uint32_t s = s0 + threadIdx.x;
-    bool keep = false;
-    MemoSlot e{};
-    if (s < n_slots) {
-      e = slots[s];
-      keep = e.state == kMemoValid && e.last_hit == last;
+  constexpr uint32_t W = ptshare::kClaimWaves;
+  __shared__ uint32_t s_kept[2][W];
+  __shared__ unsigned long long s_first[2];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint64_t stride = (uint64_t)gridDim.x * kShareBlock;
+  uint32_t round = 0;
+  for (uint64_t s0 = (uint64_t)blockIdx.x * kShareBlock; s0 < n_slots; s0 += stride * kCompactTrips, round ^= 1u) {
+    u32x4 lo[kCompactTrips], hi[kCompactTrips];   // the trips' slots as two 16-byte halves: key, state, last_hit | b, g, r, idx
+    uint32_t keep = 0, n_kept = 0;                // bit j: trip j's slot stays
+#pragma unroll
+    for (uint32_t j = 0; j < kCompactTrips; ++j) {
+      const uint64_t s = s0 + j * stride + threadIdx.x;
+      const u32x4* from = reinterpret_cast<const u32x4*>(slots + (s < n_slots ? s : n_slots - 1u));   // (no branch round the loads)
+      lo[j] = from[0]; hi[j] = from[1];
+      keep |= (s < n_slots && lo[j].z == kMemoValid && lo[j].w == last ? 1u : 0u) << j;
     }
-    const uint64_t m = __ballot(keep);
-    unsigned long long first = 0;
-    if (m) {
-      const int leader = __ffsll((long long)m) - 1;
-      if (lane == (uint32_t)leader) first = atomicAdd(counters + kMemoRetained, (unsigned long long)__popcll(m));
-      first = __shfl(first, leader, 64);
+#pragma unroll
+    for (uint32_t j = 0; j < kCompactTrips; ++j) n_kept += (uint32_t)__popcll(__ballot((keep >> j) & 1u));
+    if (lane == 0) s_kept[round][wave] = n_kept;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t total = ptshare::claim_wave_offset(s_kept[round], W);
+      s_first[round] = total ? atomicAdd(counters + kMemoRetained, (unsigned long long)total) : 0ull;
     }
-    if (keep) {
-      const unsigned long long i = first + lane_rank(m);
-      if (i < list_cap) list[i] = e;
+    __syncthreads();
+    unsigned long long next = s_first[round] + ptshare::claim_wave_offset(s_kept[round], wave);
+#pragma unroll
+    for (uint32_t j = 0; j < kCompactTrips; ++j) {
+      const uint64_t m = __ballot((keep >> j) & 1u);
+      if ((keep >> j) & 1u) {
+        const unsigned long long i = next + lane_rank(m);
+        if (i < list_cap) { u32x4* to = reinterpret_cast<u32x4*>(list + i); to[0] = lo[j]; to[1] = hi[j]; }
+      }
+      next += (unsigned long long)__popcll(m);
     }
   }
 }

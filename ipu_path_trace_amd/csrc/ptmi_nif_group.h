@@ -238,15 +238,15 @@ static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const 
     Q.d_count = h->group.d_share_count + b.index;
     Q.base = b.store_base;
     Q.overflowed = h->group.d_share_over;
-    const dim3 grid = b.group_grid(), block(ptd::kShareBlock);
+    const dim3 grid = b.group_grid(), tiles = b.claim_grid(), block(ptd::kShareBlock);
     if (mode.memo) {
-      hipLaunchKernelGGL(ptd::memo_lookup_kernel, grid, block, 0, h->trace_stream, Q, memo_table(h));
+      hipLaunchKernelGGL(ptd::memo_lookup_kernel, tiles, block, 0, h->trace_stream, Q, memo_table(h));
       PT_HIP(hipGetLastError());
       hipLaunchKernelGGL(ptd::memo_resolve_kernel, grid, block, 0, h->trace_stream, Q, memo_table(h));
     } else {
       if (mode.share == PT_NIF_SHARE_BATCH)   // one table per batch
         PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
-      hipLaunchKernelGGL(ptd::share_claim_kernel, grid, block, 0, h->trace_stream, Q, share_table(h));
+      hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_table(h));
       PT_HIP(hipGetLastError());
       hipLaunchKernelGGL(ptd::share_resolve_kernel, grid, block, 0, h->trace_stream, Q, share_table(h));
     }
@@ -380,6 +380,87 @@ int pt_diag_set_nif_memo_slots(pt_handle h, uint32_t slots) {
   while (p < slots) p <<= 1;
   return alloc_memo(h, p);
 }
+
+// test build only: the claim and resolve passes over a queue the caller supplies, with buffers of its own (the handle gives
+// the device and the stream; nothing of its sharing state is touched).  u, v: [n_regions x region_cap] as the trace kernel
+// lays its queue out; region_count[r] <= region_cap entries of region r are live.  memo = 0: a ShareTable of table_slots
+// slots (a power of two).  memo = 1: a MemoTable, `passes` times (1 or 2) over the same queue with a publish of zeros between
+// them, as two steps would run; the outputs are the last pass's.  Out, on the host: owner [n_regions x region_cap] (live
+// entries), the distinct queue d_u / d_v (same capacity; store index = position), its length, the overflow count, the memo's
+// four counters (memo = 1; may be null) and the table's keys [table_slots] (may be null).
+int pt_diag_claim_resolve(pt_handle h, int32_t memo, uint32_t passes, const float* u, const float* v, const uint32_t* region_count,
+                          uint32_t n_regions, uint32_t region_cap, uint32_t table_slots, uint32_t* owner, float* d_u, float* d_v,
+                          uint32_t* d_count, uint64_t* overflowed, uint64_t* memo_counters, uint64_t* table_keys) {
+  if (!h || !u || !v || !region_count || !owner || !d_u || !d_v || !d_count || !overflowed) return PT_ERR_INVALID_ARGUMENT;
+  const uint64_t n64 = (uint64_t)n_regions * region_cap;
+  if (n_regions == 0 || region_cap == 0 || n64 >= ptshare::kMaxStoreEntries || table_slots < 2 || table_slots > ptshare::kMaxSlots ||
+      (table_slots & (table_slots - 1u)) || passes < 1 || passes > (memo ? 2u : 1u))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_claim_resolve: sizes out of range");
+  for (uint32_t r = 0; r < n_regions; ++r)
+    if (region_count[r] > region_cap) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_claim_resolve: a region's count exceeds its capacity");
+  const size_t n = (size_t)n64;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t s = h->stream;
+  DevBuf<float> q_u, q_v, du, dv, bgr;
+  DevBuf<uint32_t> counts, own, len, vals, d_slot;
+  DevBuf<unsigned long long> over, keys, ctr;
+  DevBuf<ptd::MemoSlot> slots;
+  PT_HIP(dev_alloc(q_u, n)); PT_HIP(dev_alloc(q_v, n)); PT_HIP(dev_alloc(du, n)); PT_HIP(dev_alloc(dv, n));
+  PT_HIP(dev_alloc(counts, n_regions)); PT_HIP(dev_alloc(own, n)); PT_HIP(dev_alloc(len, 1)); PT_HIP(dev_alloc(over, 1));
+  PT_HIP(hipMemcpyAsync(q_u, u, n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(q_v, v, n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(counts, region_count, (size_t)n_regions * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemsetAsync(own, 0xff, n * 4, s));   // an entry no pass writes reads as pending
+  PT_HIP(hipMemsetAsync(over, 0, 8, s));
+  ptd::GroupQueue Q;
+  Q.q_u = q_u; Q.q_v = q_v; Q.region_count = counts; Q.region_cap = region_cap; Q.owner = own;
+  Q.d_u = du; Q.d_v = dv; Q.d_count = len; Q.base = 0; Q.overflowed = over;
+  const dim3 grid((region_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock, n_regions), tiles(ptshare::claim_tiles(region_cap), n_regions);
+  const dim3 block(ptd::kShareBlock);
+  if (memo) {
+    PT_HIP(dev_alloc(slots, table_slots)); PT_HIP(dev_alloc(d_slot, n)); PT_HIP(dev_alloc(ctr, ptd::kMemoCounters)); PT_HIP(dev_alloc(bgr, 3 * n));
+    PT_HIP(hipMemsetAsync(slots, 0xff, (size_t)table_slots * sizeof(ptd::MemoSlot), s));
+    PT_HIP(hipMemsetAsync(ctr, 0, ptd::kMemoCounters * 8, s));
+    PT_HIP(hipMemsetAsync(bgr, 0, 3 * n * 4, s));
+    for (uint32_t pass = 1; pass <= passes; ++pass) {
+      const ptd::MemoTable T{slots, table_slots - 1u, pass, d_slot, ctr};
+      PT_HIP(hipMemsetAsync(len, 0, 4, s));
+      PT_HIP(hipMemsetAsync(over, 0, 8, s));
+      PT_HIP(hipMemsetAsync(ctr + ptd::kMemoServedCount, 0, (ptd::kMemoCounters - 1) * 8, s));   // as the step's prologue
+      hipLaunchKernelGGL(ptd::memo_lookup_kernel, tiles, block, 0, s, Q, T);
+      PT_HIP(hipGetLastError());
+      hipLaunchKernelGGL(ptd::memo_resolve_kernel, grid, block, 0, s, Q, T);
+      PT_HIP(hipGetLastError());
+      if (pass < passes) {
+        const dim3 pgrid(std::min<uint32_t>(ptd::kMemoGrid, (uint32_t)((n + ptd::kShareBlock - 1u) / ptd::kShareBlock)), 1);
+        hipLaunchKernelGGL(ptd::memo_publish_kernel, pgrid, block, 0, s, slots, d_slot, bgr, len, (uint32_t)n, pass);
+        PT_HIP(hipGetLastError());
+      }
+    }
+  } else {
+    PT_HIP(dev_alloc(keys, table_slots)); PT_HIP(dev_alloc(vals, table_slots));
+    PT_HIP(hipMemsetAsync(keys, 0xff, (size_t)table_slots * 8, s));
+    PT_HIP(hipMemsetAsync(len, 0, 4, s));
+    const ptd::ShareTable T{keys, vals, table_slots - 1u};
+    hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, s, Q, T);
+    PT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ptd::share_resolve_kernel, grid, block, 0, s, Q, T);
+    PT_HIP(hipGetLastError());
+  }
+  PT_HIP(hipMemcpyAsync(owner, own, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(d_u, du, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(d_v, dv, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(d_count, len, 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(overflowed, over, 8, hipMemcpyDeviceToHost, s));
+  if (memo && memo_counters) PT_HIP(hipMemcpyAsync(memo_counters, ctr, ptd::kMemoCounters * 8, hipMemcpyDeviceToHost, s));
+  if (table_keys) {
+    if (memo) PT_HIP(hipMemcpy2DAsync(table_keys, 8, slots, sizeof(ptd::MemoSlot), 8, table_slots, hipMemcpyDeviceToHost, s));
+    else PT_HIP(hipMemcpyAsync(table_keys, keys, (size_t)table_slots * 8, hipMemcpyDeviceToHost, s));
+  }
+  PT_HIP(hipStreamSynchronize(s));
+  return PT_OK;
+}
 #endif
+
 
 }  // extern "C"

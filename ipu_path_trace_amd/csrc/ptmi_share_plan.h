@@ -1,7 +1,8 @@
 // ptmi_share_plan.h -- the arithmetic of NIF sharing and the memo (pt_set_nif_sharing, pt_set_nif_memo; pt_nif_group.h): the
 // format of an owner word, how many slots the table of a batch or a step gets, whether the automatic default may take the
-// memory it needs, and how many slots a memo of a given size has.  Plain C++ (nothing from HIP), so that
-// tests/share_plan_main.cpp checks it on a CPU; ptmi.hip includes it ahead of the device headers.
+// memory it needs, how many slots a memo of a given size has, and the tiles of the claim pass.  Plain C++ (nothing from
+// HIP), so that tests/share_plan_main.cpp and tests/claim_plan_main.cpp check it on a CPU; ptmi.hip includes it ahead of the
+// device headers.
 #pragma once
 
 #include <cstdint>
@@ -20,6 +21,26 @@ constexpr bool owner_is_store(uint32_t o) { return !(o & kOwnerTagged); }
 constexpr bool owner_is_pending(uint32_t o) { return (o & kOwnerPending) == kOwnerPending; }
 constexpr bool owner_is_served(uint32_t o) { return (o & kOwnerPending) == kOwnerTagged; }
 constexpr uint32_t owner_slot(uint32_t o) { return o & kOwnerSlotBits; }
+
+// The claim pass's tiles (group_claim in pt_nif_group.h): a workgroup of kClaimBlock threads takes kClaimTile consecutive
+// entries of one region, thread t the entries tile base + k * kClaimBlock + t for k < kClaimK, and reserves the tile's places
+// in the distinct queue with one atomic.  Grid (claim_tiles(region_cap), regions).
+constexpr uint32_t kClaimBlock = 256;
+constexpr uint32_t kClaimK = 8;
+constexpr uint32_t kClaimTile = kClaimBlock * kClaimK;
+constexpr uint32_t kClaimWaves = kClaimBlock / 64;
+constexpr uint32_t claim_tiles(uint32_t region_cap) { return region_cap / kClaimTile + (region_cap % kClaimTile ? 1u : 0u); }
+// a tile with no entry below the region's count: the same answer for every thread of the workgroup
+constexpr bool claim_tile_idle(uint32_t tile, uint32_t count) { return (uint64_t)tile * kClaimTile >= count; }
+// the entry of its region that thread `thread` of tile `tile` takes as its k-th (taken only if below the region's count)
+constexpr uint32_t claim_entry(uint32_t tile, uint32_t thread, uint32_t k) { return tile * kClaimTile + k * kClaimBlock + thread; }
+// where wave `wave` starts inside its tile's reservation: the appends of the waves before it (wave = kClaimWaves: the
+// reservation itself)
+constexpr uint32_t claim_wave_offset(const uint32_t* wave_appends, uint32_t wave) {
+  uint32_t off = 0;
+  for (uint32_t w = 0; w < wave; ++w) off += wave_appends[w];
+  return off;
+}
 
 constexpr uint64_t kMinSlots = 1024;            // smallest table the sizing rules give
 constexpr uint64_t kMaxSlots = (uint64_t)kOwnerSlotBits + 1;   // a tagged owner word holds the slot
