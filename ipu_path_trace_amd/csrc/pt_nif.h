@@ -902,18 +902,18 @@ __global__ void clear_accum_kernel(uint32_t n, Accum A) {
 
 // AccumulateContributions::compute (codelets.cpp:249-301) for the k iterations of one batch, in
 // iteration order so the fp32 sums match the reference's (and the oracle's) order exactly.
-// Block reduction of the two step counters -> one 64-bit atomic pair per workgroup.
+// The two step counters: a wave reduction each, the four waves' sums through 32 bytes of LDS and one barrier, one 64-bit
+// atomic pair per workgroup (integers: the order of the adds does not matter).  A wave's sum stays below 2^32 (256 items x
+// 65535 iterations x 127 segments); the workgroup's is taken in 64 bits.
 __device__ __forceinline__ void accumulate_counters(uint32_t segs, uint32_t esc, unsigned long long* counters) {
-  __shared__ uint32_t ssegs[256], sesc[256];
-  ssegs[threadIdx.x] = segs; sesc[threadIdx.x] = esc;
+  __shared__ uint32_t wave_sum[2][4];   // launch bounds: 256 threads, four waves
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) { segs += __shfl_down(segs, s); esc += __shfl_down(esc, s); }
+  if ((threadIdx.x & 63u) == 0) { wave_sum[0][threadIdx.x >> 6] = segs; wave_sum[1][threadIdx.x >> 6] = esc; }
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) { ssegs[threadIdx.x] += ssegs[threadIdx.x + s]; sesc[threadIdx.x] += sesc[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    atomicAdd(&counters[0], (unsigned long long)ssegs[0]);
-    atomicAdd(&counters[1], (unsigned long long)sesc[0]);
+  if (threadIdx.x < 2) {
+    const uint32_t* w = wave_sum[threadIdx.x];
+    atomicAdd(&counters[threadIdx.x], (unsigned long long)w[0] + w[1] + w[2] + w[3]);
   }
 }
 
@@ -934,7 +934,7 @@ __global__ __launch_bounds__(256) void accumulate_kernel(uint32_t n, uint32_t it
 #pragma unroll
       for (uint32_t j = 0; j < U; ++j) {
         const uint32_t k = (k0 + j < iters) ? k0 + j : iters - 1u;
-        const size_t p = (size_t)k * n + i;
+        const uint32_t p = k * n + i;   // a batch's path indices stay below 2^31 (pt_create)
         pl[j] = plen[p];
         vr[j] = rad_r[p]; vg[j] = rad_g[p]; vb[j] = rad_b[p];
       }
@@ -960,6 +960,8 @@ __global__ __launch_bounds__(256) void accumulate_kernel(uint32_t n, uint32_t it
 // one 4-byte load of the four path records and three 16-byte loads of their radiance per iteration instead of four 1-byte
 // and twelve 4-byte ones -- a wave's load instruction covers 256 B / 1 KiB of consecutive memory, not 64 B / 256 B.  Each
 // pixel's adds are the same adds in the same (iteration) order: bit-identical to the kernel above.
+// Both kernels stay within what fits beside two NIF waves per SIMD -- 80 allocated VGPRs, no scratch (DESIGN.md section 4.3;
+// scripts/kernel_resources.py --step-budget): a wave that does not fit waits for the NIF launch's workgroups to leave.
 __global__ __launch_bounds__(256) void accumulate4_kernel(uint32_t n, uint32_t iters, const uint8_t* plen, const float* rad_r,
                                                           const float* rad_g, const float* rad_b, Accum A, unsigned long long* counters) {
   const uint32_t i = 4u * (blockIdx.x * blockDim.x + threadIdx.x);
@@ -968,14 +970,14 @@ __global__ __launch_bounds__(256) void accumulate4_kernel(uint32_t n, uint32_t i
     float4 r = *reinterpret_cast<const float4*>(A.r + i), g = *reinterpret_cast<const float4*>(A.g + i),
            b = *reinterpret_cast<const float4*>(A.b + i);
     uint32_t len[4] = {0, 0, 0, 0};
-    constexpr uint32_t U = 4;   // iterations in flight per thread: 4 x 52 B
+    constexpr uint32_t U = 3;   // iterations in flight per thread: 3 x 52 B in 63 VGPRs (four took 90, or 76 with the 32-bit index)
     for (uint32_t k0 = 0; k0 < iters; k0 += U) {
       uint32_t pl[U];
       float4 vr[U], vg[U], vb[U];
 #pragma unroll
       for (uint32_t j = 0; j < U; ++j) {
         const uint32_t k = (k0 + j < iters) ? k0 + j : iters - 1u;
-        const size_t p = (size_t)k * n + i;
+        const uint32_t p = k * n + i;   // a batch's path indices stay below 2^31 (pt_create): 32-bit index arithmetic
         pl[j] = *reinterpret_cast<const uint32_t*>(plen + p);
         vr[j] = *reinterpret_cast<const float4*>(rad_r + p);
         vg[j] = *reinterpret_cast<const float4*>(rad_g + p);
