@@ -365,8 +365,8 @@ int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uin
  * memory (pt_mesh_info.device_bytes), owned by the handle and freed by pt_destroy or by the next scene.
  *
  * Triangle j of a mesh.  v0, v1, v2 are vertices[indices[3 j + 0 .. 2]]; e1 = v1 - v0 and e2 = v2 - v0 in binary32, and the
- * stored normal is n = c / sqrtf(dot(c, c)), c = cross(e1, e2), exactly as for a PT_SHAPE_TRIANGLE object.  Shading is FLAT:
- * there are no vertex normals and no texture coordinates.
+ * stored normal is n = c / sqrtf(dot(c, c)), c = cross(e1, e2), exactly as for a PT_SHAPE_TRIANGLE object.  Shading is FLAT unless
+ * normals are attached (pt_set_mesh_normals below); there are no texture coordinates.
  *
  * Intersection.  A triangle is tested by the expression sequence of a PT_SHAPE_TRIANGLE object, unchanged, then by the scene's
  * t > eps and t < tbest in declaration order, as every object is.  Ties inside one mesh: the smallest t wins and, among equal
@@ -445,6 +445,75 @@ int pt_get_mesh_info(pt_handle h, uint32_t mesh, pt_mesh_info* out);
 enum { PT_MESH_INTERSECT_BVH = 0, PT_MESH_INTERSECT_BRUTE = 1 };
 int pt_mesh_intersect(pt_handle h, const float* origin, const float* dir, size_t n, int32_t mode,
                       float* out_t, int32_t* out_object, int32_t* out_triangle);
+
+/* Vertex normals of a mesh (smooth shading) -- an EXTENSION, opt-in and additive: PTMI_ABI_VERSION stays 5, pt_mesh, pt_mesh_info
+ * and every other struct and entry point keep layout and behaviour, and a process that never attaches normals launches the
+ * kernels it launched before and renders the same bits.  The new code lives in kernel instances of its own (SMOOTH), launched only
+ * while a mesh of the scene in force has normals.
+ *
+ * Attaching and removing.  pt_set_mesh_normals gives mesh `mesh` of the scene in force (counted as in pt_get_mesh_info) its
+ * normals.  normal_indices == NULL: corner c of triangle j uses normals[indices[3 j + c]] -- per-vertex normals; n_normals must
+ * equal the mesh's n_vertices.  Otherwise corner c uses normals[normal_indices[3 j + c]] -- per-corner normals, as OBJ's v//vn,
+ * which allow creases.  (h, mesh, NULL, 0, NULL) removes the normals: the mesh is flat again and renders the flat bits.  Any
+ * pt_set_scene* drops all normals with the scene.  A mesh WITHOUT normals beside one with normals takes none of the steps
+ * below and renders its flat bits (a flag per mesh row).
+ *
+ * Copies and memory.  The library copies everything.  The handle keeps the world normals per corner in triangle order (36 bytes
+ * per triangle of a mesh with normals; a pose change needs them) and the mesh's own indices (12 bytes per triangle).  The device
+ * holds three 16-byte vectors per triangle SLOT in leaf order, indexed by the global slot a hit carries: 48 bytes per triangle,
+ * which pt_mesh_normals_info.device_bytes reports for a mesh with normals: THIS MESH'S SHARE.  The buffer itself spans the slots
+ * of all meshes of the scene, the flat ones included (the slot of a hit indexes it directly), is allocated whole by the first call
+ * that attaches normals and PERSISTS until the next scene or pt_destroy: removing the last normals does not free it, so that
+ * attaching again, and every rebuild in between, allocates nothing.  The device memory held for normals is therefore
+ * 48 x (the sum of pt_mesh_info.n_triangles over the scene's meshes) from the first attachment on, which the sum of device_bytes
+ * under-reports by the flat meshes' slots and, after a removal, by the removed mesh's.  On PT_ERR_OUT_OF_MEMORY the mesh stays as
+ * it was.
+ *
+ * Host preparation.  Each referenced normal is normalised once, n / sqrtf(dot(n, n)) in binary32, every intermediate rounded,
+ * the sum left to right -- a disc normal's expressions.
+ *
+ * Validation returns PT_ERR_INVALID_ARGUMENT, and pt_last_error names the mesh, the triangle, the normal and the field: a NULL
+ * handle (pt_last_error(NULL)); no mesh `mesh` in force; NULL normals with n_normals > 0 (or with indices); n_normals different
+ * from n_vertices when normal_indices is NULL; then per triangle and corner an index >= n_normals, a referenced normal that is not
+ * finite, or whose dot(n, n) is not > 0 and finite.  Unreferenced normals are not examined.  After a rejection the mesh keeps
+ * what it had.
+ *
+ * Camera.  A normal is a direction: under a pose it enters the kernels as R^T n from the world value, as e1, e2 and the stored n
+ * do.  The rebuild a pose change triggers re-expands the normals into the new slot order and allocates nothing on the device.
+ *
+ * The shading normal (csrc/pt_mesh.h: shading_normal, one function for the kernels and the host), at a hit of the ray (o, d) on a
+ * triangle of a mesh with normals; every operation one rounded binary32, no contraction:
+ *   1. a, b by the triangle test's own expressions on the winning triangle (formed again at the hit: the same bits), c = (1 - a) - b.
+ *   2. m = ((c n0) + (a n1)) + (b n2) per component, l2 = dot(m, m); ns = m * (1 / sqrtf(l2)) -- the kernels' normalise -- when
+ *      l2 > 1e-12, else ns = ng, the triangle's stored geometric normal.
+ *   3. Orientation: dot(ns, ng) < 0 -> ns = -ns.  Normals wound against the triangle shade as if wound with it.
+ *   4. Side: (dot(ns, d) > 0) != (dot(ng, d) > 0) -> ns = ng.  At grazing incidence a shading normal that would put the ray on the
+ *      other side of the surface is dropped for this hit; glass therefore decides inside / outside exactly as the geometry does.
+ *   5. n = ns and the bounce continues unchanged: the two-sided flip for diffuse and specular, glass's own flip, the hemisphere
+ *      about n, cos = dot(d', n).  Both guides use this n.
+ *   6. Specular only: after v = d - 2 dot(d, n) n, if dot(v, ng_f) <= 0 (ng_f: ng flipped to face the ray) v is formed again with
+ *      ng_f in place of n.  A mirror never reflects into its own surface.
+ *   7. Diffuse and glass get no such correction: a diffuse direction with dot(d', n) > 0 that points below the geometric surface
+ *      is taken and meets the mesh again -- the usual shading-normal terminator, a documented limit like the non-watertight edges.
+ * Emissive hits return before any normal is formed.  Feature buffers: `normal` is the shading normal after steps 1-4, flipped to
+ * face the centre ray, then rotated to world space; object id, depth and albedo are unchanged. */
+int pt_set_mesh_normals(pt_handle h, uint32_t mesh, const float* normals /* [n_normals][3], world space */, uint32_t n_normals,
+                        const uint32_t* normal_indices /* [n_triangles][3], or NULL */);
+typedef struct pt_mesh_normals_info {   /* 24 bytes */
+  uint32_t struct_size;               /* in: sizeof(pt_mesh_normals_info) */
+  uint32_t has_normals;               /* 1: the mesh shades smooth */
+  uint32_t per_corner;                /* 1: given with normal_indices */
+  uint32_t n_normals;                 /* as given */
+  uint64_t device_bytes;              /* this mesh's share: 48 per triangle while it has normals, else 0 (the buffer: see above) */
+} pt_mesh_normals_info;
+int pt_get_mesh_normals_info(pt_handle h, uint32_t mesh, pt_mesh_normals_info* out);
+/* Kernel-level hook, like pt_mesh_intersect: world-space rays, the camera IGNORED.  The smooth instances' own nearest hit and the
+ * shading-normal function.  out_t, out_object, out_triangle as pt_mesh_intersect's; for a hit on a mesh triangle out_bary[i] is
+ * (a, b) and out_normal[i] the normal after steps 1-5 with the two-sided flip (it faces the ray), in world space -- for a mesh
+ * without normals the flipped stored normal.  For a miss or a hit on anything but a mesh triangle both are zero.
+ * PT_ERR_NOT_READY without a mesh in force; n == 0 is a no-op. */
+int pt_mesh_shade(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object,
+                  int32_t* out_triangle, float* out_bary /* [n][2] */, float* out_normal /* [n][3] */);
 
 /* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
  * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an

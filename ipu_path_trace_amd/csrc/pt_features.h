@@ -19,7 +19,7 @@ namespace ptd {
 
 constexpr int kFeatureBlock = 256;
 
-template <bool POLY, bool MESH = false>
+template <bool POLY, bool MESH = false, bool SMOOTH = false>
 __device__ __forceinline__ void features_body(const TraceParams& P, float4* __restrict__ f0, float4* __restrict__ f1) {
   const uint32_t i = blockIdx.x * kFeatureBlock + threadIdx.x;
   if (i >= P.width * P.height) return;   // width, height <= 65535: the product fits 32 bits
@@ -45,7 +45,19 @@ __device__ __forceinline__ void features_body(const TraceParams& P, float4* __re
     // rounding as the production shading forms it (shade_hit); disc or polygon (shape code >= 1): its stored normal
     n = ob.is_disc ? mk(ob.nx, ob.ny, ob.nz) : normalise(sub(scale(st.d, tbest), mk(ob.cx, ob.cy, ob.cz)));
     if constexpr (MESH) {   // a mesh: the hit triangle's stored normal
-      if (ob.is_disc == SHAPE_MESH) { const ptmesh::F4 tn = P.mesh_tris[3u * (size_t)hit_slot(packed) + 2u]; n = mk(tn.y, tn.z, tn.w); }
+      if (ob.is_disc == SHAPE_MESH) {
+        const ptmesh::F4 tn = P.mesh_tris[3u * (size_t)hit_slot(packed) + 2u];
+        n = mk(tn.y, tn.z, tn.w);
+        if constexpr (SMOOTH) {   // pt_set_mesh_normals: the shading normal of the centre ray, as shade_hit forms it (rules 1-4)
+          if (__float_as_uint(P.poly[best].e2y) != 0u) {
+            const size_t slot = (size_t)hit_slot(packed);
+            const float ov[3] = {0.f, 0.f, 0.f}, dv[3] = {st.d.x, st.d.y, st.d.z}, ng[3] = {tn.y, tn.z, tn.w};
+            float a, b, ns[3];
+            ptmesh::shading_normal(ov, dv, ptmesh::load_tri(P.mesh_tris + 3u * slot), ng, P.mesh_normals + 3u * slot, a, b, ns);
+            n = mk(ns[0], ns[1], ns[2]);
+          }
+        }
+      }
     }
     if (dot(n, st.d) > 0.0f) n = scale(n, -1.0f);                     // faces the ray
     if (P.cam_pose) n = normalise(to_world(P, n));                    // reported in world space; unit again after the rotation's roundings
@@ -65,6 +77,10 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel_poly(const Trac
 // pt_set_scene_meshes: launched only while the scene in force holds a mesh
 __global__ __launch_bounds__(kFeatureBlock) void features_kernel_mesh(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
   features_body<true, true>(P, f0, f1);
+}
+// pt_set_mesh_normals: launched only while a mesh in force has vertex normals
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel_smooth(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
+  features_body<true, true, true>(P, f0, f1);
 }
 
 }  // namespace ptd

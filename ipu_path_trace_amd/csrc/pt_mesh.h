@@ -124,4 +124,58 @@ PT_MESH_HD int brute(const F4* tris, const uint32_t* orig, uint32_t n_triangles,
   return best_slot;
 }
 
+// ---- vertex normals (pt_set_mesh_normals, include/ptmi.h): the shading normal of a hit on a triangle of a mesh with normals.
+//
+// The barycentrics are formed AGAIN, here, by tri_intersect's own expressions (pv, det, inv, tv, a, qv, b) on the ray that hit:
+// the same bits as the walk computed, without two more registers alive across the walk.  vn: the triangle slot's three corner
+// normals (unit to rounding, in the kernel's frame; .w unused).  ng: the triangle's stored geometric normal.  Steps, every
+// operation one rounded binary32:
+//   c = (1 - a) - b;  m = ((c n0) + (a n1)) + (b n2) per component;  l2 = dot(m, m)
+//   ns = m * (1 / sqrtf(l2)) when l2 > 1e-12 (the kernels' normalise), else ng
+//   orientation: dot(ns, ng) < 0 -> ns = -ns      (normals wound against the triangle shade as if wound with it)
+//   side: (dot(ns, d) > 0) != (dot(ng, d) > 0) -> ns = ng   (a shading normal that puts the ray on the other side is dropped)
+constexpr float kSmoothMinLen2 = 1e-12f;
+PT_MESH_HD float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+PT_MESH_HD void tri_bary(const float* o, const float* d, const Tri& T, float& a, float& b) {
+  const float* e1 = T.e1;
+  const float* e2 = T.e2;
+  const float pvx = d[1] * e2[2] - d[2] * e2[1], pvy = d[2] * e2[0] - d[0] * e2[2], pvz = d[0] * e2[1] - d[1] * e2[0];   // cross(d, e2)
+  const float det = e1[0] * pvx + e1[1] * pvy + e1[2] * pvz;
+  const float inv = 1.0f / det;
+  const float tvx = o[0] - T.v0[0], tvy = o[1] - T.v0[1], tvz = o[2] - T.v0[2];
+  a = (tvx * pvx + tvy * pvy + tvz * pvz) * inv;
+  const float qvx = tvy * e1[2] - tvz * e1[1], qvy = tvz * e1[0] - tvx * e1[2], qvz = tvx * e1[1] - tvy * e1[0];         // cross(tv, e1)
+  b = (d[0] * qvx + d[1] * qvy + d[2] * qvz) * inv;
+}
+// Steps 2-4 from the barycentrics (the kernels call the two halves one after the other, so that the corner normals are fetched
+// once the triangle's twelve floats are dead).
+PT_MESH_HD void blend_normal(float a, float b, const float* d, const float* ng, const F4* vn, float* ns) {
+  const float c = (1.0f - a) - b;
+  const F4 n0 = vn[0], n1 = vn[1], n2 = vn[2];
+  const float mx = ((c * n0.x) + (a * n1.x)) + (b * n2.x), my = ((c * n0.y) + (a * n1.y)) + (b * n2.y),
+              mz = ((c * n0.z) + (a * n1.z)) + (b * n2.z);
+  const float l2 = mx * mx + my * my + mz * mz;
+  const bool ok = l2 > kSmoothMinLen2;
+  const float inv = 1.0f / sqrtf(ok ? l2 : 1.0f);
+  float x = ok ? mx * inv : ng[0], y = ok ? my * inv : ng[1], z = ok ? mz * inv : ng[2];
+  if (x * ng[0] + y * ng[1] + z * ng[2] < 0.0f) { x = -x; y = -y; z = -z; }
+  const bool drop = (x * d[0] + y * d[1] + z * d[2] > 0.0f) != (ng[0] * d[0] + ng[1] * d[1] + ng[2] * d[2] > 0.0f);
+  ns[0] = drop ? ng[0] : x; ns[1] = drop ? ng[1] : y; ns[2] = drop ? ng[2] : z;
+}
+// Step 6, specular only: v = d - 2 dot(d, n) n was formed with the (flipped) shading normal; if it points into the surface --
+// dot(v, ng_f) <= 0 with ng_f the geometric normal flipped to face the ray -- it is formed again with ng_f in place of n.
+PT_MESH_HD void mirror_guard(const float* d, const float* ng, float* v) {
+  const bool back = ng[0] * d[0] + ng[1] * d[1] + ng[2] * d[2] > 0.0f;
+  const float fx = back ? -ng[0] : ng[0], fy = back ? -ng[1] : ng[1], fz = back ? -ng[2] : ng[2];
+  if (v[0] * fx + v[1] * fy + v[2] * fz <= 0.0f) {
+    const float cost = d[0] * fx + d[1] * fy + d[2] * fz;
+    v[0] = d[0] - fx * (cost * 2.0f); v[1] = d[1] - fy * (cost * 2.0f); v[2] = d[2] - fz * (cost * 2.0f);
+  }
+}
+PT_MESH_HD void shading_normal(const float* o, const float* d, const Tri& T, const float* ng, const F4* vn, float& a, float& b,
+                               float* ns) {
+  tri_bary(o, d, T, a, b);
+  blend_normal(a, b, d, ng, vn, ns);
+}
+
 }  // namespace ptmesh

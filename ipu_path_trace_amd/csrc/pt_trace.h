@@ -77,7 +77,9 @@ static_assert(ptmesh::kEps == kEps, "one intersection epsilon");
 // A mesh row (pt_set_scene_meshes) has no edges of its own: its PolyEdges slot carries, as bit patterns, where its tree and its
 // triangles lie in the arrays below the scene (mesh_nodes, mesh_tris / mesh_orig).  The MESH instances alone read it.
 struct MeshRow {
-  uint32_t node_base, tri_base, n_nodes, n_triangles, unused[2];
+  uint32_t node_base, tri_base, n_nodes, n_triangles;
+  uint32_t smooth;   // the mesh has vertex normals (pt_set_mesh_normals): the SMOOTH instances alone read it
+  uint32_t unused;
 };
 static_assert(sizeof(MeshRow) == sizeof(PolyEdges), "a mesh row travels in its PolyEdges slot");
 constexpr int kHitObjectBits = 5;   // a MESH instance's hit: object | slot << 5 (the slot counts over all meshes: < 2^22)
@@ -136,6 +138,10 @@ struct TraceParams {
   const ptmesh::Node* mesh_nodes;
   const ptmesh::F4* mesh_tris;
   const uint32_t* mesh_orig;
+  // Vertex normals (pt_set_mesh_normals): three vectors per triangle slot (the corner normals in the kernel's frame, .w unused),
+  // indexed by the global slot of a packed hit; read by the SMOOTH instances alone, which are launched only while a mesh in force
+  // has normals.  Last again.
+  const ptmesh::F4* mesh_normals;
 };
 static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
 
@@ -464,10 +470,15 @@ struct HitRow {
   float4 colour;   // r, g, b, bits of (type | is_disc << 8)
 };
 constexpr size_t hit_table_bytes(uint32_t n_objects) { return (size_t)n_objects * sizeof(HitRow); }
+// SMOOTH: a mesh row's centre.w carries the bits of its row's `smooth` flag (MeshRow), so that a lane learns with the row it reads
+// anyway whether the mesh it hit has vertex normals.
+template <bool SMOOTH = false>
 __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab) {
 #pragma unroll 1
   for (int i = 0; i < (int)P.n_objects; ++i) {
-    tab[i].centre = make_float4(P.obj[i].cx, P.obj[i].cy, P.obj[i].cz, 0.f);
+    float flag = 0.f;
+    if constexpr (SMOOTH) { if (P.obj[i].is_disc == SHAPE_MESH) flag = P.poly[i].e2y; }
+    tab[i].centre = make_float4(P.obj[i].cx, P.obj[i].cy, P.obj[i].cz, flag);
     tab[i].normal = make_float4(P.obj[i].nx, P.obj[i].ny, P.obj[i].nz, 0.f);
     tab[i].colour = make_float4(P.obj[i].colr, P.obj[i].colg, P.obj[i].colb,
                                 __uint_as_float((uint32_t)P.obj[i].type | ((uint32_t)P.obj[i].is_disc << 8)));
@@ -478,7 +489,9 @@ __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab
 // are rotated between camera and world space, as in emit_escaped (CAM_LENS: when P.cam_pose says so).
 // PLAMPS: the emitter guide's table may list polygons (pt_set_light_guide_ex; with LIGHTS and POLY alone).
 // MESH: `best` is a packed hit (nearest_hit), and a mesh triangle's normal comes from global memory.
-template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false>
+// SMOOTH (implies MESH): a mesh may have vertex normals (pt_set_mesh_normals); the hit's shading normal replaces the stored one.
+template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false,
+          bool SMOOTH = false>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length);
 
@@ -487,14 +500,14 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
 // Returns the path length (contribution-stack size, codelets.cpp:253) through `length` when the
 // path ends.
 template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false,
-          bool POLY = false, bool PLAMPS = false, bool MESH = false>
+          bool POLY = false, bool PLAMPS = false, bool MESH = false, bool SMOOTH = false>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length);
 #ifdef PTMI_DIAG_BUILD
 __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3 d, float& tbest);
 __device__ __forceinline__ int shade_hit_r3(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                             const uint32_t (&w)[4], float rr, uint32_t& length);
 #endif
-template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH>
+template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH, bool SMOOTH>
 __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length) {
   uint32_t w[4];
   philox4x32_10(s.pixel, s.sample, 1u + s.depth, 0x5054u, P.seed_lo, P.seed_hi, w);
@@ -526,7 +539,7 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
 #ifdef PTMI_DIAG_BUILD
   if constexpr (LEGACY) return shade_hit_r3(P, tab, s, best, tbest, w, rr, length);
 #endif
-  return shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH>(P, tab, s, best, tbest, w, rr, length);
+  return shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, tab, s, best, tbest, w, rr, length);
 }
 
 // The basis of light::diffuse (codelets.cpp:199-204) about a unit vector n: rx, ry with (rx, ry, n) orthonormal.  Its branch as
@@ -559,7 +572,7 @@ namespace ptd {
 
 // The second half of a loop trip of RayTraceKernel::compute (codelets.cpp:192-216): the ray has hit object `best` at
 // distance `tbest`; w = the bounce's Philox block, rr = its roulette weight.
-template <bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH>
+template <bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH, bool SMOOTH>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int packed, float tbest,
                                          const uint32_t (&w)[4], float rr, uint32_t& length) {
   // the hit object's row, by per-lane index
@@ -577,11 +590,35 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
     length = s.depth + 1u;
     return STEP_EMITTED;
   }
+  static_assert(MESH || !SMOOTH, "SMOOTH implies MESH");
   Vec3 hp = add(s.o, scale(s.d, tbest));
+  [[maybe_unused]] const Vec3 o0 = s.o;   // (SMOOTH: the barycentrics are formed from the ray that hit)
   s.o = hp;
   Vec3 n = is_disc ? mk(nx, ny, nz) : normalise(sub(hp, mk(cx, cy, cz)));
+  [[maybe_unused]] bool smooth = false;   // the hit is on a mesh with vertex normals: n is a shading normal
   if constexpr (MESH) {   // a mesh triangle's stored normal: the last three floats of its third vector, one 16-byte load per mesh hit
-    if (is_disc == SHAPE_MESH) { const ptmesh::F4 tn = P.mesh_tris[3u * (size_t)hit_slot(packed) + 2u]; n = mk(tn.y, tn.z, tn.w); }
+    if (is_disc == SHAPE_MESH) {
+      const ptmesh::F4* const tri = P.mesh_tris + 3u * (size_t)hit_slot(packed);
+      if (SMOOTH && __float_as_uint(hc.w) != 0u) {
+        // pt_set_mesh_normals: the shading normal (pt_mesh.h), rules 1-4; the flat mesh beside it takes the branch below.  The
+        // barycentrics first, from the ray that hit; the corner normals are asked for once the triangle's floats are dead.
+        if constexpr (SMOOTH) {
+          smooth = true;
+          const float ov[3] = {o0.x, o0.y, o0.z}, dv[3] = {s.d.x, s.d.y, s.d.z};
+          const ptmesh::F4 t2 = tri[2];
+          float a, b, ns[3];
+          { const ptmesh::F4 t0 = tri[0], t1 = tri[1];
+            ptmesh::tri_bary(ov, dv, ptmesh::Tri{{t0.x, t0.y, t0.z}, {t0.w, t1.x, t1.y}, {t1.z, t1.w, t2.x}}, a, b); }
+          __builtin_amdgcn_sched_barrier(0);
+          const float ng[3] = {t2.y, t2.z, t2.w};
+          ptmesh::blend_normal(a, b, dv, ng, P.mesh_normals + 3u * (size_t)hit_slot(packed), ns);
+          n = mk(ns[0], ns[1], ns[2]);
+        }
+      } else {
+        const ptmesh::F4 tn = tri[2];
+        n = mk(tn.y, tn.z, tn.w);
+      }
+    }
   }
   if constexpr (POLY) {   // a polygon is two-sided: its stored normal faces the ray (the refractive branch flips the normal itself)
     if (is_disc >= SHAPE_TRIANGLE && type != MAT_REFRACTIVE && dot(n, s.d) > 0.0f) n = scale(n, -1.0f);
@@ -663,6 +700,15 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
     if (type == MAT_SPECULAR) {
       float cost = dot(s.d, n);
       v = sub(s.d, scale(n, cost * 2.0f));
+      if constexpr (SMOOTH) {   // a mirror never reflects into its own surface: against the geometric normal, facing the ray, then
+        if (smooth) {           // (its vector is loaded again: not kept alive across the branches above)
+          const ptmesh::F4 tn = P.mesh_tris[3u * (size_t)hit_slot(packed) + 2u];
+          const float dv[3] = {s.d.x, s.d.y, s.d.z}, ng[3] = {tn.y, tn.z, tn.w};
+          float vv[3] = {v.x, v.y, v.z};
+          ptmesh::mirror_guard(dv, ng, vv);
+          v = mk(vv[0], vv[1], vv[2]);
+        }
+      }
     } else {
       float u = uniform01(w[1], P.samples_half);
       float nn = P.ri;
@@ -772,7 +818,7 @@ namespace ptd {
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
 template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false, bool POLY = false,
-          bool PLAMPS = false, bool MESH = false>
+          bool PLAMPS = false, bool MESH = false, bool SMOOTH = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
@@ -780,7 +826,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   __shared__ uint32_t wg_state;            // survivors still alive after their first shading
   extern __shared__ __attribute__((aligned(16))) char smem[];
   HitRow* const hit_table = reinterpret_cast<HitRow*>(smem);   // P.n_objects rows (dynamic LDS: hit_table_bytes)
-  if (threadIdx.x == 0) { wg_count = 0; wg_front = 0; wg_back = 0; wg_state = 0; fill_hit_table(P, hit_table); }
+  if (threadIdx.x == 0) { wg_count = 0; wg_front = 0; wg_back = 0; wg_state = 0; fill_hit_table<SMOOTH>(P, hit_table); }
   __syncthreads();
 
   const uint32_t lane = threadIdx.x & 63u;
@@ -893,7 +939,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if constexpr ((OPT & 64) != 0) res = shade_hit_r3(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       else
 #endif
-      res = shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
+      res = shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       if (res == STEP_CONTINUE) alive = true;
       else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full (guided: or the guide pointed below the surface)
       // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
@@ -965,7 +1011,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     int res = STEP_CONTINUE;
     uint32_t length = 0;
-    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH>(P, hit_table, st, length);
+    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, hit_table, st, length);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
     const bool emitted = active && res == STEP_EMITTED;
@@ -1038,6 +1084,23 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true>(P); }
+// pt_set_mesh_normals: the twelve mesh instances again with the shading normal (SMOOTH), launched only while a mesh in force has
+// vertex normals.  A flat mesh beside a smooth one takes none of the new steps (its row's flag).  The plain three are held to
+// five waves per SIMD, where their MESH twins sit at 94 VGPRs: left alone the allocator takes 99 and four waves; held, 93, no VGPR
+// spilled and no scratch access the twins do not have.  The env-guided three stay at four waves like their twins (107 against
+// 102 VGPRs); the emitter-guided six are pinned to six as everywhere.  Resource rows: profiles/r24_mesh_normals.txt.
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void trace_kernel_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void trace_kernel_pose_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void trace_kernel_lens_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, false, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true, true>(P); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true, true>(P); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -1050,12 +1113,12 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
 
 // One thread per requested path; same device functions as trace_kernel.  GUIDE: the guided twin (the camera is read at run
 // time either way: CAM_LENS rotates when P.cam_pose says so).  LIGHTS: the emitter-guided twin.
-template <bool GUIDE, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false>
+template <bool GUIDE, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false, bool SMOOTH = false>
 __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                  uint32_t n, PathRecordOut* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   HitRow* const hit_table = reinterpret_cast<HitRow*>(smem);   // P.n_objects rows (dynamic LDS)
-  if (threadIdx.x == 0) fill_hit_table(P, hit_table);
+  if (threadIdx.x == 0) fill_hit_table<SMOOTH>(P, hit_table);
   __syncthreads();
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1065,7 +1128,7 @@ __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uin
   if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
-  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY, PLAMPS, MESH>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
+  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
@@ -1102,6 +1165,16 @@ __global__ void trace_paths_lights_mesh_kernel(const TraceParams P, const uint16
 __global__ void trace_paths_lights_plamps_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                       uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true>(P, u, v, sample, n, out); }
 
+// pt_set_mesh_normals: the smooth twins of the four above
+__global__ void trace_paths_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                          uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true, false, true, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_guide_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                                uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true, false, true, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_lights_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                                 uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, false, true, true>(P, u, v, sample, n, out); }
+__global__ void trace_paths_lights_plamps_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                                        uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true, true>(P, u, v, sample, n, out); }
+
 // pt_mesh_intersect: the MESH instances' own nearest hit over caller rays, one thread per ray (the scene in the kernel arguments
 // is the world table).  BRUTE: a loop over all triangles of each mesh in place of the walk.
 template <bool BRUTE>
@@ -1121,5 +1194,34 @@ __global__ void mesh_intersect_kernel(const TraceParams P, const float* origin, 
                                       int32_t* out_object, int32_t* out_triangle) { mesh_intersect_body<false>(P, origin, dir, n, out_t, out_object, out_triangle); }
 __global__ void mesh_intersect_brute_kernel(const TraceParams P, const float* origin, const float* dir, uint32_t n, float* out_t,
                                             int32_t* out_object, int32_t* out_triangle) { mesh_intersect_body<true>(P, origin, dir, n, out_t, out_object, out_triangle); }
+
+// pt_mesh_shade: the SMOOTH instances' own nearest hit and shading normal over caller rays, one thread per ray (the world table).
+// out_normal: n as the bounce forms it for a two-sided surface -- the shading normal of a mesh with normals (pt_mesh.h), the stored
+// normal of a flat one, flipped to face the ray; zero, like out_bary, for a miss or a hit on anything but a mesh triangle.
+__global__ void mesh_shade_kernel(const TraceParams P, const float* origin, const float* dir, uint32_t n, float* out_t,
+                                  int32_t* out_object, int32_t* out_triangle, float* out_bary, float* out_normal) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float ov[3] = {origin[3 * i], origin[3 * i + 1], origin[3 * i + 2]}, dv[3] = {dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
+  float tbest;
+  const int best = nearest_hit<false, true, true, false>(P, mk(ov[0], ov[1], ov[2]), mk(dv[0], dv[1], dv[2]), tbest);
+  const int obj = best < 0 ? -1 : hit_object<true>(best);
+  const bool mesh = obj >= 0 && P.obj[obj].is_disc == SHAPE_MESH;
+  float a = 0.f, b = 0.f, ns[3] = {0.f, 0.f, 0.f};
+  if (mesh) {
+    const size_t slot = (size_t)hit_slot(best);
+    const ptmesh::F4 tn = P.mesh_tris[3u * slot + 2u];
+    const float ng[3] = {tn.y, tn.z, tn.w};
+    const ptmesh::Tri T = ptmesh::load_tri(P.mesh_tris + 3u * slot);
+    if (__float_as_uint(P.poly[obj].e2y) != 0u) ptmesh::shading_normal(ov, dv, T, ng, P.mesh_normals + 3u * slot, a, b, ns);
+    else { ptmesh::tri_bary(ov, dv, T, a, b); ns[0] = ng[0]; ns[1] = ng[1]; ns[2] = ng[2]; }
+    if (ptmesh::dot3(ns, dv) > 0.0f) { ns[0] = -ns[0]; ns[1] = -ns[1]; ns[2] = -ns[2]; }
+  }
+  out_t[i] = best < 0 ? 0.f : tbest;
+  out_object[i] = obj;
+  out_triangle[i] = mesh ? (int32_t)P.mesh_orig[hit_slot(best)] : -1;
+  out_bary[2 * i] = a; out_bary[2 * i + 1] = b;
+  out_normal[3 * i] = ns[0]; out_normal[3 * i + 1] = ns[1]; out_normal[3 * i + 2] = ns[2];
+}
 
 }  // namespace ptd

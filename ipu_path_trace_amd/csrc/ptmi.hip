@@ -537,6 +537,15 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
         if (P.lights.n && h->light.polygons)
           kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_mesh : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_mesh : ptd::trace_kernel_lights_plamps_mesh);
       }
+      if (h->scene_n && h->scene_mesh && h->mesh.smooth()) {   // a mesh in force has vertex normals (pt_set_mesh_normals): the smooth twin of each of the twelve
+        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_smooth : (P.cam_pose ? ptd::trace_kernel_pose_smooth : ptd::trace_kernel_smooth);
+        if (h->guide_set)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_smooth : (P.cam_pose ? ptd::trace_kernel_pose_guide_smooth : ptd::trace_kernel_guide_smooth);
+        if (P.lights.n)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_smooth : (P.cam_pose ? ptd::trace_kernel_pose_lights_smooth : ptd::trace_kernel_lights_smooth);
+        if (P.lights.n && h->light.polygons)
+          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_smooth : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_smooth : ptd::trace_kernel_lights_plamps_smooth);
+      }
       hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
     PT_HIP(hipGetLastError());
@@ -1434,6 +1443,8 @@ int pt_set_scene_meshes(pt_handle h, const pt_scene_object_ex* objects, uint32_t
     pt_context::MeshSet::One one{};
     one.object_index = i;
     one.n_triangles = meshes[m].n_triangles;
+    one.n_vertices = meshes[m].n_vertices;
+    M.indices.insert(M.indices.end(), meshes[m].indices, meshes[m].indices + 3 * (size_t)meshes[m].n_triangles);
     one.tri_base = (uint32_t)triangles;
     one.node_base = (uint32_t)nodes;
     ptmesh::world_frames(meshes[m], M.world);
@@ -1516,6 +1527,86 @@ int pt_mesh_intersect(pt_handle h, const float* origin, const float* dir, size_t
   });
 }
 
+// Vertex normals of mesh `mesh` of the scene in force.  Checked and copied on the host, and the device buffer allocated, before
+// anything of the mesh changes; the trees are then marked stale, so that the next call that traces re-expands the normals into the
+// slot order of the frame it traces in (build_meshes), exactly as after a pose change.
+int pt_set_mesh_normals(pt_handle h, uint32_t mesh, const float* normals, uint32_t n_normals, const uint32_t* normal_indices) {
+  if (!h) { g_create_error = "pt_set_mesh_normals: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
+  if (mesh >= count)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_mesh_normals: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
+  pt_context::MeshSet& M = h->mesh;
+  pt_context::MeshSet::One& m = M.mesh[mesh];
+  try {
+  if (!normals && n_normals == 0 && !normal_indices) {   // remove: the mesh is flat again
+    if (m.normals.empty()) return PT_OK;
+    std::vector<float>().swap(m.normals);
+    m.n_normals = 0; m.per_corner = false;
+  } else {
+    const std::string bad = ptmesh::check_normals(mesh, m.n_vertices, m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, normals,
+                                                  n_normals, normal_indices);
+    if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the mesh keeps what it had
+    std::vector<float> corner;
+    ptmesh::corner_normals(m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, normals, normal_indices, corner);
+    if (!M.d_normals) {
+      PT_HIP(hipSetDevice(h->cfg.device));
+      size_t triangles = 0;
+      for (const pt_context::MeshSet::One& o : M.mesh) triangles += o.n_triangles;
+      const hipError_t e = dev_alloc(M.d_normals, 3 * triangles);
+      if (e != hipSuccess)
+        return fail(h, hip_status(e), "pt_set_mesh_normals: allocating " + std::to_string(3 * triangles * sizeof(ptmesh::F4)) + " bytes: " + hipGetErrorString(e));
+    }
+    m.normals.swap(corner);
+    m.n_normals = n_normals; m.per_corner = normal_indices != nullptr;
+  }
+  } catch (const std::bad_alloc&) {
+    return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_mesh_normals: out of host memory for the normals' copy");
+  }
+  M.built = false;        // the next trace rebuilds: rows' flags and the normals in slot order
+  h->feature_gen += 1;
+  return PT_OK;
+}
+
+int pt_get_mesh_normals_info(pt_handle h, uint32_t mesh, pt_mesh_normals_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_mesh_normals_info))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_normals_info: struct_size must be " + std::to_string(sizeof(pt_mesh_normals_info)));
+  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
+  if (mesh >= count)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_normals_info: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
+  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->has_normals = m.normals.empty() ? 0u : 1u;
+  out->per_corner = m.per_corner ? 1u : 0u;
+  out->n_normals = m.n_normals;
+  out->device_bytes = m.normals.empty() ? 0u : (uint64_t)m.n_triangles * 3 * sizeof(ptmesh::F4);
+  return PT_OK;
+}
+
+int pt_mesh_shade(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object, int32_t* out_triangle,
+                  float* out_bary, float* out_normal) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_shade: the scene in force holds no mesh (pt_set_scene_meshes)");
+  if (n == 0) return PT_OK;
+  if (!origin || !dir || !out_t || !out_object || !out_triangle || !out_bary || !out_normal) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31) / 3) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many rays");
+  if (int rc = ensure_meshes(h, true)) return rc;   // the world frame, whatever the camera
+  ptd::TraceParams P;
+  memset(&P, 0, sizeof(P));
+  fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->mesh.row);
+  bind_meshes(h, P);
+  GuideSpan s[7] = {{origin, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr}, {nullptr, out_t, n * 4, nullptr},
+                    {nullptr, out_object, n * 4, nullptr}, {nullptr, out_triangle, n * 4, nullptr}, {nullptr, out_bary, n * 8, nullptr},
+                    {nullptr, out_normal, n * 12, nullptr}};
+  return guide_hook(h, s, 7, [&]() {
+    hipLaunchKernelGGL(ptd::mesh_shade_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
+                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev), (uint32_t)n,
+                       reinterpret_cast<float*>(s[2].dev), reinterpret_cast<int32_t*>(s[3].dev), reinterpret_cast<int32_t*>(s[4].dev),
+                       reinterpret_cast<float*>(s[5].dev), reinterpret_cast<float*>(s[6].dev));
+  });
+}
+
 int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uint32_t* n) {
   if (!n) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "null count") : PT_ERR_INVALID_ARGUMENT;
   pt_scene_object builtin[ptd::kBuiltinObjects];
@@ -1583,6 +1674,9 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   if (h->scene_n && h->scene_mesh)   // the mesh twins (pt_set_scene_meshes)
     kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_mesh_kernel : ptd::trace_paths_lights_mesh_kernel)
                         : (h->guide_set ? ptd::trace_paths_guide_mesh_kernel : ptd::trace_paths_mesh_kernel);
+  if (h->scene_n && h->scene_mesh && h->mesh.smooth())   // the smooth twins (pt_set_mesh_normals)
+    kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_smooth_kernel : ptd::trace_paths_lights_smooth_kernel)
+                        : (h->guide_set ? ptd::trace_paths_guide_smooth_kernel : ptd::trace_paths_smooth_kernel);
   hipLaunchKernelGGL(kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
                      ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());

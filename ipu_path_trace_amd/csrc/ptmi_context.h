@@ -202,12 +202,19 @@ struct pt_context {
       uint32_t object_index, n_triangles, tri_base, node_base, n_nodes, max_leaf, depth;
       float pad;
       double build_ms;
+      // vertex normals (pt_set_mesh_normals): the world normals per corner in triangle order, nine floats per triangle; empty: flat
+      uint32_t n_vertices, n_normals;
+      bool per_corner;
+      std::vector<float> normals;
     };
     std::vector<One> mesh;                 // in declaration order
     std::vector<float> world;              // twelve floats per triangle (v0, e1, e2, n), the meshes one after the other
     DevBuf<ptmesh::Node> d_nodes;          // mesh m at node_base = sum over the meshes before it of 2 T - 1
     DevBuf<ptmesh::F4> d_tris;             // three per slot, mesh m's slots from tri_base
     DevBuf<uint32_t> d_orig;               // slot -> triangle index in its mesh
+    std::vector<uint32_t> indices;         // the meshes' own [n_triangles][3], one after the other: per-vertex normals are looked up by them
+    DevBuf<ptmesh::F4> d_normals;          // three per slot over ALL slots, allocated by the first pt_set_mesh_normals of the scene
+    bool smooth() const { for (const One& m : mesh) if (!m.normals.empty()) return true; return false; }
     ptd::PolyEdges row[PT_MAX_SCENE_OBJECTS] = {};   // what a mesh's row carries in the kernel arguments (ptd::MeshRow)
     bool built = false, built_world = false;         // the trees on the device are valid / were built in the world frame ...
     ptcamera::Basis built_for{};                     // ... or for this camera
@@ -473,6 +480,7 @@ void bind_meshes(pt_handle h, ptd::TraceParams& P) {
   P.mesh_nodes = h->mesh.d_nodes;
   P.mesh_tris = h->mesh.d_tris;
   P.mesh_orig = h->mesh.d_orig;
+  P.mesh_normals = h->mesh.d_normals;
 }
 
 // Transforms every mesh of M into the frame of `cam` (nullptr: the world frame, which is the built-in camera's), builds its tree
@@ -485,6 +493,7 @@ int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam
       if (s) PT_HIP(hipStreamSynchronize(s));
   M.built = false;
   std::vector<float> frames;
+  std::vector<ptmesh::F4> normals;
   ptmesh::Built B;
   for (pt_context::MeshSet::One& m : M.mesh) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -499,7 +508,12 @@ int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam
     PT_HIP(hipMemcpy(M.d_nodes + m.node_base, B.nodes.data(), B.nodes.size() * sizeof(ptmesh::Node), hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(M.d_tris + 3 * (size_t)m.tri_base, B.tris.data(), B.tris.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(M.d_orig + m.tri_base, B.orig.data(), B.orig.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    const ptd::MeshRow row{m.node_base, m.tri_base, m.n_nodes, m.n_triangles, {0u, 0u}};
+    if (!m.normals.empty()) {   // the corner normals into the new slot order (the buffer exists: pt_set_mesh_normals)
+      normals.resize(3 * (size_t)m.n_triangles);
+      ptmesh::slot_normals(m.normals.data(), B.orig.data(), m.n_triangles, cam, normals.data());
+      PT_HIP(hipMemcpy(M.d_normals + 3 * (size_t)m.tri_base, normals.data(), normals.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
+    }
+    const ptd::MeshRow row{m.node_base, m.tri_base, m.n_nodes, m.n_triangles, m.normals.empty() ? 0u : 1u, 0u};
     memcpy(&M.row[m.object_index], &row, sizeof(row));
   }
   M.built = true;

@@ -83,6 +83,60 @@ inline std::string check(const pt_scene_object_ex* objs, uint32_t n, uint32_t st
   return "";
 }
 
+// ---- vertex normals (pt_set_mesh_normals, include/ptmi.h)
+
+// The checks of pt_set_mesh_normals that need no device, in the contract's order; "" if the normals are valid.  indices: the
+// mesh's own [n_triangles][3] (used when normal_indices is null: per-vertex normals).  Only referenced normals are examined.
+inline std::string check_normals(uint32_t mesh, uint32_t n_vertices, uint32_t n_triangles, const uint32_t* indices, const float* normals,
+                                 uint32_t n_normals, const uint32_t* normal_indices) {
+  const std::string at = "mesh " + std::to_string(mesh) + ": ";
+  if (!normals) return at + "null normals with n_normals = " + std::to_string(n_normals);
+  if (!normal_indices && n_normals != n_vertices)
+    return at + "n_normals must equal n_vertices = " + std::to_string(n_vertices) + " when normal_indices is null (got " + std::to_string(n_normals) + ")";
+  const uint32_t* ix = normal_indices ? normal_indices : indices;
+  for (uint32_t j = 0; j < n_triangles; ++j)
+    for (int c = 0; c < 3; ++c) {
+      const std::string tri = at + "triangle " + std::to_string(j) + ": ";
+      const uint32_t k = ix[3 * (size_t)j + c];
+      if (k >= n_normals)
+        return tri + (normal_indices ? "normal_indices[" : "indices[") + std::to_string(c) + "] must be < n_normals = " + std::to_string(n_normals) + " (got " + std::to_string(k) + ")";
+      const float* v = normals + 3 * (size_t)k;
+      for (int q = 0; q < 3; ++q)
+        if (!std::isfinite(v[q])) return tri + "normals[" + std::to_string(k) + "] must be finite (got " + ptscene::num(v[q]) + ")";
+      volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
+      volatile float d0 = xx + yy, d1 = d0 + zz;
+      if (!(d1 > 0.f) || !std::isfinite(d1)) return tri + "normals[" + std::to_string(k) + "] must have a finite dot(n, n) > 0 (got " + ptscene::num(d1) + ")";
+    }
+  return "";
+}
+
+// The world normals per corner in triangle order, nine floats per triangle: each n / sqrtf(dot(n, n)) by a disc normal's
+// expressions (ptscene::normalise).  Call on normals check_normals() accepted.
+inline void corner_normals(uint32_t n_triangles, const uint32_t* indices, const float* normals, const uint32_t* normal_indices,
+                           std::vector<float>& out) {
+  const uint32_t* ix = normal_indices ? normal_indices : indices;
+  out.resize(9 * (size_t)n_triangles);
+  for (size_t e = 0; e < 3 * (size_t)n_triangles; ++e) {
+    const float* v = normals + 3 * (size_t)ix[e];
+    volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
+    volatile float d0 = xx + yy, d1 = d0 + zz;
+    volatile float len = sqrtf(d1);
+    for (int k = 0; k < 3; ++k) out[3 * e + k] = v[k] / len;
+  }
+}
+
+// The corner normals as the kernel reads them: three vectors per slot in leaf order (orig: slot -> triangle), each a direction
+// through the camera's transform from its world value (cam == nullptr: the world value as it is).
+inline void slot_normals(const float* corner, const uint32_t* orig, size_t n_triangles, const ptcamera::Basis* cam, F4* out) {
+  for (size_t s = 0; s < n_triangles; ++s)
+    for (int c = 0; c < 3; ++c) {
+      const float* w = corner + 9 * (size_t)orig[s] + 3 * c;
+      float o[3] = {w[0], w[1], w[2]};
+      if (cam) ptcamera::to_camera_direction(*cam, w, o);
+      out[3 * s + c] = F4{o[0], o[1], o[2], 0.f};
+    }
+}
+
 // ---- frames: twelve floats per triangle, v0, e1, e2, n
 
 constexpr size_t kFrameFloats = 12;

@@ -96,7 +96,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
-      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}; a \"triangle\" or \"parallelogram\" takes \"vertices\": [[x, y, z], [x, y, z], [x, y, z]] (v0, v1, v2; the parallelogram's fourth corner is v1 + v2 - v0) instead of centre, radius and normal; a \"mesh\" (one object of the table, one material, flat shading) takes either \"vertices\": [[x, y, z], ...] and \"triangles\": [[a, b, c], ...] (indices from 0) or \"file\": \"x.obj\" (relative to the scene file; v and f lines, faces triangulated as fans), and optionally \"scale\": s or [sx, sy, sz] and \"translate\": [x, y, z], applied in binary32 on the host as v * scale + translate before anything else.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
+      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}; a \"triangle\" or \"parallelogram\" takes \"vertices\": [[x, y, z], [x, y, z], [x, y, z]] (v0, v1, v2; the parallelogram's fourth corner is v1 + v2 - v0) instead of centre, radius and normal; a \"mesh\" (one object of the table, one material, flat shading unless \"normals\" is given) takes either \"vertices\": [[x, y, z], ...] and \"triangles\": [[a, b, c], ...] (indices from 0) or \"file\": \"x.obj\" (relative to the scene file; v and f lines, faces triangulated as fans), and optionally \"scale\": s or [sx, sy, sz] and \"translate\": [x, y, z], applied in binary32 on the host as v * scale + translate before anything else; \"normals\": \"file\" (the OBJ's vn lines and v//vn or v/vt/vn corners) or \"normals\": [[x, y, z], ...] with an optional \"normal_indices\": [[a, b, c], ...] per triangle (else one normal per vertex) shades the mesh smooth; normals are not scaled, so a non-uniform \"scale\" is refused with them.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
       {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
       {"env-guide", 0, "", false, false, "FILE | map | env: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map; 'env' needs no file: the guide is built on the device from the environment in force -- the NIF of --assets, the map or the constant -- and follows a NIF loaded later). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
@@ -162,6 +162,8 @@ std::uint64_t nifMemoBytes(const std::string& text) {
 // `camera` receives the file's optional top-level "camera" (every key optional, defaults of pt_camera), checked like the table.
 // A "triangle" or "parallelogram" takes "vertices": [[..], [..], [..]] instead of centre / radius / normal; a file that holds one is
 // checked as pt_set_scene_ex checks it and leaves its table in `ex` (empty otherwise: the file goes through pt_set_scene as ever).
+// A "mesh" also takes "normals" -- "file" (the OBJ's vn lines and corner indices) or an inline array of directions with an optional
+// "normal_indices", one triple per triangle -- and then shades smooth (pt_set_mesh_normals); without the key it stays flat.
 // A "mesh" takes inline "vertices" / "triangles" or "file": "x.obj" (relative to the scene file), and optionally "scale" and
 // "translate", applied here in binary32 -- v * scale, then + translate, one rounded operation each -- before anything else; a
 // file that holds one is checked as pt_set_scene_meshes checks it and leaves its geometry in `meshes`, in the order of its rows.
@@ -204,7 +206,7 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     for (const auto& kv : v.obj)
       if (kv.first != "shape" && kv.first != "material" && kv.first != "centre" && kv.first != "radius" && kv.first != "normal" &&
           kv.first != "colour" && kv.first != "emission" && kv.first != "vertices" && kv.first != "triangles" && kv.first != "file" &&
-          kv.first != "scale" && kv.first != "translate")
+          kv.first != "scale" && kv.first != "translate" && kv.first != "normals" && kv.first != "normal_indices")
         throw std::runtime_error(at + obj + "unknown key \"" + kv.first + "\"");
     pt_scene_object& o = objs[i];
     o = pt_scene_object{};
@@ -225,7 +227,7 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     pt_scene_object_ex& x = objsEx[i];
     x = pt_scene_object_ex{};
     if (!mesh)
-      for (const char* key : {"triangles", "file", "scale", "translate"})
+      for (const char* key : {"triangles", "file", "scale", "translate", "normals", "normal_indices"})
         if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a " + shape);
     if (mesh) {
       for (const char* key : {"centre", "radius", "normal"})
@@ -237,7 +239,11 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
         const std::string& name = v.at("file").str;
         const std::size_t slash = path.find_last_of('/');
         const std::string full = (!name.empty() && name[0] == '/') || slash == std::string::npos ? name : path.substr(0, slash + 1) + name;
-        try { m = objreader::read(full); } catch (const std::exception& e) { throw std::runtime_error(at + obj + e.what()); }
+        // "normals": "file" takes the OBJ's vn lines and its corners' normal indices (smooth shading: pt_set_mesh_normals)
+        const bool fromFile = v.has("normals") && v.at("normals").type == json::Value::String;
+        if (fromFile && v.at("normals").str != "file") throw std::runtime_error(at + obj + "\"normals\" must be \"file\" or an array of directions");
+        if (fromFile && v.has("normal_indices")) throw std::runtime_error(at + obj + "\"normal_indices\" does not apply to \"normals\": \"file\"");
+        try { m = objreader::read(full, fromFile); } catch (const std::exception& e) { throw std::runtime_error(at + obj + e.what()); }
       } else {
         if (!v.has("vertices") || !v.has("triangles")) throw std::runtime_error(at + obj + "a mesh needs \"file\", or \"vertices\" and \"triangles\"");
         const json::Value& vs = v.at("vertices");
@@ -260,12 +266,41 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
           }
         }
       }
+      if (v.has("normals") && v.at("normals").type == json::Value::String) {
+        if (!v.has("file")) throw std::runtime_error(at + obj + "\"normals\": \"file\" needs \"file\"");
+      } else if (v.has("normals")) {   // inline: directions, and optionally an index triple per triangle (else one normal per vertex)
+        const json::Value& ns = v.at("normals");
+        if (ns.type != json::Value::Array || ns.arr.empty()) throw std::runtime_error(at + obj + "\"normals\" must be \"file\" or a non-empty array of directions");
+        for (const json::Value& q : ns.arr) {
+          if (q.type != json::Value::Array || q.arr.size() != 3) throw std::runtime_error(at + obj + "\"normals\" must hold arrays of 3 numbers");
+          for (const json::Value& c : q.arr) {
+            if (c.type != json::Value::Number) throw std::runtime_error(at + obj + "\"normals\" must hold numbers");
+            m.normals.push_back((float)c.num);
+          }
+        }
+        if (v.has("normal_indices")) {
+          const json::Value& is = v.at("normal_indices");
+          if (is.type != json::Value::Array || is.arr.size() != m.indices.size() / 3)
+            throw std::runtime_error(at + obj + "\"normal_indices\" must hold one index triple per triangle");
+          for (const json::Value& q : is.arr) {
+            if (q.type != json::Value::Array || q.arr.size() != 3) throw std::runtime_error(at + obj + "\"normal_indices\" must hold arrays of 3 indices");
+            for (const json::Value& c : q.arr) {
+              if (c.type != json::Value::Number || !(c.num >= 0.0) || c.num > 4294967295.0 || c.num != std::floor(c.num))
+                throw std::runtime_error(at + obj + "\"normal_indices\" must hold non-negative integers");
+              m.normal_indices.push_back((std::uint32_t)c.num);
+            }
+          }
+        }
+      } else if (v.has("normal_indices")) throw std::runtime_error(at + obj + "\"normal_indices\" needs \"normals\"");
       float scale[3] = {1.f, 1.f, 1.f}, translate[3] = {0.f, 0.f, 0.f};
       if (v.has("scale")) {
         if (v.at("scale").type == json::Value::Number) scale[0] = scale[1] = scale[2] = (float)v.at("scale").num;
         else numbers("scale", scale, 3);
       }
       if (v.has("translate")) numbers("translate", translate, 3);
+      // "scale" applies to positions only: under a non-uniform one a normal would need the inverse transpose, which is not built
+      if (!m.normals.empty() && (scale[0] != scale[1] || scale[1] != scale[2]))
+        throw std::runtime_error(at + obj + "a non-uniform \"scale\" cannot be combined with \"normals\" (normals are not transformed)");
       if (v.has("scale") || v.has("translate"))
         for (std::size_t k = 0; k < m.vertices.size(); ++k) {
           volatile float scaled = m.vertices[k] * scale[k % 3];
@@ -313,6 +348,14 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
                           : anyPolygon ? ptscene::check_ex(objsEx.data(), (std::uint32_t)objsEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex))
                                      : ptscene::check(objs.data(), (std::uint32_t)objs.size());
   if (!bad.empty()) throw std::runtime_error(at + bad);
+  for (std::size_t k = 0; k < meshes.size(); ++k) {   // the normals, as pt_set_mesh_normals checks them, before a device is attached
+    const objreader::Mesh& m = meshes[k];
+    if (m.normals.empty()) continue;
+    const std::string badn = ptmesh::check_normals((std::uint32_t)k, (std::uint32_t)(m.vertices.size() / 3), (std::uint32_t)(m.indices.size() / 3),
+                                                   m.indices.data(), m.normals.data(), (std::uint32_t)(m.normals.size() / 3),
+                                                   m.normal_indices.empty() ? nullptr : m.normal_indices.data());
+    if (!badn.empty()) throw std::runtime_error(at + badn);
+  }
   ex.clear();
   if (anyPolygon) ex = objsEx;
   camera = ptcamera::default_camera();
@@ -609,6 +652,12 @@ void PathTracerApp::attach() {
       if (pt_set_scene_meshes(h, sceneEx.data(), (std::uint32_t)sceneEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex), views.data(),
                               (std::uint32_t)views.size()))
         throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
+      for (std::size_t k = 0; k < sceneMeshes.size(); ++k) {   // a mesh with "normals" shades smooth
+        const objreader::Mesh& m = sceneMeshes[k];
+        if (!m.normals.empty() && pt_set_mesh_normals(h, (std::uint32_t)k, m.normals.data(), (std::uint32_t)(m.normals.size() / 3),
+                                                     m.normal_indices.empty() ? nullptr : m.normal_indices.data()))
+          throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
+      }
     } else if (!sceneEx.empty()) {   // the file holds a polygon
       if (pt_set_scene_ex(h, sceneEx.data(), (std::uint32_t)sceneEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex)))
         throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));

@@ -52,7 +52,8 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_nif_train_get_precision_state", "pt_set_env_guide", "pt_env_guide_sample", "pt_env_guide_eval",
            "pt_set_light_guide", "pt_set_light_guide_ex", "pt_get_light_guide_flags", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
            "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
-           "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect"]
+           "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect", "pt_set_mesh_normals",
+           "pt_get_mesh_normals_info", "pt_mesh_shade"]
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
@@ -285,7 +286,7 @@ def scene_meshes(objects):
         if not _is_mesh_shape(o["shape"]):
             rows.append(o)
             continue
-        unknown = set(o) - {"shape", "material", "vertices", "triangles", "colour", "emission"}
+        unknown = set(o) - {"shape", "material", "vertices", "triangles", "colour", "emission", "normals", "normal_indices"}
         if unknown:
             raise ValueError("scene object %d: unknown key(s) %s" % (i, sorted(unknown)))
         vertices = np.ascontiguousarray(o["vertices"], dtype=np.float32)
@@ -304,6 +305,49 @@ def scene_meshes(objects):
         if _is_mesh_shape(o["shape"]):
             table[i]["shape"] = SHAPE_MESH
     return table, meshes
+
+
+def mesh_normals(objects):
+    """[(k, normals, normal_indices or None)] for the meshes of a list of dicts that carry "normals" (N, 3), optionally with
+    "normal_indices" (T, 3): k counts the mesh rows in order, as pt_set_mesh_normals does."""
+    out, k = [], 0
+    for i, o in enumerate(objects):
+        if not _is_mesh_shape(o["shape"]):
+            continue
+        if o.get("normals") is not None:
+            out.append((k, o["normals"], o.get("normal_indices")))
+        elif o.get("normal_indices") is not None:
+            raise ValueError("scene object %d: normal_indices without normals" % i)
+        k += 1
+    return out
+
+
+def vertex_normals(vertices, triangles):
+    """Angle-weighted vertex normals of a mesh that comes without any: for every vertex the sum over its triangles of the
+    triangle's unit normal times the corner's angle, normalised.  Computed in float64, returned as float32 (V, 3).  A vertex no
+    triangle uses, or whose sum vanishes, gets (0, 0, 0): pt_set_mesh_normals refuses it if a triangle refers to it."""
+    v = np.asarray(vertices, dtype=np.float64)
+    t = np.asarray(triangles, dtype=np.int64)
+    if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("vertices must have shape (V, 3) and triangles (T, 3)")
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError("triangles must index vertices")
+    p = v[t]                                              # (T, 3, 3)
+    fn = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    fl = np.linalg.norm(fn, axis=1, keepdims=True)
+    fn = np.divide(fn, fl, out=np.zeros_like(fn), where=fl > 0)
+    acc = np.zeros_like(v)
+    for c in range(3):
+        e0 = p[:, (c + 1) % 3] - p[:, c]
+        e1 = p[:, (c + 2) % 3] - p[:, c]
+        l0 = np.linalg.norm(e0, axis=1)
+        l1 = np.linalg.norm(e1, axis=1)
+        den = l0 * l1
+        cosang = np.divide(np.einsum("ij,ij->i", e0, e1), den, out=np.ones_like(den), where=den > 0)
+        ang = np.arccos(np.clip(cosang, -1.0, 1.0))
+        np.add.at(acc, t[:, c], fn * ang[:, None])
+    ln = np.linalg.norm(acc, axis=1, keepdims=True)
+    return np.divide(acc, ln, out=np.zeros_like(acc), where=ln > 0).astype(np.float32)
 
 
 def builtin_scene_ex():
@@ -344,7 +388,16 @@ class MeshInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
-assert C.sizeof(Mesh) == 32 and C.sizeof(MeshInfo) == 48
+class MeshNormalsInfo(C.Structure):
+    """pt_mesh_normals_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("has_normals", C.c_uint32), ("per_corner", C.c_uint32), ("n_normals", C.c_uint32),
+                ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
+assert C.sizeof(Mesh) == 32 and C.sizeof(MeshInfo) == 48 and C.sizeof(MeshNormalsInfo) == 24
 
 
 class Features(C.Structure):
@@ -530,6 +583,9 @@ def load_library(diag=False):
     L.pt_set_scene_meshes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Mesh), C.c_uint32]
     L.pt_get_mesh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshInfo)]
     L.pt_mesh_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_set_mesh_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.pt_get_mesh_normals_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshNormalsInfo)]
+    L.pt_mesh_shade.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
@@ -889,6 +945,8 @@ class Renderer:
         if has_mesh(objects):
             table, meshes = scene_meshes(objects)
             self.set_scene_meshes(table, meshes)
+            for k, normals, indices in mesh_normals(objects):   # a mesh with "normals" shades smooth (pt_set_mesh_normals)
+                self.set_mesh_normals(k, normals, indices)
             return
         if (isinstance(objects, np.ndarray) and objects.dtype == SCENE_EX_DTYPE) or has_polygon(objects):
             # a triangle or a parallelogram (or an ex table as it is): pt_set_scene_ex, keys of scene_array_ex
@@ -934,6 +992,53 @@ class Renderer:
                                                 MESH_INTERSECT_BRUTE if brute else MESH_INTERSECT_BVH,
                                                 t.ctypes.data, obj.ctypes.data, tri.ctypes.data))
         return t, obj, tri
+
+    def set_mesh_normals(self, k, normals, indices=None):
+        """pt_set_mesh_normals: vertex normals (N, 3) for mesh k of the scene in force, which then shades smooth.  indices None:
+        one normal per vertex, looked up by the mesh's own triangles; else (T, 3) indices into normals, per corner (creases).
+        normals None removes them: the mesh is flat again.  The library copies everything."""
+        if normals is None:
+            if indices is not None:
+                raise ValueError("indices without normals")
+            self._check(self._lib.pt_set_mesh_normals(self.handle, int(k), None, 0, None))
+            return
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[1] != 3 or len(nrm) == 0:
+            raise ValueError("normals must be an array of shape (N, 3), N >= 1")
+        idx = None
+        if indices is not None:
+            raw = np.asarray(indices)
+            if raw.ndim != 2 or raw.shape[1] != 3 or not np.issubdtype(raw.dtype, np.integer) or raw.min() < 0 or raw.max() > 0xffffffff:
+                raise ValueError("indices must be an array of shape (T, 3) of unsigned 32-bit indices")
+            if len(raw) != self.mesh_info(k)["n_triangles"]:
+                raise ValueError("indices must have one row per triangle of mesh %d (%d), got %d" % (k, self.mesh_info(k)["n_triangles"], len(raw)))
+            idx = np.ascontiguousarray(raw, dtype=np.uint32)
+        self._check(self._lib.pt_set_mesh_normals(self.handle, int(k), nrm.ctypes.data, len(nrm),
+                                                  idx.ctypes.data if idx is not None else None))
+
+    def mesh_normals_info(self, k):
+        """pt_get_mesh_normals_info of mesh k of the scene in force as a dict: has_normals, per_corner, n_normals, device_bytes."""
+        info = MeshNormalsInfo(struct_size=C.sizeof(MeshNormalsInfo))
+        self._check(self._lib.pt_get_mesh_normals_info(self.handle, int(k), C.byref(info)))
+        return info.as_dict()
+
+    def mesh_shade(self, origin, direction):
+        """pt_mesh_shade: the smooth kernels' nearest hit and shading normal over world-space rays origin (n, 3), direction (n, 3),
+        the camera ignored.  Returns (t, object, triangle, bary (n, 2), normal (n, 3)): bary and normal are zero unless a mesh
+        triangle was hit; the normal faces the ray."""
+        o = np.ascontiguousarray(origin, dtype=np.float32)
+        d = np.ascontiguousarray(direction, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("origin and direction must both have shape (n, 3)")
+        n = len(o)
+        t = np.zeros(n, np.float32)
+        obj = np.full(n, -1, np.int32)
+        tri = np.full(n, -1, np.int32)
+        bary = np.zeros((n, 2), np.float32)
+        nrm = np.zeros((n, 3), np.float32)
+        self._check(self._lib.pt_mesh_shade(self.handle, o.ctypes.data, d.ctypes.data, n, t.ctypes.data, obj.ctypes.data,
+                                            tri.ctypes.data, bary.ctypes.data, nrm.ctypes.data))
+        return t, obj, tri, bary, nrm
 
     def scene_ex(self):
         """The scene in force as a SCENE_EX_DTYPE array (pt_get_scene_ex): a polygon with centre = v0, radius 0 and its stored
