@@ -253,10 +253,10 @@ __device__ __forceinline__ void group_resolve(const GroupQueue& Q, const Table& 
 }
 
 // the per-path radiance of the NIF heads' per-path mode, from the owner's decoded BGR in the step store or the served slot
-// (resolve has left no pending word: whatever is not a store index is served).  A table that serves reads the three values
-// in one go ahead of the stores -- a sixth difference, of schedule alone: its slots lie anywhere in a table of gigabytes,
-// and with three reads that each wait for the store before them the memo's passes took a sixth more time per step
-// (profiles/r18_nif_group.txt).  Without one the reads stay where share_expand_kernel always had them.
+// (resolve has left no pending word: whatever is not a store index is served).  The three values, the throughputs and the
+// path are read ahead of the stores with either table: nothing tells the compiler that rad_* and the store do not alias, and
+// three reads that each wait for the store before them cost the memo's passes a sixth more time per step
+// (profiles/r18_nif_group.txt); the sharing pass has read ahead since round 25 (profiles/r25_step_head_tail.txt).
 template <class Table>
 __device__ __forceinline__ void group_expand(const GroupExpand& E, const Table& T) {
   const uint32_t r = blockIdx.y, local = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x;
@@ -264,16 +264,15 @@ __device__ __forceinline__ void group_expand(const GroupExpand& E, const Table& 
   const uint32_t q = r * E.region_cap + local;
   const uint32_t o = E.owner[q];
   const float* bgr = E.bgr + 3 * (size_t)o;
-  float held[3];
   if constexpr (Table::kServes) {
     if (!ptshare::owner_is_store(o)) bgr = T.served_bgr(ptshare::owner_slot(o));
-    held[0] = bgr[0]; held[1] = bgr[1]; held[2] = bgr[2];
-    bgr = held;
   }
+  const float held[3] = {bgr[0], bgr[1], bgr[2]};
   const uint32_t path = E.q_path[q];
-  E.rad_r[path] = bgr[2] * E.q_tr[q];
-  E.rad_g[path] = bgr[1] * E.q_tg[q];
-  E.rad_b[path] = bgr[0] * E.q_tb[q];
+  const float tr = E.q_tr[q], tg = E.q_tg[q], tb = E.q_tb[q];
+  E.rad_r[path] = held[2] * tr;
+  E.rad_g[path] = held[1] * tg;
+  E.rad_b[path] = held[0] * tb;
 }
 
 __global__ __launch_bounds__(kShareBlock) void share_claim_kernel(GroupQueue Q, ShareTable T) { group_claim(Q, T); }

@@ -629,6 +629,8 @@ static int enqueue_path_trace(pt_handle h) {
   if (mode.memo)   // counters, and a clear or a retain pass if one is due
     if (int rc = ev.timed(h->trace_stream, pt_context::kSpanMemo, [&]() { return enqueue_memo_prologue(h); })) return rc;
 
+  const bool handoff = mode.kind() == ptshare::StepKind::kStep;   // the next step-scope step finds its table cleared
+  hipEvent_t e_clean = nullptr;
   uint32_t store_cap = 0, first_iter = 0;
   for (uint32_t i = 0; i < batches; first_iter += deal[i], ++i) {
     const uint32_t slot = ptplan::ring_slot(i, h->ring_depth);
@@ -640,10 +642,13 @@ static int enqueue_path_trace(pt_handle h) {
     if (mode.grouped())
       if (int rc = stage_group(h, ev, mode, b)) return rc;
     if (int rc = stage_nif(h, ev, mode, b)) return rc;
+    if (handoff && i + 1 == batches)   // behind the last S(b) and its B.traced: the table is not read again in this step
+      if (int rc = enqueue_table_handoff(h, ev, e_clean)) return rc;
     if (mode.grouped())
       if (int rc = stage_expand(h, ev, mode, b)) return rc;
     if (int rc = stage_accumulate(h, ev, b)) return rc;
   }
+  if (e_clean) PT_HIP(hipStreamWaitEvent(h->stream, e_clean, 0));   // the step ends with its table clean for the next one
 
   if (int rc = ev.record(h->acc_stream, e_acc, e_acc_i)) return rc;
   PT_HIP(hipStreamWaitEvent(h->stream, e_acc, 0));          // later work on `stream` sees the accumulated film
@@ -738,6 +743,10 @@ int pt_path_trace(pt_handle h) {
   }
   const bool failed = rc || s0 != hipSuccess || s1 != hipSuccess || s2 != hipSuccess || s3 != hipSuccess;
   if (failed) memo_new_generation(h);   // claims of this step were never published: a new generation
+  // the sharing table after this step: cleared for the next one by a step-scope step that ran to its end, untouched with
+  // sharing off, otherwise not known (a failed step may have stopped anywhere between its claims and its clear)
+  h->group.share_clean_slots = ptshare::mark_after_step(h->group.share_clean_slots,
+      StepMode{h->group.share_mode_last, h->group.memo_ran}.kind(), h->group.share_slots, !failed);
   if (rc) return rc;   // h->error names the failing call
   for (hipError_t e : {s0, s1, s2, s3})
     if (e != hipSuccess) return fail(h, PT_ERR_HIP, std::string("path_trace: ") + hipGetErrorString(e));

@@ -285,8 +285,9 @@ struct pt_context {
 
   // NIF sharing and the memo (ptmi_nif_group.h; kernels: pt_nif_group.h, pt_nif_memo.h)
   struct NifGroup {
-    // exact sharing of NIF evaluations (pt_set_nif_sharing).  Nothing here survives a step: the table is
-    // cleared at the start of every batch (PT_NIF_SHARE_BATCH) or step (PT_NIF_SHARE_STEP), the counts at every step.
+    // exact sharing of NIF evaluations (pt_set_nif_sharing).  No key survives a step: the table is cleared at the start
+    // of every batch (PT_NIF_SHARE_BATCH) or, for PT_NIF_SHARE_STEP, at the end of the step before (share_clean_slots says
+    // so) or else at the start of the step; the counts at every step.
     int32_t share_mode = 0;                    // requested: taken up by the next pt_path_trace
     bool share_mode_set = false;               // pt_set_nif_sharing or pt_set_nif_memo was called; until then the step chooses (auto_share_mode)
     bool share_auto_failed = false;            // the automatic default could not allocate: off until pt_set_nif_sharing
@@ -294,6 +295,7 @@ struct pt_context {
     DevBuf<unsigned long long> d_share_keys;
     DevBuf<uint32_t> d_share_vals;
     uint32_t share_slots = 0;                  // table capacity, a power of two
+    uint32_t share_clean_slots = 0;            // the clean-table mark (ptmi_share_plan.h): slots at which the table is known to hold no key, 0 = not known
     uint32_t share_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_share_capacity), 0 = sized from memory
     DevBuf<uint32_t> d_share_owner[kBatchSets];        // per batch-buffer set: [queue_cap] owner word of every entry (ptmi_share_plan.h)
     // the step's distinct queues and their decoded BGR, region-structured: batch b's at store region (b, or at batch scope its set) x queue_cap

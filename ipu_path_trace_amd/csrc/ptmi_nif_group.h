@@ -51,6 +51,7 @@ static int alloc_share_table(pt_handle h, uint32_t slots) {
   PT_HIP(hipStreamSynchronize(h->stream));
   h->group.d_share_keys.reset(); h->group.d_share_vals.reset();
   h->group.share_slots = 0;
+  h->group.share_clean_slots = 0;   // new memory: nothing is known of it
   if (!slots) return PT_OK;
   PT_HIP(dev_alloc(h->group.d_share_keys, slots));
   PT_HIP(dev_alloc(h->group.d_share_vals, slots));
@@ -85,6 +86,7 @@ static int alloc_share_buffers(pt_handle h) {
 static void free_share_buffers(pt_handle h) {   // (the counts and the overflow counter are a few bytes: they stay)
   h->group.d_share_keys.reset(); h->group.d_share_vals.reset();
   h->group.share_slots = 0;
+  h->group.share_clean_slots = 0;
   h->group.d_share_u.reset(); h->group.d_share_v.reset(); h->group.d_share_bgr.reset();
   h->group.share_regions = 0;
   for (auto& o : h->group.d_share_owner) o.reset();
@@ -186,6 +188,10 @@ struct StepMode {
   bool memo;
   bool grouped() const { return share || memo; }   // N runs over distinct queues in the step store
   bool step_scope() const { return memo || share == PT_NIF_SHARE_STEP; }
+  ptshare::StepKind kind() const {   // what the step does to the sharing table (ptmi_share_plan.h: the clean-table hand-off)
+    return memo ? ptshare::StepKind::kMemo : share == PT_NIF_SHARE_STEP ? ptshare::StepKind::kStep
+           : share == PT_NIF_SHARE_BATCH ? ptshare::StepKind::kBatch : ptshare::StepKind::kOff;
+  }
 };
 
 // The mode of a handle on which neither pt_set_nif_sharing nor pt_set_nif_memo was ever called: step scope if the environment
@@ -210,14 +216,25 @@ static int32_t auto_share_mode(pt_handle h, size_t batches) {
 }
 
 // Before the first batch of a grouped step: the buffers at the step's size, and the counts, the overflow counter and a
-// step-scope table cleared on the trace stream, where S runs (after e_begin: part of the step).
+// step-scope table cleared on the trace stream, where S runs (after e_begin: part of the step) -- unless the step before
+// handed the table over clean (enqueue_table_handoff; the mark is checked after the buffers have their size).
 static int prepare_group_store(pt_handle h, const StepMode& mode, size_t batches) {
   if (int rc = ensure_group_buffers(h, mode.memo, mode.step_scope(), batches)) return rc;
   PT_HIP(hipMemsetAsync(h->group.d_share_count, 0, batches * 4, h->trace_stream));
   PT_HIP(hipMemsetAsync(h->group.d_share_over, 0, 8, h->trace_stream));
-  if (!mode.memo && mode.share == PT_NIF_SHARE_STEP)   // one table for the step
+  if (mode.kind() == ptshare::StepKind::kStep &&   // one table for the step
+      !ptshare::clear_skippable(h->group.share_clean_slots, mode.kind(), h->group.share_slots))
     PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
   return PT_OK;
+}
+
+// Behind the last S(b) of a step-scope step, which is the table's last reader: the clear for the NEXT step, on the trace
+// stream, where it runs beside the last NIF launches instead of ahead of the next step's T(0).  `clean` is recorded behind
+// it; the step's end waits for it, and pt_path_trace sets the mark (ptshare::mark_after_step) once the step has returned.
+static int enqueue_table_handoff(pt_handle h, StepEvents& ev, hipEvent_t& clean) {
+  PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
+  size_t at = 0;
+  return ev.record(h->trace_stream, clean, at);
 }
 
 static ptd::ShareTable share_table(pt_handle h) { return {h->group.d_share_keys, h->group.d_share_vals, h->group.share_slots - 1u}; }

@@ -1,8 +1,8 @@
 // ptmi_share_plan.h -- the arithmetic of NIF sharing and the memo (pt_set_nif_sharing, pt_set_nif_memo; pt_nif_group.h): the
 // format of an owner word, how many slots the table of a batch or a step gets, whether the automatic default may take the
-// memory it needs, how many slots a memo of a given size has, and the tiles of the claim pass.  Plain C++ (nothing from
-// HIP), so that tests/share_plan_main.cpp and tests/claim_plan_main.cpp check it on a CPU; ptmi.hip includes it ahead of the
-// device headers.
+// memory it needs, how many slots a memo of a given size has, the tiles of the claim pass, and when a step-scope step may
+// skip the clear of its table.  Plain C++ (nothing from HIP), so that tests/share_plan_main.cpp, tests/claim_plan_main.cpp
+// and tests/handoff_plan_main.cpp check it on a CPU; ptmi.hip includes it ahead of the device headers.
 #pragma once
 
 #include <cstdint>
@@ -21,6 +21,20 @@ constexpr bool owner_is_store(uint32_t o) { return !(o & kOwnerTagged); }
 constexpr bool owner_is_pending(uint32_t o) { return (o & kOwnerPending) == kOwnerPending; }
 constexpr bool owner_is_served(uint32_t o) { return (o & kOwnerPending) == kOwnerTagged; }
 constexpr uint32_t owner_slot(uint32_t o) { return o & kOwnerSlotBits; }
+
+// The clean-table hand-off.  A step-scope step clears the table behind its last S(b), for the step after it, and the handle
+// keeps a mark: the number of slots at which the table is known to hold no key, 0 if it is not known.  The next step-scope
+// step skips its own clear only if the mark is the size of the table it is about to use.  A reallocation, a forced capacity
+// and free_share_buffers set the mark to 0 where they happen (the host side); a step leaves the mark mark_after_step gives.
+enum class StepKind : uint32_t { kOff, kBatch, kStep, kMemo };   // sharing off (or a constant environment), batch scope, step scope, the memo
+constexpr bool clear_skippable(uint32_t mark, StepKind kind, uint32_t table_slots) {
+  return kind == StepKind::kStep && table_slots != 0 && mark == table_slots;
+}
+// ok: the step returned no error.  Off leaves the table as it was; batch scope leaves its last batch's keys; a memo step
+// and a failed step leave nothing that is relied on.
+constexpr uint32_t mark_after_step(uint32_t mark, StepKind kind, uint32_t table_slots, bool ok) {
+  return !ok ? 0u : kind == StepKind::kStep ? table_slots : kind == StepKind::kOff ? mark : 0u;
+}
 
 // The claim pass's tiles (group_claim in pt_nif_group.h): a workgroup of kClaimBlock threads takes kClaimTile consecutive
 // entries of one region, thread t the entries tile base + k * kClaimBlock + t for k < kClaimK, and reserves the tile's places
