@@ -366,7 +366,7 @@ int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uin
  *
  * Triangle j of a mesh.  v0, v1, v2 are vertices[indices[3 j + 0 .. 2]]; e1 = v1 - v0 and e2 = v2 - v0 in binary32, and the
  * stored normal is n = c / sqrtf(dot(c, c)), c = cross(e1, e2), exactly as for a PT_SHAPE_TRIANGLE object.  Shading is FLAT unless
- * normals are attached (pt_set_mesh_normals below); there are no texture coordinates.
+ * normals are attached (pt_set_mesh_normals below), and a mesh has one colour unless a texture is attached (pt_set_mesh_texture).
  *
  * Intersection.  A triangle is tested by the expression sequence of a PT_SHAPE_TRIANGLE object, unchanged, then by the scene's
  * t > eps and t < tbest in declaration order, as every object is.  Ties inside one mesh: the smallest t wins and, among equal
@@ -514,6 +514,90 @@ int pt_get_mesh_normals_info(pt_handle h, uint32_t mesh, pt_mesh_normals_info* o
  * PT_ERR_NOT_READY without a mesh in force; n == 0 is a no-op. */
 int pt_mesh_shade(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object,
                   int32_t* out_triangle, float* out_bary /* [n][2] */, float* out_normal /* [n][3] */);
+
+/* Texture coordinates and an image texture for a mesh -- an EXTENSION, opt-in and additive: PTMI_ABI_VERSION stays 5, no existing
+ * struct or entry point changes, and a process that never attaches a texture launches the kernels it launched before and renders
+ * the same bits.  The new code lives in kernel instances of its own (TEX, which carry the SMOOTH code as well: a flag per mesh row
+ * decides per hit), launched only while a mesh of the scene in force has a texture.
+ *
+ * Limits.  LINEAR FLOAT IMAGES ONLY: texels are linear radiometric factors in binary32; there is no 8-bit format and no sRGB
+ * decoding.  ONE texture per mesh, each mesh with its own copy of its image (sharing one image between meshes is not built).
+ * NO mip maps and no filtering by footprint: a lookup is one texel (nearest) or four (bilinear) whatever the distance.  An
+ * emissive textured mesh is NOT in the emitter guide, as no emissive mesh is.
+ *
+ * The lookup (csrc/pt_mesh.h: tri_bary, blend_uv, tex_wrap, texel -- one set of functions for the kernels and the host), at a hit of
+ * the ray (o, d) on triangle j of a textured mesh; every operation one rounded binary32, no contraction:
+ *   1. Barycentrics.  a, b by the triangle test's own expressions on the ray that hit (the same bits the walk computed),
+ *      c = (1 - a) - b.
+ *   2. Interpolation.  s = ((c s0) + (a s1)) + (b s2), t likewise.  Corner k's (s, t) is uvs[uv_indices[3 j + k]], or
+ *      uvs[indices[3 j + k]] when uv_indices == NULL (per-vertex uvs; n_uvs must equal the mesh's n_vertices).
+ *   3. Wrap, x being s or t.  REPEAT: x' = x - floorf(x).  CLAMP: x' = fminf(fmaxf(x, 0), 1).  A value that is not >= 0 after that
+ *      becomes 0.  x' lies in [0, 1], both ends included; no bit pattern reads outside the image.
+ *   4. Texel position.  (s, t) = (0, 0) is the BOTTOM-LEFT corner of the image (OBJ's convention), s runs across a row, and rows
+ *      are stored top to bottom, so the row coordinate uses 1 - t'.  Texel centres sit at half-integers.
+ *      NEAREST: X = s' (float)width, Y = (1 - t') (float)height, c0 = (int)floorf(X), r0 = (int)floorf(Y); an index equal to the
+ *      size wraps to 0 under REPEAT and becomes size - 1 under CLAMP.  The result is texel (r0, c0), bit for bit.
+ *      BILINEAR: X = s' width - 0.5, Y = (1 - t') height - 0.5 (a product, then a difference); c0 = floorf(X), fx = X - c0,
+ *      c1 = c0 + 1, rows the same way with fy.  Each index is wrapped (-1 becomes size - 1, size becomes 0) or clamped by the mode.
+ *      Per channel top = fmaf(fx, t01 - t00, t00), bot = fmaf(fx, t11 - t10, t10), out = fmaf(fy, bot - top, top) with txy the
+ *      texel of row ry, column cx: the environment map's lerp.
+ *   5. Effect.  The texel multiplies the row's colour, one multiply per channel, before the material branch: the effective R is
+ *      colour[0] x texel.R, G and B likewise.  Diffuse: the factor.  Refractive: the tint of a refracted ray.  Emissive: the
+ *      emitted radiance (a textured emissive mesh forms the barycentrics before its early return).  Specular ignores it, as it
+ *      ignores its colour.  So a texture of all ones renders the untextured bits, and a constant texture k renders the bits of the
+ *      untextured scene with colour fl(colour x k).
+ *   6. Feature buffers.  `albedo` of a diffuse or refractive hit on a textured mesh is that product at the centre ray's hit;
+ *      everything else is unchanged.  pt_set_mesh_texture invalidates the feature cache.
+ *   7. Independence and lifetime.  Textures are independent of normals: a mesh may have either, both or neither.  A mesh WITHOUT a
+ *      texture beside a textured one takes none of the steps and renders its own bits.  (h, mesh, NULL) removes the texture.  Any
+ *      pt_set_scene* drops all textures with the scene.  A pose change re-expands the uvs into the new slot order, untransformed,
+ *      and allocates nothing on the device.  A texture touches neither the worklist, the film, the camera, NIF sharing, the memo
+ *      nor the guides: both guides see the textured colour only through the throughput.
+ *
+ * Copies and memory.  The library copies everything.  The handle keeps the (s, t) per corner in triangle order, 24 bytes per
+ * triangle of a textured mesh.  The device holds 24 bytes per triangle SLOT in leaf order, indexed by the global slot a hit
+ * carries: one buffer over the slots of ALL meshes of the scene, allocated whole by the first call that attaches a texture,
+ * together with a 1 KiB table of per-row descriptors, and kept until the next scene or pt_destroy (removing the last texture does
+ * not free it).  It also holds 16 bytes per texel (B, G, R, 0), each mesh its own copy, freed when the texture is removed or
+ * replaced.  pt_mesh_texture_info.device_bytes is THIS MESH'S SHARE: 24 per triangle + 16 per texel while it has a texture, else 0.
+ * On PT_ERR_OUT_OF_MEMORY the mesh keeps what it had.
+ *
+ * Validation returns PT_ERR_INVALID_ARGUMENT, and pt_last_error names mesh, triangle, corner, texel and field.  The checks run in
+ * this order, before any device call: a NULL handle (pt_last_error(NULL)); no mesh `mesh` in force; struct_size; width or height
+ * outside 1..PT_MESH_TEXTURE_MAX_SIZE; filter, then wrap, out of range; NULL bgr, then NULL uvs; n_uvs different from n_vertices
+ * when uv_indices is NULL; a texel that is not finite or is negative, naming row, column and channel, in storage order; then per
+ * triangle and corner an index >= n_uvs or a referenced uv that is not finite.  Unreferenced uvs are not examined.  After a
+ * rejection the mesh keeps what it had. */
+enum { PT_TEX_FILTER_NEAREST = 0, PT_TEX_FILTER_BILINEAR = 1 };
+enum { PT_TEX_WRAP_REPEAT = 0, PT_TEX_WRAP_CLAMP = 1 };
+#define PT_MESH_TEXTURE_MAX_SIZE 8192
+typedef struct pt_mesh_texture {      /* 56 bytes */
+  uint32_t struct_size;               /* sizeof(pt_mesh_texture) */
+  uint32_t width, height;             /* 1..PT_MESH_TEXTURE_MAX_SIZE */
+  int32_t filter, wrap;
+  const float* bgr;                   /* [height][width][3] float32, B,G,R, rows top to bottom, linear values, finite and >= 0 */
+  const float* uvs;                   /* [n_uvs][2] (s, t), finite */
+  uint32_t n_uvs;
+  const uint32_t* uv_indices;         /* [n_triangles][3] per corner (OBJ's v/vt), or NULL: per vertex, n_uvs == n_vertices */
+} pt_mesh_texture;
+int pt_set_mesh_texture(pt_handle h, uint32_t mesh, const pt_mesh_texture* t);   /* NULL removes it */
+typedef struct pt_mesh_texture_info { /* 40 bytes */
+  uint32_t struct_size;               /* in: sizeof(pt_mesh_texture_info) */
+  uint32_t has_texture;               /* 1: the mesh is textured */
+  uint32_t per_corner;                /* 1: given with uv_indices */
+  uint32_t width, height;
+  int32_t filter, wrap;
+  uint32_t n_uvs;                     /* as given */
+  uint64_t device_bytes;              /* this mesh's share: 24 per triangle + 16 per texel while it has a texture, else 0 */
+} pt_mesh_texture_info;
+int pt_get_mesh_texture_info(pt_handle h, uint32_t mesh, pt_mesh_texture_info* out);
+/* Kernel-level hook, like pt_mesh_shade: world-space rays, the camera IGNORED.  The textured instances' own nearest hit, uv
+ * interpolation and lookup.  out_t, out_object, out_triangle as pt_mesh_intersect's.  For a hit on a triangle of a textured mesh
+ * out_uv[i] is the interpolated (s, t) of rule 2 and out_bgr[i] the texel of rule 4, NOT multiplied by the row's colour; for a
+ * mesh triangle without a texture uv is 0 and bgr is (1, 1, 1); for a miss or a hit on anything else both are 0.
+ * PT_ERR_NOT_READY without a mesh in force; n == 0 is a no-op. */
+int pt_mesh_texel(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object,
+                  int32_t* out_triangle, float* out_uv /* [n][2] */, float* out_bgr /* [n][3] */);
 
 /* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
  * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an

@@ -19,8 +19,9 @@ namespace ptd {
 
 constexpr int kFeatureBlock = 256;
 
-template <bool POLY, bool MESH = false, bool SMOOTH = false>
-__device__ __forceinline__ void features_body(const TraceParams& P, float4* __restrict__ f0, float4* __restrict__ f1) {
+template <bool POLY, bool MESH = false, bool SMOOTH = false, bool TEX = false>
+__device__ __forceinline__ void features_body(const TraceParams& P, float4* __restrict__ f0, float4* __restrict__ f1,
+                                              [[maybe_unused]] const TexParams* X = nullptr) {
   const uint32_t i = blockIdx.x * kFeatureBlock + threadIdx.x;
   if (i >= P.width * P.height) return;   // width, height <= 65535: the product fits 32 bits
   const uint32_t v = i / P.width, u = i - v * P.width;
@@ -62,6 +63,11 @@ __device__ __forceinline__ void features_body(const TraceParams& P, float4* __re
     if (dot(n, st.d) > 0.0f) n = scale(n, -1.0f);                     // faces the ray
     if (P.cam_pose) n = normalise(to_world(P, n));                    // reported in world space; unit again after the rotation's roundings
     if (ob.type == MAT_DIFFUSE || ob.type == MAT_REFRACTIVE) alb = mk(ob.colr, ob.colg, ob.colb);   // mirrors, emitters and misses demodulate by 1
+    if constexpr (TEX) {   // pt_set_mesh_texture: colour x texel at the centre ray's hit, the product shade_hit forms (rules 1-5)
+      if (ob.is_disc == SHAPE_MESH && __float_as_uint(P.poly[best].e2z) != 0u && (ob.type == MAT_DIFFUSE || ob.type == MAT_REFRACTIVE)) {
+        texture_colour(P, *X, best, packed, mk(0.f, 0.f, 0.f), st.d, alb.x, alb.y, alb.z);
+      }
+    }
   }
   f0[i] = make_float4(n.x, n.y, n.z, depth);
   f1[i] = make_float4(alb.z, alb.y, alb.x, __int_as_float(best));     // B, G, R like every image of the ABI
@@ -81,6 +87,11 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel_mesh(const Trac
 // pt_set_mesh_normals: launched only while a mesh in force has vertex normals
 __global__ __launch_bounds__(kFeatureBlock) void features_kernel_smooth(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
   features_body<true, true, true>(P, f0, f1);
+}
+// pt_set_mesh_texture: launched only while a mesh in force has a texture (the second argument: TexParams, pt_trace.h)
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel_tex(const TraceParams P, const TexParams X, float4* __restrict__ f0,
+                                                                     float4* __restrict__ f1) {
+  features_body<true, true, true, true>(P, f0, f1, &X);
 }
 
 }  // namespace ptd

@@ -178,4 +178,63 @@ PT_MESH_HD void shading_normal(const float* o, const float* d, const Tri& T, con
   blend_normal(a, b, d, ng, vn, ns);
 }
 
+// ---- texture coordinates and image textures (pt_set_mesh_texture, include/ptmi.h): the texel of a hit on a triangle of a
+// textured mesh.  The barycentrics are tri_bary's, on the ray that hit.  Every operation one rounded binary32; the lerp is
+// spelled with fmaf, as the environment map's is, so that no contraction setting changes it.
+//   c = (1 - a) - b;  s = ((c s0) + (a s1)) + (b s2), t likewise                            (rule 2)
+//   REPEAT: x' = x - floorf(x);  CLAMP: x' = fminf(fmaxf(x, 0), 1);  not (x' >= 0) -> 0      (rule 3)
+//   (s, t) = (0, 0) is the image's bottom-left corner; rows are stored top to bottom         (rule 4)
+constexpr int kTexNearest = 0, kTexBilinear = 1;   // PT_TEX_FILTER_NEAREST / _BILINEAR
+constexpr int kTexRepeat = 0, kTexClamp = 1;       // PT_TEX_WRAP_REPEAT / _CLAMP
+// What a textured mesh's row looks its image up by: one per scene row in a device table (a row without a texture: all zero).
+struct alignas(16) TexDesc {
+  const F4* texels;          // [height][width] (B, G, R, 0), rows top to bottom
+  uint32_t width, height;
+  int32_t filter, wrap;
+  uint32_t pad[2];
+};
+static_assert(sizeof(TexDesc) == 32, "texture descriptor layout");
+// uv: the slot's three corners (s0, t0, s1, t1, s2, t2)
+PT_MESH_HD void blend_uv(float a, float b, const float* uv, float& s, float& t) {
+  const float c = (1.0f - a) - b;
+  s = ((c * uv[0]) + (a * uv[2])) + (b * uv[4]);
+  t = ((c * uv[1]) + (a * uv[3])) + (b * uv[5]);
+}
+PT_MESH_HD float tex_wrap(float x, int wrap) {
+  const float w = wrap == kTexClamp ? fminf(fmaxf(x, 0.0f), 1.0f) : x - floorf(x);
+  return w >= 0.0f ? w : 0.0f;   // (inf - inf, or a NaN that came in)
+}
+// An index in [-1, size] into [0, size): wrapped or clamped by the mode.  Whatever comes in, what goes out is inside the image.
+PT_MESH_HD uint32_t tex_index(int i, uint32_t size, int wrap) {
+  const int n = (int)size;
+  if (wrap == kTexClamp) i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+  else i = i < 0 ? i + n : (i >= n ? i - n : i);
+  return (uint32_t)(i < 0 ? 0 : (i >= n ? n - 1 : i));
+}
+PT_MESH_HD float tex_lerp(float f, float p, float q) { return fmaf(f, q - p, p); }
+PT_MESH_HD void texel(const TexDesc& D, float s, float t, float* bgr) {
+  const float sw = tex_wrap(s, D.wrap), tw = tex_wrap(t, D.wrap);
+  const float fw = (float)D.width, fh = (float)D.height;
+  const float tv = 1.0f - tw;
+  if (D.filter == kTexNearest) {
+    const float X = sw * fw, Y = tv * fh;
+    const uint32_t c0 = tex_index((int)floorf(X), D.width, D.wrap), r0 = tex_index((int)floorf(Y), D.height, D.wrap);
+    const F4 q = D.texels[(size_t)r0 * D.width + c0];
+    bgr[0] = q.x; bgr[1] = q.y; bgr[2] = q.z;
+    return;
+  }
+  const float X = sw * fw - 0.5f, Y = tv * fh - 0.5f;
+  const float xf = floorf(X), yf = floorf(Y);
+  const float fx = X - xf, fy = Y - yf;
+  const int ci = (int)xf, ri = (int)yf;
+  const uint32_t c0 = tex_index(ci, D.width, D.wrap), c1 = tex_index(ci + 1, D.width, D.wrap);
+  const uint32_t r0 = tex_index(ri, D.height, D.wrap), r1 = tex_index(ri + 1, D.height, D.wrap);
+  const F4* row0 = D.texels + (size_t)r0 * D.width;
+  const F4* row1 = D.texels + (size_t)r1 * D.width;
+  const F4 t00 = row0[c0], t01 = row0[c1], t10 = row1[c0], t11 = row1[c1];   // four loads in flight
+  bgr[0] = tex_lerp(fy, tex_lerp(fx, t00.x, t01.x), tex_lerp(fx, t10.x, t11.x));
+  bgr[1] = tex_lerp(fy, tex_lerp(fx, t00.y, t01.y), tex_lerp(fx, t10.y, t11.y));
+  bgr[2] = tex_lerp(fy, tex_lerp(fx, t00.z, t01.z), tex_lerp(fx, t10.z, t11.z));
+}
+
 }  // namespace ptmesh

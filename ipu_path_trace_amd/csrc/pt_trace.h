@@ -79,7 +79,7 @@ static_assert(ptmesh::kEps == kEps, "one intersection epsilon");
 struct MeshRow {
   uint32_t node_base, tri_base, n_nodes, n_triangles;
   uint32_t smooth;   // the mesh has vertex normals (pt_set_mesh_normals): the SMOOTH instances alone read it
-  uint32_t unused;
+  uint32_t textured;   // the mesh has a texture (pt_set_mesh_texture): the TEX instances alone read it
 };
 static_assert(sizeof(MeshRow) == sizeof(PolyEdges), "a mesh row travels in its PolyEdges slot");
 constexpr int kHitObjectBits = 5;   // a MESH instance's hit: object | slot << 5 (the slot counts over all meshes: < 2^22)
@@ -144,6 +144,15 @@ struct TraceParams {
   const ptmesh::F4* mesh_normals;
 };
 static_assert(sizeof(TraceParams) <= 4096, "the scene travels in the kernel arguments: 4 KiB at most");
+
+// Mesh textures (pt_set_mesh_texture): the SECOND kernel argument of the TEX instances, which are launched only while a mesh in
+// force has a texture.  TraceParams does not grow and no other kernel's argument layout moves.  uvs: three (s, t) per triangle
+// slot, indexed by the global slot of a packed hit (24 bytes per slot); desc: one descriptor per scene row, in device memory.
+struct TexParams {
+  const float* mesh_uvs;
+  const ptmesh::TexDesc* desc;
+};
+static_assert(sizeof(TraceParams) + sizeof(TexParams) <= 4096, "both arguments of a TEX kernel travel in the 4 KiB of kernel arguments");
 
 // path index -> (work item, sample iteration).  A 32-bit division costs ~25 vector instructions on this chip and every path
 // needs one (survivors two more); n_items is fixed per launch, so the host supplies the round-up reciprocal.
@@ -471,13 +480,17 @@ struct HitRow {
 };
 constexpr size_t hit_table_bytes(uint32_t n_objects) { return (size_t)n_objects * sizeof(HitRow); }
 // SMOOTH: a mesh row's centre.w carries the bits of its row's `smooth` flag (MeshRow), so that a lane learns with the row it reads
-// anyway whether the mesh it hit has vertex normals.
-template <bool SMOOTH = false>
+// anyway whether the mesh it hit has vertex normals.  TEX (implies SMOOTH): bit 0 the smooth flag, bit 1 the row's `textured`.
+constexpr uint32_t kRowSmooth = 1u, kRowTextured = 2u;
+template <bool SMOOTH = false, bool TEX = false>
 __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab) {
 #pragma unroll 1
   for (int i = 0; i < (int)P.n_objects; ++i) {
     float flag = 0.f;
-    if constexpr (SMOOTH) { if (P.obj[i].is_disc == SHAPE_MESH) flag = P.poly[i].e2y; }
+    if constexpr (TEX) {
+      if (P.obj[i].is_disc == SHAPE_MESH)
+        flag = __uint_as_float((__float_as_uint(P.poly[i].e2y) != 0u ? kRowSmooth : 0u) | (__float_as_uint(P.poly[i].e2z) != 0u ? kRowTextured : 0u));
+    } else if constexpr (SMOOTH) { if (P.obj[i].is_disc == SHAPE_MESH) flag = P.poly[i].e2y; }
     tab[i].centre = make_float4(P.obj[i].cx, P.obj[i].cy, P.obj[i].cz, flag);
     tab[i].normal = make_float4(P.obj[i].nx, P.obj[i].ny, P.obj[i].nz, 0.f);
     tab[i].colour = make_float4(P.obj[i].colr, P.obj[i].colg, P.obj[i].colb,
@@ -485,30 +498,56 @@ __device__ __forceinline__ void fill_hit_table(const TraceParams& P, HitRow* tab
   }
 }
 
+// pt_set_mesh_texture, rules 1-4, the ONE place the kernels look a texel up: the interpolated (ts, tt) and the texel (B, G, R) at
+// the hit `packed` of the ray (o, d) on row `row`, a textured mesh.  The barycentrics from the ray that hit, by tri_bary; the uv
+// triple and the texels are asked for once the triangle's twelve floats are dead.
+__device__ __forceinline__ void texel_at_hit(const TraceParams& P, const TexParams& X, int row, int packed, Vec3 o, Vec3 d, float& ts,
+                                             float& tt, float (&bgr)[3]) {
+  const size_t slot = (size_t)hit_slot(packed);
+  const float ov[3] = {o.x, o.y, o.z}, dv[3] = {d.x, d.y, d.z};
+  float a, b;
+  ptmesh::tri_bary(ov, dv, ptmesh::load_tri(P.mesh_tris + 3u * slot), a, b);
+  __builtin_amdgcn_sched_barrier(0);
+  const float2* const q = reinterpret_cast<const float2*>(X.mesh_uvs + 6u * slot);
+  const float2 q0 = q[0], q1 = q[1], q2 = q[2];
+  const float uv[6] = {q0.x, q0.y, q1.x, q1.y, q2.x, q2.y};
+  ptmesh::blend_uv(a, b, uv, ts, tt);
+  ptmesh::texel(X.desc[row], ts, tt, bgr);
+}
+// Rule 5: the colour (cr, cg, cb) of the row times that texel, one multiply per channel.
+__device__ __forceinline__ void texture_colour(const TraceParams& P, const TexParams& X, int row, int packed, Vec3 o, Vec3 d, float& cr,
+                                               float& cg, float& cb) {
+  float ts, tt, bgr[3];
+  texel_at_hit(P, X, row, packed, o, d, ts, tt, bgr);
+  cr = cr * bgr[2]; cg = cg * bgr[1]; cb = cb * bgr[0];
+}
+
 // GUIDE: the diffuse bounce mixes the hemisphere with the environment guide (pt_env_guide.h); CAM tells it whether directions
 // are rotated between camera and world space, as in emit_escaped (CAM_LENS: when P.cam_pose says so).
 // PLAMPS: the emitter guide's table may list polygons (pt_set_light_guide_ex; with LIGHTS and POLY alone).
 // MESH: `best` is a packed hit (nearest_hit), and a mesh triangle's normal comes from global memory.
 // SMOOTH (implies MESH): a mesh may have vertex normals (pt_set_mesh_normals); the hit's shading normal replaces the stored one.
+// TEX (implies SMOOTH): a mesh may have a texture (pt_set_mesh_texture); the texel multiplies the row's colour.  X: the TEX
+// instances' second kernel argument, nullptr everywhere else.
 template <bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false,
-          bool SMOOTH = false>
+          bool SMOOTH = false, bool TEX = false>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
-                                         const uint32_t (&w)[4], float rr, uint32_t& length);
+                                         const uint32_t (&w)[4], float rr, uint32_t& length, const TexParams* X = nullptr);
 
 // One iteration of the while loop of RayTraceKernel::compute (codelets.cpp:173-216) with the
 // AccumulateContributions fold (codelets.cpp:255-292) carried forward as throughput T.
 // Returns the path length (contribution-stack size, codelets.cpp:253) through `length` when the
 // path ends.
 template <bool LEGACY = false, bool SCENE_C = false, bool PIPE = false, bool GUIDE = false, int CAM = CAM_BUILTIN, bool LIGHTS = false,
-          bool POLY = false, bool PLAMPS = false, bool MESH = false, bool SMOOTH = false>
-__device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length);
+          bool POLY = false, bool PLAMPS = false, bool MESH = false, bool SMOOTH = false, bool TEX = false>
+__device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length, const TexParams* X = nullptr);
 #ifdef PTMI_DIAG_BUILD
 __device__ __forceinline__ int nearest_hit_r3(const TraceParams& P, Vec3 o, Vec3 d, float& tbest);
 __device__ __forceinline__ int shade_hit_r3(const TraceParams& P, const HitRow* tab, PathState& s, int best, float tbest,
                                             const uint32_t (&w)[4], float rr, uint32_t& length);
 #endif
-template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH, bool SMOOTH>
-__device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length) {
+template <bool LEGACY, bool SCENE_C, bool PIPE, bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH, bool SMOOTH, bool TEX>
+__device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, PathState& s, uint32_t& length, const TexParams* X) {
   uint32_t w[4];
   philox4x32_10(s.pixel, s.sample, 1u + s.depth, 0x5054u, P.seed_lo, P.seed_hi, w);
   float rr = 1.0f;
@@ -539,7 +578,7 @@ __device__ __forceinline__ int bounce(const TraceParams& P, const HitRow* tab, P
 #ifdef PTMI_DIAG_BUILD
   if constexpr (LEGACY) return shade_hit_r3(P, tab, s, best, tbest, w, rr, length);
 #endif
-  return shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, tab, s, best, tbest, w, rr, length);
+  return shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH, TEX>(P, tab, s, best, tbest, w, rr, length, X);
 }
 
 // The basis of light::diffuse (codelets.cpp:199-204) about a unit vector n: rx, ry with (rx, ry, n) orthonormal.  Its branch as
@@ -572,15 +611,23 @@ namespace ptd {
 
 // The second half of a loop trip of RayTraceKernel::compute (codelets.cpp:192-216): the ray has hit object `best` at
 // distance `tbest`; w = the bounce's Philox block, rr = its roulette weight.
-template <bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH, bool SMOOTH>
+template <bool GUIDE, int CAM, bool LIGHTS, bool POLY, bool PLAMPS, bool MESH, bool SMOOTH, bool TEX>
 __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab, PathState& s, int packed, float tbest,
-                                         const uint32_t (&w)[4], float rr, uint32_t& length) {
+                                         const uint32_t (&w)[4], float rr, uint32_t& length, [[maybe_unused]] const TexParams* X) {
   // the hit object's row, by per-lane index
   const int best = hit_object<MESH>(packed);
   const float4 hc = tab[best].centre, hn = tab[best].normal, hcol = tab[best].colour;
-  const float cx = hc.x, cy = hc.y, cz = hc.z, nx = hn.x, ny = hn.y, nz = hn.z, cr = hcol.x, cg = hcol.y, cb = hcol.z;
+  const float cx = hc.x, cy = hc.y, cz = hc.z, nx = hn.x, ny = hn.y, nz = hn.z;
+  float cr = hcol.x, cg = hcol.y, cb = hcol.z;
   const uint32_t bits = __float_as_uint(hcol.w);
   const int type = (int)(bits & 0xffu), is_disc = (int)(bits >> 8);
+  static_assert(SMOOTH || !TEX, "TEX implies SMOOTH");
+  if constexpr (TEX) {
+    // pt_set_mesh_texture: the texel multiplies the row's colour before the material branch (rule 5), so an emitter's radiance
+    // too -- the barycentrics are formed ahead of its early return.  A mirror ignores its colour, so it takes none of the steps.
+    if (is_disc == SHAPE_MESH && (__float_as_uint(hc.w) & kRowTextured) != 0u && type != MAT_SPECULAR)
+      texture_colour(P, *X, best, packed, s.o, s.d, cr, cg, cb);
+  }
   if (type == MAT_EMISSIVE) {                                 // :192-196 EMIT (the material type is not consulted), folded like ESCAPED (:269-271)
     // the radiance emission (.) T goes back in s.o (the path needs no hit point); s.d stays the ray that hit.  Tested before
     // the hit point and normal are formed: 62 VGPRs (63 with the per-wave emitter count); in the mirror / glass branch or after it
@@ -599,7 +646,7 @@ __device__ __forceinline__ int shade_hit(const TraceParams& P, const HitRow* tab
   if constexpr (MESH) {   // a mesh triangle's stored normal: the last three floats of its third vector, one 16-byte load per mesh hit
     if (is_disc == SHAPE_MESH) {
       const ptmesh::F4* const tri = P.mesh_tris + 3u * (size_t)hit_slot(packed);
-      if (SMOOTH && __float_as_uint(hc.w) != 0u) {
+      if (SMOOTH && (TEX ? (__float_as_uint(hc.w) & kRowSmooth) != 0u : __float_as_uint(hc.w) != 0u)) {
         // pt_set_mesh_normals: the shading normal (pt_mesh.h), rules 1-4; the flat mesh beside it takes the branch below.  The
         // barycentrics first, from the ray that hit; the corner normals are asked for once the triangle's floats are dead.
         if constexpr (SMOOTH) {
@@ -818,15 +865,15 @@ namespace ptd {
 // kernel's 157 KiB, so the trace kernel loses its place under the MFMA kernel (profiles/r04_trace_ablation.txt).
 constexpr int kTraceOpt = 3;   // (profiling build, bit 7: the object loop unrolled over the compile-time scene, diag/pt_trace_scene_c.h)
 template <uint32_t REFILL, int OPT = kTraceOpt, int CAM = CAM_BUILTIN, bool GUIDE = false, bool LIGHTS = false, bool POLY = false,
-          bool PLAMPS = false, bool MESH = false, bool SMOOTH = false>
-__device__ __forceinline__ void trace_body(const TraceParams& P) {
+          bool PLAMPS = false, bool MESH = false, bool SMOOTH = false, bool TEX = false>
+__device__ __forceinline__ void trace_body(const TraceParams& P, [[maybe_unused]] const TexParams* X = nullptr) {
   constexpr bool MAGIC = (OPT & 1) != 0, PRIMARY = (OPT & 2) != 0, SCENE_C = (OPT & 128) != 0, PIPE = (OPT & 256) != 0;
   __shared__ uint32_t wg_count;   // escaped paths queued by this workgroup
   __shared__ uint32_t wg_front, wg_back;   // camera rays of this workgroup that hit a diffuse / a mirror or glass object
   __shared__ uint32_t wg_state;            // survivors still alive after their first shading
   extern __shared__ __attribute__((aligned(16))) char smem[];
   HitRow* const hit_table = reinterpret_cast<HitRow*>(smem);   // P.n_objects rows (dynamic LDS: hit_table_bytes)
-  if (threadIdx.x == 0) { wg_count = 0; wg_front = 0; wg_back = 0; wg_state = 0; fill_hit_table<SMOOTH>(P, hit_table); }
+  if (threadIdx.x == 0) { wg_count = 0; wg_front = 0; wg_back = 0; wg_state = 0; fill_hit_table<SMOOTH, TEX>(P, hit_table); }
   __syncthreads();
 
   const uint32_t lane = threadIdx.x & 63u;
@@ -885,7 +932,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     const bool other = hit && !diffuse && !emitted;
     Vec3 erad = mk(0.f, 0.f, 0.f);
     if (emitted) {
-      const float4 e = hit_table[hit_object<MESH>(best)].colour;
+      float4 e = hit_table[hit_object<MESH>(best)].colour;
+      if constexpr (TEX) {   // a textured emissive mesh seen by the camera ray: colour x texel, as shade_hit forms it (only a mesh row's flag is set)
+        if ((__float_as_uint(hit_table[hit_object<MESH>(best)].centre.w) & kRowTextured) != 0u)
+          texture_colour(P, *X, hit_object<MESH>(best), best, st.o, st.d, e.x, e.y, e.z);
+      }
       erad = mk(e.x * st.T.x, e.y * st.T.y, e.z * st.T.z);
       P.plen[idx] = (uint8_t)(1u | 0x80u);
     }
@@ -939,7 +990,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       if constexpr ((OPT & 64) != 0) res = shade_hit_r3(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
       else
 #endif
-      res = shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length);
+      res = shade_hit<GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH, TEX>(P, hit_table, st, (int)note.w, __uint_as_float(note.z), w, 1.0f, length, X);
       if (res == STEP_CONTINUE) alive = true;
       else P.plen[idx] = (uint8_t)length;                                  // max_path_length = 1: the stack is full (guided: or the guide pointed below the surface)
       // (an emitter is never shaded here: the primary phase ends its camera rays and lists no survivor for them)
@@ -1011,7 +1062,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
     }
     int res = STEP_CONTINUE;
     uint32_t length = 0;
-    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, hit_table, st, length);
+    if (active) res = bounce<(OPT & 64) != 0, SCENE_C, PIPE, GUIDE, CAM, LIGHTS, POLY, PLAMPS, MESH, SMOOTH, TEX>(P, hit_table, st, length, X);
     const bool ended = active && res != STEP_CONTINUE;
     const bool escaped = active && res == STEP_ESCAPED;
     const bool emitted = active && res == STEP_EMITTED;
@@ -1101,6 +1152,22 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true, true>(P); }
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true, true>(P); }
+// pt_set_mesh_texture: the twelve again with the texture lookup (TEX, which carries the SMOOTH code: the rows' flags decide per
+// hit), launched only while a mesh in force has a texture.  The second argument holds the uv slots and the rows' descriptors.
+// No occupancy is pinned on the six that are not emitter-guided: the allocator's choice is recorded in
+// profiles/r26_mesh_textures.txt.  The emitter-guided six are pinned to six waves as everywhere.
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, false, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true, true, true>(P, &X); }
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true, true, true>(P, &X); }
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -1113,12 +1180,12 @@ struct PathRecordOut {  // layout of pt_path_record (include/ptmi.h)
 
 // One thread per requested path; same device functions as trace_kernel.  GUIDE: the guided twin (the camera is read at run
 // time either way: CAM_LENS rotates when P.cam_pose says so).  LIGHTS: the emitter-guided twin.
-template <bool GUIDE, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false, bool SMOOTH = false>
+template <bool GUIDE, bool LIGHTS = false, bool POLY = false, bool PLAMPS = false, bool MESH = false, bool SMOOTH = false, bool TEX = false>
 __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                                 uint32_t n, PathRecordOut* out) {
+                                                 uint32_t n, PathRecordOut* out, [[maybe_unused]] const TexParams* X = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   HitRow* const hit_table = reinterpret_cast<HitRow*>(smem);   // P.n_objects rows (dynamic LDS)
-  if (threadIdx.x == 0) fill_hit_table<SMOOTH>(P, hit_table);
+  if (threadIdx.x == 0) fill_hit_table<SMOOTH, TEX>(P, hit_table);
   __syncthreads();
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1128,7 +1195,7 @@ __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uin
   if (P.lens_a > 0.f) lens_ray(P, st.pixel, st.sample, camx, camy, st.o, st.d);
   uint32_t length = 0;
   int res;
-  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY, PLAMPS, MESH, SMOOTH>(P, hit_table, st, length); } while (res == STEP_CONTINUE);
+  do { res = bounce<false, false, false, GUIDE, CAM_LENS, LIGHTS, POLY, PLAMPS, MESH, SMOOTH, TEX>(P, hit_table, st, length, X); } while (res == STEP_CONTINUE);
   PathRecordOut r = {};
   r.length = length;
   r.escaped = res == STEP_ESCAPED ? 1u : (res == STEP_EMITTED ? 2u : 0u);   // 2: ended on an emitter (include/ptmi.h)
@@ -1174,6 +1241,16 @@ __global__ void trace_paths_lights_smooth_kernel(const TraceParams P, const uint
                                                  uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, false, true, true>(P, u, v, sample, n, out); }
 __global__ void trace_paths_lights_plamps_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
                                                         uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true, true>(P, u, v, sample, n, out); }
+
+// pt_set_mesh_texture: the textured twins of the four above
+__global__ void trace_paths_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                       uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true, false, true, true, true>(P, u, v, sample, n, out, &X); }
+__global__ void trace_paths_guide_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                             uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true, false, true, true, true>(P, u, v, sample, n, out, &X); }
+__global__ void trace_paths_lights_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                              uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, false, true, true, true>(P, u, v, sample, n, out, &X); }
+__global__ void trace_paths_lights_plamps_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
+                                                     uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true, true, true>(P, u, v, sample, n, out, &X); }
 
 // pt_mesh_intersect: the MESH instances' own nearest hit over caller rays, one thread per ray (the scene in the kernel arguments
 // is the world table).  BRUTE: a loop over all triangles of each mesh in place of the walk.
@@ -1222,6 +1299,30 @@ __global__ void mesh_shade_kernel(const TraceParams P, const float* origin, cons
   out_triangle[i] = mesh ? (int32_t)P.mesh_orig[hit_slot(best)] : -1;
   out_bary[2 * i] = a; out_bary[2 * i + 1] = b;
   out_normal[3 * i] = ns[0]; out_normal[3 * i + 1] = ns[1]; out_normal[3 * i + 2] = ns[2];
+}
+
+// pt_mesh_texel: the TEX instances' own nearest hit, uv interpolation and lookup over caller rays, one thread per ray (the world
+// table).  out_uv: the interpolated (s, t) of a hit on a triangle of a textured mesh; out_bgr: its texel, not multiplied by the
+// row's colour.  A mesh triangle without a texture: uv 0, bgr (1, 1, 1).  A miss or a hit on anything else: both 0.
+__global__ void mesh_texel_kernel(const TraceParams P, const TexParams X, const float* origin, const float* dir, uint32_t n, float* out_t,
+                                  int32_t* out_object, int32_t* out_triangle, float* out_uv, float* out_bgr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float ov[3] = {origin[3 * i], origin[3 * i + 1], origin[3 * i + 2]}, dv[3] = {dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
+  float tbest;
+  const int best = nearest_hit<false, true, true, false>(P, mk(ov[0], ov[1], ov[2]), mk(dv[0], dv[1], dv[2]), tbest);
+  const int obj = best < 0 ? -1 : hit_object<true>(best);
+  const bool mesh = obj >= 0 && P.obj[obj].is_disc == SHAPE_MESH;
+  float ts = 0.f, tt = 0.f, bgr[3] = {0.f, 0.f, 0.f};
+  if (mesh) {
+    bgr[0] = bgr[1] = bgr[2] = 1.f;
+    if (__float_as_uint(P.poly[obj].e2z) != 0u) texel_at_hit(P, X, obj, best, mk(ov[0], ov[1], ov[2]), mk(dv[0], dv[1], dv[2]), ts, tt, bgr);
+  }
+  out_t[i] = best < 0 ? 0.f : tbest;
+  out_object[i] = obj;
+  out_triangle[i] = mesh ? (int32_t)P.mesh_orig[hit_slot(best)] : -1;
+  out_uv[2 * i] = ts; out_uv[2 * i + 1] = tt;
+  out_bgr[3 * i] = bgr[0]; out_bgr[3 * i + 1] = bgr[1]; out_bgr[3 * i + 2] = bgr[2];
 }
 
 }  // namespace ptd

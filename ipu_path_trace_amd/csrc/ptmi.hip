@@ -546,6 +546,16 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
         if (P.lights.n && h->light.polygons)
           kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_smooth : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_smooth : ptd::trace_kernel_lights_plamps_smooth);
       }
+      if (h->scene_n && h->scene_mesh && h->mesh.textured()) {   // a mesh in force has a texture (pt_set_mesh_texture): the textured twin of each of the twelve, with its second argument
+        auto tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_tex : (P.cam_pose ? ptd::trace_kernel_pose_tex : ptd::trace_kernel_tex);
+        if (h->guide_set)
+          tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_tex : (P.cam_pose ? ptd::trace_kernel_pose_guide_tex : ptd::trace_kernel_guide_tex);
+        if (P.lights.n)
+          tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_tex : (P.cam_pose ? ptd::trace_kernel_pose_lights_tex : ptd::trace_kernel_lights_tex);
+        if (P.lights.n && h->light.polygons)
+          tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_tex : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_tex : ptd::trace_kernel_lights_plamps_tex);
+        hipLaunchKernelGGL(tex, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P, tex_params(h));
+      } else
       hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
     PT_HIP(hipGetLastError());
@@ -1616,6 +1626,126 @@ int pt_mesh_shade(pt_handle h, const float* origin, const float* dir, size_t n, 
   });
 }
 
+// The texture of mesh `mesh` of the scene in force.  Checked and copied on the host, and every device buffer allocated and filled,
+// before anything of the mesh changes; the trees are then marked stale, so that the next call that traces re-expands the uvs into
+// the slot order of the frame it traces in (build_meshes), exactly as after a pose change.
+int pt_set_mesh_texture(pt_handle h, uint32_t mesh, const pt_mesh_texture* t) {
+  if (!h) { g_create_error = "pt_set_mesh_texture: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
+  if (mesh >= count)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_mesh_texture: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
+  pt_context::MeshSet& M = h->mesh;
+  pt_context::MeshSet::One& m = M.mesh[mesh];
+  const auto drain = [&]() -> hipError_t {   // a step in flight may still read the image and the descriptors
+    for (hipStream_t s : {h->stream, h->trace_stream, h->acc_stream})
+      if (s) if (hipError_t e = hipStreamSynchronize(s)) return e;
+    return hipSuccess;
+  };
+  try {
+  if (!t) {   // remove: the mesh has its one colour again
+    if (m.uvs.empty()) return PT_OK;
+    PT_HIP(hipSetDevice(h->cfg.device));
+    PT_HIP(drain());
+    ptmesh::TexDesc table[PT_MAX_SCENE_OBJECTS];   // the new table in a temporary: committed only once it is on the device
+    memcpy(table, M.desc, sizeof(table));
+    table[m.object_index] = ptmesh::TexDesc{};
+    PT_HIP(hipMemcpy(M.d_desc, table, sizeof(table), hipMemcpyHostToDevice));
+    memcpy(M.desc, table, sizeof(table));
+    M.d_texels[mesh].reset();
+    std::vector<float>().swap(m.uvs);
+    m.n_uvs = 0; m.tex_w = m.tex_h = 0; m.tex_filter = m.tex_wrap = 0; m.uv_per_corner = false;
+  } else {
+    const std::string bad = ptmesh::check_texture(mesh, m.n_vertices, m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, t);
+    if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the mesh keeps what it had
+    std::vector<float> corner;
+    ptmesh::corner_uvs(m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, t->uvs, t->uv_indices, corner);
+    std::vector<ptmesh::F4> texels;
+    ptmesh::texel_vectors(t, texels);
+    if (M.d_texels.size() < M.mesh.size()) M.d_texels.resize(M.mesh.size());
+    PT_HIP(hipSetDevice(h->cfg.device));
+    if (!M.d_uvs) {
+      size_t triangles = 0;
+      for (const pt_context::MeshSet::One& o : M.mesh) triangles += o.n_triangles;
+      DevBuf<float> uvs;
+      DevBuf<ptmesh::TexDesc> desc;
+      hipError_t e = dev_alloc(uvs, 6 * triangles);
+      if (e == hipSuccess) e = dev_alloc(desc, PT_MAX_SCENE_OBJECTS);
+      if (e == hipSuccess) e = hipMemset(uvs, 0, 6 * triangles * sizeof(float));
+      if (e != hipSuccess)
+        return fail(h, hip_status(e), "pt_set_mesh_texture: allocating " + std::to_string(6 * triangles * sizeof(float) + sizeof(M.desc)) + " bytes: " + hipGetErrorString(e));
+      M.d_uvs = std::move(uvs);
+      M.d_desc = std::move(desc);
+    }
+    DevBuf<ptmesh::F4> image;
+    hipError_t e = dev_alloc(image, texels.size());
+    if (e == hipSuccess) e = hipMemcpy(image, texels.data(), texels.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+      return fail(h, hip_status(e), "pt_set_mesh_texture: allocating " + std::to_string(texels.size() * sizeof(ptmesh::F4)) + " bytes: " + hipGetErrorString(e));
+    PT_HIP(drain());
+    ptmesh::TexDesc d{};
+    d.texels = image; d.width = t->width; d.height = t->height; d.filter = t->filter; d.wrap = t->wrap;
+    ptmesh::TexDesc table[PT_MAX_SCENE_OBJECTS];   // the new table in a temporary: a failed copy leaves the host's table, and with it
+    memcpy(table, M.desc, sizeof(table));          // every later upload, without a pointer into the image freed on the way out
+    table[m.object_index] = d;
+    PT_HIP(hipMemcpy(M.d_desc, table, sizeof(table), hipMemcpyHostToDevice));
+    memcpy(M.desc, table, sizeof(table));
+    M.d_texels[mesh] = std::move(image);   // (frees the image it replaces)
+    m.uvs.swap(corner);
+    m.n_uvs = t->n_uvs; m.tex_w = t->width; m.tex_h = t->height; m.tex_filter = t->filter; m.tex_wrap = t->wrap;
+    m.uv_per_corner = t->uv_indices != nullptr;
+  }
+  } catch (const std::bad_alloc&) {
+    return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_mesh_texture: out of host memory for the texture's copy");
+  }
+  M.built = false;        // the next trace rebuilds: rows' flags and the uvs in slot order
+  h->feature_gen += 1;
+  return PT_OK;
+}
+
+int pt_get_mesh_texture_info(pt_handle h, uint32_t mesh, pt_mesh_texture_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_mesh_texture_info))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_texture_info: struct_size must be " + std::to_string(sizeof(pt_mesh_texture_info)));
+  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
+  if (mesh >= count)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_texture_info: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
+  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  if (m.uvs.empty()) return PT_OK;
+  out->has_texture = 1u;
+  out->per_corner = m.uv_per_corner ? 1u : 0u;
+  out->width = m.tex_w; out->height = m.tex_h;
+  out->filter = m.tex_filter; out->wrap = m.tex_wrap;
+  out->n_uvs = m.n_uvs;
+  out->device_bytes = (uint64_t)m.n_triangles * 6 * sizeof(float) + (uint64_t)m.tex_w * m.tex_h * sizeof(ptmesh::F4);
+  return PT_OK;
+}
+
+int pt_mesh_texel(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object, int32_t* out_triangle,
+                  float* out_uv, float* out_bgr) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_texel: the scene in force holds no mesh (pt_set_scene_meshes)");
+  if (n == 0) return PT_OK;
+  if (!origin || !dir || !out_t || !out_object || !out_triangle || !out_uv || !out_bgr) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
+  if (n >= (1ull << 31) / 3) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many rays");
+  if (int rc = ensure_meshes(h, true)) return rc;   // the world frame, whatever the camera
+  ptd::TraceParams P;
+  memset(&P, 0, sizeof(P));
+  fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->mesh.row);
+  bind_meshes(h, P);
+  const ptd::TexParams X = tex_params(h);   // (no textured mesh: every row's flag is 0 and the kernel reads neither pointer)
+  GuideSpan s[7] = {{origin, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr}, {nullptr, out_t, n * 4, nullptr},
+                    {nullptr, out_object, n * 4, nullptr}, {nullptr, out_triangle, n * 4, nullptr}, {nullptr, out_uv, n * 8, nullptr},
+                    {nullptr, out_bgr, n * 12, nullptr}};
+  return guide_hook(h, s, 7, [&]() {
+    hipLaunchKernelGGL(ptd::mesh_texel_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P, X,
+                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev), (uint32_t)n,
+                       reinterpret_cast<float*>(s[2].dev), reinterpret_cast<int32_t*>(s[3].dev), reinterpret_cast<int32_t*>(s[4].dev),
+                       reinterpret_cast<float*>(s[5].dev), reinterpret_cast<float*>(s[6].dev));
+  });
+}
+
 int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uint32_t* n) {
   if (!n) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "null count") : PT_ERR_INVALID_ARGUMENT;
   pt_scene_object builtin[ptd::kBuiltinObjects];
@@ -1686,6 +1816,12 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   if (h->scene_n && h->scene_mesh && h->mesh.smooth())   // the smooth twins (pt_set_mesh_normals)
     kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_smooth_kernel : ptd::trace_paths_lights_smooth_kernel)
                         : (h->guide_set ? ptd::trace_paths_guide_smooth_kernel : ptd::trace_paths_smooth_kernel);
+  if (h->scene_n && h->scene_mesh && h->mesh.textured()) {   // the textured twins (pt_set_mesh_texture)
+    auto tex = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_tex_kernel : ptd::trace_paths_lights_tex_kernel)
+                          : (h->guide_set ? ptd::trace_paths_guide_tex_kernel : ptd::trace_paths_tex_kernel);
+    hipLaunchKernelGGL(tex, dim3(((uint32_t)n + 127) / 128), dim3(128),
+                       ptd::hit_table_bytes(P.n_objects), h->stream, P, tex_params(h), d_u, d_v, d_s, (uint32_t)n, d_out);
+  } else
   hipLaunchKernelGGL(kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
                      ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());

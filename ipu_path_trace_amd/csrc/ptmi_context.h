@@ -206,6 +206,11 @@ struct pt_context {
       uint32_t n_vertices, n_normals;
       bool per_corner;
       std::vector<float> normals;
+      // texture (pt_set_mesh_texture): the (s, t) per corner in triangle order, six floats per triangle; empty: no texture
+      uint32_t n_uvs = 0, tex_w = 0, tex_h = 0;
+      int32_t tex_filter = 0, tex_wrap = 0;
+      bool uv_per_corner = false;
+      std::vector<float> uvs;
     };
     std::vector<One> mesh;                 // in declaration order
     std::vector<float> world;              // twelve floats per triangle (v0, e1, e2, n), the meshes one after the other
@@ -215,6 +220,11 @@ struct pt_context {
     std::vector<uint32_t> indices;         // the meshes' own [n_triangles][3], one after the other: per-vertex normals are looked up by them
     DevBuf<ptmesh::F4> d_normals;          // three per slot over ALL slots, allocated by the first pt_set_mesh_normals of the scene
     bool smooth() const { for (const One& m : mesh) if (!m.normals.empty()) return true; return false; }
+    DevBuf<float> d_uvs;                   // six per slot over ALL slots, allocated by the first pt_set_mesh_texture of the scene
+    DevBuf<ptmesh::TexDesc> d_desc;        // one per scene row (PT_MAX_SCENE_OBJECTS), allocated with d_uvs; desc: its host copy
+    std::vector<DevBuf<ptmesh::F4>> d_texels;   // mesh m's own image, (B, G, R, 0) per texel; one entry per mesh once a texture was attached
+    ptmesh::TexDesc desc[PT_MAX_SCENE_OBJECTS] = {};
+    bool textured() const { for (const One& m : mesh) if (!m.uvs.empty()) return true; return false; }
     ptd::PolyEdges row[PT_MAX_SCENE_OBJECTS] = {};   // what a mesh's row carries in the kernel arguments (ptd::MeshRow)
     bool built = false, built_world = false;         // the trees on the device are valid / were built in the world frame ...
     ptcamera::Basis built_for{};                     // ... or for this camera
@@ -484,6 +494,8 @@ void bind_meshes(pt_handle h, ptd::TraceParams& P) {
   P.mesh_orig = h->mesh.d_orig;
   P.mesh_normals = h->mesh.d_normals;
 }
+// The TEX instances' second argument (pt_set_mesh_texture): valid while h->mesh.textured()
+ptd::TexParams tex_params(pt_handle h) { return ptd::TexParams{h->mesh.d_uvs, h->mesh.d_desc}; }
 
 // Transforms every mesh of M into the frame of `cam` (nullptr: the world frame, which is the built-in camera's), builds its tree
 // and copies trees and triangles into M's device buffers, which hold any tree of these triangles (2 T - 1 nodes): no allocation on
@@ -496,6 +508,7 @@ int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam
   M.built = false;
   std::vector<float> frames;
   std::vector<ptmesh::F4> normals;
+  std::vector<float> uvs;
   ptmesh::Built B;
   for (pt_context::MeshSet::One& m : M.mesh) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -515,7 +528,12 @@ int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam
       ptmesh::slot_normals(m.normals.data(), B.orig.data(), m.n_triangles, cam, normals.data());
       PT_HIP(hipMemcpy(M.d_normals + 3 * (size_t)m.tri_base, normals.data(), normals.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
     }
-    const ptd::MeshRow row{m.node_base, m.tri_base, m.n_nodes, m.n_triangles, m.normals.empty() ? 0u : 1u, 0u};
+    if (!m.uvs.empty()) {   // the corner uvs into the new slot order, untransformed (the buffer exists: pt_set_mesh_texture)
+      uvs.resize(6 * (size_t)m.n_triangles);
+      ptmesh::slot_uvs(m.uvs.data(), B.orig.data(), m.n_triangles, uvs.data());
+      PT_HIP(hipMemcpy(M.d_uvs + 6 * (size_t)m.tri_base, uvs.data(), uvs.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const ptd::MeshRow row{m.node_base, m.tri_base, m.n_nodes, m.n_triangles, m.normals.empty() ? 0u : 1u, m.uvs.empty() ? 0u : 1u};
     memcpy(&M.row[m.object_index], &row, sizeof(row));
   }
   M.built = true;

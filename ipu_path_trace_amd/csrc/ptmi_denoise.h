@@ -35,6 +35,10 @@ int ensure_features(pt_handle h) {
   const uint32_t px = h->cfg.width * h->cfg.height;
   auto kernel = h->scene_n && h->scene_poly ? ptd::features_kernel_poly : ptd::features_kernel;
   if (h->scene_n && h->scene_mesh) kernel = h->mesh.smooth() ? ptd::features_kernel_smooth : ptd::features_kernel_mesh;
+  if (h->scene_n && h->scene_mesh && h->mesh.textured())   // pt_set_mesh_texture: albedo = colour x texel
+    hipLaunchKernelGGL(ptd::features_kernel_tex, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0,
+                       h->stream, P, tex_params(h), h->d_feat[0], h->d_feat[1]);
+  else
   hipLaunchKernelGGL(kernel, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0, h->stream, P,
                      h->d_feat[0], h->d_feat[1]);
   PT_HIP(hipGetLastError());

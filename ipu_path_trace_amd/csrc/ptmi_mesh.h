@@ -137,6 +137,68 @@ inline void slot_normals(const float* corner, const uint32_t* orig, size_t n_tri
     }
 }
 
+// ---- textures (pt_set_mesh_texture, include/ptmi.h)
+
+// The checks of pt_set_mesh_texture that need no device, in the contract's order; "" if the texture is valid.  indices: the mesh's
+// own [n_triangles][3] (used when uv_indices is null: per-vertex uvs).  Only referenced uvs are examined.
+inline std::string check_texture(uint32_t mesh, uint32_t n_vertices, uint32_t n_triangles, const uint32_t* indices, const pt_mesh_texture* t) {
+  const std::string at = "mesh " + std::to_string(mesh) + ": ";
+  if (t->struct_size != sizeof(pt_mesh_texture))
+    return at + "texture: struct_size must be " + std::to_string(sizeof(pt_mesh_texture)) + " (got " + std::to_string(t->struct_size) + ")";
+  if (t->width < 1 || t->width > PT_MESH_TEXTURE_MAX_SIZE || t->height < 1 || t->height > PT_MESH_TEXTURE_MAX_SIZE)
+    return at + "texture: width and height must be in 1.." + std::to_string(PT_MESH_TEXTURE_MAX_SIZE) + " (got " + std::to_string(t->width) + " x " + std::to_string(t->height) + ")";
+  if (t->filter != PT_TEX_FILTER_NEAREST && t->filter != PT_TEX_FILTER_BILINEAR)
+    return at + "texture: filter must be 0 (nearest) or 1 (bilinear) (got " + std::to_string(t->filter) + ")";
+  if (t->wrap != PT_TEX_WRAP_REPEAT && t->wrap != PT_TEX_WRAP_CLAMP)
+    return at + "texture: wrap must be 0 (repeat) or 1 (clamp) (got " + std::to_string(t->wrap) + ")";
+  if (!t->bgr) return at + "texture: null bgr";
+  if (!t->uvs) return at + "texture: null uvs with n_uvs = " + std::to_string(t->n_uvs);
+  if (!t->uv_indices && t->n_uvs != n_vertices)
+    return at + "texture: n_uvs must equal n_vertices = " + std::to_string(n_vertices) + " when uv_indices is null (got " + std::to_string(t->n_uvs) + ")";
+  for (uint32_t r = 0; r < t->height; ++r)
+    for (uint32_t c = 0; c < t->width; ++c)
+      for (int k = 0; k < 3; ++k) {
+        const float v = t->bgr[3 * ((size_t)r * t->width + c) + k];
+        if (!std::isfinite(v) || v < 0.f)
+          return at + "texture: texel (row " + std::to_string(r) + ", column " + std::to_string(c) + ") channel " + std::to_string(k) +
+                 " must be finite and >= 0 (got " + ptscene::num(v) + ")";
+      }
+  const uint32_t* ix = t->uv_indices ? t->uv_indices : indices;
+  for (uint32_t j = 0; j < n_triangles; ++j)
+    for (int c = 0; c < 3; ++c) {
+      const std::string tri = at + "triangle " + std::to_string(j) + ": ";
+      const uint32_t k = ix[3 * (size_t)j + c];
+      if (k >= t->n_uvs)
+        return tri + (t->uv_indices ? "uv_indices[" : "indices[") + std::to_string(c) + "] must be < n_uvs = " + std::to_string(t->n_uvs) + " (got " + std::to_string(k) + ")";
+      for (int q = 0; q < 2; ++q)
+        if (!std::isfinite(t->uvs[2 * (size_t)k + q])) return tri + "uvs[" + std::to_string(k) + "] must be finite (got " + ptscene::num(t->uvs[2 * (size_t)k + q]) + ")";
+    }
+  return "";
+}
+
+// The (s, t) per corner in triangle order, six floats per triangle.  Call on a texture check_texture() accepted.
+inline void corner_uvs(uint32_t n_triangles, const uint32_t* indices, const float* uvs, const uint32_t* uv_indices, std::vector<float>& out) {
+  const uint32_t* ix = uv_indices ? uv_indices : indices;
+  out.resize(6 * (size_t)n_triangles);
+  for (size_t e = 0; e < 3 * (size_t)n_triangles; ++e) {
+    out[2 * e] = uvs[2 * (size_t)ix[e]];
+    out[2 * e + 1] = uvs[2 * (size_t)ix[e] + 1];
+  }
+}
+
+// The corner uvs as the kernel reads them: six floats per slot in leaf order (orig: slot -> triangle).  No frame applies to them.
+inline void slot_uvs(const float* corner, const uint32_t* orig, size_t n_triangles, float* out) {
+  for (size_t s = 0; s < n_triangles; ++s)
+    for (int k = 0; k < 6; ++k) out[6 * s + k] = corner[6 * (size_t)orig[s] + k];
+}
+
+// The image as the kernel reads it: one (B, G, R, 0) vector per texel.
+inline void texel_vectors(const pt_mesh_texture* t, std::vector<F4>& out) {
+  const size_t n = (size_t)t->width * t->height;
+  out.resize(n);
+  for (size_t i = 0; i < n; ++i) out[i] = F4{t->bgr[3 * i], t->bgr[3 * i + 1], t->bgr[3 * i + 2], 0.f};
+}
+
 // ---- frames: twelve floats per triangle, v0, e1, e2, n
 
 constexpr size_t kFrameFloats = 12;

@@ -96,7 +96,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"devices", 0, "", false, false, "GPU ordinal of every logical device, e.g. 0,1,2,3 (default: 0 .. ipus-1). Several logical devices may share a GPU (0,0): HDR tiles are then gathered through the host."},
       {"host-gather", 0, "false", false, true, "Gather the HDR tiles of the devices through the host (one copy per device) instead of over an RCCL communicator."},
       {"share-nif-evaluations", 0, "off", false, false, "off | batch | step: escaped paths with bit-identical (u, v) share one NIF evaluation within a kernel batch or a whole step (exact: the image is bit-identical to off; the reference evaluates every escaped path)."},
-      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}; a \"triangle\" or \"parallelogram\" takes \"vertices\": [[x, y, z], [x, y, z], [x, y, z]] (v0, v1, v2; the parallelogram's fourth corner is v1 + v2 - v0) instead of centre, radius and normal; a \"mesh\" (one object of the table, one material, flat shading unless \"normals\" is given) takes either \"vertices\": [[x, y, z], ...] and \"triangles\": [[a, b, c], ...] (indices from 0) or \"file\": \"x.obj\" (relative to the scene file; v and f lines, faces triangulated as fans), and optionally \"scale\": s or [sx, sy, sz] and \"translate\": [x, y, z], applied in binary32 on the host as v * scale + translate before anything else; \"normals\": \"file\" (the OBJ's vn lines and v//vn or v/vt/vn corners) or \"normals\": [[x, y, z], ...] with an optional \"normal_indices\": [[a, b, c], ...] per triangle (else one normal per vertex) shades the mesh smooth; normals are not scaled, so a non-uniform \"scale\" is refused with them.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
+      {"scene", 0, "", false, false, "FILE.json: render the scene of the file instead of the built-in one -- {\"objects\": [...]}, 1..32 objects, each {\"shape\": \"sphere\" | \"disc\", \"centre\": [x, y, z], \"radius\": r, \"normal\": [x, y, z] (disc), \"material\": \"diffuse\" | \"specular\" | \"refractive\" | \"emissive\", \"colour\": [r, g, b] (\"emission\" for an emitter; default 1, 1, 1)}; a \"triangle\" or \"parallelogram\" takes \"vertices\": [[x, y, z], [x, y, z], [x, y, z]] (v0, v1, v2; the parallelogram's fourth corner is v1 + v2 - v0) instead of centre, radius and normal; a \"mesh\" (one object of the table, one material, flat shading unless \"normals\" is given) takes either \"vertices\": [[x, y, z], ...] and \"triangles\": [[a, b, c], ...] (indices from 0) or \"file\": \"x.obj\" (relative to the scene file; v and f lines, faces triangulated as fans), and optionally \"scale\": s or [sx, sy, sz] and \"translate\": [x, y, z], applied in binary32 on the host as v * scale + translate before anything else; \"normals\": \"file\" (the OBJ's vn lines and v//vn or v/vt/vn corners) or \"normals\": [[x, y, z], ...] with an optional \"normal_indices\": [[a, b, c], ...] per triangle (else one normal per vertex) shades the mesh smooth; normals are not scaled, so a non-uniform \"scale\" is refused with them; \"texture\": \"x.hdr|.pfm|.exr\" (relative to the scene file; a LINEAR float image, no 8-bit formats and no sRGB decoding) with \"uvs\": \"file\" (the OBJ's vt lines and v/vt or v/vt/vn corners) or \"uvs\": [[s, t], ...] with an optional \"uv_indices\": [[a, b, c], ...] per triangle (else one per vertex), and optionally \"texture_filter\": \"nearest\" | \"bilinear\" (default) and \"texture_wrap\": \"repeat\" (default) | \"clamp\", multiplies the mesh's colour by the image.  Optional \"camera\": {\"position\": [x, y, z], \"look_at\": [x, y, z], \"up\": [x, y, z], \"lens_radius\": a, \"focus_distance\": F} (defaults: the built-in pinhole at the origin looking down -z; a lens needs a focus distance)."},
       {"env-map", 0, "", false, false, "FILE: an equirectangular HDR image as the environment light instead of the NIF -- Radiance .hdr / .pic (RGBE, orientation -Y H +X W), .pfm or .exr (uncompressed float B, G, R). No NIF is loaded; not together with --constant-env. --env-map-rotation applies as to the NIF."},
       {"env-map-filter", 0, "bilinear", false, false, "nearest | bilinear: how --env-map is looked up between texels."},
       {"env-guide", 0, "", false, false, "FILE | map | env: guide diffuse bounces by the luminance of an equirectangular HDR image (formats of --env-map; 'map' reuses the file of --env-map; 'env' needs no file: the guide is built on the device from the environment in force -- the NIF of --assets, the map or the constant -- and follows a NIF loaded later). Changes how directions are sampled, not the light: the image stays unbiased under any environment, e.g. a NIF guided by the image it was trained from."},
@@ -164,11 +164,29 @@ std::uint64_t nifMemoBytes(const std::string& text) {
 // checked as pt_set_scene_ex checks it and leaves its table in `ex` (empty otherwise: the file goes through pt_set_scene as ever).
 // A "mesh" also takes "normals" -- "file" (the OBJ's vn lines and corner indices) or an inline array of directions with an optional
 // "normal_indices", one triple per triangle -- and then shades smooth (pt_set_mesh_normals); without the key it stays flat.
+// A "mesh" also takes "texture": an image file read through EnvMapReader, relative to the scene file, with "uvs" -- "file" (the OBJ's
+// vt lines and corner indices) or an inline array of (s, t) with an optional "uv_indices" -- and optionally "texture_filter" and
+// "texture_wrap" (pt_set_mesh_texture); `textures` receives one entry per mesh, an empty image for a mesh without the key.
 // A "mesh" takes inline "vertices" / "triangles" or "file": "x.obj" (relative to the scene file), and optionally "scale" and
 // "translate", applied here in binary32 -- v * scale, then + translate, one rounded operation each -- before anything else; a
 // file that holds one is checked as pt_set_scene_meshes checks it and leaves its geometry in `meshes`, in the order of its rows.
+// What pt_set_mesh_texture takes, over a mesh's texture coordinates and its image as read.  (A size beyond 32 bits cannot come out
+// of EnvMapReader: it caps a side at 16384; the library's own cap of 8192 is its check's to report.)
+static pt_mesh_texture meshTextureView(const objreader::Mesh& m, const SceneTexture& tex) {
+  pt_mesh_texture t{};
+  t.struct_size = (std::uint32_t)sizeof(t);
+  t.width = (std::uint32_t)tex.image.width; t.height = (std::uint32_t)tex.image.height;
+  t.filter = tex.filter; t.wrap = tex.wrap;
+  t.bgr = tex.image.bgr.data();
+  t.uvs = m.uvs.data();
+  t.n_uvs = (std::uint32_t)(m.uvs.size() / 2);
+  t.uv_indices = m.uv_indices.empty() ? nullptr : m.uv_indices.data();
+  return t;
+}
+
 std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& camera, bool& hasCamera,
-                                           std::vector<pt_scene_object_ex>& ex, std::vector<objreader::Mesh>& meshes) {
+                                           std::vector<pt_scene_object_ex>& ex, std::vector<objreader::Mesh>& meshes,
+                                           std::vector<SceneTexture>& textures) {
   const std::string at = "--scene '" + path + "': ";
   std::ifstream in(path, std::ios::binary);
   if (!in) throw std::runtime_error(at + "cannot open the file");
@@ -206,7 +224,8 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     for (const auto& kv : v.obj)
       if (kv.first != "shape" && kv.first != "material" && kv.first != "centre" && kv.first != "radius" && kv.first != "normal" &&
           kv.first != "colour" && kv.first != "emission" && kv.first != "vertices" && kv.first != "triangles" && kv.first != "file" &&
-          kv.first != "scale" && kv.first != "translate" && kv.first != "normals" && kv.first != "normal_indices")
+          kv.first != "scale" && kv.first != "translate" && kv.first != "normals" && kv.first != "normal_indices" &&
+          kv.first != "texture" && kv.first != "uvs" && kv.first != "uv_indices" && kv.first != "texture_filter" && kv.first != "texture_wrap")
         throw std::runtime_error(at + obj + "unknown key \"" + kv.first + "\"");
     pt_scene_object& o = objs[i];
     o = pt_scene_object{};
@@ -227,23 +246,37 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
     pt_scene_object_ex& x = objsEx[i];
     x = pt_scene_object_ex{};
     if (!mesh)
-      for (const char* key : {"triangles", "file", "scale", "translate", "normals", "normal_indices"})
+      for (const char* key : {"triangles", "file", "scale", "translate", "normals", "normal_indices", "texture", "uvs", "uv_indices",
+                              "texture_filter", "texture_wrap"})
         if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a " + shape);
     if (mesh) {
       for (const char* key : {"centre", "radius", "normal"})
         if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a mesh");
       objreader::Mesh m;
+      SceneTexture tex;
+      const std::size_t slash = path.find_last_of('/');
+      auto beside = [&](const std::string& name) {   // a file named in the scene file is relative to it
+        return (!name.empty() && name[0] == '/') || slash == std::string::npos ? name : path.substr(0, slash + 1) + name;
+      };
       if (v.has("file")) {
         if (v.has("vertices") || v.has("triangles")) throw std::runtime_error(at + obj + "give \"file\" or \"vertices\" and \"triangles\", not both");
         if (v.at("file").type != json::Value::String) throw std::runtime_error(at + obj + "\"file\" must be a string");
         const std::string& name = v.at("file").str;
-        const std::size_t slash = path.find_last_of('/');
-        const std::string full = (!name.empty() && name[0] == '/') || slash == std::string::npos ? name : path.substr(0, slash + 1) + name;
+        const std::string full = beside(name);
         // "normals": "file" takes the OBJ's vn lines and its corners' normal indices (smooth shading: pt_set_mesh_normals)
         const bool fromFile = v.has("normals") && v.at("normals").type == json::Value::String;
         if (fromFile && v.at("normals").str != "file") throw std::runtime_error(at + obj + "\"normals\" must be \"file\" or an array of directions");
         if (fromFile && v.has("normal_indices")) throw std::runtime_error(at + obj + "\"normal_indices\" does not apply to \"normals\": \"file\"");
         try { m = objreader::read(full, fromFile); } catch (const std::exception& e) { throw std::runtime_error(at + obj + e.what()); }
+        if (v.has("uvs") && v.at("uvs").type == json::Value::String) {   // "uvs": "file" takes the OBJ's vt lines and its corners' texture indices
+          if (v.at("uvs").str != "file") throw std::runtime_error(at + obj + "\"uvs\" must be \"file\" or an array of (s, t) pairs");
+          if (v.has("uv_indices")) throw std::runtime_error(at + obj + "\"uv_indices\" does not apply to \"uvs\": \"file\"");
+          try {
+            objreader::Mesh t = objreader::read_with_uvs(full);   // the same triangles in the same order: one fan rule
+            m.uvs = std::move(t.uvs);
+            m.uv_indices = std::move(t.uv_indices);
+          } catch (const std::exception& e) { throw std::runtime_error(at + obj + e.what()); }
+        }
       } else {
         if (!v.has("vertices") || !v.has("triangles")) throw std::runtime_error(at + obj + "a mesh needs \"file\", or \"vertices\" and \"triangles\"");
         const json::Value& vs = v.at("vertices");
@@ -292,6 +325,54 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
           }
         }
       } else if (v.has("normal_indices")) throw std::runtime_error(at + obj + "\"normal_indices\" needs \"normals\"");
+      if (v.has("texture")) {
+        if (v.at("texture").type != json::Value::String) throw std::runtime_error(at + obj + "\"texture\" must be a string (an .hdr, .pfm or .exr file)");
+        if (!v.has("uvs")) throw std::runtime_error(at + obj + "\"texture\" needs \"uvs\" (\"file\" or an array of (s, t) pairs)");
+        if (v.at("uvs").type == json::Value::String) {
+          if (!v.has("file")) throw std::runtime_error(at + obj + "\"uvs\": \"file\" needs \"file\"");
+        } else {   // inline: (s, t) pairs, and optionally an index triple per triangle (else one pair per vertex)
+          const json::Value& us = v.at("uvs");
+          if (us.type != json::Value::Array || us.arr.empty()) throw std::runtime_error(at + obj + "\"uvs\" must be \"file\" or a non-empty array of (s, t) pairs");
+          for (const json::Value& q : us.arr) {
+            if (q.type != json::Value::Array || q.arr.size() != 2) throw std::runtime_error(at + obj + "\"uvs\" must hold arrays of 2 numbers");
+            for (const json::Value& c : q.arr) {
+              if (c.type != json::Value::Number) throw std::runtime_error(at + obj + "\"uvs\" must hold numbers");
+              m.uvs.push_back((float)c.num);
+            }
+          }
+          if (v.has("uv_indices")) {
+            const json::Value& is = v.at("uv_indices");
+            if (is.type != json::Value::Array || is.arr.size() != m.indices.size() / 3)
+              throw std::runtime_error(at + obj + "\"uv_indices\" must hold one index triple per triangle");
+            for (const json::Value& q : is.arr) {
+              if (q.type != json::Value::Array || q.arr.size() != 3) throw std::runtime_error(at + obj + "\"uv_indices\" must hold arrays of 3 indices");
+              for (const json::Value& c : q.arr) {
+                if (c.type != json::Value::Number || !(c.num >= 0.0) || c.num > 4294967295.0 || c.num != std::floor(c.num))
+                  throw std::runtime_error(at + obj + "\"uv_indices\" must hold non-negative integers");
+                m.uv_indices.push_back((std::uint32_t)c.num);
+              }
+            }
+          }
+        }
+        for (const char* key : {"texture_filter", "texture_wrap"})
+          if (v.has(key) && v.at(key).type != json::Value::String) throw std::runtime_error(at + obj + "\"" + key + "\" must be a string");
+        if (v.has("texture_filter")) {
+          const std::string& f = v.at("texture_filter").str;
+          if (f == "nearest") tex.filter = PT_TEX_FILTER_NEAREST;
+          else if (f == "bilinear") tex.filter = PT_TEX_FILTER_BILINEAR;
+          else throw std::runtime_error(at + obj + "unknown \"texture_filter\" '" + f + "' (nearest, bilinear)");
+        }
+        if (v.has("texture_wrap")) {
+          const std::string& w = v.at("texture_wrap").str;
+          if (w == "repeat") tex.wrap = PT_TEX_WRAP_REPEAT;
+          else if (w == "clamp") tex.wrap = PT_TEX_WRAP_CLAMP;
+          else throw std::runtime_error(at + obj + "unknown \"texture_wrap\" '" + w + "' (repeat, clamp)");
+        }
+        try { tex.image = env_map::read(beside(v.at("texture").str)); } catch (const std::exception& e) { throw std::runtime_error(at + obj + "\"texture\": " + e.what()); }
+      } else {
+        for (const char* key : {"uvs", "uv_indices", "texture_filter", "texture_wrap"})
+          if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" needs \"texture\"");
+      }
       float scale[3] = {1.f, 1.f, 1.f}, translate[3] = {0.f, 0.f, 0.f};
       if (v.has("scale")) {
         if (v.at("scale").type == json::Value::Number) scale[0] = scale[1] = scale[2] = (float)v.at("scale").num;
@@ -308,6 +389,7 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
           m.vertices[k] = moved;
         }
       meshes.push_back(std::move(m));
+      textures.push_back(std::move(tex));
     } else if (polygon) {
       for (const char* key : {"centre", "radius", "normal"})
         if (v.has(key)) throw std::runtime_error(at + obj + "\"" + key + "\" does not apply to a " + shape + " (it takes \"vertices\")");
@@ -355,6 +437,14 @@ std::vector<pt_scene_object> loadSceneFile(const std::string& path, pt_camera& c
                                                    m.indices.data(), m.normals.data(), (std::uint32_t)(m.normals.size() / 3),
                                                    m.normal_indices.empty() ? nullptr : m.normal_indices.data());
     if (!badn.empty()) throw std::runtime_error(at + badn);
+  }
+  for (std::size_t k = 0; k < meshes.size(); ++k) {   // the textures, as pt_set_mesh_texture checks them, before a device is attached
+    const objreader::Mesh& m = meshes[k];
+    if (textures[k].image.bgr.empty()) continue;
+    const pt_mesh_texture t = meshTextureView(m, textures[k]);
+    const std::string badt = ptmesh::check_texture((std::uint32_t)k, (std::uint32_t)(m.vertices.size() / 3), (std::uint32_t)(m.indices.size() / 3),
+                                                   m.indices.data(), &t);
+    if (!badt.empty()) throw std::runtime_error(at + badt);
   }
   ex.clear();
   if (anyPolygon) ex = objsEx;
@@ -430,7 +520,7 @@ void PathTracerApp::init(const OptionMap& options) {
     throw std::runtime_error("--denoise-iterations must be 1..6; got " + args.str("denoise-iterations"));
   for (const char* name : {"denoise-sigma-colour", "denoise-sigma-normal", "denoise-sigma-depth"})
     if (!std::isfinite(args.f32(name))) throw std::runtime_error(std::string("--") + name + " must be finite; got " + args.str(name));
-  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera, sceneEx, sceneMeshes);
+  if (args.has("scene") && !args.str("scene").empty()) scene = loadSceneFile(args.str("scene"), camera, hasCamera, sceneEx, sceneMeshes, sceneTextures);
   // the reference hands --outfile to cv::imwrite, which picks the codec by extension (AccumulatedImage.cpp:49) and throws for one
   // it has no writer for -- here before anything is rendered, not at the first save interval
   if (!image_io::ldrWriterFor(args.str("outfile")))
@@ -657,6 +747,11 @@ void PathTracerApp::attach() {
         if (!m.normals.empty() && pt_set_mesh_normals(h, (std::uint32_t)k, m.normals.data(), (std::uint32_t)(m.normals.size() / 3),
                                                      m.normal_indices.empty() ? nullptr : m.normal_indices.data()))
           throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
+      }
+      for (std::size_t k = 0; k < sceneMeshes.size(); ++k) {   // a mesh with "texture", after its normals
+        if (sceneTextures[k].image.bgr.empty()) continue;
+        const pt_mesh_texture t = meshTextureView(sceneMeshes[k], sceneTextures[k]);
+        if (pt_set_mesh_texture(h, (std::uint32_t)k, &t)) throw std::runtime_error(std::string("--scene: ") + pt_last_error(h));
       }
     } else if (!sceneEx.empty()) {   // the file holds a polygon
       if (pt_set_scene_ex(h, sceneEx.data(), (std::uint32_t)sceneEx.size(), (std::uint32_t)sizeof(pt_scene_object_ex)))

@@ -24,6 +24,13 @@ struct PathTracerState {
   AccumulatedImage film;
 };
 
+/// --scene: the "texture" of a mesh -- the image as EnvMapReader read it and the two modes (pt_set_mesh_texture); the texture
+/// coordinates travel in the mesh (objreader::Mesh::uvs, uv_indices).
+struct SceneTexture {
+  env_map::Image image;
+  std::int32_t filter = PT_TEX_FILTER_BILINEAR, wrap = PT_TEX_WRAP_REPEAT;
+};
+
 struct PathTracerApp {
   PathTracerApp();
   virtual ~PathTracerApp();
@@ -91,6 +98,7 @@ private:
   std::vector<pt_scene_object> scene;   ///< --scene: the table every handle renders (empty: the built-in scene)
   std::vector<pt_scene_object_ex> sceneEx;   ///< --scene: the same with vertices, when the file holds a polygon (else empty)
   std::vector<objreader::Mesh> sceneMeshes;   ///< --scene: the meshes of the file's "mesh" objects, in the order of their rows
+  std::vector<SceneTexture> sceneTextures;    ///< --scene: one per mesh, in the same order (an empty image: the mesh has no texture)
   pt_camera camera{};                   ///< --scene: the file's "camera", set on every handle when hasCamera
   env_map::Image envMap;                ///< --env-map: the image every handle takes as its environment (empty: NIF or constant)
   std::int32_t envMapFilterMode = 1;    ///< --env-map-filter (PT_ENV_FILTER_*)

@@ -53,7 +53,12 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_set_light_guide", "pt_set_light_guide_ex", "pt_get_light_guide_flags", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
            "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
            "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect", "pt_set_mesh_normals",
-           "pt_get_mesh_normals_info", "pt_mesh_shade"]
+           "pt_get_mesh_normals_info", "pt_mesh_shade", "pt_set_mesh_texture", "pt_get_mesh_texture_info", "pt_mesh_texel"]
+TEX_FILTER_NEAREST, TEX_FILTER_BILINEAR = 0, 1
+TEX_FILTERS = {"nearest": TEX_FILTER_NEAREST, "bilinear": TEX_FILTER_BILINEAR}
+TEX_WRAP_REPEAT, TEX_WRAP_CLAMP = 0, 1
+TEX_WRAPS = {"repeat": TEX_WRAP_REPEAT, "clamp": TEX_WRAP_CLAMP}
+MESH_TEXTURE_MAX_SIZE = 8192
 NIF_SHARE_OFF, NIF_SHARE_BATCH, NIF_SHARE_STEP = 0, 1, 2
 NIF_SHARE_MODES = {"off": NIF_SHARE_OFF, "batch": NIF_SHARE_BATCH, "step": NIF_SHARE_STEP}
 ENV_FILTER_NEAREST, ENV_FILTER_BILINEAR = 0, 1
@@ -286,7 +291,8 @@ def scene_meshes(objects):
         if not _is_mesh_shape(o["shape"]):
             rows.append(o)
             continue
-        unknown = set(o) - {"shape", "material", "vertices", "triangles", "colour", "emission", "normals", "normal_indices"}
+        unknown = set(o) - {"shape", "material", "vertices", "triangles", "colour", "emission", "normals", "normal_indices",
+                            "texture", "uvs", "uv_indices", "texture_filter", "texture_wrap"}
         if unknown:
             raise ValueError("scene object %d: unknown key(s) %s" % (i, sorted(unknown)))
         vertices = np.ascontiguousarray(o["vertices"], dtype=np.float32)
@@ -318,6 +324,26 @@ def mesh_normals(objects):
             out.append((k, o["normals"], o.get("normal_indices")))
         elif o.get("normal_indices") is not None:
             raise ValueError("scene object %d: normal_indices without normals" % i)
+        k += 1
+    return out
+
+
+def mesh_textures(objects):
+    """[(k, image, uvs, uv_indices or None, filter, wrap)] for the meshes of a list of dicts that carry "texture" (H, W, 3 B,G,R)
+    and "uvs" (N, 2), optionally with "uv_indices" (T, 3), "texture_filter" and "texture_wrap": k counts the mesh rows in order,
+    as pt_set_mesh_texture does."""
+    out, k = [], 0
+    for i, o in enumerate(objects):
+        if not _is_mesh_shape(o["shape"]):
+            continue
+        if o.get("texture") is not None:
+            if o.get("uvs") is None:
+                raise ValueError("scene object %d: texture without uvs" % i)
+            out.append((k, o["texture"], o["uvs"], o.get("uv_indices"), o.get("texture_filter", "bilinear"), o.get("texture_wrap", "repeat")))
+        else:
+            for key in ("uvs", "uv_indices", "texture_filter", "texture_wrap"):
+                if o.get(key) is not None:
+                    raise ValueError("scene object %d: %s without texture" % (i, key))
         k += 1
     return out
 
@@ -397,7 +423,23 @@ class MeshNormalsInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+class MeshTexture(C.Structure):
+    """pt_mesh_texture"""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("filter", C.c_int32), ("wrap", C.c_int32),
+                ("bgr", C.c_void_p), ("uvs", C.c_void_p), ("n_uvs", C.c_uint32), ("uv_indices", C.c_void_p)]
+
+
+class MeshTextureInfo(C.Structure):
+    """pt_mesh_texture_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("has_texture", C.c_uint32), ("per_corner", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("filter", C.c_int32), ("wrap", C.c_int32), ("n_uvs", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
 assert C.sizeof(Mesh) == 32 and C.sizeof(MeshInfo) == 48 and C.sizeof(MeshNormalsInfo) == 24
+assert C.sizeof(MeshTexture) == 56 and C.sizeof(MeshTextureInfo) == 40
 
 
 class Features(C.Structure):
@@ -586,6 +628,9 @@ def load_library(diag=False):
     L.pt_set_mesh_normals.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     L.pt_get_mesh_normals_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshNormalsInfo)]
     L.pt_mesh_shade.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_set_mesh_texture.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshTexture)]
+    L.pt_get_mesh_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshTextureInfo)]
+    L.pt_mesh_texel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
@@ -947,6 +992,8 @@ class Renderer:
             self.set_scene_meshes(table, meshes)
             for k, normals, indices in mesh_normals(objects):   # a mesh with "normals" shades smooth (pt_set_mesh_normals)
                 self.set_mesh_normals(k, normals, indices)
+            for k, image, uvs, indices, filt, wrap in mesh_textures(objects):   # a mesh with "texture" (pt_set_mesh_texture)
+                self.set_mesh_texture(k, image, uvs, indices, filter=filt, wrap=wrap)
             return
         if (isinstance(objects, np.ndarray) and objects.dtype == SCENE_EX_DTYPE) or has_polygon(objects):
             # a triangle or a parallelogram (or an ex table as it is): pt_set_scene_ex, keys of scene_array_ex
@@ -1039,6 +1086,72 @@ class Renderer:
         self._check(self._lib.pt_mesh_shade(self.handle, o.ctypes.data, d.ctypes.data, n, t.ctypes.data, obj.ctypes.data,
                                             tri.ctypes.data, bary.ctypes.data, nrm.ctypes.data))
         return t, obj, tri, bary, nrm
+
+    def set_mesh_texture(self, k, image, uvs=None, indices=None, filter="bilinear", wrap="repeat"):
+        """pt_set_mesh_texture: an image (H, W, 3) of linear float B,G,R, rows top to bottom, and texture coordinates uvs (N, 2) for
+        mesh k of the scene in force.  indices None: one (s, t) per vertex, looked up by the mesh's own triangles; else (T, 3)
+        indices into uvs, per corner (OBJ's v/vt).  filter "nearest" / "bilinear", wrap "repeat" / "clamp" (or the integer codes).
+        image None removes the texture.  The library copies everything."""
+        if image is None:
+            if uvs is not None or indices is not None:
+                raise ValueError("uvs or indices without an image")
+            self._check(self._lib.pt_set_mesh_texture(self.handle, int(k), None))
+            return
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+            raise ValueError("image must be an array of shape (H, W, 3), H, W >= 1")
+        if img.shape[0] > MESH_TEXTURE_MAX_SIZE or img.shape[1] > MESH_TEXTURE_MAX_SIZE:
+            raise ValueError("image must be at most %d x %d texels" % (MESH_TEXTURE_MAX_SIZE, MESH_TEXTURE_MAX_SIZE))
+        if uvs is None:
+            raise ValueError("an image needs uvs")
+        uv = np.ascontiguousarray(uvs, dtype=np.float32)
+        if uv.ndim != 2 or uv.shape[1] != 2 or len(uv) == 0:
+            raise ValueError("uvs must be an array of shape (N, 2), N >= 1")
+        if isinstance(filter, str):
+            if filter not in TEX_FILTERS:
+                raise ValueError("filter must be one of %s" % sorted(TEX_FILTERS))
+            filter = TEX_FILTERS[filter]
+        if isinstance(wrap, str):
+            if wrap not in TEX_WRAPS:
+                raise ValueError("wrap must be one of %s" % sorted(TEX_WRAPS))
+            wrap = TEX_WRAPS[wrap]
+        idx = None
+        if indices is not None:
+            raw = np.asarray(indices)
+            if raw.ndim != 2 or raw.shape[1] != 3 or not np.issubdtype(raw.dtype, np.integer) or raw.min() < 0 or raw.max() > 0xffffffff:
+                raise ValueError("indices must be an array of shape (T, 3) of unsigned 32-bit indices")
+            if len(raw) != self.mesh_info(k)["n_triangles"]:
+                raise ValueError("indices must have one row per triangle of mesh %d (%d), got %d" % (k, self.mesh_info(k)["n_triangles"], len(raw)))
+            idx = np.ascontiguousarray(raw, dtype=np.uint32)
+        t = MeshTexture(struct_size=C.sizeof(MeshTexture), width=img.shape[1], height=img.shape[0], filter=int(filter), wrap=int(wrap),
+                        bgr=img.ctypes.data, uvs=uv.ctypes.data, n_uvs=len(uv), uv_indices=idx.ctypes.data if idx is not None else None)
+        self._check(self._lib.pt_set_mesh_texture(self.handle, int(k), C.byref(t)))
+
+    def mesh_texture_info(self, k):
+        """pt_get_mesh_texture_info of mesh k of the scene in force as a dict: has_texture, per_corner, width, height, filter, wrap,
+        n_uvs, device_bytes."""
+        info = MeshTextureInfo(struct_size=C.sizeof(MeshTextureInfo))
+        self._check(self._lib.pt_get_mesh_texture_info(self.handle, int(k), C.byref(info)))
+        return info.as_dict()
+
+    def mesh_texel(self, origin, direction):
+        """pt_mesh_texel: the textured kernels' nearest hit, uv interpolation and lookup over world-space rays origin (n, 3),
+        direction (n, 3), the camera ignored.  Returns (t, object, triangle, uv (n, 2), bgr (n, 3)): for a hit on a textured mesh
+        the interpolated (s, t) and the texel (not multiplied by the row's colour); an untextured mesh triangle gives uv 0 and
+        bgr 1; a miss or any other hit gives 0."""
+        o = np.ascontiguousarray(origin, dtype=np.float32)
+        d = np.ascontiguousarray(direction, dtype=np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("origin and direction must both have shape (n, 3)")
+        n = len(o)
+        t = np.zeros(n, np.float32)
+        obj = np.full(n, -1, np.int32)
+        tri = np.full(n, -1, np.int32)
+        uv = np.zeros((n, 2), np.float32)
+        bgr = np.zeros((n, 3), np.float32)
+        self._check(self._lib.pt_mesh_texel(self.handle, o.ctypes.data, d.ctypes.data, n, t.ctypes.data, obj.ctypes.data,
+                                            tri.ctypes.data, uv.ctypes.data, bgr.ctypes.data))
+        return t, obj, tri, uv, bgr
 
     def scene_ex(self):
         """The scene in force as a SCENE_EX_DTYPE array (pt_get_scene_ex): a polygon with centre = v0, radius 0 and its stored
