@@ -73,25 +73,18 @@ __device__ __forceinline__ void features_body(const TraceParams& P, float4* __re
   f1[i] = make_float4(alb.z, alb.y, alb.x, __int_as_float(best));     // B, G, R like every image of the ABI
 }
 
+// One instance per geometry level of ptmi_trace_variant.h, launched while the scene in force is at that level: a polygon
+// (pt_set_scene_ex), a mesh (pt_set_scene_meshes), vertex normals (pt_set_mesh_normals), a texture (pt_set_mesh_texture: the
+// instance with the second argument, TexParams of pt_trace.h).
+template <int GEOM>
 __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
-  features_body<false>(P, f0, f1);
+  static_assert(GEOM != GEOM_TEX, "a TEX instance takes TexParams: features_kernel_tex");
+  using F = VariantFlags<0, GEOM>;   // the bounce plays no part
+  features_body<F::POLY, F::MESH, F::SMOOTH, F::TEX>(P, f0, f1);
 }
-// pt_set_scene_ex: launched only while the scene in force holds a polygon
-__global__ __launch_bounds__(kFeatureBlock) void features_kernel_poly(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
-  features_body<true>(P, f0, f1);
-}
-// pt_set_scene_meshes: launched only while the scene in force holds a mesh
-__global__ __launch_bounds__(kFeatureBlock) void features_kernel_mesh(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
-  features_body<true, true>(P, f0, f1);
-}
-// pt_set_mesh_normals: launched only while a mesh in force has vertex normals
-__global__ __launch_bounds__(kFeatureBlock) void features_kernel_smooth(const TraceParams P, float4* __restrict__ f0, float4* __restrict__ f1) {
-  features_body<true, true, true>(P, f0, f1);
-}
-// pt_set_mesh_texture: launched only while a mesh in force has a texture (the second argument: TexParams, pt_trace.h)
-__global__ __launch_bounds__(kFeatureBlock) void features_kernel_tex(const TraceParams P, const TexParams X, float4* __restrict__ f0,
-                                                                     float4* __restrict__ f1) {
-  features_body<true, true, true, true>(P, f0, f1, &X);
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel_tex(const TraceParams P, const TexParams X, float4* __restrict__ f0, float4* __restrict__ f1) {
+  using F = VariantFlags<0, GEOM_TEX>;
+  features_body<F::POLY, F::MESH, F::SMOOTH, F::TEX>(P, f0, f1, &X);
 }
 
 }  // namespace ptd

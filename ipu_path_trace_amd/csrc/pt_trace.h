@@ -25,6 +25,7 @@
 #include "pt_device_math.h"
 #include "pt_env_guide.h"
 #include "pt_mesh.h"
+#include "ptmi_trace_variant.h"
 
 #include <utility>
 
@@ -1084,90 +1085,54 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, [[maybe_unused]
   if (threadIdx.x == 0) P.region_count[blockIdx.x] = wg_count;
 }
 
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel(const TraceParams P) { trace_body<kRefillThreshold>(P); }
-// pt_set_camera: a moved / rotated pinhole (escapes rotated to world space), and a thin lens (its own primary phase)
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS>(P); }
-// pt_set_env_guide: the same three with the guided diffuse bounce, launched only while a guide is set (one per camera kind: a
-// single instance reading the camera flags would carry the lens instance's primary phase for every camera)
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true>(P); }
-// pt_set_light_guide: the same three with the emitter-guided diffuse bounce, launched only while an active light guide is set.
-// They handle an environment guide too, by a wave-uniform test at run time: three instances, not a cross product.
-// amdgpu_waves_per_eu(6, 6): the grid is six workgroups per CU (pt_context::kTraceBlocksPerCu), one wave of each per SIMD; left
-// alone the allocator takes 83-84 VGPRs, five waves, and the grid's last sixth runs late (measured: 9.6 % of a guided step).
-// Held to 80 it spills no VGPR and the code has no scratch access.
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true>(P); }
-// pt_set_scene_ex: the same nine with the polygon test in the object loop and the two-sided normal, launched only while the scene
-// in force holds a triangle or a parallelogram (resource rows: profiles/r20_polygons.txt)
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_poly(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true>(P); }
-// pt_set_light_guide_ex with PT_LIGHT_GUIDE_POLYGONS: the last three with the polygon branch of the emitter guide, launched only
-// while the table in force lists a polygon.  Instances of their own: the three above sit at 80 VGPRs and compile none of this.
-// Pinned to six waves like them and for their reason: left alone the allocator takes 87-88 VGPRs, five waves; held to 80 the
-// scratch goes from 52 to 64-68 bytes per lane, 8-14 VGPRs spilled, and the trace stage of a Cornell box is still 6 % shorter
-// (8.6 against 9.2 ms; resource rows and the A/B: profiles/r21_light_guide_polygons.txt).
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true>(P); }
-// pt_set_scene_meshes: twelve more with the mesh walk in the object loop, launched only while the scene in force holds a mesh.
-// They carry the polygon code too (MESH implies POLY), and the emitter-guided ones come with and without polygon lamps, as
-// above: a mesh is never listed in the emitter guide's table.  Resource rows: profiles/r22_meshes.txt.
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, false, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_mesh(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true>(P); }
-// pt_set_mesh_normals: the twelve mesh instances again with the shading normal (SMOOTH), launched only while a mesh in force has
-// vertex normals.  A flat mesh beside a smooth one takes none of the new steps (its row's flag).  The plain three are held to
-// five waves per SIMD, where their MESH twins sit at 94 VGPRs: left alone the allocator takes 99 and four waves; held, 93, no VGPR
-// spilled and no scratch access the twins do not have.  The env-guided three stay at four waves like their twins (107 against
-// 102 VGPRs); the emitter-guided six are pinned to six as everywhere.  Resource rows: profiles/r24_mesh_normals.txt.
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void trace_kernel_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void trace_kernel_pose_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void trace_kernel_lens_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, false, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true, true>(P); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_smooth(const TraceParams P) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true, true>(P); }
-// pt_set_mesh_texture: the twelve again with the texture lookup (TEX, which carries the SMOOTH code: the rows' flags decide per
-// hit), launched only while a mesh in force has a texture.  The second argument holds the uv slots and the rows' descriptors.
-// No occupancy is pinned on the six that are not emitter-guided: the allocator's choice is recorded in
-// profiles/r26_mesh_textures.txt.  The emitter-guided six are pinned to six waves as everywhere.
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, false, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, false, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, false, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_guide_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, true, false, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_pose_guide_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, true, false, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel_lens_guide_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, true, false, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, false, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lights_plamps_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_BUILTIN, false, true, true, true, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_pose_lights_plamps_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_POSE, false, true, true, true, true, true, true>(P, &X); }
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void trace_kernel_lens_lights_plamps_tex(const TraceParams P, const TexParams X) { trace_body<kRefillThreshold, kTraceOpt, CAM_LENS, false, true, true, true, true, true, true>(P, &X); }
+// The product's instances of the kernel: one per valid (camera, bounce, geometry) of ptmi_trace_variant.h, which derives the
+// flags of trace_body and the occupancy pin from the three and picks the instance for a launch (select; the tables of
+// stage_trace in ptmi.hip).  A coordinate that is not a template flag would cost every launch the code of its other values: a
+// single instance reading the camera flags would carry the lens instance's primary phase for every camera.
+//   camera    BUILTIN / POSE / LENS (pt_set_camera): a moved or rotated pinhole rotates its escapes to world space; a thin lens
+//             has a primary phase of its own.
+//   bounce    ENV_GUIDE (pt_set_env_guide): the guided diffuse bounce, launched only while a guide is set.  LIGHT_GUIDE
+//             (pt_set_light_guide): the emitter-guided bounce, launched only while an active light guide is set; it handles an
+//             environment guide too, by a wave-uniform test at run time, so there is no cross product.  LIGHT_GUIDE_PLAMPS
+//             (pt_set_light_guide_ex with PT_LIGHT_GUIDE_POLYGONS): with the polygon branch of the emitter guide, launched only
+//             while the table in force lists a polygon -- instances of their own, since the LIGHT_GUIDE ones sit at 80 VGPRs and
+//             compile none of it.  A mesh is never listed in that table.
+//   geometry  POLY (pt_set_scene_ex): the polygon test in the object loop and the two-sided normal, launched only while the
+//             scene in force holds a triangle or a parallelogram.  MESH (pt_set_scene_meshes): the mesh walk in the object loop,
+//             while the scene holds a mesh.  SMOOTH (pt_set_mesh_normals): the shading normal, while a mesh in force has vertex
+//             normals; a flat mesh beside a smooth one takes none of the new steps (its row's flag).  TEX
+//             (pt_set_mesh_texture): the texture lookup, while a mesh in force has a texture; the rows' flags decide per hit,
+//             and the instance takes a second argument with the uv slots and the rows' descriptors -- trace_kernel_tex below.
+// amdgpu_waves_per_eu (ptvariant::waves_per_eu; 0 emits no attribute):
+//   6 for every emitter-guided instance.  The grid is six workgroups per CU (pt_context::kTraceBlocksPerCu), one wave of each
+//     per SIMD; left alone the allocator takes 83-84 VGPRs, five waves, and the grid's last sixth runs late (measured: 9.6 % of
+//     a guided step).  Held to 80 the LIGHT_GUIDE instances spill no VGPR and have no scratch access.  With polygon lamps the
+//     allocator would take 87-88; held to 80 the scratch goes from 52 to 64-68 bytes per lane, 8-14 VGPRs spilled, and the trace
+//     stage of a Cornell box is still 6 % shorter (8.6 against 9.2 ms; the A/B: profiles/r21_light_guide_polygons.txt).
+//   5 for PLAIN at SMOOTH, where the MESH twins sit at 94 VGPRs: left alone the allocator takes 99 and four waves; held, 93, no
+//     VGPR spilled and no scratch access the twins do not have.  The env-guided SMOOTH ones stay at four waves like their twins
+//     (107 against 102 VGPRs).
+//   None on the TEX instances that are not emitter-guided: the allocator's choice is recorded with their rows.
+// Resource rows: POLY profiles/r20_polygons.txt, LIGHT_GUIDE_PLAMPS r21_light_guide_polygons.txt, MESH r22_meshes.txt, SMOOTH
+// r24_mesh_normals.txt, TEX r26_mesh_textures.txt; all of them under their earlier names, and the proof that the move to one
+// template left every instance's code as it was, r27_trace_instances.txt (scripts/kernel_resources.py, kernel_isa_diff.py).
+// The kernels call their body directly: one more inlined function between the two moves a few instructions of most instances.
+template <int BOUNCE, int GEOM> using VariantFlags = ptvariant::Flags<(ptvariant::Bounce)BOUNCE, (ptvariant::Geometry)GEOM>;   // refuses an invalid pair
+constexpr int GEOM_TEX = (int)ptvariant::Geometry::TEX;
+// Every TEX instance takes TexParams and no other kernel does: the one-argument templates refuse GEOM_TEX, the _tex ones fix it.
+template <int CAM, int BOUNCE, int GEOM>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(VariantFlags<BOUNCE, GEOM>::WAVES, VariantFlags<BOUNCE, GEOM>::WAVES)))
+void trace_kernel(const TraceParams P) {
+  static_assert(GEOM != GEOM_TEX, "a TEX instance takes TexParams: trace_kernel_tex");
+  using F = VariantFlags<BOUNCE, GEOM>;
+  trace_body<kRefillThreshold, kTraceOpt, CAM, F::GUIDE, F::LIGHTS, F::POLY, F::PLAMPS, F::MESH, F::SMOOTH, F::TEX>(P);
+}
+template <int CAM, int BOUNCE>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(VariantFlags<BOUNCE, GEOM_TEX>::WAVES, VariantFlags<BOUNCE, GEOM_TEX>::WAVES)))
+void trace_kernel_tex(const TraceParams P, const TexParams X) {
+  using F = VariantFlags<BOUNCE, GEOM_TEX>;
+  trace_body<kRefillThreshold, kTraceOpt, CAM, F::GUIDE, F::LIGHTS, F::POLY, F::PLAMPS, F::MESH, F::SMOOTH, F::TEX>(P, &X);
+}
 #ifdef PTMI_DIAG_BUILD
 template <int OPT>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel_opt(const TraceParams P) { trace_body<kRefillThreshold, OPT>(P); }   // round-4 A/B (0 = the round-3 kernel; 7, 11: timing-only phase cuts)
@@ -1208,49 +1173,19 @@ __device__ __forceinline__ void trace_paths_body(const TraceParams& P, const uin
   }
   out[i] = r;
 }
-__global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                   uint32_t n, PathRecordOut* out) { trace_paths_body<false>(P, u, v, sample, n, out); }
-__global__ void trace_paths_guide_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                         uint32_t n, PathRecordOut* out) { trace_paths_body<true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_lights_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                          uint32_t n, PathRecordOut* out) { trace_paths_body<false, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_poly_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                        uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_guide_poly_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                              uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_lights_poly_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                               uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_lights_plamps_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                                 uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true>(P, u, v, sample, n, out); }
-// pt_set_scene_meshes: the mesh twins
-__global__ void trace_paths_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                        uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true, false, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_guide_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                              uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true, false, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_lights_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                               uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, false, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_lights_plamps_mesh_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                                      uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true>(P, u, v, sample, n, out); }
-
-// pt_set_mesh_normals: the smooth twins of the four above
-__global__ void trace_paths_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                          uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true, false, true, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_guide_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                                uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true, false, true, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_lights_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                                 uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, false, true, true>(P, u, v, sample, n, out); }
-__global__ void trace_paths_lights_plamps_smooth_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                                        uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true, true>(P, u, v, sample, n, out); }
-
-// pt_set_mesh_texture: the textured twins of the four above
-__global__ void trace_paths_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                       uint32_t n, PathRecordOut* out) { trace_paths_body<false, false, true, false, true, true, true>(P, u, v, sample, n, out, &X); }
-__global__ void trace_paths_guide_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                             uint32_t n, PathRecordOut* out) { trace_paths_body<true, false, true, false, true, true, true>(P, u, v, sample, n, out, &X); }
-__global__ void trace_paths_lights_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                              uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, false, true, true, true>(P, u, v, sample, n, out, &X); }
-__global__ void trace_paths_lights_plamps_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample,
-                                                     uint32_t n, PathRecordOut* out) { trace_paths_body<false, true, true, true, true, true, true>(P, u, v, sample, n, out, &X); }
+// One instance per valid (bounce, geometry) of ptmi_trace_variant.h, the camera being read at run time; the TEX ones take TexParams.
+template <int BOUNCE, int GEOM>
+__global__ void trace_paths_kernel(const TraceParams P, const uint16_t* u, const uint16_t* v, const uint32_t* sample, uint32_t n, PathRecordOut* out) {
+  static_assert(GEOM != GEOM_TEX, "a TEX instance takes TexParams: trace_paths_tex_kernel");
+  using F = VariantFlags<BOUNCE, GEOM>;
+  trace_paths_body<F::GUIDE, F::LIGHTS, F::POLY, F::PLAMPS, F::MESH, F::SMOOTH, F::TEX>(P, u, v, sample, n, out);
+}
+template <int BOUNCE>
+__global__ void trace_paths_tex_kernel(const TraceParams P, const TexParams X, const uint16_t* u, const uint16_t* v, const uint32_t* sample, uint32_t n,
+                                       PathRecordOut* out) {
+  using F = VariantFlags<BOUNCE, GEOM_TEX>;
+  trace_paths_body<F::GUIDE, F::LIGHTS, F::POLY, F::PLAMPS, F::MESH, F::SMOOTH, F::TEX>(P, u, v, sample, n, out, &X);
+}
 
 // pt_mesh_intersect: the MESH instances' own nearest hit over caller rays, one thread per ray (the scene in the kernel arguments
 // is the world table).  BRUTE: a loop over all triangles of each mesh in place of the walk.

@@ -15,6 +15,7 @@
 #include <limits.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -29,6 +30,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "ptmi.h"
@@ -500,6 +502,35 @@ struct Batch {
 
 #include "ptmi_nif_group.h"   // StepMode, S(b), E(b) and the memo's passes; pt_set_nif_sharing, pt_set_nif_memo and their stats
 
+// Which instance of the trace, trace-paths and feature kernels a launch takes (ptmi_trace_variant.h): select over what the handle
+// and the launch parameters say, and a table of the instances per kernel signature, in the order of the dense numbering.  The
+// tables instantiate the valid variants and nothing else.
+static ptvariant::Variant variant_in_force(pt_handle h, const ptd::TraceParams& P) {
+  return ptvariant::select({P.lens_a > 0.f, P.cam_pose != 0, h->guide_set, P.lights.n != 0, h->light.polygons, h->scene_n != 0,
+                            h->scene_poly, h->scene_mesh, h->mesh.smooth(), h->mesh.textured()});
+}
+template <int I> constexpr int kCam = (int)ptvariant::at(I).camera;
+template <int I> constexpr int kBounce = (int)ptvariant::at(I).bounce;
+template <int I> constexpr int kGeom = (int)ptvariant::at(I).geometry;
+template <int... I> constexpr auto trace_kernels(std::integer_sequence<int, I...>) {
+  return std::array{&ptd::trace_kernel<kCam<I>, kBounce<I>, kGeom<I>>...};
+}
+template <int... I> constexpr auto trace_tex_kernels(std::integer_sequence<int, I...>) {
+  return std::array{&ptd::trace_kernel_tex<kCam<ptvariant::kTraceTexFirst + I>, kBounce<ptvariant::kTraceTexFirst + I>>...};
+}
+template <int... I> constexpr auto paths_kernels(std::integer_sequence<int, I...>) {   // pair i of bounce and geometry: variant 3 i
+  return std::array{&ptd::trace_paths_kernel<kBounce<ptvariant::kCameras * I>, kGeom<ptvariant::kCameras * I>>...};
+}
+template <int... I> constexpr auto paths_tex_kernels(std::integer_sequence<int, I...>) {
+  return std::array{&ptd::trace_paths_tex_kernel<kBounce<ptvariant::kCameras * (ptvariant::kPathsTexFirst + I)>>...};
+}
+template <int... I> constexpr auto feature_kernels(std::integer_sequence<int, I...>) { return std::array{&ptd::features_kernel<I>...}; }
+constexpr auto kTraceKernels = trace_kernels(std::make_integer_sequence<int, ptvariant::kTraceTexFirst>{});
+constexpr auto kTraceTexKernels = trace_tex_kernels(std::make_integer_sequence<int, ptvariant::kTraceInstances - ptvariant::kTraceTexFirst>{});
+constexpr auto kPathsKernels = paths_kernels(std::make_integer_sequence<int, ptvariant::kPathsTexFirst>{});
+constexpr auto kPathsTexKernels = paths_tex_kernels(std::make_integer_sequence<int, ptvariant::kPathsInstances - ptvariant::kPathsTexFirst>{});
+constexpr auto kFeatureKernels = feature_kernels(std::make_integer_sequence<int, ptvariant::kFeatureTexFirst>{});
+
 // T(b): the persistent trace kernel, once the set's previous user -- A(b - depth) -- has consumed the buffer set.
 static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const Batch& b) {
   P.sample_base = h->sample_cursor + b.first_iter;
@@ -513,50 +544,13 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
 #ifdef PTMI_DIAG_BUILD
     if (!launch_trace_variant(h, P, b.g))   // A/B switches of the profiling build (diag/ptmi_trace_variants.h), read per launch
 #endif
-    {   // the camera picks the instance: the built-in one runs the kernel it always ran; a guide, the guided twin of each
-      auto kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens : (P.cam_pose ? ptd::trace_kernel_pose : ptd::trace_kernel);
-      if (h->guide_set)
-        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide : (P.cam_pose ? ptd::trace_kernel_pose_guide : ptd::trace_kernel_guide);
-      if (P.lights.n)   // an active light guide: the emitter-guided twin, which handles an environment guide too
-        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights : (P.cam_pose ? ptd::trace_kernel_pose_lights : ptd::trace_kernel_lights);
-      if (h->scene_n && h->scene_poly) {   // a polygon in the scene in force (pt_set_scene_ex): the polygon twin of each of the nine
-        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_poly : (P.cam_pose ? ptd::trace_kernel_pose_poly : ptd::trace_kernel_poly);
-        if (h->guide_set)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_poly : (P.cam_pose ? ptd::trace_kernel_pose_guide_poly : ptd::trace_kernel_guide_poly);
-        if (P.lights.n)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_poly : (P.cam_pose ? ptd::trace_kernel_pose_lights_poly : ptd::trace_kernel_lights_poly);
-        if (P.lights.n && h->light.polygons)   // the table lists a polygon lamp (pt_set_light_guide_ex)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps : ptd::trace_kernel_lights_plamps);
-      }
-      if (h->scene_n && h->scene_mesh) {   // a mesh in the scene in force (pt_set_scene_meshes): the mesh twin, which handles polygons too
-        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_mesh : (P.cam_pose ? ptd::trace_kernel_pose_mesh : ptd::trace_kernel_mesh);
-        if (h->guide_set)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_mesh : (P.cam_pose ? ptd::trace_kernel_pose_guide_mesh : ptd::trace_kernel_guide_mesh);
-        if (P.lights.n)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_mesh : (P.cam_pose ? ptd::trace_kernel_pose_lights_mesh : ptd::trace_kernel_lights_mesh);
-        if (P.lights.n && h->light.polygons)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_mesh : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_mesh : ptd::trace_kernel_lights_plamps_mesh);
-      }
-      if (h->scene_n && h->scene_mesh && h->mesh.smooth()) {   // a mesh in force has vertex normals (pt_set_mesh_normals): the smooth twin of each of the twelve
-        kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_smooth : (P.cam_pose ? ptd::trace_kernel_pose_smooth : ptd::trace_kernel_smooth);
-        if (h->guide_set)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_smooth : (P.cam_pose ? ptd::trace_kernel_pose_guide_smooth : ptd::trace_kernel_guide_smooth);
-        if (P.lights.n)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_smooth : (P.cam_pose ? ptd::trace_kernel_pose_lights_smooth : ptd::trace_kernel_lights_smooth);
-        if (P.lights.n && h->light.polygons)
-          kernel = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_smooth : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_smooth : ptd::trace_kernel_lights_plamps_smooth);
-      }
-      if (h->scene_n && h->scene_mesh && h->mesh.textured()) {   // a mesh in force has a texture (pt_set_mesh_texture): the textured twin of each of the twelve, with its second argument
-        auto tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_tex : (P.cam_pose ? ptd::trace_kernel_pose_tex : ptd::trace_kernel_tex);
-        if (h->guide_set)
-          tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_guide_tex : (P.cam_pose ? ptd::trace_kernel_pose_guide_tex : ptd::trace_kernel_guide_tex);
-        if (P.lights.n)
-          tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_tex : (P.cam_pose ? ptd::trace_kernel_pose_lights_tex : ptd::trace_kernel_lights_tex);
-        if (P.lights.n && h->light.polygons)
-          tex = P.lens_a > 0.f ? ptd::trace_kernel_lens_lights_plamps_tex : (P.cam_pose ? ptd::trace_kernel_pose_lights_plamps_tex : ptd::trace_kernel_lights_plamps_tex);
-        hipLaunchKernelGGL(tex, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P, tex_params(h));
-      } else
-      hipLaunchKernelGGL(kernel, dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
+    {   // camera, guide and scene in force pick the instance: with none of them set, the kernel that always ran
+      const int i = ptvariant::index(variant_in_force(h, P));
+      if (i >= ptvariant::kTraceTexFirst)   // a mesh in force has a texture (pt_set_mesh_texture): the instances with the second argument
+        hipLaunchKernelGGL(kTraceTexKernels[i - ptvariant::kTraceTexFirst], dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects),
+                           h->trace_stream, P, tex_params(h));
+      else
+        hipLaunchKernelGGL(kTraceKernels[i], dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects), h->trace_stream, P);
     }
     PT_HIP(hipGetLastError());
     return PT_OK;
@@ -1806,24 +1800,14 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   ptd::TraceParams P;
   fill_trace_params(h, P);
   P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
-  auto kernel = P.lights.n ? ptd::trace_paths_lights_kernel : (h->guide_set ? ptd::trace_paths_guide_kernel : ptd::trace_paths_kernel);
-  if (h->scene_n && h->scene_poly)   // the polygon twins (pt_set_scene_ex)
-    kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_kernel : ptd::trace_paths_lights_poly_kernel)
-                        : (h->guide_set ? ptd::trace_paths_guide_poly_kernel : ptd::trace_paths_poly_kernel);
-  if (h->scene_n && h->scene_mesh)   // the mesh twins (pt_set_scene_meshes)
-    kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_mesh_kernel : ptd::trace_paths_lights_mesh_kernel)
-                        : (h->guide_set ? ptd::trace_paths_guide_mesh_kernel : ptd::trace_paths_mesh_kernel);
-  if (h->scene_n && h->scene_mesh && h->mesh.smooth())   // the smooth twins (pt_set_mesh_normals)
-    kernel = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_smooth_kernel : ptd::trace_paths_lights_smooth_kernel)
-                        : (h->guide_set ? ptd::trace_paths_guide_smooth_kernel : ptd::trace_paths_smooth_kernel);
-  if (h->scene_n && h->scene_mesh && h->mesh.textured()) {   // the textured twins (pt_set_mesh_texture)
-    auto tex = P.lights.n ? (h->light.polygons ? ptd::trace_paths_lights_plamps_tex_kernel : ptd::trace_paths_lights_tex_kernel)
-                          : (h->guide_set ? ptd::trace_paths_guide_tex_kernel : ptd::trace_paths_tex_kernel);
-    hipLaunchKernelGGL(tex, dim3(((uint32_t)n + 127) / 128), dim3(128),
+  const ptvariant::Variant var = variant_in_force(h, P);   // the instance of the production kernel's bounce and geometry (the camera: read at run time)
+  const int i = ptvariant::paths_index(var.bounce, var.geometry);
+  if (i >= ptvariant::kPathsTexFirst)   // the textured twins (pt_set_mesh_texture)
+    hipLaunchKernelGGL(kPathsTexKernels[i - ptvariant::kPathsTexFirst], dim3(((uint32_t)n + 127) / 128), dim3(128),
                        ptd::hit_table_bytes(P.n_objects), h->stream, P, tex_params(h), d_u, d_v, d_s, (uint32_t)n, d_out);
-  } else
-  hipLaunchKernelGGL(kernel, dim3(((uint32_t)n + 127) / 128), dim3(128),
-                     ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
+  else
+    hipLaunchKernelGGL(kPathsKernels[i], dim3(((uint32_t)n + 127) / 128), dim3(128),
+                       ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_path_record), hipMemcpyDeviceToHost, h->stream));
   PT_HIP(hipStreamSynchronize(h->stream));

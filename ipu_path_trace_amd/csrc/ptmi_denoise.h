@@ -33,14 +33,13 @@ int ensure_features(pt_handle h) {
   P.lens_a = 0.f;        // ... through a pinhole
   P.emitted = nullptr;
   const uint32_t px = h->cfg.width * h->cfg.height;
-  auto kernel = h->scene_n && h->scene_poly ? ptd::features_kernel_poly : ptd::features_kernel;
-  if (h->scene_n && h->scene_mesh) kernel = h->mesh.smooth() ? ptd::features_kernel_smooth : ptd::features_kernel_mesh;
-  if (h->scene_n && h->scene_mesh && h->mesh.textured())   // pt_set_mesh_texture: albedo = colour x texel
+  const int i = (int)variant_in_force(h, P).geometry;   // the geometry level alone picks the instance
+  if (i >= ptvariant::kFeatureTexFirst)   // pt_set_mesh_texture: albedo = colour x texel
     hipLaunchKernelGGL(ptd::features_kernel_tex, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0,
                        h->stream, P, tex_params(h), h->d_feat[0], h->d_feat[1]);
   else
-  hipLaunchKernelGGL(kernel, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0, h->stream, P,
-                     h->d_feat[0], h->d_feat[1]);
+    hipLaunchKernelGGL(kFeatureKernels[i], dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0, h->stream, P,
+                       h->d_feat[0], h->d_feat[1]);
   PT_HIP(hipGetLastError());
   h->feature_cached_gen = h->feature_gen;
   return PT_OK;

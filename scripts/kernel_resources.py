@@ -10,6 +10,8 @@ memo_lookup / memo_resolve / memo_expand and both accumulate kernels -- against 
 allocated in granules of 8), no scratch, at most 3 KiB of LDS.  Exit status 1 if one is over.  The opt-in trace instances that
 sections 4.12 and 4.16 document as over -- the guided ones (frame slots reserved beside their SGPR spills) and the mesh ones
 (94 - 102 VGPRs; spilled VGPRs in the light-guided mesh ones) -- are listed apart as known and do not fail the check.
+An instance of the trace, trace-paths and feature kernel templates is printed, filtered and matched against KNOWN_OVER under the
+name of the hand-written kernel it replaced (OLD_NAMES of scripts/kernel_isa_diff.py), so rows compare with profiles/r15 - r26.
 --small compiles only the headers of the small kernels (pt_nif.h, pt_nif_group.h: seconds instead of minutes) and checks the
 sharing, memo and accumulate kernels alone.
 """
@@ -18,6 +20,8 @@ import re
 import subprocess
 import sys
 import tempfile
+
+from kernel_isa_diff import old_name   # an instance of the trace kernel templates under the hand-written name of profiles/r15 - r26
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ipu_path_trace_amd", "csrc")
@@ -65,7 +69,13 @@ def allocated_vgprs(r):
 
 
 def short_name(r):
-    return re.sub(r"^(?:void )?ptd::", "", r["name"]).split("(")[0]
+    return old_name(r["name"])
+
+
+def shown_name(r):
+    """The demangled name as the earlier tables print it: a template instance as 'ptd::<old name>(arguments)'."""
+    n = r["name"]
+    return "ptd::" + short_name(r) + n[n.index("("):] if "<" in n.split("(")[0] and "<" not in short_name(r) else n
 
 
 def step_budget(small, extra):
@@ -114,10 +124,10 @@ def main():
     if "--step-budget" in flags:
         raise SystemExit(step_budget("--small" in flags, extra))
     for r in resource_rows(os.path.join(CSRC, "ptmi.hip"), extra):
-        if flt and not any(f in r["name"] for f in flt):
+        if flt and not any(f in shown_name(r) for f in flt):
             continue
         print("%-90s VGPR %3d AGPR %3d SGPR %3d spillV %d spillS %d scratch %d LDS %6d occ %s" % (
-            r["name"][:90], r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("SGPRs", -1), r.get("VGPRs Spill", -1),
+            shown_name(r)[:90], r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("SGPRs", -1), r.get("VGPRs Spill", -1),
             r.get("SGPRs Spill", -1), r.get("ScratchSize [bytes/lane]", -1), r.get("LDS Size [bytes/block]", -1),
             r.get("Occupancy [waves/SIMD]", "?")))
 

@@ -50,13 +50,20 @@ def test_kernel_argument_budget():
     tail = src[src.index("struct TraceParams {"):src.index("static_assert(sizeof(TraceParams) <= 4096")]
     assert tail.rstrip().endswith("const ptmesh::F4* mesh_normals;\n};".rstrip())
     assert "uint32_t textured;" in src[src.index("struct MeshRow {"):src.index("static_assert(sizeof(MeshRow) == sizeof(PolyEdges)")]
-    # every TEX kernel takes the second argument, and no other kernel does
-    kernels = re.findall(r"__global__[^\n]*?void (\w+)\(const TraceParams P(, const TexParams X)?", src)
-    assert len(kernels) > 40
-    tex = sorted(k for k, second in kernels if second)
-    assert len(tex) == 17 and all(k.endswith("_tex") or k.endswith("_tex_kernel") or k == "mesh_texel_kernel" for k in tex), tex
-    assert not [k for k, second in kernels if not second and "tex" in k]
+    # every TEX kernel takes the second argument, and no other kernel does: the kernels with it are the three _tex templates, which
+    # fix the geometry to TEX, and pt_mesh_texel's; the templates without it refuse TEX (static_asserts the build compiles: this reads them)
     feat = open(os.path.join(ROOT, "ipu_path_trace_amd", "csrc", "pt_features.h")).read()
+    kernels = re.findall(r"__global__[^;{]*?void (\w+)\(const TraceParams P(, const TexParams X)?", src + feat)
+    assert len(kernels) >= 10
+    tex = sorted(k for k, second in kernels if second)
+    assert tex == ["features_kernel_tex", "mesh_texel_kernel", "trace_kernel_tex", "trace_paths_tex_kernel"], tex
+    assert not [k for k, second in kernels if not second and "tex" in k]
+    for kernel, text in (("trace_kernel", src), ("trace_paths_kernel", src), ("features_kernel", feat)):
+        body = text[text.index("void %s(const TraceParams P" % kernel):]
+        assert body[:body.index("\n}")].count("static_assert(GEOM != GEOM_TEX") == 1, kernel
+    for kernel, text in (("trace_kernel_tex", src), ("trace_paths_tex_kernel", src), ("features_kernel_tex", feat)):
+        body = text[text.index("void %s(const TraceParams P, const TexParams X" % kernel):]
+        assert re.search(r"using F = VariantFlags<\w+, GEOM_TEX>;", body[:body.index("\n}")]), kernel
     assert "void features_kernel_tex(const TraceParams P, const TexParams X" in feat
 
 
