@@ -210,21 +210,40 @@ int pt_calibrate_nif(pt_handle h, uint32_t launches, double* ms_per_launch, uint
  * (sized from the batch capacity and the free memory) and the distinct-queue store: PT_ERR_OUT_OF_MEMORY leaves the mode
  * off.  A step-scope step with more batches than the store holds grows it (pt_path_trace may then return
  * PT_ERR_OUT_OF_MEMORY).  A bad mode or a NULL handle is PT_ERR_INVALID_ARGUMENT.
- * pt_stats keeps its meaning (escaped = escaped paths); pt_get_nif_sharing_stats reports the rows the last path_trace really
- * ran: evaluations == escaped with sharing off, 0 with a constant environment (no sharing pass runs then).  The caller
+ * pt_stats keeps its meaning (escaped = escaped paths); pt_get_nif_sharing_stats reports the distinct lookups the last path_trace
+ * handed to its NIF stage: evaluations == escaped with sharing off, 0 with a constant environment (no sharing pass runs then).  The caller
  * sets struct_size = sizeof(pt_nif_sharing_stats). */
 enum { PT_NIF_SHARE_OFF = 0, PT_NIF_SHARE_BATCH = 1, PT_NIF_SHARE_STEP = 2 };
 typedef struct pt_nif_sharing_stats {
   uint32_t struct_size;          /* sizeof(pt_nif_sharing_stats), set by the caller */
   int32_t mode;                  /* mode the last path_trace really ran with, chosen or automatic (PT_NIF_SHARE_OFF with a constant environment) */
   uint64_t escaped;              /* = pt_stats.escaped */
-  uint64_t evaluations;          /* NIF rows executed by the last path_trace */
+  uint64_t evaluations;          /* distinct (u, v) bit pairs the last path_trace handed to its NIF stage: the distinct queues' length (= escaped with sharing off); the rows the network ran are pt_nif_class_stats.mlp_rows */
   uint64_t overflowed;           /* entries evaluated alone because no table slot was free */
   uint64_t table_slots;          /* table capacity in use (0 with sharing off) */
   double share_ms;               /* device time of the sharing passes (HIP events, read lazily like the stage times) */
 } pt_nif_sharing_stats;
 int pt_set_nif_sharing(pt_handle h, int32_t mode);
 int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
+
+/* The class level of the NIF stage.  Every NIF inference kernel reads a coordinate as x = (coord - 1) * 2 and then only the
+ * binary16 values half(x * 2^j), j < 16; for 2^-14 <= |x| <= 2 those are a function of half(x) alone, so two lookups whose u
+ * and whose v round to the same half get the same BGR, bit for bit, although their fp32 (u, v) differ.  Whenever the NIF stage
+ * runs over a distinct queue -- PT_NIF_SHARE_BATCH, PT_NIF_SHARE_STEP (chosen or automatic) and the memo, with a NIF as the
+ * environment -- it therefore evaluates one row per such class and copies the result to the class's other entries; the class
+ * table lives for one pt_path_trace.  Every output is the same bytes as without the level; the sharing key, the memo key and
+ * pt_nif_sharing_stats.evaluations stay what they were.  If the level's buffers do not fit a quarter of the free device memory,
+ * or their allocation fails, the step runs without it, and that is no error.  Sharing off launches nothing of it.
+ * The caller sets struct_size = sizeof(pt_nif_class_stats). */
+typedef struct pt_nif_class_stats {
+  uint32_t struct_size;          /* sizeof(pt_nif_class_stats), set by the caller */
+  int32_t ran;                   /* the last path_trace ran the class level */
+  uint64_t mlp_rows;             /* rows the NIF kernels executed in the last path_trace (= evaluations if the level did not run) */
+  uint64_t alone;                /* rows evaluated alone because no slot of the class table was free */
+  uint64_t table_slots;          /* class table capacity in use (0 if the level did not run) */
+  double class_ms;               /* device time of the level's claim, resolve and spread passes (HIP events, read lazily) */
+} pt_nif_class_stats;
+int pt_get_nif_class_stats(pt_handle h, pt_nif_class_stats* out);
 
 /* Persistent memo of NIF evaluations across steps -- an EXTENSION like sharing.  The decoded BGR of a key (the 64 raw bits of
  * (u, v), azimuth already folded in) depends on the uploaded model alone, so it stays valid from step to step until
@@ -246,7 +265,7 @@ int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
  * Allocation: pt_set_nif_memo can return PT_ERR_OUT_OF_MEMORY and the memo is then left off; max_bytes between 1 and
  * 48 KiB - 1 is PT_ERR_INVALID_ARGUMENT.  The step store of step-scope sharing (not counted in max_bytes) is used and grown
  * as with PT_NIF_SHARE_STEP.
- * pt_nif_sharing_stats keeps its meaning: `evaluations` counts the NIF rows that ran, so evaluations == escaped holds only
+ * pt_nif_sharing_stats keeps its meaning: `evaluations` counts the entries of the distinct queues, so evaluations == escaped holds only
  * when both sharing and the memo are off; with the memo on its passes are timed in memo_ms, not share_ms.  The caller sets
  * struct_size = sizeof(pt_nif_memo_stats).  A NULL handle is PT_ERR_INVALID_ARGUMENT. */
 typedef struct pt_nif_memo_stats {
@@ -254,7 +273,7 @@ typedef struct pt_nif_memo_stats {
   int32_t enabled;               /* the memo is on */
   uint64_t slots, occupied;      /* capacity in use; valid entries after the last step */
   uint64_t escaped, served;      /* escaped paths of the last step; of those, served from entries of EARLIER steps */
-  uint64_t evaluations, inserted;/* NIF rows the last step ran; new entries it published */
+  uint64_t evaluations, inserted;/* distinct (u, v) bit pairs the last step handed to its NIF stage (pt_nif_sharing_stats.evaluations); new entries it published */
   uint64_t overflowed;           /* evaluated alone: no slot within the probe limit */
   uint64_t generation, retains;  /* bumped by upload / clear / failed step; retain passes so far */
   double memo_ms;                /* device time of the memo passes of the last step (HIP events, read lazily) */

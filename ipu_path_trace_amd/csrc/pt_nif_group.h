@@ -8,7 +8,8 @@
 //   S(b)  claim + resolve (trace stream): every entry of the queue T(b) wrote claims its 64-bit key (bits of u : bits of v) in
 //         an open-addressed device table.  The entry that claims a key appends (u, v) to the batch's DISTINCT queue; every
 //         entry records an owner word (ptmi_share_plan.h): the index of its owner in the step's BGR store, or the table slot
-//         it is served from.
+//         it is served from.  (Step scope and the memo run the resolve pass at the head of N(b), on the NIF stream:
+//         ptmi_nif_group.h, resolve_on_nif_stream.)
 //   N(b)  the unmodified NIF kernels in their out_bgr mode (as pt_nif_infer drives them) over the distinct queue.
 //   E(b)  expand (accumulate stream, ahead of the accumulate kernel): rad_r[q_path[q]] = bgr_owner[2] * q_tr[q], and likewise
 //         for g and b -- the head's own expressions, so every per-path radiance is the per-path mode's bit for bit.
@@ -28,6 +29,13 @@
 //   store_index(s)       the owner's store index of a slot claimed in this step, for resolve
 //   served_bgr(s)        the BGR of a served slot, for expand
 //   count(served, fresh) the table's own counters, a claim tile's sums at a time (only a table that serves has any)
+//   key_of(u, v)         the key an entry claims: the 64 raw bits for ShareTable and MemoTable
+//
+// The class level of N(b).  ClassTable is ShareTable with another key_of: ptshare::class_key, under which two entries are
+// equal when the NIF kernels compute the same output for them (ptmi_share_plan.h).  That is a property of the kernels'
+// encoder, not of (u, v), so it sits one layer down: on the NIF stream, claim and resolve run once more, over the batch's
+// distinct queue as one region; the NIF kernels then run over the class queue, and class_spread_kernel copies every distinct
+// entry's BGR from its class owner, so that E(b) and the memo's publish pass read the step store as before.
 #pragma once
 
 #include "ptmi_share_plan.h"
@@ -86,17 +94,27 @@ struct GroupExpand {
   float* rad_r; float* rad_g; float* rad_b;
 };
 
+__device__ __forceinline__ unsigned long long raw_key(float u, float v) {
+  return ((unsigned long long)__float_as_uint(u) << 32) | (unsigned long long)__float_as_uint(v);
+}
+
 // slot_mask + 1 slots, a power of two <= 2^30: key and store index of its owner
 struct ShareTable {
   unsigned long long* keys;
   uint32_t* vals;
   uint32_t slot_mask;
   static constexpr bool kServes = false;
+  static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return raw_key(u, v); }
   __device__ __forceinline__ unsigned long long* key(uint32_t s) const { return keys + s; }
   __device__ __forceinline__ void append(uint32_t, bool, uint32_t) const {}
   __device__ __forceinline__ void claim(uint32_t s, uint32_t g) const { vals[s] = g; }
   __device__ __forceinline__ void stamp(uint32_t) const {}
   __device__ __forceinline__ uint32_t store_index(uint32_t s) const { return vals[s]; }
+};
+
+// the class level's table (ptmi_share_plan.h: class_slots): key = the class of (u, v), value = the class-store index of its owner
+struct ClassTable : ShareTable {
+  static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return ptshare::class_key(u, v); }
 };
 
 // slot_mask + 1 slots of pt_nif_memo.h
@@ -107,6 +125,7 @@ struct MemoTable {
   uint32_t* d_slot;          // [store index]: memo slot to publish the entry into, or kMemoNoSlot
   unsigned long long* counters;   // kMemoCounters
   static constexpr bool kServes = true;
+  static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return raw_key(u, v); }
   __device__ __forceinline__ unsigned long long* key(uint32_t s) const { return &slots[s].key; }
   // valid only if published by an earlier step (publish runs after every lookup of its step): a claim of this step whose
   // state is not written yet reads kMemoFree or the stamp, never kMemoValid.  A plain load, no atomic operation.
@@ -166,14 +185,14 @@ __device__ __forceinline__ void group_claim(const GroupQueue& Q, const Table& T)
   unsigned long long cur[K];
 #pragma unroll
   for (uint32_t k = 0; k < K; ++k) {
-    const unsigned long long key = ((unsigned long long)__float_as_uint(u[k]) << 32) | (unsigned long long)__float_as_uint(v[k]);
+    const unsigned long long key = Table::key_of(u[k], v[k]);
     slot[k] = share_hash(key) & T.slot_mask;
     cur[k] = __hip_atomic_load(T.key(slot[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (no branch, as above)
   }
 #pragma unroll
   for (uint32_t k = 0; k < K; ++k) {
     if (!((valid >> k) & 1u)) continue;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(u[k]) << 32) | (unsigned long long)__float_as_uint(v[k]);
+    const unsigned long long key = Table::key_of(u[k], v[k]);
     bool none = true;
     if (key != kShareEmpty) {
       uint32_t s = slot[k];
@@ -281,5 +300,23 @@ __global__ __launch_bounds__(kShareBlock) void share_expand_kernel(GroupExpand E
 __global__ __launch_bounds__(kShareBlock) void memo_lookup_kernel(GroupQueue Q, MemoTable T) { group_claim(Q, T); }
 __global__ __launch_bounds__(kShareBlock) void memo_resolve_kernel(GroupQueue Q, MemoTable T) { group_resolve(Q, T); }
 __global__ __launch_bounds__(kShareBlock) void memo_expand_kernel(GroupExpand E, MemoTable T) { group_expand(E, T); }
+
+// The class level: claim and resolve over a batch's distinct queue (one region; Q.owner: [position in the distinct queue], the
+// class-store index of the entry's class owner; Q.d_u / d_v: the batch's class queue), and the spread behind the NIF launch.
+__global__ __launch_bounds__(kShareBlock) void class_claim_kernel(GroupQueue Q, ClassTable T) { group_claim(Q, T); }
+__global__ __launch_bounds__(kShareBlock) void class_resolve_kernel(GroupQueue Q, ClassTable T) { group_resolve(Q, T); }
+
+// bgr[i] = class_bgr[owner[i]] for the *count entries of a batch's distinct queue: 12-byte copies, no arithmetic.  bgr: the
+// batch's region of the step store; class_bgr: the step's class store from index 0.  Grid-stride over `cap` >= *count.
+__global__ __launch_bounds__(kShareBlock) void class_spread_kernel(const uint32_t* count, const uint32_t* owner, const float* class_bgr,
+                                                                   float* bgr) {
+  const uint32_t n = *count;
+  for (uint32_t i = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x; i < n; i += gridDim.x * (uint32_t)kShareBlock) {
+    const float* from = class_bgr + 3 * (size_t)owner[i];
+    const float b = from[0], g = from[1], r = from[2];
+    float* to = bgr + 3 * (size_t)i;
+    to[0] = b; to[1] = g; to[2] = r;
+  }
+}
 
 }  // namespace ptd

@@ -319,6 +319,27 @@ struct pt_context {
     uint64_t share_evals = 0, share_overflowed = 0;
     double share_ms = 0;
 
+    // the class level of the NIF stage (pt_nif_group.h: ClassTable): whenever N(b) runs over a distinct queue of a NIF, it
+    // evaluates one row per class of the kernels' encoder input.  The table and the class store live for one pt_path_trace,
+    // whatever the sharing mode: cleared at the start of every step, batch b's class queue at region b.  If the buffers do
+    // not fit (ptshare::class_fits) or an allocation fails, the handle runs without the level: the same bytes, no error.
+    DevBuf<unsigned long long> d_class_keys;
+    DevBuf<uint32_t> d_class_vals;
+    uint32_t class_slots = 0;                  // table capacity, a power of two
+    uint32_t class_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_class_capacity), 0 = sized by the rule
+    DevBuf<uint32_t> d_class_owner;            // [queue_cap]: class-store index of the owner of every entry of the distinct queue in flight
+    DevBuf<float> d_class_u, d_class_v, d_class_bgr;   // class queues and their decoded BGR: class_regions x queue_cap
+    size_t class_regions = 0;
+    DevBuf<uint32_t> d_class_count;            // [batch] class-queue length
+    DevBuf<unsigned long long> d_class_over;   // rows evaluated alone
+    PinnedBuf<uint32_t> h_class_count;         // pinned copies, written at the end of the step on `stream`
+    PinnedBuf<unsigned long long> h_class_over;
+    size_t class_count_cap = 0;
+    bool class_failed = false;                 // an allocation failed: no class level on this handle from now on
+    bool class_ran = false;                    // the last pt_path_trace ran the level
+    uint64_t class_rows = 0, class_alone = 0;
+    double class_ms = 0;
+
     // persistent memo of decoded NIF values (pt_set_nif_memo).  Unlike the sharing table it outlives the step:
     // it is cleared at allocation, on a new generation (pt_upload_nif, pt_clear_nif_memo, a failed pt_path_trace) and by the
     // retain pass.  With the memo on, every step uses the step-scope store above (d_share_u / _v / _bgr, d_share_count).
@@ -340,7 +361,7 @@ struct pt_context {
   // host time a step of a small image should not pay (BASELINE configs[0] is one millisecond of device work per step).
   pt_stats stats{};
   std::vector<hipEvent_t> events;
-  enum SpanKind { kSpanNone = -1, kSpanTrace, kSpanNif, kSpanAccumulate, kSpanShare, kSpanMemo };
+  enum SpanKind { kSpanNone = -1, kSpanTrace, kSpanNif, kSpanAccumulate, kSpanShare, kSpanMemo, kSpanClass };
   struct StageSpan { size_t a, b; int kind; };   // event pair (indices into `events`) around one stage of one batch
   std::vector<StageSpan> spans;
   size_t e_begin_i = 0, e_end_i = 0;

@@ -1,6 +1,6 @@
 // ptmi_nif_group.h -- host side of NIF sharing and the memo (pt_set_nif_sharing, pt_set_nif_memo; kernels: pt_nif_group.h,
 // pt_nif_memo.h; arithmetic: ptmi_share_plan.h): the buffers of pt_context::group, the mode a step runs in, the stages S(b) and
-// E(b) and the memo's publish pass, the entry points and the test build's hooks.  Part of the one translation unit ptmi.hip,
+// E(b) and the memo's publish pass, the class level of N(b), the entry points and the test build's hooks.  Part of the one translation unit ptmi.hip,
 // included there behind `Batch` and ahead of the other stages of a step, which take the StepMode.
 #pragma once
 
@@ -186,6 +186,7 @@ static int enqueue_memo_prologue(pt_handle h) {
 struct StepMode {
   int32_t share;   // sharing mode in force (off for a constant environment)
   bool memo;
+  bool classes = false;   // N(b) evaluates a row per class of its distinct queue (prepare_class_level)
   bool grouped() const { return share || memo; }   // N runs over distinct queues in the step store
   bool step_scope() const { return memo || share == PT_NIF_SHARE_STEP; }
   ptshare::StepKind kind() const {   // what the step does to the sharing table (ptmi_share_plan.h: the clean-table hand-off)
@@ -228,6 +229,109 @@ static int prepare_group_store(pt_handle h, const StepMode& mode, size_t batches
   return PT_OK;
 }
 
+// ---- the class level of N(b) (pt_nif_group.h: ClassTable; sizes: ptmi_share_plan.h).  All of it runs on the NIF stream.
+static void free_class_buffers(pt_handle h) {
+  h->group.d_class_keys.reset(); h->group.d_class_vals.reset();
+  h->group.class_slots = 0;
+  h->group.d_class_u.reset(); h->group.d_class_v.reset(); h->group.d_class_bgr.reset();
+  h->group.class_regions = 0;
+  h->group.d_class_owner.reset();
+}
+
+static int alloc_class_buffers(pt_handle h, uint32_t slots, size_t batches) {
+  PT_HIP(hipStreamSynchronize(h->stream));
+  if (!h->group.d_class_keys || (h->group.class_diag_slots ? slots != h->group.class_slots : slots > h->group.class_slots)) {
+    h->group.d_class_keys.reset(); h->group.d_class_vals.reset();
+    h->group.class_slots = 0;
+    PT_HIP(dev_alloc(h->group.d_class_keys, slots));
+    PT_HIP(dev_alloc(h->group.d_class_vals, slots));
+    h->group.class_slots = slots;
+  }
+  if (batches > h->group.class_regions) {
+    h->group.d_class_u.reset(); h->group.d_class_v.reset(); h->group.d_class_bgr.reset();
+    h->group.class_regions = 0;
+    PT_HIP(dev_alloc(h->group.d_class_u, batches * h->queue_cap));
+    PT_HIP(dev_alloc(h->group.d_class_v, batches * h->queue_cap));
+    PT_HIP(dev_alloc(h->group.d_class_bgr, 3 * batches * h->queue_cap));
+    h->group.class_regions = batches;
+  }
+  if (!h->group.d_class_owner) PT_HIP(dev_alloc(h->group.d_class_owner, h->queue_cap));
+  if (!h->group.d_class_over) {
+    PT_HIP(dev_alloc(h->group.d_class_over, 1));
+    PT_HIP(dev_alloc(h->group.h_class_over, 1));
+  }
+  if (batches > h->group.class_count_cap) {
+    h->group.class_count_cap = 0;
+    PT_HIP(dev_alloc(h->group.d_class_count, batches));
+    PT_HIP(dev_alloc(h->group.h_class_count, batches));
+    h->group.class_count_cap = batches;
+  }
+  return PT_OK;
+}
+
+// Before the first batch of a grouped step, behind prepare_group_store (the sharing buffers come first): whether the step
+// runs the class level -- the environment is a NIF, and the level's buffers at the step's size are held or fit the budget
+// (ptshare::class_fits) and could be allocated -- and, if it does, the table, the counts and the alone counter cleared on the
+// NIF stream, where they overlap T(0).  Declining is no error: the step is then the one without the level.
+static int prepare_class_level(pt_handle h, size_t batches, bool& classes) {
+  classes = false;
+  if (h->env_map || h->group.class_failed) return PT_OK;
+  const uint64_t free_b = free_device_bytes();
+  const uint32_t slots = h->group.class_diag_slots ? h->group.class_diag_slots : ptshare::class_slots(batches * (uint64_t)h->queue_cap, free_b);
+  ptshare::ClassHeld held;
+  held.table_slots = h->group.d_class_keys ? (h->group.class_diag_slots ? (h->group.class_slots == slots ? slots : 0) : h->group.class_slots) : 0;
+  held.store_regions = h->group.class_regions;
+  held.owner_maps = h->group.d_class_owner ? 1 : 0;
+  if (!ptshare::class_fits(slots, batches, h->queue_cap, held, free_b)) return PT_OK;
+  if (alloc_class_buffers(h, slots, batches) != PT_OK) {   // give back what was taken and run without the level from now on
+    (void)hipGetLastError();
+    free_class_buffers(h);
+    h->group.class_failed = true;
+    h->error.clear();
+    return PT_OK;
+  }
+  PT_HIP(hipMemsetAsync(h->group.d_class_keys, 0xff, (size_t)h->group.class_slots * 8, h->stream));
+  PT_HIP(hipMemsetAsync(h->group.d_class_count, 0, batches * 4, h->stream));
+  PT_HIP(hipMemsetAsync(h->group.d_class_over, 0, 8, h->stream));
+  classes = true;
+  return PT_OK;
+}
+
+static ptd::ClassTable class_table(pt_handle h) { return {{h->group.d_class_keys, h->group.d_class_vals, h->group.class_slots - 1u}}; }
+
+// The head of N(b) with the class level: claim and resolve over the batch's distinct queue, one region whose count S(b) left
+// on the device.  An entry that claims a class appends its own (u, v) to the batch's class queue (class region b).
+static int stage_class_claim(pt_handle h, StepEvents& ev, const Batch& b) {
+  return ev.timed(h->stream, pt_context::kSpanClass, [&]() -> int {
+    ptd::GroupQueue Q;
+    Q.q_u = h->group.d_share_u + b.store_base; Q.q_v = h->group.d_share_v + b.store_base;
+    Q.region_count = h->group.d_share_count + b.index;
+    Q.region_cap = b.store_cap;
+    Q.owner = h->group.d_class_owner;
+    Q.d_u = h->group.d_class_u + b.class_base; Q.d_v = h->group.d_class_v + b.class_base;
+    Q.d_count = h->group.d_class_count + b.index;
+    Q.base = b.class_base;
+    Q.overflowed = h->group.d_class_over;
+    const dim3 tiles(ptshare::claim_tiles(b.store_cap), 1), grid((b.store_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock, 1), block(ptd::kShareBlock);
+    hipLaunchKernelGGL(ptd::class_claim_kernel, tiles, block, 0, h->stream, Q, class_table(h));
+    PT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ptd::class_resolve_kernel, grid, block, 0, h->stream, Q, class_table(h));
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+  });
+}
+
+// ... and its tail: every entry of the distinct queue gets the BGR of its class owner, into the step store.
+static int stage_class_spread(pt_handle h, StepEvents& ev, const Batch& b, hipEvent_t* done) {
+  return ev.timed(h->stream, pt_context::kSpanClass, [&]() -> int {
+    const uint32_t grid = std::min<uint32_t>(ptd::kMemoGrid, (b.store_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock);
+    hipLaunchKernelGGL(ptd::class_spread_kernel, dim3(grid), dim3(ptd::kShareBlock), 0, h->stream, h->group.d_share_count + b.index,
+                       h->group.d_class_owner, h->group.d_class_bgr, h->group.d_share_bgr + 3 * (size_t)b.store_base);
+    PT_HIP(hipGetLastError());
+    return PT_OK;
+  }, done);
+}
+
 // Behind the last S(b) of a step-scope step, which is the table's last reader: the clear for the NEXT step, on the trace
 // stream, where it runs beside the last NIF launches instead of ahead of the next step's T(0).  `clean` is recorded behind
 // it; the step's end waits for it, and pt_path_trace sets the mark (ptshare::mark_after_step) once the step has returned.
@@ -242,34 +346,55 @@ static ptd::MemoTable memo_table(pt_handle h) {
   return {h->group.d_memo, h->group.memo_slots - 1u, h->group.memo_step, h->group.d_memo_slot, h->group.d_memo_ctr};
 }
 
-// S(b), right behind T(b) (it hides under N(b - 1) as T(b) does): claim a slot per key -- in the sharing table, or with the
-// memo look the key up -- then resolve the owners claimed in this step.
-static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b) {
-  return ev.timed(h->trace_stream, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
-    ptd::GroupQueue Q;   // the batch's queue, its owner map and its distinct queue in the store
-    Q.q_u = b.B->q_u; Q.q_v = b.B->q_v;
-    Q.region_count = b.B->region_count;
-    Q.region_cap = b.g.region_cap;
-    Q.owner = h->group.d_share_owner[b.set()];
-    Q.d_u = h->group.d_share_u + b.store_base; Q.d_v = h->group.d_share_v + b.store_base;
-    Q.d_count = h->group.d_share_count + b.index;
-    Q.base = b.store_base;
-    Q.overflowed = h->group.d_share_over;
-    const dim3 grid = b.group_grid(), tiles = b.claim_grid(), block(ptd::kShareBlock);
-    if (mode.memo) {
-      hipLaunchKernelGGL(ptd::memo_lookup_kernel, tiles, block, 0, h->trace_stream, Q, memo_table(h));
-      PT_HIP(hipGetLastError());
-      hipLaunchKernelGGL(ptd::memo_resolve_kernel, grid, block, 0, h->trace_stream, Q, memo_table(h));
-    } else {
-      if (mode.share == PT_NIF_SHARE_BATCH)   // one table per batch
-        PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
-      hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_table(h));
-      PT_HIP(hipGetLastError());
-      hipLaunchKernelGGL(ptd::share_resolve_kernel, grid, block, 0, h->trace_stream, Q, share_table(h));
-    }
+// The batch's queue, its owner map and its distinct queue in the store, as claim and resolve take them.
+static ptd::GroupQueue group_queue(pt_handle h, const Batch& b) {
+  ptd::GroupQueue Q;
+  Q.q_u = b.B->q_u; Q.q_v = b.B->q_v;
+  Q.region_count = b.B->region_count;
+  Q.region_cap = b.g.region_cap;
+  Q.owner = h->group.d_share_owner[b.set()];
+  Q.d_u = h->group.d_share_u + b.store_base; Q.d_v = h->group.d_share_v + b.store_base;
+  Q.d_count = h->group.d_share_count + b.index;
+  Q.base = b.store_base;
+  Q.overflowed = h->group.d_share_over;
+  return Q;
+}
+
+// The resolve pass of S(b) on stream `s`: the owners claimed in this step get their store index.
+static int stage_resolve(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b, hipStream_t s) {
+  return ev.timed(s, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
+    const ptd::GroupQueue Q = group_queue(h, b);
+    if (mode.memo) hipLaunchKernelGGL(ptd::memo_resolve_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, s, Q, memo_table(h));
+    else hipLaunchKernelGGL(ptd::share_resolve_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, s, Q, share_table(h));
     PT_HIP(hipGetLastError());
     return PT_OK;
   });
+}
+
+// Since the class level the NIF stream has room and the trace stream is what a step waits for (profiles/r28_nif_classes.txt),
+// so a step-scope step (the memo included) resolves at the head of N(b), on the NIF stream.  Nothing on the trace stream
+// writes what the pass reads: claims of later batches write the value of slots they claim fresh, the pass reads the values
+// of slots claimed up to its own batch, and the table's clears touch the keys alone.  Batch scope reuses its table from batch
+// to batch and resolves where it claims.
+static bool resolve_on_nif_stream(const StepMode& mode) { return mode.step_scope(); }
+
+// S(b), right behind T(b) (it hides under N(b - 1) as T(b) does): claim a slot per key -- in the sharing table, or with the
+// memo look the key up -- then (batch scope) resolve the owners claimed in this batch.
+static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b) {
+  if (int rc = ev.timed(h->trace_stream, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
+        const ptd::GroupQueue Q = group_queue(h, b);
+        const dim3 tiles = b.claim_grid(), block(ptd::kShareBlock);
+        if (mode.memo) {
+          hipLaunchKernelGGL(ptd::memo_lookup_kernel, tiles, block, 0, h->trace_stream, Q, memo_table(h));
+        } else {
+          if (mode.share == PT_NIF_SHARE_BATCH)   // one table per batch
+            PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
+          hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_table(h));
+        }
+        PT_HIP(hipGetLastError());
+        return PT_OK;
+      })) return rc;
+  return resolve_on_nif_stream(mode) ? PT_OK : stage_resolve(h, ev, mode, b, h->trace_stream);
 }
 
 // E(b), ahead of A(b) (it overlaps N(b + 1) as A(b) does): per-path radiance from the owners' BGR in the step store, or with
@@ -328,6 +453,18 @@ int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out) {
   out->overflowed = h->group.share_overflowed;
   out->table_slots = h->group.share_mode_last && !h->group.memo_ran ? h->group.share_slots : 0;
   out->share_ms = h->group.share_ms;
+  return PT_OK;
+}
+
+int pt_get_nif_class_stats(pt_handle h, pt_nif_class_stats* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_nif_class_stats)) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_nif_class_stats.struct_size mismatch");
+  if (int rc = resolve_stage_times(h)) return rc;
+  out->ran = h->group.class_ran;
+  out->mlp_rows = h->group.class_ran ? h->group.class_rows : h->group.share_evals;
+  out->alone = h->group.class_ran ? h->group.class_alone : 0;
+  out->table_slots = h->group.class_ran ? h->group.class_slots : 0;
+  out->class_ms = h->group.class_ms;
   return PT_OK;
 }
 
@@ -474,6 +611,58 @@ int pt_diag_claim_resolve(pt_handle h, int32_t memo, uint32_t passes, const floa
     if (memo) PT_HIP(hipMemcpy2DAsync(table_keys, 8, slots, sizeof(ptd::MemoSlot), 8, table_slots, hipMemcpyDeviceToHost, s));
     else PT_HIP(hipMemcpyAsync(table_keys, keys, (size_t)table_slots * 8, hipMemcpyDeviceToHost, s));
   }
+  PT_HIP(hipStreamSynchronize(s));
+  return PT_OK;
+}
+
+// test build only: the class table gets exactly `slots` slots (rounded up to a power of two; 0 = sized by the rule again), so that
+// a test reaches the evaluated-alone path with a small image
+int pt_diag_set_nif_class_capacity(pt_handle h, uint32_t slots) {
+  if (!h || slots > ptshare::kClassMaxSlots) return PT_ERR_INVALID_ARGUMENT;
+  uint32_t p = slots ? 2 : 0;
+  while (p < slots) p <<= 1;
+  h->group.class_diag_slots = p;
+  h->group.class_failed = false;
+  return PT_OK;
+}
+
+// test build only: the class level's claim and resolve over a distinct queue the caller supplies -- one region of n rows --
+// with buffers of its own and a ClassTable of table_slots slots (a power of two).  Out, on the host: owner [n] (the position
+// in the class queue of every row's class owner), the class queue c_u / c_v [n], its length and the rows evaluated alone.
+int pt_diag_class_claim(pt_handle h, const float* u, const float* v, uint32_t n, uint32_t table_slots, uint32_t* owner, float* c_u,
+                        float* c_v, uint32_t* c_count, uint64_t* alone) {
+  if (!h || !u || !v || !owner || !c_u || !c_v || !c_count || !alone) return PT_ERR_INVALID_ARGUMENT;
+  if (n == 0 || n >= ptshare::kMaxStoreEntries || table_slots < 2 || table_slots > ptshare::kClassMaxSlots || (table_slots & (table_slots - 1u)))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_class_claim: sizes out of range");
+  PT_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t s = h->stream;
+  DevBuf<float> q_u, q_v, du, dv;
+  DevBuf<uint32_t> count, own, len, vals;
+  DevBuf<unsigned long long> over, keys;
+  PT_HIP(dev_alloc(q_u, n)); PT_HIP(dev_alloc(q_v, n)); PT_HIP(dev_alloc(du, n)); PT_HIP(dev_alloc(dv, n));
+  PT_HIP(dev_alloc(count, 1)); PT_HIP(dev_alloc(own, n)); PT_HIP(dev_alloc(len, 1)); PT_HIP(dev_alloc(over, 1));
+  PT_HIP(dev_alloc(keys, table_slots)); PT_HIP(dev_alloc(vals, table_slots));
+  PT_HIP(hipMemcpyAsync(q_u, u, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(q_v, v, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(count, &n, 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemsetAsync(own, 0xff, (size_t)n * 4, s));   // an entry no pass writes reads as pending
+  PT_HIP(hipMemsetAsync(over, 0, 8, s));
+  PT_HIP(hipMemsetAsync(len, 0, 4, s));
+  PT_HIP(hipMemsetAsync(keys, 0xff, (size_t)table_slots * 8, s));
+  ptd::GroupQueue Q;
+  Q.q_u = q_u; Q.q_v = q_v; Q.region_count = count; Q.region_cap = n; Q.owner = own;
+  Q.d_u = du; Q.d_v = dv; Q.d_count = len; Q.base = 0; Q.overflowed = over;
+  const ptd::ClassTable T{{keys, vals, table_slots - 1u}};
+  const dim3 grid((n + ptd::kShareBlock - 1u) / ptd::kShareBlock, 1), tiles(ptshare::claim_tiles(n), 1), block(ptd::kShareBlock);
+  hipLaunchKernelGGL(ptd::class_claim_kernel, tiles, block, 0, s, Q, T);
+  PT_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ptd::class_resolve_kernel, grid, block, 0, s, Q, T);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipMemcpyAsync(owner, own, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(c_u, du, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(c_v, dv, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(c_count, len, 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(alone, over, 8, hipMemcpyDeviceToHost, s));
   PT_HIP(hipStreamSynchronize(s));
   return PT_OK;
 }

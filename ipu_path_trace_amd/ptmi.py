@@ -43,6 +43,7 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_comm_get_unique_id", "pt_comm_init_rank", "pt_comm_init_all", "pt_comm_info", "pt_comm_set_timeout", "pt_comm_abort",
            "pt_gather_hdr", "pt_film_accumulate", "pt_tile_costs_enable", "pt_tile_costs", "pt_film_seed",
            "pt_nif_kernel_name", "pt_calibrate_nif", "pt_runtime_info", "pt_set_nif_sharing", "pt_get_nif_sharing_stats",
+           "pt_get_nif_class_stats",
            "pt_set_nif_memo", "pt_clear_nif_memo", "pt_get_nif_memo_stats", "pt_set_scene", "pt_get_scene",
            "pt_set_camera", "pt_get_camera", "pt_set_env_map", "pt_env_map_lookup", "pt_feature_buffers",
            "pt_denoise_default_params", "pt_denoise", "pt_nif_train_default_params", "pt_nif_train_begin",
@@ -547,6 +548,14 @@ class NifSharingStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
+class NifClassStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ran", C.c_int32), ("mlp_rows", C.c_uint64), ("alone", C.c_uint64),
+                ("table_slots", C.c_uint64), ("class_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 class NifMemoStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("enabled", C.c_int32), ("slots", C.c_uint64), ("occupied", C.c_uint64),
                 ("escaped", C.c_uint64), ("served", C.c_uint64), ("evaluations", C.c_uint64), ("inserted", C.c_uint64),
@@ -615,6 +624,7 @@ def load_library(diag=False):
     L.pt_runtime_info.argtypes = [C.c_char_p, C.c_size_t]
     L.pt_set_nif_sharing.argtypes = [C.c_void_p, C.c_int32]
     L.pt_get_nif_sharing_stats.argtypes = [C.c_void_p, C.POINTER(NifSharingStats)]
+    L.pt_get_nif_class_stats.argtypes = [C.c_void_p, C.POINTER(NifClassStats)]
     L.pt_set_nif_memo.argtypes = [C.c_void_p, C.c_uint64]
     L.pt_clear_nif_memo.argtypes = [C.c_void_p]
     L.pt_get_nif_memo_stats.argtypes = [C.c_void_p, C.POINTER(NifMemoStats)]
@@ -671,6 +681,8 @@ def load_library(diag=False):
         L.pt_diag_set_nif_share_capacity.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_claim_resolve.argtypes = [C.c_void_p, C.c_int32, C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p] * 7
+        L.pt_diag_set_nif_class_capacity.argtypes = [C.c_void_p, C.c_uint32]
+        L.pt_diag_class_claim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
         L.pt_diag_inject_fault.argtypes = [C.c_void_p, C.c_int32]
         L.pt_diag_stamps.argtypes = [C.c_void_p, C.c_void_p]
         L.pt_diag_nif_clock.argtypes = [C.c_void_p, C.c_void_p]
@@ -977,6 +989,16 @@ class Renderer:
         self._check(self._lib.pt_get_nif_sharing_stats(self.handle, C.byref(st)))
         d = st.as_dict()
         d["mode"] = {v: k for k, v in NIF_SHARE_MODES.items()}.get(d["mode"], d["mode"])
+        return d
+
+    def nif_class_stats(self):
+        """The class level of the NIF stage in the last path_trace (include/ptmi.h, pt_nif_class_stats): dict of ran, mlp_rows
+        (rows the NIF kernels executed), alone, table_slots, class_ms."""
+        st = NifClassStats()
+        st.struct_size = C.sizeof(NifClassStats)
+        self._check(self._lib.pt_get_nif_class_stats(self.handle, C.byref(st)))
+        d = st.as_dict()
+        d["ran"] = bool(d["ran"])
         return d
 
     def set_scene(self, objects):

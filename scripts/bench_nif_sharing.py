@@ -47,7 +47,7 @@ def run(name, warmup, steps, MODES=MODES):
         r.setup(work.copy())
         handles[mode] = r
     acc = {m: {"sec": 0.0, "paths": 0, "escaped": 0, "evaluations": 0, "overflowed": 0, "nif_ms": 0.0, "share_ms": 0.0,
-               "total_ms": 0.0, "table_slots": 0} for m in MODES}
+               "total_ms": 0.0, "table_slots": 0, "mlp_rows": 0, "class_alone": 0, "class_ms": 0.0, "class_slots": 0} for m in MODES}
     for i in range(warmup + steps):
         for mode in MODES:
             r = handles[mode]
@@ -66,6 +66,11 @@ def run(name, warmup, steps, MODES=MODES):
                 a[k] += sh[k]
             a["table_slots"] = sh["table_slots"]
             a["ran"] = sh["mode"]
+            cl = r.nif_class_stats()   # the class level of the NIF stage: the rows the network really ran
+            a["mlp_rows"] += cl["mlp_rows"]
+            a["class_alone"] += cl["alone"]
+            a["class_ms"] += cl["class_ms"]
+            a["class_slots"] = cl["table_slots"]
     films = {}
     for mode in MODES:
         r = handles[mode]
@@ -81,6 +86,8 @@ def run(name, warmup, steps, MODES=MODES):
             "shared_fraction": round(1.0 - a["evaluations"] / a["escaped"], 4) if a["escaped"] else 0.0,
             "overflowed_per_step": a["overflowed"] // steps, "table_slots": a["table_slots"],
             "nif_ms_per_step": round(a["nif_ms"] / steps, 2), "share_ms_per_step": round(a["share_ms"] / steps, 2),
+            "mlp_rows_per_step": a["mlp_rows"] // steps, "class_alone_per_step": a["class_alone"] // steps,
+            "class_table_slots": a["class_slots"], "class_ms_per_step": round(a["class_ms"] / steps, 2),
             "film_sha256": films[mode][:16], "film_equal_to_off": films[mode] == films["off"],
         }), flush=True)
     return all(films[m] == films["off"] for m in MODES)

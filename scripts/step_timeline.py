@@ -9,7 +9,8 @@ claim pass are the sharing handle's, the last --last of them the timed ones.  Pe
 kernel's end), the time a NIF launch is running, the share of the step with none.  Per batch b (--batches): A(b)'s begin and
 end relative to N(b+1)'s begin and end, and T(b+3)'s begin relative to A(b)'s end -- the edge that closes the ring of batch
 sets.  Then per-launch means of T, claim, resolve, N, E, A and the table's clear (a fill kernel of
-more than 0.2 ms)."""
+more than 0.2 ms) and, where the NIF stage has its class level, of its class claim, class resolve and spread passes; and for
+how much of a step each stream has a kernel of the step running."""
 import argparse
 import csv
 import glob
@@ -33,6 +34,9 @@ def kind(name):
     if "film_accumulate" in name: return "film"
     if "share_claim" in name or "memo_lookup" in name: return "claim"
     if "share_resolve" in name or "memo_resolve" in name: return "resolve"
+    if "class_claim" in name: return "cclaim"
+    if "class_resolve" in name: return "cresolve"
+    if "class_spread" in name: return "spread"
     if "share_expand" in name or "memo_expand" in name: return "expand"
     if "accumulate4_kernel" in name or "accumulate_kernel" in name: return "acc"
     if "trace_kernel" in name: return "trace"
@@ -72,12 +76,14 @@ def main():
     shared = [s for s in steps if any(kind(r[2]) == "claim" for r in s)]
     print("%s: %d steps in the trace, %d with a claim pass; the last %d are the timed ones" % (a.label, len(steps), len(shared), a.last))
     timed = shared[-a.last:]
-    per = {k: [] for k in ("trace", "claim", "resolve", "nif", "expand", "acc", "clear")}
+    KINDS = ("trace", "claim", "resolve", "cclaim", "cresolve", "nif", "spread", "expand", "acc")
+    per = {k: [] for k in KINDS + ("clear",)}
+    busy = {}
     streams = {k: set() for k in per}
     idle = []
     a_in_n, t_wait = [], []
     for si, s in enumerate(timed):
-        by = {k: [r for r in s if kind(r[2]) == k] for k in ("trace", "claim", "resolve", "nif", "expand", "acc")}
+        by = {k: [r for r in s if kind(r[2]) == k] for k in KINDS}
         clears = [r for r in s if kind(r[2]) == "fill" and r[1] - r[0] > 200000]
         core = [r for r in s if kind(r[2]) in by]   # the step proper: its own passes (and the clears)
         t0 = min(r[0] for r in core + clears)
@@ -90,6 +96,8 @@ def main():
             streams[k] |= {"s%s/q%s" % (r[3], r[4]) for r in by[k]}
         per["clear"] += [(r[1] - r[0]) / 1e6 for r in clears]
         streams["clear"] |= {"s%s/q%s" % (r[3], r[4]) for r in clears}
+        for q in {r[3] for r in core + clears}:
+            busy.setdefault(q, []).append(100.0 * union_ms([(r[0], r[1]) for r in core + clears if r[3] == q]) / span)
         head = (by["nif"][0][0] - t0) / 1e6 if by["nif"] else 0.0
         print("%s step %d: %d batches, span %.2f ms, NIF running %.2f ms, no NIF launch running %.1f %% of the step, first N begins at %.2f ms; clears: %s"
               % (a.label, si, len(by["nif"]), span, nif_ms, idle[-1], head,
@@ -110,10 +118,12 @@ def main():
                 t_wait.append((T[b + 3][0] - A[b][1]) / 1e6)
             if a.batches:
                 print(line)
-    for k in ("trace", "claim", "resolve", "nif", "expand", "acc", "clear"):
+    for k in KINDS + ("clear",):
         if per[k]:
             print("%s %-8s n %4d  mean per launch %.3f ms  per step %.2f ms  streams %s"
                   % (a.label, k, len(per[k]), statistics.mean(per[k]), sum(per[k]) / max(1, len(timed)), sorted(streams[k])))
+    for q in sorted(busy):
+        print("%s stream %s has a kernel of the step running for %.1f %% of a step on average" % (a.label, q, statistics.mean(busy[q])))
     if idle:
         print("%s no NIF launch running: min %.1f %%, mean %.1f %%, max %.1f %% of a step" % (a.label, min(idle), statistics.mean(idle), max(idle)))
     if a_in_n:
