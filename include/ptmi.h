@@ -221,7 +221,7 @@ typedef struct pt_nif_sharing_stats {
   uint64_t evaluations;          /* distinct (u, v) bit pairs the last path_trace handed to its NIF stage: the distinct queues' length (= escaped with sharing off); the rows the network ran are pt_nif_class_stats.mlp_rows */
   uint64_t overflowed;           /* entries evaluated alone because no table slot was free */
   uint64_t table_slots;          /* table capacity in use (0 with sharing off) */
-  double share_ms;               /* device time of the sharing passes (HIP events, read lazily like the stage times) */
+  double share_ms;               /* device time of the sharing passes (HIP events, read lazily like the stage times); at step scope without the memo these claim the class too (pt_nif_class_stats), and their time is all here */
 } pt_nif_sharing_stats;
 int pt_set_nif_sharing(pt_handle h, int32_t mode);
 int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
@@ -234,6 +234,10 @@ int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
  * table lives for one pt_path_trace.  Every output is the same bytes as without the level; the sharing key, the memo key and
  * pt_nif_sharing_stats.evaluations stay what they were.  If the level's buffers do not fit a quarter of the free device memory,
  * or their allocation fails, the step runs without it, and that is no error.  Sharing off launches nothing of it.
+ * In a PT_NIF_SHARE_STEP step (chosen or automatic) without the memo the level has no passes of its own: the sharing passes
+ * claim an entry's class where they claim its (u, v) pair and hand every path the BGR of its class's row.  class_ms is then 0
+ * and pt_nif_sharing_stats.share_ms covers the claim of both levels, the resolve and the expand pass; with PT_NIF_SHARE_BATCH
+ * and with the memo, class_ms is the level's own claim, resolve and spread passes.
  * The caller sets struct_size = sizeof(pt_nif_class_stats). */
 typedef struct pt_nif_class_stats {
   uint32_t struct_size;          /* sizeof(pt_nif_class_stats), set by the caller */
@@ -241,7 +245,7 @@ typedef struct pt_nif_class_stats {
   uint64_t mlp_rows;             /* rows the NIF kernels executed in the last path_trace (= evaluations if the level did not run) */
   uint64_t alone;                /* rows evaluated alone because no slot of the class table was free */
   uint64_t table_slots;          /* class table capacity in use (0 if the level did not run) */
-  double class_ms;               /* device time of the level's claim, resolve and spread passes (HIP events, read lazily) */
+  double class_ms;               /* device time of the level's own claim, resolve and spread passes (batch scope, the memo); 0 where the sharing passes claim the class (step scope without the memo) (HIP events, read lazily) */
 } pt_nif_class_stats;
 int pt_get_nif_class_stats(pt_handle h, pt_nif_class_stats* out);
 

@@ -36,6 +36,12 @@
 // encoder, not of (u, v), so it sits one layer down: on the NIF stream, claim and resolve run once more, over the batch's
 // distinct queue as one region; the NIF kernels then run over the class queue, and class_spread_kernel copies every distinct
 // entry's BGR from its class owner, so that E(b) and the memo's publish pass read the step store as before.
+//
+// The fused step (step scope, no memo).  ShareClassTable is ShareTable plus the step's class table and the batch's class queue: the raw table
+// claims and counts raw pairs exactly as ShareTable does, but an entry that appends to the distinct queue looks its class up in
+// the same pass, and what its raw slot's value and its owner word get is a CLASS-store index, or a pending class word
+// (ptmi_share_plan.h: owner_class).  Resolve takes up to two hops, the NIF kernels run over the class queue, and E(b) gathers
+// from the class store: no class pass of its own on the NIF stream, no spread, and no BGR in the step store.
 #pragma once
 
 #include "ptmi_share_plan.h"
@@ -45,6 +51,7 @@ namespace ptd {
 constexpr unsigned long long kShareEmpty = ~0ull;     // empty slot: u and v both the all-ones NaN pattern
 constexpr uint32_t kShareMaxProbes = 32;              // linear probes before a key is evaluated alone
 constexpr int kShareBlock = 256;
+constexpr uint32_t kClassInFlight = 2;                // class lookups a lane of the fused claim has in flight (of its kClaimK entries)
 static_assert(kShareBlock == (int)ptshare::kClaimBlock, "the claim tiles of ptmi_share_plan.h are for this workgroup");
 
 // 64-bit finaliser of MurmurHash3: neighbouring (u, v) bit patterns land on unrelated slots
@@ -104,6 +111,7 @@ struct ShareTable {
   uint32_t* vals;
   uint32_t slot_mask;
   static constexpr bool kServes = false;
+  static constexpr bool kClasses = false;
   static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return raw_key(u, v); }
   __device__ __forceinline__ unsigned long long* key(uint32_t s) const { return keys + s; }
   __device__ __forceinline__ void append(uint32_t, bool, uint32_t) const {}
@@ -117,6 +125,17 @@ struct ClassTable : ShareTable {
   static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return ptshare::class_key(u, v); }
 };
 
+// the fused claim's table: the raw table, whose values are class-store indices or pending class words, the step's class table
+// and the batch's class queue (c_u / c_v: class-store index c_base + i; *c_count its length; *c_alone: rows that found no class slot)
+struct ShareClassTable : ShareTable {
+  ClassTable classes;
+  float* c_u; float* c_v;
+  uint32_t* c_count;
+  uint32_t c_base;
+  unsigned long long* c_alone;
+  static constexpr bool kClasses = true;
+};
+
 // slot_mask + 1 slots of pt_nif_memo.h
 struct MemoTable {
   MemoSlot* slots;
@@ -125,6 +144,7 @@ struct MemoTable {
   uint32_t* d_slot;          // [store index]: memo slot to publish the entry into, or kMemoNoSlot
   unsigned long long* counters;   // kMemoCounters
   static constexpr bool kServes = true;
+  static constexpr bool kClasses = false;
   static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return raw_key(u, v); }
   __device__ __forceinline__ unsigned long long* key(uint32_t s) const { return &slots[s].key; }
   // valid only if published by an earlier step (publish runs after every lookup of its step): a claim of this step whose
@@ -213,6 +233,86 @@ __device__ __forceinline__ void group_claim(const GroupQueue& Q, const Table& T)
     if (none) alone |= 1u << k;
   }
   const uint32_t append = fresh | alone;
+  // The class phase (ShareClassTable): every entry that appends looks its class up in the class table, by the same probe rule.
+  // c_append: claimed a class, or found no class slot -- a row of the class queue; otherwise c_slot[k] holds the class.
+  [[maybe_unused]] uint32_t c_append = 0, c_fresh = 0, c_slot[K];
+  if constexpr (Table::kClasses) {
+    __shared__ uint32_t s_c_appends[W], s_c_alone[W];
+    __shared__ uint32_t s_c_first;
+    uint32_t c_alone = 0;
+    // kClassInFlight lookups at a time, not kClaimK: about a quarter of a tile's entries append, and eight more key words
+    // beside (u, v), the raw slots and the class slots of eight entries do not fit the step's register budget
+    static_assert(K % kClassInFlight == 0, "the class phase takes a lane's entries in whole groups");
+#pragma unroll
+    for (uint32_t k0 = 0; k0 < K; k0 += kClassInFlight) {
+      unsigned long long c_key[kClassInFlight], c_cur[kClassInFlight];
+#pragma unroll
+      for (uint32_t j = 0; j < kClassInFlight; ++j) {   // the first slots of the group's appending entries, in flight together
+        const uint32_t k = k0 + j;
+        c_slot[k] = 0u;
+        c_key[j] = c_cur[j] = kShareEmpty;
+        if ((append >> k) & 1u) {   // key and hash for the entries that append alone: the others never look at theirs
+          c_key[j] = ptshare::class_key(u[k], v[k]);
+          c_slot[k] = share_hash(c_key[j]) & T.classes.slot_mask;
+          c_cur[j] = __hip_atomic_load(T.classes.key(c_slot[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < kClassInFlight; ++j) {
+        const uint32_t k = k0 + j;
+        if (!((append >> k) & 1u)) continue;
+        const unsigned long long key = c_key[j];
+        bool none = true;
+        if (key != kShareEmpty) {
+          uint32_t s = c_slot[k];
+          unsigned long long c = c_cur[j];
+#pragma unroll 1
+          for (uint32_t p = 0;;) {
+            if (c == kShareEmpty) c = atomicCAS(T.classes.key(s), kShareEmpty, key);
+            if (c == kShareEmpty) { c_fresh |= 1u << k; none = false; c_slot[k] = s; break; }
+            if (c == key) { none = false; c_slot[k] = s; break; }
+            if (++p == kShareMaxProbes) break;
+            s = (s + 1u) & T.classes.slot_mask;
+            c = __hip_atomic_load(T.classes.key(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+        if (none) c_alone |= 1u << k;
+      }
+    }
+    c_append = c_fresh | c_alone;
+    // a second reservation per tile, in the class queue
+    uint32_t n_c_append = 0, n_c_alone = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < K; ++k) {
+      n_c_append += (uint32_t)__popcll(__ballot((c_append >> k) & 1u));
+      n_c_alone += (uint32_t)__popcll(__ballot((c_alone >> k) & 1u));
+    }
+    if (lane == 0) { s_c_appends[wave] = n_c_append; s_c_alone[wave] = n_c_alone; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t total = ptshare::claim_wave_offset(s_c_appends, W);
+      s_c_first = total ? atomicAdd(T.c_count, total) : 0u;
+      const uint32_t over = ptshare::claim_wave_offset(s_c_alone, W);
+      if (over) atomicAdd(T.c_alone, (unsigned long long)over);
+    }
+    __syncthreads();
+    uint32_t c_next = s_c_first + ptshare::claim_wave_offset(s_c_appends, wave);
+#pragma unroll
+    for (uint32_t k = 0; k < K; ++k) {   // c_slot[k] becomes the entry's word: its row of the class store, or its pending class
+      const uint32_t bit = 1u << k;
+      const uint64_t m = __ballot((c_append & bit) != 0);
+      if (c_append & bit) {
+        const uint32_t i = c_next + lane_rank(m);
+        T.c_u[i] = u[k]; T.c_v[i] = v[k];
+        const uint32_t g = T.c_base + i;
+        if (c_fresh & bit) T.classes.claim(c_slot[k], g);
+        c_slot[k] = g;
+      } else {
+        c_slot[k] = ptshare::owner_class(c_slot[k]);
+      }
+      c_next += (uint32_t)__popcll(m);
+    }
+  }
   // the wave's counts (wave ballots: scalar work), then the workgroup's through LDS
   uint32_t n_append = 0, n_alone = 0, n_served = 0, n_fresh = 0;
 #pragma unroll
@@ -246,7 +346,8 @@ __device__ __forceinline__ void group_claim(const GroupQueue& Q, const Table& T)
     if (append & bit) {
       const uint32_t i = next + lane_rank(m);
       Q.d_u[i] = u[k]; Q.d_v[i] = v[k];
-      const uint32_t g = Q.base + i;
+      uint32_t g = Q.base + i;
+      if constexpr (Table::kClasses) g = c_slot[k];   // what the slot and the owner word name is the class row, not the raw one
       T.append(g, (fresh & bit) != 0, slot[k]);
       if (fresh & bit) T.claim(slot[k], g);
       Q.owner[q] = g;
@@ -268,7 +369,16 @@ __device__ __forceinline__ void group_resolve(const GroupQueue& Q, const Table& 
   if (local >= Q.region_count[r]) return;
   const uint32_t q = r * Q.region_cap + local;
   const uint32_t o = Q.owner[q];
-  if (ptshare::owner_is_pending(o)) Q.owner[q] = T.store_index(ptshare::owner_slot(o));
+  if constexpr (Table::kClasses) {
+    // two hops (ptmi_share_plan.h): raw slot -> pending class word -> class slot.  The final index goes back into the raw slot,
+    // so that hits of later batches take one hop: every writer stores the same word, and readers accept either form.
+    uint32_t back;
+    const uint32_t w = ptshare::resolve_two_hops(o, T.vals, T.classes.vals, &back);
+    if (back != ptshare::kNoWriteBack) T.vals[back] = w;
+    if (w != o) Q.owner[q] = w;
+  } else {
+    if (ptshare::owner_is_pending(o)) Q.owner[q] = T.store_index(ptshare::owner_slot(o));
+  }
 }
 
 // the per-path radiance of the NIF heads' per-path mode, from the owner's decoded BGR in the step store or the served slot
@@ -300,6 +410,13 @@ __global__ __launch_bounds__(kShareBlock) void share_expand_kernel(GroupExpand E
 __global__ __launch_bounds__(kShareBlock) void memo_lookup_kernel(GroupQueue Q, MemoTable T) { group_claim(Q, T); }
 __global__ __launch_bounds__(kShareBlock) void memo_resolve_kernel(GroupQueue Q, MemoTable T) { group_resolve(Q, T); }
 __global__ __launch_bounds__(kShareBlock) void memo_expand_kernel(GroupExpand E, MemoTable T) { group_expand(E, T); }
+
+// The fused step: raw claim with the class lookup inside, two-hop resolve, and the expand from the class store (E.bgr).  The
+// claim states its occupancy: six waves per SIMD are the 80 registers of the step's budget (scripts/kernel_resources.py
+// --step-budget), which the allocator keeps without scratch with kClassInFlight lookups at a time and not with more.
+__global__ __launch_bounds__(kShareBlock) __attribute__((amdgpu_waves_per_eu(6))) void share_class_claim_kernel(GroupQueue Q, ShareClassTable T) { group_claim(Q, T); }
+__global__ __launch_bounds__(kShareBlock) void share_class_resolve_kernel(GroupQueue Q, ShareClassTable T) { group_resolve(Q, T); }
+__global__ __launch_bounds__(kShareBlock) void share_class_expand_kernel(GroupExpand E, ShareClassTable T) { group_expand(E, T); }
 
 // The class level: claim and resolve over a batch's distinct queue (one region; Q.owner: [position in the distinct queue], the
 // class-store index of the entry's class owner; Q.d_u / d_v: the batch's class queue), and the spread behind the NIF launch.

@@ -487,7 +487,9 @@ static void forget_replay_state(pt_handle h) {   // pt_calibrate_nif may only re
 // set travels N -> E -> A -> T -> S -> N, and `depth` batches share one trip: with two sets the trip, not any one stream, set
 // the pace of a step with sharing.  The A(b) are ordered among themselves (one stream), which keeps
 // every pixel's fp32 sum in iteration order.  With NIF sharing or the memo (ptmi_nif_group.h), S(b) runs behind T(b) and E(b) ahead of A(b),
-// and N(b) itself is class claim + resolve, the NIF launch over the batch's class queue, and the spread, all on `stream`.
+// and N(b) itself is class claim + resolve, the NIF launch over the batch's class queue, and the spread, all on `stream` -- with
+// the memo or at batch scope.  A step-scope step without the memo is fused (StepMode::fused): S(b) claims the class too, N(b) is the resolve and the NIF launch
+// over the class queue, and E(b) reads the class store.
 
 // One batch: its sample iterations, trace grid and buffer set, and (grouped) where its distinct queue lies in the store.
 struct Batch {
@@ -569,7 +571,7 @@ static int stage_nif(pt_handle h, StepEvents& ev, const StepMode& mode, const Ba
   hipEvent_t done = nullptr;
   if (mode.grouped() && resolve_on_nif_stream(mode))   // the resolve pass of S(b), behind its claims (B.traced)
     if (int rc = stage_resolve(h, ev, mode, b, h->stream)) return rc;
-  if (mode.classes)
+  if (mode.classes && !mode.fused())   // (fused: S(b) claimed the classes and filled the class queue)
     if (int rc = stage_class_claim(h, ev, b)) return rc;
   if (int rc = ev.timed(h->stream, h->env_const ? pt_context::kSpanNone : pt_context::kSpanNif, [&]() -> int {
         if (h->env_const) return PT_OK;
@@ -591,7 +593,7 @@ static int stage_nif(pt_handle h, StepEvents& ev, const StepMode& mode, const Ba
         h->stats.nif_launches += 1;
         return PT_OK;
       }, &done)) return rc;
-  if (mode.classes)
+  if (mode.classes && !mode.fused())   // (fused: E(b) reads the class store itself)
     if (int rc = stage_class_spread(h, ev, b, &done)) return rc;
   PT_HIP(hipStreamWaitEvent(h->acc_stream, done, 0));
   return PT_OK;
@@ -630,7 +632,7 @@ static int enqueue_path_trace(pt_handle h) {
   fill_trace_params(h, P);
   P.n_items = n;
   StepEvents ev{h};
-  hipEvent_t e_begin = nullptr, e_acc = nullptr, e_end = nullptr;
+  hipEvent_t e_begin = nullptr, e_acc = nullptr, e_end = nullptr, e_class_cleared = nullptr;
   size_t e_acc_i = 0;
   if (int rc = ev.record(h->stream, e_begin, h->e_begin_i)) return rc;
   PT_HIP(hipStreamWaitEvent(h->trace_stream, e_begin, 0));   // counters memset and earlier work on `stream`
@@ -642,7 +644,7 @@ static int enqueue_path_trace(pt_handle h) {
   h->group.memo_ran = mode.memo;
   if (mode.grouped()) {
     if (int rc = prepare_group_store(h, mode, batches)) return rc;
-    if (int rc = prepare_class_level(h, batches, mode.classes)) return rc;
+    if (int rc = prepare_class_level(h, ev, batches, mode, e_class_cleared)) return rc;
   }
   h->group.class_ran = mode.classes;
   if (mode.memo)   // counters, and a clear or a retain pass if one is due
@@ -660,7 +662,7 @@ static int enqueue_path_trace(pt_handle h) {
     store_cap = std::max(store_cap, b.store_cap);
     if (int rc = stage_trace(h, ev, P, b)) return rc;
     if (mode.grouped())
-      if (int rc = stage_group(h, ev, mode, b)) return rc;
+      if (int rc = stage_group(h, ev, mode, b, e_class_cleared)) return rc;
     if (int rc = stage_nif(h, ev, mode, b)) return rc;
     if (handoff && i + 1 == batches)   // behind the last S(b) and its B.traced: the table is not read again in this step
       if (int rc = enqueue_table_handoff(h, ev, e_clean)) return rc;

@@ -327,7 +327,7 @@ struct pt_context {
     DevBuf<uint32_t> d_class_vals;
     uint32_t class_slots = 0;                  // table capacity, a power of two
     uint32_t class_diag_slots = 0;             // test build: forced capacity (pt_diag_set_nif_class_capacity), 0 = sized by the rule
-    DevBuf<uint32_t> d_class_owner;            // [queue_cap]: class-store index of the owner of every entry of the distinct queue in flight
+    DevBuf<uint32_t> d_class_owner;            // [queue_cap]: class-store index of the owner of every entry of the distinct queue in flight (the memo's steps; a fused step keeps class-store indices in d_share_owner and the raw table's values)
     DevBuf<float> d_class_u, d_class_v, d_class_bgr;   // class queues and their decoded BGR: class_regions x queue_cap
     size_t class_regions = 0;
     DevBuf<uint32_t> d_class_count;            // [batch] class-queue length

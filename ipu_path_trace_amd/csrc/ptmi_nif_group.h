@@ -187,6 +187,11 @@ struct StepMode {
   int32_t share;   // sharing mode in force (off for a constant environment)
   bool memo;
   bool classes = false;   // N(b) evaluates a row per class of its distinct queue (prepare_class_level)
+  // the class is claimed inside S(b) and E(b) gathers from the class store (pt_nif_group.h: ShareClassTable): a step-scope step
+  // with the class level and without the memo, whose publish pass reads the raw BGR store.  Batch scope keeps the level's own
+  // passes in N(b) as the memo does: its tables forget a pair from batch to batch, so 2.5 times as many entries append, and
+  // their class lookups on the trace stream cost it more than the NIF stream saves (profiles/r29_class_in_claim.txt)
+  bool fused() const { return classes && !memo && share == PT_NIF_SHARE_STEP; }
   bool grouped() const { return share || memo; }   // N runs over distinct queues in the step store
   bool step_scope() const { return memo || share == PT_NIF_SHARE_STEP; }
   ptshare::StepKind kind() const {   // what the step does to the sharing table (ptmi_share_plan.h: the clean-table hand-off)
@@ -272,8 +277,12 @@ static int alloc_class_buffers(pt_handle h, uint32_t slots, size_t batches) {
 // Before the first batch of a grouped step, behind prepare_group_store (the sharing buffers come first): whether the step
 // runs the class level -- the environment is a NIF, and the level's buffers at the step's size are held or fit the budget
 // (ptshare::class_fits) and could be allocated -- and, if it does, the table, the counts and the alone counter cleared on the
-// NIF stream, where they overlap T(0).  Declining is no error: the step is then the one without the level.
-static int prepare_class_level(pt_handle h, size_t batches, bool& classes) {
+// NIF stream, where they overlap T(0).  Declining is no error: the step is then the one without the level.  In a fused step
+// the first to touch what is cleared here is S(0), on the trace stream: `cleared` is recorded behind the clears, and
+// stage_group makes the trace stream wait for it ahead of S(0) -- not ahead of T(0), which the clears still overlap.  Every
+// other step touches them on the NIF stream alone and records no event.
+static int prepare_class_level(pt_handle h, StepEvents& ev, size_t batches, StepMode& mode, hipEvent_t& cleared) {
+  bool& classes = mode.classes;
   classes = false;
   if (h->env_map || h->group.class_failed) return PT_OK;
   const uint64_t free_b = free_device_bytes();
@@ -294,7 +303,9 @@ static int prepare_class_level(pt_handle h, size_t batches, bool& classes) {
   PT_HIP(hipMemsetAsync(h->group.d_class_count, 0, batches * 4, h->stream));
   PT_HIP(hipMemsetAsync(h->group.d_class_over, 0, 8, h->stream));
   classes = true;
-  return PT_OK;
+  if (!mode.fused()) return PT_OK;
+  size_t at = 0;
+  return ev.record(h->stream, cleared, at);
 }
 
 static ptd::ClassTable class_table(pt_handle h) { return {{h->group.d_class_keys, h->group.d_class_vals, h->group.class_slots - 1u}}; }
@@ -342,6 +353,17 @@ static int enqueue_table_handoff(pt_handle h, StepEvents& ev, hipEvent_t& clean)
 }
 
 static ptd::ShareTable share_table(pt_handle h) { return {h->group.d_share_keys, h->group.d_share_vals, h->group.share_slots - 1u}; }
+// the fused step's table for batch b: the raw table, the step's class table and the batch's class queue (class region b)
+static ptd::ShareClassTable share_class_table(pt_handle h, const Batch& b) {
+  ptd::ShareClassTable T;
+  static_cast<ptd::ShareTable&>(T) = share_table(h);
+  T.classes = class_table(h);
+  T.c_u = h->group.d_class_u + b.class_base; T.c_v = h->group.d_class_v + b.class_base;
+  T.c_count = h->group.d_class_count + b.index;
+  T.c_base = b.class_base;
+  T.c_alone = h->group.d_class_over;
+  return T;
+}
 static ptd::MemoTable memo_table(pt_handle h) {
   return {h->group.d_memo, h->group.memo_slots - 1u, h->group.memo_step, h->group.d_memo_slot, h->group.d_memo_ctr};
 }
@@ -365,6 +387,7 @@ static int stage_resolve(pt_handle h, StepEvents& ev, const StepMode& mode, cons
   return ev.timed(s, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
     const ptd::GroupQueue Q = group_queue(h, b);
     if (mode.memo) hipLaunchKernelGGL(ptd::memo_resolve_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, s, Q, memo_table(h));
+    else if (mode.fused()) hipLaunchKernelGGL(ptd::share_class_resolve_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, s, Q, share_class_table(h, b));
     else hipLaunchKernelGGL(ptd::share_resolve_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, s, Q, share_table(h));
     PT_HIP(hipGetLastError());
     return PT_OK;
@@ -375,12 +398,17 @@ static int stage_resolve(pt_handle h, StepEvents& ev, const StepMode& mode, cons
 // so a step-scope step (the memo included) resolves at the head of N(b), on the NIF stream.  Nothing on the trace stream
 // writes what the pass reads: claims of later batches write the value of slots they claim fresh, the pass reads the values
 // of slots claimed up to its own batch, and the table's clears touch the keys alone.  Batch scope reuses its table from batch
-// to batch and resolves where it claims.
+// to batch and resolves where it claims.  The fused step's two-hop resolve stands on the same argument, for both tables: a
+// claim writes the value of a raw or a class slot only if it claimed the slot fresh, every slot the pass reaches (a raw slot
+// through an owner word, a class slot through a pending class word) was claimed up to its own batch, and both tables' clears
+// touch keys alone.  Its write-back stores into raw slots claimed up to its own batch, which no claim writes again; the only
+// other readers and writers of those values are resolve passes, which follow each other on one stream.
 static bool resolve_on_nif_stream(const StepMode& mode) { return mode.step_scope(); }
 
 // S(b), right behind T(b) (it hides under N(b - 1) as T(b) does): claim a slot per key -- in the sharing table, or with the
 // memo look the key up -- then (batch scope) resolve the owners claimed in this batch.
-static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b) {
+static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const Batch& b, hipEvent_t class_cleared) {
+  if (mode.fused() && b.index == 0) PT_HIP(hipStreamWaitEvent(h->trace_stream, class_cleared, 0));   // prepare_class_level's clears
   if (int rc = ev.timed(h->trace_stream, mode.memo ? pt_context::kSpanMemo : pt_context::kSpanShare, [&]() -> int {
         const ptd::GroupQueue Q = group_queue(h, b);
         const dim3 tiles = b.claim_grid(), block(ptd::kShareBlock);
@@ -389,7 +417,8 @@ static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const 
         } else {
           if (mode.share == PT_NIF_SHARE_BATCH)   // one table per batch
             PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
-          hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_table(h));
+          if (mode.fused()) hipLaunchKernelGGL(ptd::share_class_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_class_table(h, b));
+          else hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_table(h));
         }
         PT_HIP(hipGetLastError());
         return PT_OK;
@@ -406,10 +435,11 @@ static int stage_expand(pt_handle h, StepEvents& ev, const StepMode& mode, const
     X.region_count = B.region_count;
     X.region_cap = b.g.region_cap;
     X.owner = h->group.d_share_owner[b.set()];
-    X.bgr = h->group.d_share_bgr;
+    X.bgr = mode.fused() ? h->group.d_class_bgr : h->group.d_share_bgr;   // (fused: the owner words are class-store indices)
     X.q_tr = B.q_tr; X.q_tg = B.q_tg; X.q_tb = B.q_tb; X.q_path = B.q_path;
     X.rad_r = B.rad_r; X.rad_g = B.rad_g; X.rad_b = B.rad_b;
     if (mode.memo) hipLaunchKernelGGL(ptd::memo_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, memo_table(h));
+    else if (mode.fused()) hipLaunchKernelGGL(ptd::share_class_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, share_class_table(h, b));
     else hipLaunchKernelGGL(ptd::share_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, share_table(h));
     PT_HIP(hipGetLastError());
     return PT_OK;
@@ -664,6 +694,67 @@ int pt_diag_class_claim(pt_handle h, const float* u, const float* v, uint32_t n,
   PT_HIP(hipMemcpyAsync(c_count, len, 4, hipMemcpyDeviceToHost, s));
   PT_HIP(hipMemcpyAsync(alone, over, 8, hipMemcpyDeviceToHost, s));
   PT_HIP(hipStreamSynchronize(s));
+  return PT_OK;
+}
+
+// test build only: the fused claim and the two-hop resolve over a queue the caller supplies (laid out as for
+// pt_diag_claim_resolve), with buffers of its own: a raw table of raw_slots and a class table of class_slots slots (powers of
+// two).  Out, on the host: owner [n_regions x region_cap] (live entries: positions in the class queue), the distinct queue
+// d_u / d_v and the class queue c_u / c_v (same capacity each), and counters[4]: the distinct queue's length, the raw
+// overflows, the class queue's length, the rows that found no class slot.
+int pt_diag_share_class_claim(pt_handle h, const float* u, const float* v, const uint32_t* region_count, uint32_t n_regions,
+                              uint32_t region_cap, uint32_t raw_slots, uint32_t class_slots, uint32_t* owner, float* d_u, float* d_v,
+                              float* c_u, float* c_v, uint64_t* counters) {
+  if (!h || !u || !v || !region_count || !owner || !d_u || !d_v || !c_u || !c_v || !counters) return PT_ERR_INVALID_ARGUMENT;
+  const uint64_t n64 = (uint64_t)n_regions * region_cap;
+  if (n_regions == 0 || region_cap == 0 || n64 >= ptshare::kMaxStoreEntries || raw_slots < 2 || raw_slots > ptshare::kMaxSlots ||
+      (raw_slots & (raw_slots - 1u)) || class_slots < 2 || class_slots > ptshare::kClassMaxSlots || (class_slots & (class_slots - 1u)))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_share_class_claim: sizes out of range");
+  for (uint32_t r = 0; r < n_regions; ++r)
+    if (region_count[r] > region_cap) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_share_class_claim: a region's count exceeds its capacity");
+  const size_t n = (size_t)n64;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t s = h->stream;
+  DevBuf<float> q_u, q_v, du, dv, cu, cv;
+  DevBuf<uint32_t> counts, own, len, vals, c_vals;   // len: [0] the distinct queue's length, [1] the class queue's
+  DevBuf<unsigned long long> over, keys, c_keys;     // over: [0] raw overflows, [1] rows alone
+  PT_HIP(dev_alloc(q_u, n)); PT_HIP(dev_alloc(q_v, n)); PT_HIP(dev_alloc(du, n)); PT_HIP(dev_alloc(dv, n));
+  PT_HIP(dev_alloc(cu, n)); PT_HIP(dev_alloc(cv, n));
+  PT_HIP(dev_alloc(counts, n_regions)); PT_HIP(dev_alloc(own, n)); PT_HIP(dev_alloc(len, 2)); PT_HIP(dev_alloc(over, 2));
+  PT_HIP(dev_alloc(keys, raw_slots)); PT_HIP(dev_alloc(vals, raw_slots));
+  PT_HIP(dev_alloc(c_keys, class_slots)); PT_HIP(dev_alloc(c_vals, class_slots));
+  PT_HIP(hipMemcpyAsync(q_u, u, n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(q_v, v, n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(counts, region_count, (size_t)n_regions * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemsetAsync(own, 0xff, n * 4, s));   // an entry no pass writes reads as pending
+  PT_HIP(hipMemsetAsync(over, 0, 16, s));
+  PT_HIP(hipMemsetAsync(len, 0, 8, s));
+  PT_HIP(hipMemsetAsync(keys, 0xff, (size_t)raw_slots * 8, s));
+  PT_HIP(hipMemsetAsync(c_keys, 0xff, (size_t)class_slots * 8, s));
+  ptd::GroupQueue Q;
+  Q.q_u = q_u; Q.q_v = q_v; Q.region_count = counts; Q.region_cap = region_cap; Q.owner = own;
+  Q.d_u = du; Q.d_v = dv; Q.d_count = len; Q.base = 0; Q.overflowed = over;
+  ptd::ShareClassTable T;
+  static_cast<ptd::ShareTable&>(T) = ptd::ShareTable{keys, vals, raw_slots - 1u};
+  T.classes = ptd::ClassTable{{c_keys, c_vals, class_slots - 1u}};
+  T.c_u = cu; T.c_v = cv; T.c_count = len + 1; T.c_base = 0; T.c_alone = over + 1;
+  const dim3 grid((region_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock, n_regions), tiles(ptshare::claim_tiles(region_cap), n_regions);
+  const dim3 block(ptd::kShareBlock);
+  hipLaunchKernelGGL(ptd::share_class_claim_kernel, tiles, block, 0, s, Q, T);
+  PT_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ptd::share_class_resolve_kernel, grid, block, 0, s, Q, T);
+  PT_HIP(hipGetLastError());
+  uint32_t h_len[2] = {0, 0};
+  unsigned long long h_over[2] = {0, 0};
+  PT_HIP(hipMemcpyAsync(owner, own, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(d_u, du, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(d_v, dv, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(c_u, cu, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(c_v, cv, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(h_len, len, 8, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(h_over, over, 16, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipStreamSynchronize(s));
+  counters[0] = h_len[0]; counters[1] = h_over[0]; counters[2] = h_len[1]; counters[3] = h_over[1];
   return PT_OK;
 }
 #endif

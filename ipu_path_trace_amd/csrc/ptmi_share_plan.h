@@ -2,7 +2,7 @@
 // format of an owner word, how many slots the table of a batch or a step gets, whether the automatic default may take the
 // memory it needs, how many slots a memo of a given size has, the tiles of the claim pass, when a step-scope step may
 // skip the clear of its table, and the key and the sizes of the NIF stage's class level.  Plain C++ (nothing from HIP), so that tests/share_plan_main.cpp, tests/claim_plan_main.cpp,
-// tests/handoff_plan_main.cpp and tests/class_key_main.cpp check it on a CPU; ptmi.hip includes it ahead of the device headers.
+// tests/handoff_plan_main.cpp, tests/class_key_main.cpp and tests/fused_claim_main.cpp check it on a CPU; ptmi.hip includes it ahead of the device headers.
 #pragma once
 
 #include <cstdint>
@@ -21,6 +21,32 @@ constexpr bool owner_is_store(uint32_t o) { return !(o & kOwnerTagged); }
 constexpr bool owner_is_pending(uint32_t o) { return (o & kOwnerPending) == kOwnerPending; }
 constexpr bool owner_is_served(uint32_t o) { return (o & kOwnerPending) == kOwnerTagged; }
 constexpr uint32_t owner_slot(uint32_t o) { return o & kOwnerSlotBits; }
+
+// The fused claim (pt_nif_group.h: ShareClassTable) writes class-store indices, and reuses tag 10 -- which a table that does
+// not serve never produces -- for a PENDING CLASS word: the slot of the CLASS table whose value is the class-store index.  Such
+// a word stands in owner[q] and in the value of a raw slot; class slots are at most 2^29 (kClassMaxSlots), within the slot bits.
+constexpr uint32_t owner_class(uint32_t class_slot) { return kOwnerTagged | class_slot; }
+constexpr bool owner_is_class(uint32_t o) { return (o & kOwnerPending) == kOwnerTagged; }
+// The two-hop resolve of an owner word of the fused claim.  raw_vals / class_vals: the value arrays of the two tables.  A pending
+// raw word reads the raw slot's value; a pending class word -- there, or in owner[q] itself -- reads the class slot's value.
+// *write_back (may be null): the raw slot whose value was a pending class word, or kNoWriteBack: the caller may store the result
+// there, so that a later hit on the slot takes one hop (every writer stores the same word, and readers accept either form).
+constexpr uint32_t kNoWriteBack = ~0u;
+template <class RawVals, class ClassVals>
+constexpr uint32_t resolve_two_hops(uint32_t o, const RawVals& raw_vals, const ClassVals& class_vals, uint32_t* write_back = nullptr) {
+  if (write_back) *write_back = kNoWriteBack;
+  if (owner_is_pending(o)) {
+    const uint32_t s = owner_slot(o);
+    o = raw_vals[s];
+    if (owner_is_class(o)) {
+      o = class_vals[owner_slot(o)];
+      if (write_back) *write_back = s;
+    }
+  } else if (owner_is_class(o)) {
+    o = class_vals[owner_slot(o)];
+  }
+  return o;
+}
 
 // The clean-table hand-off.  A step-scope step clears the table behind its last S(b), for the step after it, and the handle
 // keeps a mark: the number of slots at which the table is known to hold no key, 0 if it is not known.  The next step-scope

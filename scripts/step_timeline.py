@@ -32,6 +32,9 @@ def load(path):
 
 def kind(name):
     if "film_accumulate" in name: return "film"
+    if "share_class_claim" in name: return "claim"       # the fused step's passes: the class is claimed inside the claim pass
+    if "share_class_resolve" in name: return "resolve"
+    if "share_class_expand" in name: return "expand"
     if "share_claim" in name or "memo_lookup" in name: return "claim"
     if "share_resolve" in name or "memo_resolve" in name: return "resolve"
     if "class_claim" in name: return "cclaim"
