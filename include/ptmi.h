@@ -400,7 +400,8 @@ int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uin
  * them.  A closed unit box about the camera lets 8 of 6144 mirror paths and 22 of 6144 diffuse paths of six bounces out.  The
  * same triangles as PT_SHAPE_TRIANGLE rows let the identical paths out: it is the polygon test's property, and the tree adds none.
  *
- * The tree.  Each mesh gets a binary bounding-volume hierarchy, built on the host by binned SAH with at most four triangles per
+ * The tree.  Each mesh gets a binary bounding-volume hierarchy, built on the host by binned SAH (or, opt-in, on the device:
+ * pt_set_mesh_build below) with at most four triangles per
  * leaf and walked by the kernels without a stack (depth-first node order with skip links).  Node boxes are padded outward by one
  * value per mesh, pad = 2^-16 x the largest absolute coordinate of the mesh's box (pt_mesh_info.pad).  The pad is a safety margin,
  * not a proof: the triangle test's rounding grows at grazing incidence and with the distance of the ray's origin (from thousands
@@ -425,7 +426,7 @@ int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uin
  * pt_set_camera that changes the pose makes the meshes stale: they are transformed and rebuilt before the next pt_path_trace,
  * pt_trace_paths, pt_feature_buffers or pt_mesh_intersect.  Device buffers are sized once, at pt_set_scene_meshes (a tree of T
  * triangles has at most 2 T - 1 nodes): a rebuild allocates no device memory and cannot run out of it.  pt_mesh_info.build_ms
- * reports the last build.
+ * reports the last build.  (pt_set_mesh_build below: the build can run on the device, and a pose change can refit instead.)
  *
  * Validation returns PT_ERR_INVALID_ARGUMENT, and pt_last_error names the object, the mesh, the triangle and the field.  The
  * checks run in this order, before any device call: stride; n outside 1..32; a NULL table; per row the checks of
@@ -454,7 +455,7 @@ typedef struct pt_mesh_info {         /* 48 bytes */
   uint32_t n_triangles, n_nodes;
   uint32_t max_leaf, depth;           /* most triangles in a leaf (<= 4); levels of the tree */
   uint64_t device_bytes;              /* this mesh's share of the device buffers, sized for 2 T - 1 nodes */
-  double build_ms;                    /* host time of the last transform + build of this mesh */
+  double build_ms;                    /* host time of the last transform + build of this mesh (pt_set_mesh_build: device time under the device paths) */
   float pad;                          /* the outward pad of its node boxes, in the kernel's frame */
 } pt_mesh_info;
 int pt_get_mesh_info(pt_handle h, uint32_t mesh, pt_mesh_info* out);
@@ -621,6 +622,83 @@ int pt_get_mesh_texture_info(pt_handle h, uint32_t mesh, pt_mesh_texture_info* o
  * PT_ERR_NOT_READY without a mesh in force; n == 0 is a no-op. */
 int pt_mesh_texel(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object,
                   int32_t* out_triangle, float* out_uv /* [n][2] */, float* out_bgr /* [n][3] */);
+
+/* Mesh trees built and refitted on the device -- an EXTENSION, opt-in and additive: PTMI_ABI_VERSION stays 5, no existing struct
+ * moves, no trace kernel is added or changed, and a process that never calls pt_set_mesh_build runs the host builder and the
+ * rebuild on every pose change that it ran before, call for call.
+ *
+ * Options.  builder says who builds a scene's trees: PT_MESH_BUILDER_HOST (binned SAH on one host thread, as above) or
+ * PT_MESH_BUILDER_DEVICE (a linear BVH built by kernels on the handle's stream).  on_pose says what a change of frame does to
+ * trees that exist: PT_MESH_POSE_REBUILD builds them again, PT_MESH_POSE_REFIT keeps topology and slot order and refits.  The
+ * options belong to the handle and survive pt_set_scene*.  A change of builder makes the trees of the scene in force stale: they
+ * are built again before whatever traces next; a change of on_pose alone makes nothing stale.  NULL options: the defaults,
+ * HOST + REBUILD.  Validation, in this order, before any device call, pt_last_error naming the field: struct_size, builder,
+ * on_pose, then a NULL handle (pt_last_error(NULL)).
+ *
+ * Memory.  While builder is DEVICE or on_pose is REFIT the handle holds, for the scene in force, the world frames on the device
+ * (48 bytes per triangle), triangle-order copies of the corner normals (36) and uvs (24) once a mesh has them, and the builder's
+ * arrays for the LARGEST mesh: keys and indices before and after the sort (24 per triangle), parents, ranges and counters (44),
+ * 16 bytes per mesh, and the sort's histograms (1 KiB per 1024 triangles).  All of it is allocated by pt_set_mesh_build (for the scene in force), by
+ * every pt_set_scene_meshes under such an option, and by pt_set_mesh_normals / pt_set_mesh_texture for what they add, so a build
+ * or a refit allocates no device memory and, as above, cannot run out of it.  PT_ERR_OUT_OF_MEMORY leaves the previous options,
+ * or the previous scene, in force.  pt_mesh_build_info.device_bytes reports the sum; it is given back with the scene.
+ *
+ * The device builder (csrc/pt_mesh_build.h states the rule; ONE set of functions for the kernels, the sequential reference
+ * builder and the test program).  Triangles are ordered by the 63-bit Morton code of their boxes' centres (21 bits per axis over
+ * the centres' bounds, ties by triangle index); a range of more than four keys splits at the highest differing bit of its first
+ * and last key (equal codes: of their sorted positions), a range of at most four is a leaf.  Layout, boxes and pad are exactly the
+ * host builder's.  The keys are sorted on the device by the library's own stable radix sort (sort_on_device = 1; a build that
+ * had to sort them on the host would report 0: the same order, the same tree).  After pt_set_scene_meshes, pt_set_mesh_normals
+ * and pt_set_mesh_texture have uploaded their triangle-order copies no per-triangle data crosses to or from the host.
+ * TREE QUALITY IS BELOW SAH.  On the host walk over the test program's rays, box tests per ray rose from 47.4 to 53.6 (+13 %) on
+ * icosphere4, 29.8 to 45.0 (+51 %) on grid and 60.8 to 69.9 (+15 %) on sliver; triangle tests rose by 4 %, 26 % and 4 %.  With
+ * camera rays on icospheres of 82 k to 1.3 M triangles box tests moved by +5 %, +5 % and -1 %.  THE RESULT OF A TRACE DOES NOT
+ * DEPEND ON THE TREE: the tie rule lives in the walk, so the device builder and the refit render the host tree's bits.  That
+ * promise is as empirical as the one above: the pad is a margin, not a proof.
+ *
+ * Refit.  Under PT_MESH_POSE_REFIT, whenever trees of the same triangles by the builder in force lie on the device and only the
+ * frame changes -- pt_set_camera, and the world-frame switch that pt_mesh_intersect, pt_mesh_shade and pt_mesh_texel force -- the
+ * kernel frames are formed again from the device copy of the world frames and written into the unchanged slot order; every leaf
+ * box is recomputed from its triangles' boxes and every inner box from its two children; the pad is computed from the new root
+ * box and applied by the builder's own expressions.  n_nodes, depth, max_leaf, skips, leaf words and the slot -> triangle map do
+ * not change; corner normals go through the direction transform into the same slots; uvs are not touched.  It serves host-built
+ * (SAH) and device-built topology alike.  The first build of a scene, a build after a change of builder, and the build after
+ * pt_set_mesh_normals or pt_set_mesh_texture are always builds.
+ *
+ * pt_mesh_info under the device paths: build_ms is the DEVICE time of that mesh's last build or refit (HIP events on the handle's
+ * stream); n_nodes, depth, max_leaf and pad are read back from the device, four words per mesh.
+ *
+ * pt_mesh_tree is a kernel-level hook like pt_get_env_guide_tables: it brings the trees up to date for the camera in force,
+ * exactly as a render would, then copies mesh `mesh`'s nodes as the kernels read them (padded boxes, skip, leaf word;
+ * pt_mesh_info.n_nodes of them) and its slot -> triangle map (n_triangles words).  A NULL pointer with capacity 0 means "not
+ * wanted"; a capacity that is too small (or a NULL pointer with a capacity) is PT_ERR_INVALID_ARGUMENT; without a mesh in force
+ * it is PT_ERR_NOT_READY. */
+enum { PT_MESH_BUILDER_HOST = 0, PT_MESH_BUILDER_DEVICE = 1 };
+enum { PT_MESH_POSE_REBUILD = 0, PT_MESH_POSE_REFIT = 1 };
+typedef struct pt_mesh_build_options { /* 12 bytes */
+  uint32_t struct_size;               /* sizeof(pt_mesh_build_options) */
+  int32_t builder;                    /* PT_MESH_BUILDER_* */
+  int32_t on_pose;                    /* PT_MESH_POSE_* */
+} pt_mesh_build_options;
+int pt_set_mesh_build(pt_handle h, const pt_mesh_build_options* o);   /* NULL: the defaults, HOST + REBUILD */
+enum { PT_MESH_LAST_NONE = 0, PT_MESH_LAST_HOST_BUILD = 1, PT_MESH_LAST_DEVICE_BUILD = 2, PT_MESH_LAST_REFIT = 3 };
+typedef struct pt_mesh_build_info {   /* 64 bytes */
+  uint32_t struct_size;               /* in: sizeof(pt_mesh_build_info) */
+  int32_t builder, on_pose;           /* the options in force */
+  uint32_t sort_on_device;            /* 1: the device builder sorts its keys on the device */
+  uint64_t host_builds, device_builds, refits;   /* passes over the scene's meshes since pt_create */
+  int32_t last_kind;                  /* PT_MESH_LAST_*: the last pass */
+  uint32_t reserved;
+  double last_ms;                     /* its time over all meshes: host time, or for device work HIP events on the handle's stream */
+  uint64_t device_bytes;              /* held for the device paths (0 unless an option asked for them) */
+} pt_mesh_build_info;
+int pt_get_mesh_build_info(pt_handle h, pt_mesh_build_info* out);
+typedef struct pt_mesh_node {         /* 32 bytes: a node as the kernels read it (csrc/pt_mesh.h) */
+  float lo[3], hi[3];                 /* the padded box, in the kernel's frame */
+  uint32_t skip;                      /* the node to continue at after a miss or a leaf; n_nodes ends the walk */
+  uint32_t leaf;                      /* first slot << 3 | count; 0: an inner node, its left child at node + 1 */
+} pt_mesh_node;
+int pt_mesh_tree(pt_handle h, uint32_t mesh, pt_mesh_node* nodes, uint32_t node_capacity, uint32_t* orig, uint32_t orig_capacity);
 
 /* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
  * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an

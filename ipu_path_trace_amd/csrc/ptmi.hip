@@ -202,7 +202,9 @@ int pt_destroy(pt_handle h) {
   for (hipEvent_t e : h->chunk_join)
     if (e) (void)hipEventDestroy(e);
   if (h->chunk_fork) (void)hipEventDestroy(h->chunk_fork);
-  delete h;   // the memory: every DevBuf / PinnedBuf of the handle frees itself here
+  for (hipEvent_t e : h->mesh_event)
+    if (e) (void)hipEventDestroy(e);
+  delete h;  // the memory: every DevBuf / PinnedBuf of the handle frees itself here
   for (hipStream_t s : own)
     if (s) (void)hipStreamDestroy(s);
   return PT_OK;
@@ -1498,7 +1500,9 @@ int pt_set_scene_meshes(pt_handle h, const pt_scene_object_ex* objects, uint32_t
   PT_HIP(dev_alloc(M.d_tris, 3 * triangles));
   PT_HIP(dev_alloc(M.d_orig, triangles));
   const ptcamera::Basis& cb = h->camera_basis;
-  if (int rc = build_meshes(h, M, cb.identity ? nullptr : &cb)) return rc;
+  if (mesh_device_option(h))   // (pt_set_mesh_build: the options outlive the scene, so their storage comes with every scene)
+    if (int rc = ensure_mesh_device(h, M)) return rc;
+  if (int rc = update_meshes(h, M, cb.identity ? nullptr : &cb)) return rc;
   // commit: the table as stored -- a mesh row with shape 4, its material and colour, and zeros
   pt_scene_object_ex stored[PT_MAX_SCENE_OBJECTS];
   std::copy(objects, objects + n, stored);
@@ -1541,6 +1545,72 @@ int pt_get_mesh_info(pt_handle h, uint32_t mesh, pt_mesh_info* out) {
   out->device_bytes = (2 * (uint64_t)m.n_triangles - 1) * sizeof(ptmesh::Node) + (uint64_t)m.n_triangles * (3 * sizeof(ptmesh::F4) + sizeof(uint32_t));
   out->build_ms = m.build_ms;
   out->pad = m.pad;
+  return PT_OK;
+}
+
+// Who builds the trees and what a pose change does to them (include/ptmi.h).  Everything the device paths need is allocated here,
+// before the options change: a failed allocation leaves them as they were.
+int pt_set_mesh_build(pt_handle h, const pt_mesh_build_options* o) {
+  const pt_mesh_build_options defaults{sizeof(pt_mesh_build_options), PT_MESH_BUILDER_HOST, PT_MESH_POSE_REBUILD};
+  const pt_mesh_build_options& O = o ? *o : defaults;
+  std::string bad;
+  if (O.struct_size != sizeof(pt_mesh_build_options))
+    bad = "pt_set_mesh_build: struct_size must be " + std::to_string(sizeof(pt_mesh_build_options)) + " (got " + std::to_string(O.struct_size) + ")";
+  else if (O.builder != PT_MESH_BUILDER_HOST && O.builder != PT_MESH_BUILDER_DEVICE)
+    bad = "pt_set_mesh_build: builder must be 0 (host) or 1 (device) (got " + std::to_string(O.builder) + ")";
+  else if (O.on_pose != PT_MESH_POSE_REBUILD && O.on_pose != PT_MESH_POSE_REFIT)
+    bad = "pt_set_mesh_build: on_pose must be 0 (rebuild) or 1 (refit) (got " + std::to_string(O.on_pose) + ")";
+  if (!bad.empty()) {
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) { g_create_error = "pt_set_mesh_build: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  const bool device = O.builder == PT_MESH_BUILDER_DEVICE || O.on_pose == PT_MESH_POSE_REFIT;
+  if (device && h->scene_n && h->scene_mesh)
+    if (int rc = ensure_mesh_device(h, h->mesh)) return rc;
+  if (O.builder != h->mesh_builder) {   // the trees of the scene in force are the other builder's: stale, and no refit may keep them
+    h->mesh.built = false;
+    h->mesh.topo_builder = -1;
+  }
+  h->mesh_builder = O.builder;
+  h->mesh_on_pose = O.on_pose;
+  return PT_OK;
+}
+
+int pt_get_mesh_build_info(pt_handle h, pt_mesh_build_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_mesh_build_info))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_build_info: struct_size must be " + std::to_string(sizeof(pt_mesh_build_info)));
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->builder = h->mesh_builder;
+  out->on_pose = h->mesh_on_pose;
+  out->sort_on_device = PT_LBVH_DEVICE_SORT;
+  out->host_builds = h->mesh_host_builds;
+  out->device_builds = h->mesh_device_builds;
+  out->refits = h->mesh_refits;
+  out->last_kind = h->mesh_last_kind;
+  out->last_ms = h->mesh_last_ms;
+  out->device_bytes = (h->scene_n && h->scene_mesh) ? h->mesh.dev.bytes : 0u;
+  return PT_OK;
+}
+
+static_assert(sizeof(pt_mesh_node) == sizeof(ptmesh::Node) && sizeof(pt_mesh_build_options) == 12 && sizeof(pt_mesh_build_info) == 64,
+              "pt_mesh_node / pt_mesh_build_* layout");
+int pt_mesh_tree(pt_handle h, uint32_t mesh, pt_mesh_node* nodes, uint32_t node_capacity, uint32_t* orig, uint32_t orig_capacity) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_tree: the scene in force holds no mesh (pt_set_scene_meshes)");
+  if (mesh >= h->mesh.mesh.size())
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: mesh " + std::to_string(mesh) + " of " + std::to_string(h->mesh.mesh.size()) + " in the scene in force");
+  if ((!nodes && node_capacity) || (!orig && orig_capacity)) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: a null buffer with a capacity");
+  if (int rc = ensure_meshes(h)) return rc;   // the camera in force, exactly as a render
+  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
+  if (nodes && node_capacity < m.n_nodes)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: node_capacity must be >= " + std::to_string(m.n_nodes) + " (got " + std::to_string(node_capacity) + ")");
+  if (orig && orig_capacity < m.n_triangles)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: orig_capacity must be >= " + std::to_string(m.n_triangles) + " (got " + std::to_string(orig_capacity) + ")");
+  if (nodes) PT_HIP(hipMemcpy(nodes, h->mesh.d_nodes + m.node_base, m.n_nodes * sizeof(ptmesh::Node), hipMemcpyDeviceToHost));
+  if (orig) PT_HIP(hipMemcpy(orig, h->mesh.d_orig + m.tri_base, m.n_triangles * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return PT_OK;
 }
 
@@ -1597,13 +1667,17 @@ int pt_set_mesh_normals(pt_handle h, uint32_t mesh, const float* normals, uint32
       if (e != hipSuccess)
         return fail(h, hip_status(e), "pt_set_mesh_normals: allocating " + std::to_string(3 * triangles * sizeof(ptmesh::F4)) + " bytes: " + hipGetErrorString(e));
     }
+    if (mesh_device_option(h))   // (pt_set_mesh_build: the triangle-order copy the device paths expand from)
+      if (int rc = ensure_mesh_device(h, M, true, false)) return rc;
     m.normals.swap(corner);
     m.n_normals = n_normals; m.per_corner = normal_indices != nullptr;
+    if (int rc = upload_mesh_corners(h, M, mesh)) return rc;
   }
   } catch (const std::bad_alloc&) {
     return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_mesh_normals: out of host memory for the normals' copy");
   }
   M.built = false;        // the next trace rebuilds: rows' flags and the normals in slot order
+  M.topo_builder = -1;    // (a build, never a refit: pt_set_mesh_build)
   h->feature_gen += 1;
   return PT_OK;
 }
@@ -1703,6 +1777,8 @@ int pt_set_mesh_texture(pt_handle h, uint32_t mesh, const pt_mesh_texture* t) {
     if (e == hipSuccess) e = hipMemcpy(image, texels.data(), texels.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice);
     if (e != hipSuccess)
       return fail(h, hip_status(e), "pt_set_mesh_texture: allocating " + std::to_string(texels.size() * sizeof(ptmesh::F4)) + " bytes: " + hipGetErrorString(e));
+    if (mesh_device_option(h))   // (pt_set_mesh_build: the triangle-order copy the device builder expands from)
+      if (int rc = ensure_mesh_device(h, M, false, true)) return rc;
     PT_HIP(drain());
     ptmesh::TexDesc d{};
     d.texels = image; d.width = t->width; d.height = t->height; d.filter = t->filter; d.wrap = t->wrap;
@@ -1715,11 +1791,13 @@ int pt_set_mesh_texture(pt_handle h, uint32_t mesh, const pt_mesh_texture* t) {
     m.uvs.swap(corner);
     m.n_uvs = t->n_uvs; m.tex_w = t->width; m.tex_h = t->height; m.tex_filter = t->filter; m.tex_wrap = t->wrap;
     m.uv_per_corner = t->uv_indices != nullptr;
+    if (int rc = upload_mesh_corners(h, M, mesh)) return rc;
   }
   } catch (const std::bad_alloc&) {
     return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_mesh_texture: out of host memory for the texture's copy");
   }
   M.built = false;        // the next trace rebuilds: rows' flags and the uvs in slot order
+  M.topo_builder = -1;    // (a build, never a refit: pt_set_mesh_build)
   h->feature_gen += 1;
   return PT_OK;
 }

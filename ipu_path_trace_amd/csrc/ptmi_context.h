@@ -228,7 +228,27 @@ struct pt_context {
     ptd::PolyEdges row[PT_MAX_SCENE_OBJECTS] = {};   // what a mesh's row carries in the kernel arguments (ptd::MeshRow)
     bool built = false, built_world = false;         // the trees on the device are valid / were built in the world frame ...
     ptcamera::Basis built_for{};                     // ... or for this camera
+    // pt_set_mesh_build (ptmi_mesh_build.h): what the device builder and the refit need, allocated while a device option is set
+    // and sized for the largest mesh -- empty for a handle that never sets one
+    struct DeviceBuild {
+      DevBuf<float> world;                           // the world frames, twelve floats per triangle, as `world` above
+      DevBuf<float> corner, corner_uv;               // world corner normals (nine per triangle) / uvs (six), triangle order, over ALL triangles
+      DevBuf<uint64_t> code[2];                      // Morton codes before / after the sort
+      DevBuf<uint32_t> index[2];                     // triangle indices before / after the sort
+      DevBuf<uint32_t> words;                        // ptlbvh::Scratch (kScratchWords per key) and the centroids' bounds
+      DevBuf<uint32_t> stats;                        // ptlbvh::kStats words per mesh: n_nodes, depth, max_leaf, pad
+      DevBuf<uint8_t> sort_tmp;                      // the radix sort's temporary storage
+      size_t cap = 0;                                // triangles of the largest mesh
+      uint64_t bytes = 0;
+    } dev;
+    int topo_builder = -1;                           // the builder whose topology lies on the device for these triangles (-1: none a refit may use)
   } mesh;
+  // pt_set_mesh_build: the options belong to the handle and outlive the scene
+  int32_t mesh_builder = 0, mesh_on_pose = 0;        // PT_MESH_BUILDER_HOST, PT_MESH_POSE_REBUILD
+  uint64_t mesh_host_builds = 0, mesh_device_builds = 0, mesh_refits = 0;
+  int32_t mesh_last_kind = 0;
+  double mesh_last_ms = 0;
+  hipEvent_t mesh_event[2] = {nullptr, nullptr};     // start / stop of one mesh's device work on `stream`
 
   // camera (pt_set_camera): the values as given, and the frame made from them once (ptmi_camera.h)
   pt_camera camera = ptcamera::default_camera();
@@ -531,12 +551,15 @@ int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam
   std::vector<ptmesh::F4> normals;
   std::vector<float> uvs;
   ptmesh::Built B;
+  M.topo_builder = -1;
+  double total_ms = 0;
   for (pt_context::MeshSet::One& m : M.mesh) {
     const auto t0 = std::chrono::steady_clock::now();
     frames.resize(ptmesh::kFrameFloats * (size_t)m.n_triangles);
     ptmesh::kernel_frames(M.world.data() + ptmesh::kFrameFloats * (size_t)m.tri_base, m.n_triangles, cam, frames.data());
     ptmesh::build(frames.data(), m.n_triangles, B);
     m.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    total_ms += m.build_ms;
     m.n_nodes = (uint32_t)B.nodes.size();
     m.max_leaf = B.max_leaf; m.depth = B.depth; m.pad = B.pad;
     if (B.nodes.size() > 2 * (size_t)m.n_triangles - 1 || B.orig.size() != m.n_triangles)
@@ -560,9 +583,25 @@ int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam
   M.built = true;
   M.built_world = cam == nullptr;
   if (cam) M.built_for = *cam;
+  M.topo_builder = PT_MESH_BUILDER_HOST;
+  h->mesh_host_builds += 1;
+  h->mesh_last_kind = PT_MESH_LAST_HOST_BUILD;
+  h->mesh_last_ms = total_ms;
   return PT_OK;
 } catch (const std::bad_alloc&) {   // the builder's host arrays: the trees stay marked stale, the next call tries again
   return fail(h, PT_ERR_OUT_OF_MEMORY, "meshes: out of host memory while building the trees");
+}
+
+}  // (namespace: ptmi_mesh_build.h opens its own)
+#include "ptmi_mesh_build.h"
+namespace {
+
+// The trees of M for the frame of `cam`, by the options in force (pt_set_mesh_build): a refit where trees of these triangles by
+// the builder in force lie on the device and only the frame changes, else a build by that builder.
+int update_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam) {
+  if (h->mesh_on_pose == PT_MESH_POSE_REFIT && M.topo_builder == h->mesh_builder && M.dev.world) return refit_meshes(h, M, cam);
+  if (h->mesh_builder == PT_MESH_BUILDER_DEVICE) return build_meshes_device(h, M, cam);
+  return build_meshes(h, M, cam);
 }
 
 // Before anything traces a mesh scene: the trees follow the camera in force (world = true, pt_mesh_intersect: the world frame).
@@ -576,7 +615,7 @@ int ensure_meshes(pt_handle h, bool world = false) {
            !memcmp(a.position, b.position, sizeof a.position);
   };
   if (M.built && (cam ? (!M.built_world && same(M.built_for, *cam)) : M.built_world)) return PT_OK;
-  return build_meshes(h, M, cam);
+  return update_meshes(h, M, cam);
 }
 
 // The emitter guide's table into the kernel arguments.  P.lights.n stays 0 -- no light-guided instance is launched -- unless a

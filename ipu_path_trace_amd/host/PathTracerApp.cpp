@@ -111,8 +111,16 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"denoise-sigma-normal", 0, "0.5", false, false, "Normal stop of the denoiser; <= 0 disables it."},
       {"denoise-sigma-depth", 0, "0.1", false, false, "Relative depth stop of the denoiser; <= 0 disables it."},
       {"save-features", 0, "false", false, true, "Also write the first-hit feature buffers at every save: <basename>_normal.exr (world x, y, z in the B, G, R channels), _albedo.exr (B, G, R) and _depth.exr (the hit distance in all three channels)."},
+      {"mesh-builder", 0, "host", false, false, "host | device: who builds the trees of --scene's meshes -- binned SAH on one host thread, or a linear BVH built by kernels (pt_set_mesh_build; faster to build, somewhat slower to trace). The image is bit-identical either way."},
       {"nif-memo-gib", 0, "0", false, false, "GiB of device memory for a memo of decoded NIF values kept across steps, per logical device (0 = off). Exact: the image is bit-identical to off. Escaped paths whose (u, v) an earlier step evaluated are served from it; the memo is forgotten when a new NIF is loaded."},
   };
+}
+
+// --mesh-builder (an extension: pt_set_mesh_build)
+std::int32_t meshBuilderMode(const std::string& name) {
+  if (name == "host") return PT_MESH_BUILDER_HOST;
+  if (name == "device") return PT_MESH_BUILDER_DEVICE;
+  throw std::runtime_error("--mesh-builder must be one of host, device; got '" + name + "'");
 }
 
 // --share-nif-evaluations (an extension: the reference evaluates the NIF on every escaped path, PathTracerApp.cpp:147-198)
@@ -508,6 +516,7 @@ void PathTracerApp::init(const OptionMap& options) {
   if (samplesPerIpuStep == 0) throw std::runtime_error("--samples-per-step must be at least 1.");
   nifSharing = nifSharingMode(args.str("share-nif-evaluations"));
   nifMemo = nifMemoBytes(args.str("nif-memo-gib"));
+  meshBuilder = meshBuilderMode(args.str("mesh-builder"));
   // --denoise (an extension): the values are checked here, before any device is attached
   denoise = args.flag("denoise");
   saveFeatures = args.flag("save-features");
@@ -734,6 +743,10 @@ void PathTracerApp::attach() {
     devices.push_back(h);
     if (pt_set_nif_sharing(h, nifSharing))
       throw std::runtime_error(std::string("--share-nif-evaluations: ") + pt_last_error(h));
+    if (meshBuilder != PT_MESH_BUILDER_HOST) {   // (the default makes no call at all)
+      const pt_mesh_build_options mo{(std::uint32_t)sizeof(pt_mesh_build_options), meshBuilder, PT_MESH_POSE_REBUILD};
+      if (pt_set_mesh_build(h, &mo)) throw std::runtime_error(std::string("--mesh-builder: ") + pt_last_error(h));
+    }
     if (!sceneMeshes.empty()) {   // the file holds a mesh
       std::vector<pt_mesh> views;
       for (const objreader::Mesh& m : sceneMeshes)

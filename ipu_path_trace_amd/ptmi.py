@@ -54,7 +54,14 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_set_light_guide", "pt_set_light_guide_ex", "pt_get_light_guide_flags", "pt_get_light_guide_info", "pt_light_guide_sample", "pt_light_guide_eval",
            "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
            "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect", "pt_set_mesh_normals",
-           "pt_get_mesh_normals_info", "pt_mesh_shade", "pt_set_mesh_texture", "pt_get_mesh_texture_info", "pt_mesh_texel"]
+           "pt_get_mesh_normals_info", "pt_mesh_shade", "pt_set_mesh_texture", "pt_get_mesh_texture_info", "pt_mesh_texel",
+           "pt_set_mesh_build", "pt_get_mesh_build_info", "pt_mesh_tree"]
+MESH_BUILDER_HOST, MESH_BUILDER_DEVICE = 0, 1
+MESH_BUILDERS = {"host": MESH_BUILDER_HOST, "device": MESH_BUILDER_DEVICE}
+MESH_POSE_REBUILD, MESH_POSE_REFIT = 0, 1
+MESH_POSES = {"rebuild": MESH_POSE_REBUILD, "refit": MESH_POSE_REFIT}
+MESH_LAST_NONE, MESH_LAST_HOST_BUILD, MESH_LAST_DEVICE_BUILD, MESH_LAST_REFIT = 0, 1, 2, 3
+MESH_NODE_DTYPE = np.dtype([("lo", np.float32, 3), ("hi", np.float32, 3), ("skip", np.uint32), ("leaf", np.uint32)])   # pt_mesh_node
 TEX_FILTER_NEAREST, TEX_FILTER_BILINEAR = 0, 1
 TEX_FILTERS = {"nearest": TEX_FILTER_NEAREST, "bilinear": TEX_FILTER_BILINEAR}
 TEX_WRAP_REPEAT, TEX_WRAP_CLAMP = 0, 1
@@ -415,6 +422,21 @@ class MeshInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+class MeshBuildOptions(C.Structure):
+    """pt_mesh_build_options"""
+    _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32), ("on_pose", C.c_int32)]
+
+
+class MeshBuildInfo(C.Structure):
+    """pt_mesh_build_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32), ("on_pose", C.c_int32), ("sort_on_device", C.c_uint32),
+                ("host_builds", C.c_uint64), ("device_builds", C.c_uint64), ("refits", C.c_uint64), ("last_kind", C.c_int32),
+                ("reserved", C.c_uint32), ("last_ms", C.c_double), ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved")}
+
+
 class MeshNormalsInfo(C.Structure):
     """pt_mesh_normals_info"""
     _fields_ = [("struct_size", C.c_uint32), ("has_normals", C.c_uint32), ("per_corner", C.c_uint32), ("n_normals", C.c_uint32),
@@ -641,6 +663,9 @@ def load_library(diag=False):
     L.pt_set_mesh_texture.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshTexture)]
     L.pt_get_mesh_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshTextureInfo)]
     L.pt_mesh_texel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pt_set_mesh_build.argtypes = [C.c_void_p, C.POINTER(MeshBuildOptions)]
+    L.pt_get_mesh_build_info.argtypes = [C.c_void_p, C.POINTER(MeshBuildInfo)]
+    L.pt_mesh_tree.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_set_env_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32]
@@ -1045,6 +1070,35 @@ class Renderer:
         info = MeshInfo(struct_size=C.sizeof(MeshInfo))
         self._check(self._lib.pt_get_mesh_info(self.handle, int(k), C.byref(info)))
         return info.as_dict()
+
+    def set_mesh_build(self, builder="host", on_pose="rebuild"):
+        """pt_set_mesh_build: who builds the meshes' trees ("host": binned SAH on one host thread; "device": a linear BVH built by
+        kernels) and what a pose change does to them ("rebuild", or "refit": topology and slot order stay, frames and boxes
+        follow).  The options belong to the renderer and outlive the scene; the defaults are ("host", "rebuild")."""
+        if builder not in MESH_BUILDERS:
+            raise ValueError("builder must be one of %s (got %r)" % (sorted(MESH_BUILDERS), builder))
+        if on_pose not in MESH_POSES:
+            raise ValueError("on_pose must be one of %s (got %r)" % (sorted(MESH_POSES), on_pose))
+        o = MeshBuildOptions(C.sizeof(MeshBuildOptions), MESH_BUILDERS[builder], MESH_POSES[on_pose])
+        self._check(self._lib.pt_set_mesh_build(self.handle, C.byref(o)))
+
+    def mesh_build_info(self):
+        """pt_get_mesh_build_info as a dict: builder, on_pose, sort_on_device, host_builds, device_builds, refits, last_kind,
+        last_ms, device_bytes."""
+        info = MeshBuildInfo(struct_size=C.sizeof(MeshBuildInfo))
+        self._check(self._lib.pt_get_mesh_build_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
+    def mesh_tree(self, k):
+        """pt_mesh_tree: mesh k's tree as the kernels read it, brought up to date for the camera in force: (nodes, orig), nodes a
+        MESH_NODE_DTYPE array of mesh_info(k)["n_nodes"] rows, orig the slot -> triangle map."""
+        k = int(k)
+        self._check(self._lib.pt_mesh_tree(self.handle, k, None, 0, None, 0))   # (the trees follow the camera: n_nodes may change)
+        info = self.mesh_info(k)
+        nodes = np.zeros(info["n_nodes"], MESH_NODE_DTYPE)
+        orig = np.zeros(info["n_triangles"], np.uint32)
+        self._check(self._lib.pt_mesh_tree(self.handle, k, nodes.ctypes.data, nodes.size, orig.ctypes.data, orig.size))
+        return nodes, orig
 
     def mesh_intersect(self, origin, direction, brute=False):
         """pt_mesh_intersect: the kernels' nearest hit over world-space rays origin (n, 3), direction (n, 3), the camera ignored.
