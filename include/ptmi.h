@@ -483,7 +483,8 @@ int pt_mesh_intersect(pt_handle h, const float* origin, const float* dir, size_t
  * below and renders its flat bits (a flag per mesh row).
  *
  * Copies and memory.  The library copies everything.  The handle keeps the world normals per corner in triangle order (36 bytes
- * per triangle of a mesh with normals; a pose change needs them) and the mesh's own indices (12 bytes per triangle).  The device
+ * per triangle of a mesh with normals; a pose change needs them), the mesh's own indices (12 bytes per triangle) and, for per-corner
+ * normals, the caller's normal_indices (12 bytes per triangle; pt_update_mesh_vertices looks new normals up by them).  The device
  * holds three 16-byte vectors per triangle SLOT in leaf order, indexed by the global slot a hit carries: 48 bytes per triangle,
  * which pt_mesh_normals_info.device_bytes reports for a mesh with normals: THIS MESH'S SHARE.  The buffer itself spans the slots
  * of all meshes of the scene, the flat ones included (the slot of a hit indexes it directly), is allocated whole by the first call
@@ -699,6 +700,78 @@ typedef struct pt_mesh_node {         /* 32 bytes: a node as the kernels read it
   uint32_t leaf;                      /* first slot << 3 | count; 0: an inner node, its left child at node + 1 */
 } pt_mesh_node;
 int pt_mesh_tree(pt_handle h, uint32_t mesh, pt_mesh_node* nodes, uint32_t node_capacity, uint32_t* orig, uint32_t orig_capacity);
+
+/* Animated meshes: one mesh's vertices replaced on the device and its tree refitted or rebuilt -- an EXTENSION, opt-in and
+ * additive: PTMI_ABI_VERSION stays 5, no existing struct moves, no trace, NIF, sharing or accumulate kernel is added or changed,
+ * and a process that never calls pt_update_mesh_vertices launches what it launched before, call for call.
+ *
+ * What it does.  pt_update_mesh_vertices gives mesh `mesh` of the scene in force new vertex positions (and, optionally, new
+ * normals).  TOPOLOGY DOES NOT CHANGE: the indices, the triangle count and n_vertices are the mesh's own, and only whole-array
+ * updates are supported.  The other meshes (nodes, slots, normals, uvs), this mesh's uvs and texture, the scene table and the
+ * camera are not touched.  The mesh then renders, bit for bit, what a fresh handle renders after pt_set_scene_meshes with the
+ * new vertices (plus pt_set_mesh_normals / pt_set_mesh_texture as attached): the result of a trace does not depend on the tree.
+ *
+ * On the device (csrc/pt_mesh_update.h states the rule; ONE set of functions for the kernels, the host and the test program).
+ * One kernel forms every triangle's frame -- e1 = v1 - v0, e2 = v2 - v0, c = cross(e1, e2), n = c / sqrtf(dot(c, c)), every
+ * operation one rounded binary32, the bytes pt_set_scene_meshes computes on the host -- and checks it by that call's rules in that
+ * call's order: a referenced vertex that is not finite, then vertex differences or a cross product that are not finite, then
+ * collinear vertices.  The LOWEST offending triangle is reported.  Only if there is none does a second kernel write the frames
+ * (and the normalised corner normals) into the device copies the builder and the refit read.  A REJECTED UPDATE LEAVES EVERY BYTE
+ * OF THE GEOMETRY IN FORCE AS IT WAS; pt_last_error names scene object, mesh, triangle and field exactly as pt_set_scene_meshes
+ * (for normals: pt_set_mesh_normals) names the same data.
+ *
+ * The tree.  PT_MESH_UPDATE_REFIT keeps the mesh's topology, slot order, slot -> triangle map and uvs: the kernel frames are formed
+ * again in the frame the trees are built for and the boxes and the pad follow, as under PT_MESH_POSE_REFIT.  It serves host-built
+ * (SAH) and device-built topology.  A refit never changes what is rendered, but a tree refitted over a large deformation is a
+ * worse tree: PT_MESH_UPDATE_REBUILD builds the mesh again by the builder in force (pt_set_mesh_build) -- on the device from the
+ * device copy, or on the host from the host copy, which is first brought back from the device.  REFIT needs valid trees: where
+ * the trees of the scene are stale (nothing traced since pt_set_mesh_normals, pt_set_mesh_texture or a change of builder) the
+ * scene's trees are built instead, as the next trace would have, and pt_mesh_update_info counts a fallback.
+ *
+ * Normals.  normals != NULL: the mesh must have normals attached and n_normals must equal the attached count; the attached layout
+ * (per vertex, or per corner through the normal_indices given to pt_set_mesh_normals, which the handle keeps) is reused, and the
+ * new normals are checked and normalised by pt_set_mesh_normals' rules.  normals == NULL (n_normals must be 0) on a mesh with
+ * normals KEEPS THE ATTACHED NORMALS AS THEY ARE: whether they still suit the moved surface is the caller's business.
+ *
+ * Memory.  PT_MESH_UPDATE_HOST_MEMORY: vertices and normals are host arrays, copied before the call returns.
+ * PT_MESH_UPDATE_DEVICE_MEMORY: they are device memory on the handle's device; the caller guarantees that every write to them is
+ * complete before the call and that they are untouched until it returns; the library copies them device to device into its own
+ * staging buffers on the handle's stream and never keeps the pointer.  The first update of a scene allocates, once, and holds until
+ * the next pt_set_scene*: the device paths' storage of pt_set_mesh_build if no option asked for it yet, the scene's triangle
+ * indices (12 bytes per triangle), a vertex staging buffer for the mesh with the most vertices (12 per vertex) and, for meshes
+ * with normals, a normal staging buffer and the per-corner normal indices (12 per triangle).  Later updates allocate nothing
+ * (pt_set_mesh_normals in between has the normal buffers sized again at the next update).  PT_ERR_OUT_OF_MEMORY leaves everything
+ * as it was.  The handle's streams are drained first; the work runs on the handle's stream and is complete when the call returns.
+ *
+ * Validation returns PT_ERR_INVALID_ARGUMENT before any device call, in this order, pt_last_error naming the field: struct_size
+ * (or a NULL struct), mode, memory, NULL vertices, normals NULL with n_normals > 0 or not NULL with n_normals == 0, then a NULL
+ * handle (pt_last_error(NULL)), no mesh `mesh` in force, n_vertices different from the mesh's, normals for a mesh without normals
+ * or n_normals different from the attached count; then the device check above.
+ *
+ * pt_mesh_build_info counts an update's tree pass as a pass (a pass over one mesh is a pass). */
+enum { PT_MESH_UPDATE_REFIT = 0, PT_MESH_UPDATE_REBUILD = 1 };
+enum { PT_MESH_UPDATE_HOST_MEMORY = 0, PT_MESH_UPDATE_DEVICE_MEMORY = 1 };
+typedef struct pt_mesh_update {       /* 40 bytes */
+  uint32_t struct_size;               /* sizeof(pt_mesh_update) */
+  int32_t mode;                       /* PT_MESH_UPDATE_REFIT / _REBUILD */
+  int32_t memory;                     /* PT_MESH_UPDATE_HOST_MEMORY / _DEVICE_MEMORY: where vertices and normals lie */
+  uint32_t n_vertices;                /* must equal the mesh's */
+  const float* vertices;              /* [n_vertices][3], world space */
+  uint32_t n_normals;                 /* 0: keep what is attached (four bytes of padding follow) */
+  const float* normals;              /* [n_normals][3] or NULL; indexed as the attached normals are */
+} pt_mesh_update;
+int pt_update_mesh_vertices(pt_handle h, uint32_t mesh, const pt_mesh_update* u);
+typedef struct pt_mesh_update_info {  /* 64 bytes */
+  uint32_t struct_size;               /* in: sizeof(pt_mesh_update_info) */
+  int32_t last_kind;                  /* PT_MESH_LAST_*: the last update's tree pass */
+  uint64_t updates;                   /* accepted updates since pt_create ... */
+  uint64_t refits, rebuilds;          /* ... whose tree pass was a refit / a build (updates = refits + rebuilds) */
+  uint64_t fallbacks;                 /* of the rebuilds, those that were asked for as PT_MESH_UPDATE_REFIT */
+  double last_frames_ms;              /* the last update's copy, check and commit: HIP events on the handle's stream */
+  double last_tree_ms;                /* its tree pass (pt_mesh_build_info.last_ms) */
+  uint64_t device_bytes;              /* added by the update path for the scene in force (0 before its first update) */
+} pt_mesh_update_info;
+int pt_get_mesh_update_info(pt_handle h, pt_mesh_update_info* out);
 
 /* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
  * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an

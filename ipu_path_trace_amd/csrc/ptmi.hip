@@ -204,6 +204,8 @@ int pt_destroy(pt_handle h) {
   if (h->chunk_fork) (void)hipEventDestroy(h->chunk_fork);
   for (hipEvent_t e : h->mesh_event)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : h->mesh_update_event)
+    if (e) (void)hipEventDestroy(e);
   delete h;  // the memory: every DevBuf / PinnedBuf of the handle frees itself here
   for (hipStream_t s : own)
     if (s) (void)hipStreamDestroy(s);
@@ -1614,6 +1616,104 @@ int pt_mesh_tree(pt_handle h, uint32_t mesh, pt_mesh_node* nodes, uint32_t node_
   return PT_OK;
 }
 
+// New vertices (and normals) for mesh `mesh` of the scene in force (include/ptmi.h; ptmi_mesh_update.h).  Everything is allocated,
+// copied into staging and checked on the device before a byte of the geometry in force changes.
+static_assert(sizeof(pt_mesh_update) == 40 && offsetof(pt_mesh_update, vertices) == 16 && offsetof(pt_mesh_update, normals) == 32 &&
+              sizeof(pt_mesh_update_info) == 64, "pt_mesh_update* layout");
+int pt_update_mesh_vertices(pt_handle h, uint32_t mesh, const pt_mesh_update* u) {
+  std::string bad;
+  if (!u) bad = "pt_update_mesh_vertices: null update";
+  else if (u->struct_size != sizeof(pt_mesh_update))
+    bad = "pt_update_mesh_vertices: struct_size must be " + std::to_string(sizeof(pt_mesh_update)) + " (got " + std::to_string(u->struct_size) + ")";
+  else if (u->mode != PT_MESH_UPDATE_REFIT && u->mode != PT_MESH_UPDATE_REBUILD)
+    bad = "pt_update_mesh_vertices: mode must be 0 (refit) or 1 (rebuild) (got " + std::to_string(u->mode) + ")";
+  else if (u->memory != PT_MESH_UPDATE_HOST_MEMORY && u->memory != PT_MESH_UPDATE_DEVICE_MEMORY)
+    bad = "pt_update_mesh_vertices: memory must be 0 (host) or 1 (device) (got " + std::to_string(u->memory) + ")";
+  else if (!u->vertices) bad = "pt_update_mesh_vertices: null vertices";
+  else if (!u->normals && u->n_normals != 0) bad = "pt_update_mesh_vertices: null normals with n_normals = " + std::to_string(u->n_normals);
+  else if (u->normals && u->n_normals == 0) bad = "pt_update_mesh_vertices: normals with n_normals = 0";
+  if (!bad.empty()) {
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) { g_create_error = "pt_update_mesh_vertices: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
+  if (mesh >= count)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_update_mesh_vertices: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
+  pt_context::MeshSet& M = h->mesh;
+  pt_context::MeshSet::One& m = M.mesh[mesh];
+  const std::string at = "pt_update_mesh_vertices: mesh " + std::to_string(mesh) + ": ";
+  if (u->n_vertices != m.n_vertices)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, at + "n_vertices must equal the mesh's " + std::to_string(m.n_vertices) + " (got " + std::to_string(u->n_vertices) + ")");
+  if (u->normals && m.normals.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, at + "normals for a mesh without normals (pt_set_mesh_normals)");
+  if (u->normals && u->n_normals != m.n_normals)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, at + "n_normals must equal the attached " + std::to_string(m.n_normals) + " (got " + std::to_string(u->n_normals) + ")");
+  // storage: nothing of the scene changes here
+  if (int rc = drain_for_meshes(h, M)) return rc;
+  const uint64_t dev_before = M.dev.bytes;
+  if (int rc = ensure_mesh_device(h, M)) return rc;
+  M.upd.bytes += M.dev.bytes - dev_before;
+  if (int rc = ensure_mesh_update(h, M)) return rc;
+  // staging, the check, and the commit
+  pt_context::MeshSet::Update& U = M.upd;
+  const hipMemcpyKind kind = u->memory == PT_MESH_UPDATE_DEVICE_MEMORY ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  const uint32_t T = m.n_triangles;
+  const uint32_t* indices = U.indices + 3 * (size_t)m.tri_base;
+  const float* normals = u->normals ? (const float*)U.normals : nullptr;
+  const uint32_t* normal_indices = !u->normals ? nullptr : m.per_corner ? U.normal_indices + 3 * (size_t)m.tri_base : indices;
+  const dim3 grid(ptupdate::blocks_for(T)), block(ptupdate::kBlock);
+  unsigned long long* fault = reinterpret_cast<unsigned long long*>((uint64_t*)U.fault);
+  uint64_t fault_host[2] = {ptupdate::kNoFault, ptupdate::kNoFault};
+  PT_HIP(hipEventRecord(h->mesh_update_event[0], h->stream));
+  PT_HIP(hipMemcpyAsync(U.vertices, u->vertices, 12 * (size_t)m.n_vertices, kind, h->stream));
+  if (normals) PT_HIP(hipMemcpyAsync(U.normals, u->normals, 12 * (size_t)m.n_normals, kind, h->stream));
+  PT_HIP(hipMemsetAsync(U.fault, 0xff, sizeof(fault_host), h->stream));
+  hipLaunchKernelGGL(ptupdate::mesh_update_check_kernel, grid, block, 0, h->stream, T, indices, (const float*)U.vertices, normal_indices, normals, fault);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipMemcpyAsync(fault_host, U.fault, sizeof(fault_host), hipMemcpyDeviceToHost, h->stream));
+  PT_HIP(hipStreamSynchronize(h->stream));
+  if (fault_host[0] != ptupdate::kNoFault || fault_host[1] != ptupdate::kNoFault)   // the geometry in force stands
+    return mesh_update_rejection(h, M, mesh, fault_host[0], fault_host[1]);
+  hipLaunchKernelGGL(ptupdate::mesh_update_commit_kernel, grid, block, 0, h->stream, T, indices, (const float*)U.vertices, normal_indices, normals,
+                     M.dev.world + ptlbvh::kFrameFloats * (size_t)m.tri_base, normals ? M.dev.corner + 9 * (size_t)m.tri_base : (float*)nullptr);
+  PT_HIP(hipGetLastError());
+  PT_HIP(hipEventRecord(h->mesh_update_event[1], h->stream));
+  PT_HIP(hipEventSynchronize(h->mesh_update_event[1]));
+  float frames_ms = 0.f;
+  PT_HIP(hipEventElapsedTime(&frames_ms, h->mesh_update_event[0], h->mesh_update_event[1]));
+  m.world_stale = true;
+  m.normals_stale = m.normals_stale || normals != nullptr;
+  h->feature_gen += 1;
+  // the tree (a pass that fails leaves the trees marked stale: the next call that traces builds them from the new frames)
+  int tree_kind = PT_MESH_LAST_NONE;
+  bool fallback = false;
+  if (int rc = mesh_update_tree(h, M, mesh, u->mode, tree_kind, fallback)) return rc;
+  h->mesh_updates += 1;
+  (tree_kind == PT_MESH_LAST_REFIT ? h->mesh_update_refits : h->mesh_update_rebuilds) += 1;
+  h->mesh_update_fallbacks += fallback ? 1 : 0;
+  h->mesh_update_last_kind = tree_kind;
+  h->mesh_update_frames_ms = frames_ms;
+  h->mesh_update_tree_ms = h->mesh_last_ms;
+  return PT_OK;
+}
+
+int pt_get_mesh_update_info(pt_handle h, pt_mesh_update_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (!out || out->struct_size != sizeof(pt_mesh_update_info))
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_update_info: struct_size must be " + std::to_string(sizeof(pt_mesh_update_info)));
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->last_kind = h->mesh_update_last_kind;
+  out->updates = h->mesh_updates;
+  out->refits = h->mesh_update_refits;
+  out->rebuilds = h->mesh_update_rebuilds;
+  out->fallbacks = h->mesh_update_fallbacks;
+  out->last_frames_ms = h->mesh_update_frames_ms;
+  out->last_tree_ms = h->mesh_update_tree_ms;
+  out->device_bytes = (h->scene_n && h->scene_mesh) ? h->mesh.upd.bytes : 0u;
+  return PT_OK;
+}
+
 int pt_mesh_intersect(pt_handle h, const float* origin, const float* dir, size_t n, int32_t mode, float* out_t, int32_t* out_object,
                       int32_t* out_triangle) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
@@ -1652,13 +1752,16 @@ int pt_set_mesh_normals(pt_handle h, uint32_t mesh, const float* normals, uint32
   if (!normals && n_normals == 0 && !normal_indices) {   // remove: the mesh is flat again
     if (m.normals.empty()) return PT_OK;
     std::vector<float>().swap(m.normals);
-    m.n_normals = 0; m.per_corner = false;
+    std::vector<uint32_t>().swap(m.normal_indices);
+    m.n_normals = 0; m.per_corner = false; m.normals_stale = false;
   } else {
     const std::string bad = ptmesh::check_normals(mesh, m.n_vertices, m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, normals,
                                                   n_normals, normal_indices);
     if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the mesh keeps what it had
     std::vector<float> corner;
     ptmesh::corner_normals(m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, normals, normal_indices, corner);
+    std::vector<uint32_t> kept;   // (pt_update_mesh_vertices looks new per-corner normals up by the caller's indices)
+    if (normal_indices) kept.assign(normal_indices, normal_indices + 3 * (size_t)m.n_triangles);
     if (!M.d_normals) {
       PT_HIP(hipSetDevice(h->cfg.device));
       size_t triangles = 0;
@@ -1670,9 +1773,11 @@ int pt_set_mesh_normals(pt_handle h, uint32_t mesh, const float* normals, uint32
     if (mesh_device_option(h))   // (pt_set_mesh_build: the triangle-order copy the device paths expand from)
       if (int rc = ensure_mesh_device(h, M, true, false)) return rc;
     m.normals.swap(corner);
-    m.n_normals = n_normals; m.per_corner = normal_indices != nullptr;
+    m.normal_indices.swap(kept);
+    m.n_normals = n_normals; m.per_corner = normal_indices != nullptr; m.normals_stale = false;
     if (int rc = upload_mesh_corners(h, M, mesh)) return rc;
   }
+  drop_mesh_update_normals(M);
   } catch (const std::bad_alloc&) {
     return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_mesh_normals: out of host memory for the normals' copy");
   }

@@ -206,6 +206,10 @@ struct pt_context {
       uint32_t n_vertices, n_normals;
       bool per_corner;
       std::vector<float> normals;
+      std::vector<uint32_t> normal_indices;   // the caller's [n_triangles][3] when per_corner (pt_update_mesh_vertices looks new normals up by them)
+      // pt_update_mesh_vertices wrote this mesh's frames / corner normals on the device: its part of `world` / `normals` on the
+      // host is stale until refresh_mesh_host copies it back
+      bool world_stale = false, normals_stale = false;
       // texture (pt_set_mesh_texture): the (s, t) per corner in triangle order, six floats per triangle; empty: no texture
       uint32_t n_uvs = 0, tex_w = 0, tex_h = 0;
       int32_t tex_filter = 0, tex_wrap = 0;
@@ -242,7 +246,23 @@ struct pt_context {
       uint64_t bytes = 0;
     } dev;
     int topo_builder = -1;                           // the builder whose topology lies on the device for these triangles (-1: none a refit may use)
+    // pt_update_mesh_vertices (ptmi_mesh_update.h): allocated by the first update of the scene, beside `dev` -- empty for a
+    // handle that never updates a mesh
+    struct Update {
+      DevBuf<uint32_t> indices;                      // the meshes' own [n_triangles][3], one after the other, as `indices` above
+      DevBuf<float> vertices;                        // staging: the new vertices of the mesh being updated (cap_vertices x 3)
+      DevBuf<uint32_t> normal_indices;               // [n_triangles][3] over ALL triangles; a per-corner mesh's part is filled
+      DevBuf<float> normals;                         // staging: the new normals (cap_normals x 3)
+      DevBuf<uint64_t> fault;                        // two words: the first fault among the frames / among the normals
+      size_t cap_vertices = 0, cap_normals = 0;
+      uint64_t bytes = 0;                            // of the above, and of what an update had ensure_mesh_device add to `dev`
+    } upd;
   } mesh;
+  // pt_update_mesh_vertices: counters since pt_create, and the last update's times
+  uint64_t mesh_updates = 0, mesh_update_refits = 0, mesh_update_rebuilds = 0, mesh_update_fallbacks = 0;
+  int32_t mesh_update_last_kind = 0;
+  double mesh_update_frames_ms = 0, mesh_update_tree_ms = 0;
+  hipEvent_t mesh_update_event[2] = {nullptr, nullptr};   // start / stop of an update's frames on `stream`
   // pt_set_mesh_build: the options belong to the handle and outlive the scene
   int32_t mesh_builder = 0, mesh_on_pose = 0;        // PT_MESH_BUILDER_HOST, PT_MESH_POSE_REBUILD
   uint64_t mesh_host_builds = 0, mesh_device_builds = 0, mesh_refits = 0;
@@ -538,47 +558,77 @@ void bind_meshes(pt_handle h, ptd::TraceParams& P) {
 // The TEX instances' second argument (pt_set_mesh_texture): valid while h->mesh.textured()
 ptd::TexParams tex_params(pt_handle h) { return ptd::TexParams{h->mesh.d_uvs, h->mesh.d_desc}; }
 
+// The host copies of what pt_update_mesh_vertices wrote on the device (ptmi_mesh_update.h): a stale mesh's frames and corner
+// normals come back with one copy each, before anything on the host reads them.
+int refresh_mesh_host(pt_handle h, pt_context::MeshSet& M) {
+  for (pt_context::MeshSet::One& m : M.mesh) {
+    if (m.world_stale) {
+      PT_HIP(hipMemcpy(M.world.data() + ptmesh::kFrameFloats * (size_t)m.tri_base, M.dev.world + ptmesh::kFrameFloats * (size_t)m.tri_base,
+                       ptmesh::kFrameFloats * (size_t)m.n_triangles * sizeof(float), hipMemcpyDeviceToHost));
+      m.world_stale = false;
+    }
+    if (m.normals_stale) {
+      PT_HIP(hipMemcpy(m.normals.data(), M.dev.corner + 9 * (size_t)m.tri_base, m.normals.size() * sizeof(float), hipMemcpyDeviceToHost));
+      m.normals_stale = false;
+    }
+  }
+  return PT_OK;
+}
+
+// The host builder's scratch, kept over the meshes of one pass.
+struct MeshHostScratch {
+  std::vector<float> frames, uvs;
+  std::vector<ptmesh::F4> normals;
+  ptmesh::Built B;
+};
+
+// Mesh m of M into the frame of `cam`: its tree built on the host and copied, with its triangles, normals and uvs in the new slot
+// order, into M's device buffers, which hold any tree of these triangles (2 T - 1 nodes): no allocation on the device.
+int build_mesh_host(pt_handle h, pt_context::MeshSet& M, pt_context::MeshSet::One& m, const ptcamera::Basis* cam, MeshHostScratch& X) {
+  ptmesh::Built& B = X.B;
+  const auto t0 = std::chrono::steady_clock::now();
+  X.frames.resize(ptmesh::kFrameFloats * (size_t)m.n_triangles);
+  ptmesh::kernel_frames(M.world.data() + ptmesh::kFrameFloats * (size_t)m.tri_base, m.n_triangles, cam, X.frames.data());
+  ptmesh::build(X.frames.data(), m.n_triangles, B);
+  m.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  m.n_nodes = (uint32_t)B.nodes.size();
+  m.max_leaf = B.max_leaf; m.depth = B.depth; m.pad = B.pad;
+  if (B.nodes.size() > 2 * (size_t)m.n_triangles - 1 || B.orig.size() != m.n_triangles)
+    return fail(h, PT_ERR_HIP, "mesh builder: a tree larger than its buffer");   // (cannot happen: a binary tree with non-empty leaves)
+  PT_HIP(hipMemcpy(M.d_nodes + m.node_base, B.nodes.data(), B.nodes.size() * sizeof(ptmesh::Node), hipMemcpyHostToDevice));
+  PT_HIP(hipMemcpy(M.d_tris + 3 * (size_t)m.tri_base, B.tris.data(), B.tris.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
+  PT_HIP(hipMemcpy(M.d_orig + m.tri_base, B.orig.data(), B.orig.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (!m.normals.empty()) {   // the corner normals into the new slot order (the buffer exists: pt_set_mesh_normals)
+    X.normals.resize(3 * (size_t)m.n_triangles);
+    ptmesh::slot_normals(m.normals.data(), B.orig.data(), m.n_triangles, cam, X.normals.data());
+    PT_HIP(hipMemcpy(M.d_normals + 3 * (size_t)m.tri_base, X.normals.data(), X.normals.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
+  }
+  if (!m.uvs.empty()) {   // the corner uvs into the new slot order, untransformed (the buffer exists: pt_set_mesh_texture)
+    X.uvs.resize(6 * (size_t)m.n_triangles);
+    ptmesh::slot_uvs(m.uvs.data(), B.orig.data(), m.n_triangles, X.uvs.data());
+    PT_HIP(hipMemcpy(M.d_uvs + 6 * (size_t)m.tri_base, X.uvs.data(), X.uvs.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  const ptd::MeshRow row{m.node_base, m.tri_base, m.n_nodes, m.n_triangles, m.normals.empty() ? 0u : 1u, m.uvs.empty() ? 0u : 1u};
+  memcpy(&M.row[m.object_index], &row, sizeof(row));
+  return PT_OK;
+}
+
 // Transforms every mesh of M into the frame of `cam` (nullptr: the world frame, which is the built-in camera's), builds its tree
-// and copies trees and triangles into M's device buffers, which hold any tree of these triangles (2 T - 1 nodes): no allocation on
-// the device.  The handle's streams are drained first: a step in flight may still read the buffers.
+// and copies trees and triangles into M's device buffers.  The handle's streams are drained first: a step in flight may still
+// read the buffers.
 int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam) try {
   PT_HIP(hipSetDevice(h->cfg.device));
   if (&M == &h->mesh)   // (a set that is not in force yet has no reader)
     for (hipStream_t s : {h->stream, h->trace_stream, h->acc_stream})
       if (s) PT_HIP(hipStreamSynchronize(s));
   M.built = false;
-  std::vector<float> frames;
-  std::vector<ptmesh::F4> normals;
-  std::vector<float> uvs;
-  ptmesh::Built B;
   M.topo_builder = -1;
+  if (int rc = refresh_mesh_host(h, M)) return rc;
+  MeshHostScratch X;
   double total_ms = 0;
   for (pt_context::MeshSet::One& m : M.mesh) {
-    const auto t0 = std::chrono::steady_clock::now();
-    frames.resize(ptmesh::kFrameFloats * (size_t)m.n_triangles);
-    ptmesh::kernel_frames(M.world.data() + ptmesh::kFrameFloats * (size_t)m.tri_base, m.n_triangles, cam, frames.data());
-    ptmesh::build(frames.data(), m.n_triangles, B);
-    m.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (int rc = build_mesh_host(h, M, m, cam, X)) return rc;
     total_ms += m.build_ms;
-    m.n_nodes = (uint32_t)B.nodes.size();
-    m.max_leaf = B.max_leaf; m.depth = B.depth; m.pad = B.pad;
-    if (B.nodes.size() > 2 * (size_t)m.n_triangles - 1 || B.orig.size() != m.n_triangles)
-      return fail(h, PT_ERR_HIP, "mesh builder: a tree larger than its buffer");   // (cannot happen: a binary tree with non-empty leaves)
-    PT_HIP(hipMemcpy(M.d_nodes + m.node_base, B.nodes.data(), B.nodes.size() * sizeof(ptmesh::Node), hipMemcpyHostToDevice));
-    PT_HIP(hipMemcpy(M.d_tris + 3 * (size_t)m.tri_base, B.tris.data(), B.tris.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
-    PT_HIP(hipMemcpy(M.d_orig + m.tri_base, B.orig.data(), B.orig.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (!m.normals.empty()) {   // the corner normals into the new slot order (the buffer exists: pt_set_mesh_normals)
-      normals.resize(3 * (size_t)m.n_triangles);
-      ptmesh::slot_normals(m.normals.data(), B.orig.data(), m.n_triangles, cam, normals.data());
-      PT_HIP(hipMemcpy(M.d_normals + 3 * (size_t)m.tri_base, normals.data(), normals.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice));
-    }
-    if (!m.uvs.empty()) {   // the corner uvs into the new slot order, untransformed (the buffer exists: pt_set_mesh_texture)
-      uvs.resize(6 * (size_t)m.n_triangles);
-      ptmesh::slot_uvs(m.uvs.data(), B.orig.data(), m.n_triangles, uvs.data());
-      PT_HIP(hipMemcpy(M.d_uvs + 6 * (size_t)m.tri_base, uvs.data(), uvs.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    const ptd::MeshRow row{m.node_base, m.tri_base, m.n_nodes, m.n_triangles, m.normals.empty() ? 0u : 1u, m.uvs.empty() ? 0u : 1u};
-    memcpy(&M.row[m.object_index], &row, sizeof(row));
   }
   M.built = true;
   M.built_world = cam == nullptr;
@@ -603,6 +653,10 @@ int update_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* ca
   if (h->mesh_builder == PT_MESH_BUILDER_DEVICE) return build_meshes_device(h, M, cam);
   return build_meshes(h, M, cam);
 }
+
+}  // (namespace: ptmi_mesh_update.h opens its own)
+#include "ptmi_mesh_update.h"
+namespace {
 
 // Before anything traces a mesh scene: the trees follow the camera in force (world = true, pt_mesh_intersect: the world frame).
 int ensure_meshes(pt_handle h, bool world = false) {

@@ -33,6 +33,20 @@ constexpr uint32_t kMaxDepthSah = 48;
 
 // ---- validation (include/ptmi.h: the order is part of the contract)
 
+// What is wrong with one triangle -- its corners' vertex indices ix and their values v --, "" if nothing: checks 10..12 of
+// pt_set_scene_meshes, lowest corner first, lowest component first.  pt_update_mesh_vertices names a rejected triangle by this.
+inline std::string triangle_fault(const uint32_t* ix, const float (&v)[3][3]) {
+  for (int c = 0; c < 3; ++c)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(v[c][k])) return "vertices[" + std::to_string(ix[c]) + "] must be finite (got " + ptscene::num(v[c][k]) + ")";
+  const ptscene::PolyFrame f = ptscene::poly_frame(v);
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(f.e1[k]) || !std::isfinite(f.e2[k]) || !std::isfinite(f.c[k]))
+      return "vertex differences and their cross product must be finite";
+  if (!(f.cc > 0.f) || !std::isfinite(f.cc)) return "vertices are collinear";
+  return "";
+}
+
 // Checks 1..12 of pt_set_scene_meshes; "" if the call is valid.
 inline std::string check(const pt_scene_object_ex* objs, uint32_t n, uint32_t stride, const pt_mesh* meshes, uint32_t n_meshes) {
   const std::string bad = ptscene::check_ex(objs, n, stride, PT_SHAPE_MESH);
@@ -66,24 +80,27 @@ inline std::string check(const pt_scene_object_ex* objs, uint32_t n, uint32_t st
         if (ix >= M.n_vertices)
           return at + "indices[" + std::to_string(c) + "] must be < n_vertices = " + std::to_string(M.n_vertices) + " (got " + std::to_string(ix) + ")";
       }
-      for (int c = 0; c < 3; ++c) {
-        const uint32_t ix = M.indices[3 * (size_t)j + c];
-        for (int k = 0; k < 3; ++k) {
-          v[c][k] = M.vertices[3 * (size_t)ix + k];
-          if (!std::isfinite(v[c][k])) return at + "vertices[" + std::to_string(ix) + "] must be finite (got " + ptscene::num(v[c][k]) + ")";
-        }
-      }
-      const ptscene::PolyFrame f = ptscene::poly_frame(v);
-      for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(f.e1[k]) || !std::isfinite(f.e2[k]) || !std::isfinite(f.c[k]))
-          return at + "vertex differences and their cross product must be finite";
-      if (!(f.cc > 0.f) || !std::isfinite(f.cc)) return at + "vertices are collinear";
+      for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 3; ++k) v[c][k] = M.vertices[3 * (size_t)M.indices[3 * (size_t)j + c] + k];
+      const std::string fault = triangle_fault(M.indices + 3 * (size_t)j, v);
+      if (!fault.empty()) return at + fault;
     }
   }
   return "";
 }
 
 // ---- vertex normals (pt_set_mesh_normals, include/ptmi.h)
+
+// What is wrong with normal k of value v, "" if nothing: the last two checks of pt_set_mesh_normals (pt_update_mesh_vertices
+// names a rejected normal by this).
+inline std::string normal_fault(uint32_t k, const float* v) {
+  for (int q = 0; q < 3; ++q)
+    if (!std::isfinite(v[q])) return "normals[" + std::to_string(k) + "] must be finite (got " + ptscene::num(v[q]) + ")";
+  volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
+  volatile float d0 = xx + yy, d1 = d0 + zz;
+  if (!(d1 > 0.f) || !std::isfinite(d1)) return "normals[" + std::to_string(k) + "] must have a finite dot(n, n) > 0 (got " + ptscene::num(d1) + ")";
+  return "";
+}
 
 // The checks of pt_set_mesh_normals that need no device, in the contract's order; "" if the normals are valid.  indices: the
 // mesh's own [n_triangles][3] (used when normal_indices is null: per-vertex normals).  Only referenced normals are examined.
@@ -100,12 +117,8 @@ inline std::string check_normals(uint32_t mesh, uint32_t n_vertices, uint32_t n_
       const uint32_t k = ix[3 * (size_t)j + c];
       if (k >= n_normals)
         return tri + (normal_indices ? "normal_indices[" : "indices[") + std::to_string(c) + "] must be < n_normals = " + std::to_string(n_normals) + " (got " + std::to_string(k) + ")";
-      const float* v = normals + 3 * (size_t)k;
-      for (int q = 0; q < 3; ++q)
-        if (!std::isfinite(v[q])) return tri + "normals[" + std::to_string(k) + "] must be finite (got " + ptscene::num(v[q]) + ")";
-      volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
-      volatile float d0 = xx + yy, d1 = d0 + zz;
-      if (!(d1 > 0.f) || !std::isfinite(d1)) return tri + "normals[" + std::to_string(k) + "] must have a finite dot(n, n) > 0 (got " + ptscene::num(d1) + ")";
+      const std::string fault = normal_fault(k, normals + 3 * (size_t)k);
+      if (!fault.empty()) return tri + fault;
     }
   return "";
 }

@@ -1,7 +1,7 @@
 // ptmi_mesh_build.h -- mesh trees built and refitted on the device (pt_set_mesh_build, include/ptmi.h): the kernels, which are
 // thin wrappers around the functions of pt_mesh_build.h (ONE definition for the device, the host reference and the test
 // program), the device storage they need, and the two passes build_meshes_device / refit_meshes that stand beside build_meshes
-// (ptmi_context.h).  Nothing here allocates during a build or a refit: ensure_mesh_device sizes everything for the largest mesh
+// (ptmi_context.h), each a loop over the one-mesh body that pt_update_mesh_vertices (ptmi_mesh_update.h) runs alone.  Nothing here allocates during a build or a refit: ensure_mesh_device sizes everything for the largest mesh
 // when the option is set and at every pt_set_scene_meshes under it.  No kernel waits on another workgroup: the bottom-up passes
 // use arrival counters, the first thread to arrive returns (pt_mesh_build.h: arrive).
 #pragma once
@@ -179,7 +179,7 @@ inline ptlbvh::Scratch mesh_scratch(const pt_context::MeshSet::DeviceBuild& D) {
 int upload_mesh_corners(pt_handle h, pt_context::MeshSet& M, size_t mesh) {
   const pt_context::MeshSet::One& m = M.mesh[mesh];
   pt_context::MeshSet::DeviceBuild& D = M.dev;
-  if (!m.normals.empty() && D.corner)
+  if (!m.normals.empty() && D.corner && !m.normals_stale)   // (stale: the device holds the newer ones, pt_update_mesh_vertices)
     PT_HIP(hipMemcpy(D.corner + 9 * (size_t)m.tri_base, m.normals.data(), m.normals.size() * sizeof(float), hipMemcpyHostToDevice));
   if (!m.uvs.empty() && D.corner_uv)
     PT_HIP(hipMemcpy(D.corner_uv + 6 * (size_t)m.tri_base, m.uvs.data(), m.uvs.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -291,57 +291,62 @@ static int drain_for_meshes(pt_handle h, pt_context::MeshSet& M) {
   return PT_OK;
 }
 
-// build_meshes on the device: every mesh of M in the frame of `cam`, from the device copy of the world frames, on the handle's
-// stream.  No per-triangle data crosses to or from the host.
+// Mesh k of M built on the device in the frame of P, from the device copy of its world frames, on the handle's stream (drained
+// by the caller).  No per-triangle data crosses to or from the host.
+static int build_mesh_device(pt_handle h, pt_context::MeshSet& M, size_t k, const ptlbvh::Pose& P) {
+  pt_context::MeshSet::DeviceBuild& D = M.dev;
+  const ptlbvh::Scratch S = mesh_scratch(D);
+  uint32_t* bounds = D.words + (size_t)ptlbvh::kScratchWords * D.cap;
+  pt_context::MeshSet::One& m = M.mesh[k];
+  const uint32_t T = m.n_triangles;
+  if (T > D.cap) return fail(h, PT_ERR_HIP, "mesh builder (device): storage smaller than the mesh");   // (cannot happen)
+  const float* world = D.world + ptlbvh::kFrameFloats * (size_t)m.tri_base;
+  uint32_t* stats = D.stats + ptlbvh::kStats * k;
+  const dim3 block(ptlbvh::kBlock), per_tri(ptlbvh::blocks_for(T)), per_node(ptlbvh::blocks_for(2 * T - 1));
+  PT_HIP(hipEventRecord(h->mesh_event[0], h->stream));
+  PT_HIP(hipMemsetAsync(bounds, 0xff, 3 * sizeof(uint32_t), h->stream));
+  PT_HIP(hipMemsetAsync(bounds + 3, 0, 3 * sizeof(uint32_t), h->stream));
+  PT_HIP(hipMemsetAsync(stats, 0, ptlbvh::kStats * sizeof(uint32_t), h->stream));
+  hipLaunchKernelGGL(ptlbvh::lbvh_bounds_kernel, per_tri, block, 0, h->stream, world, T, P, bounds);
+  hipLaunchKernelGGL(ptlbvh::lbvh_codes_kernel, per_tri, block, 0, h->stream, world, T, P, (const uint32_t*)bounds, (uint64_t*)D.code[0], (uint32_t*)D.index[0]);
+  PT_HIP(hipGetLastError());
+  {
+    const uint32_t tiles = ptlbvh::sort_tiles(T);
+    uint32_t* hist = reinterpret_cast<uint32_t*>((uint8_t*)D.sort_tmp);
+    uint32_t* totals = hist + (size_t)ptlbvh::kSortDigits * tiles;
+    for (uint32_t p = 0; p < ptlbvh::kSortPasses; ++p) {   // an even number of passes: the sorted pairs end in code[0], index[0]
+      const uint64_t* kin = D.code[p & 1u];
+      const uint32_t* vin = D.index[p & 1u];
+      hipLaunchKernelGGL(ptlbvh::lbvh_sort_hist_kernel, dim3(tiles), block, 0, h->stream, kin, T, 8u * p, tiles, hist);
+      hipLaunchKernelGGL(ptlbvh::lbvh_sort_scan_kernel, dim3(ptlbvh::kSortDigits), block, 0, h->stream, hist, tiles, totals);
+      hipLaunchKernelGGL(ptlbvh::lbvh_sort_scatter_kernel, dim3(tiles), block, 0, h->stream, kin, vin, T, 8u * p, tiles, (const uint32_t*)hist,
+                         (const uint32_t*)totals, (uint64_t*)D.code[(p + 1u) & 1u], (uint32_t*)D.index[(p + 1u) & 1u]);
+    }
+    PT_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(ptlbvh::lbvh_tree_kernel, per_tri, block, 0, h->stream, (const uint64_t*)D.code[0], T, S);
+  hipLaunchKernelGGL(ptlbvh::lbvh_count_kernel, per_tri, block, 0, h->stream, T, S);
+  hipLaunchKernelGGL(ptlbvh::lbvh_emit_kernel, per_node, block, 0, h->stream, T, S, M.d_nodes + m.node_base, stats);
+  hipLaunchKernelGGL(ptlbvh::lbvh_slots_kernel, per_tri, block, 0, h->stream, T, (const uint32_t*)D.index[0], P, world,
+                     m.normals.empty() ? (const float*)nullptr : (const float*)(D.corner + 9 * (size_t)m.tri_base),
+                     m.uvs.empty() ? (const float*)nullptr : (const float*)(D.corner_uv + 6 * (size_t)m.tri_base),
+                     M.d_tris + 3 * (size_t)m.tri_base, m.normals.empty() ? (ptmesh::F4*)nullptr : M.d_normals + 3 * (size_t)m.tri_base,
+                     M.d_orig + m.tri_base, m.uvs.empty() ? (float*)nullptr : M.d_uvs + 6 * (size_t)m.tri_base);
+  PT_HIP(hipGetLastError());
+  uint32_t stats_host[ptlbvh::kStats] = {};
+  return mesh_fit_and_read(h, M, k, 2 * T - 1, stats_host);
+}
+
+// build_meshes on the device: every mesh of M in the frame of `cam`.
 int build_meshes_device(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam) {
   if (int rc = drain_for_meshes(h, M)) return rc;
   M.built = false;
   M.topo_builder = -1;
-  pt_context::MeshSet::DeviceBuild& D = M.dev;
   const ptlbvh::Pose P = ptlbvh::pose_of(cam);
-  const ptlbvh::Scratch S = mesh_scratch(D);
-  uint32_t* bounds = D.words + (size_t)ptlbvh::kScratchWords * D.cap;
   double total_ms = 0;
   for (size_t k = 0; k < M.mesh.size(); ++k) {
-    pt_context::MeshSet::One& m = M.mesh[k];
-    const uint32_t T = m.n_triangles;
-    if (T > D.cap) return fail(h, PT_ERR_HIP, "mesh builder (device): storage smaller than the mesh");   // (cannot happen)
-    const float* world = D.world + ptlbvh::kFrameFloats * (size_t)m.tri_base;
-    uint32_t* stats = D.stats + ptlbvh::kStats * k;
-    const dim3 block(ptlbvh::kBlock), per_tri(ptlbvh::blocks_for(T)), per_node(ptlbvh::blocks_for(2 * T - 1));
-    PT_HIP(hipEventRecord(h->mesh_event[0], h->stream));
-    PT_HIP(hipMemsetAsync(bounds, 0xff, 3 * sizeof(uint32_t), h->stream));
-    PT_HIP(hipMemsetAsync(bounds + 3, 0, 3 * sizeof(uint32_t), h->stream));
-    PT_HIP(hipMemsetAsync(stats, 0, ptlbvh::kStats * sizeof(uint32_t), h->stream));
-    hipLaunchKernelGGL(ptlbvh::lbvh_bounds_kernel, per_tri, block, 0, h->stream, world, T, P, bounds);
-    hipLaunchKernelGGL(ptlbvh::lbvh_codes_kernel, per_tri, block, 0, h->stream, world, T, P, (const uint32_t*)bounds, (uint64_t*)D.code[0], (uint32_t*)D.index[0]);
-    PT_HIP(hipGetLastError());
-    {
-      const uint32_t tiles = ptlbvh::sort_tiles(T);
-      uint32_t* hist = reinterpret_cast<uint32_t*>((uint8_t*)D.sort_tmp);
-      uint32_t* totals = hist + (size_t)ptlbvh::kSortDigits * tiles;
-      for (uint32_t p = 0; p < ptlbvh::kSortPasses; ++p) {   // an even number of passes: the sorted pairs end in code[0], index[0]
-        const uint64_t* kin = D.code[p & 1u];
-        const uint32_t* vin = D.index[p & 1u];
-        hipLaunchKernelGGL(ptlbvh::lbvh_sort_hist_kernel, dim3(tiles), block, 0, h->stream, kin, T, 8u * p, tiles, hist);
-        hipLaunchKernelGGL(ptlbvh::lbvh_sort_scan_kernel, dim3(ptlbvh::kSortDigits), block, 0, h->stream, hist, tiles, totals);
-        hipLaunchKernelGGL(ptlbvh::lbvh_sort_scatter_kernel, dim3(tiles), block, 0, h->stream, kin, vin, T, 8u * p, tiles, (const uint32_t*)hist,
-                           (const uint32_t*)totals, (uint64_t*)D.code[(p + 1u) & 1u], (uint32_t*)D.index[(p + 1u) & 1u]);
-      }
-      PT_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ptlbvh::lbvh_tree_kernel, per_tri, block, 0, h->stream, (const uint64_t*)D.code[0], T, S);
-    hipLaunchKernelGGL(ptlbvh::lbvh_count_kernel, per_tri, block, 0, h->stream, T, S);
-    hipLaunchKernelGGL(ptlbvh::lbvh_emit_kernel, per_node, block, 0, h->stream, T, S, M.d_nodes + m.node_base, stats);
-    hipLaunchKernelGGL(ptlbvh::lbvh_slots_kernel, per_tri, block, 0, h->stream, T, (const uint32_t*)D.index[0], P, world,
-                       m.normals.empty() ? (const float*)nullptr : (const float*)(D.corner + 9 * (size_t)m.tri_base),
-                       m.uvs.empty() ? (const float*)nullptr : (const float*)(D.corner_uv + 6 * (size_t)m.tri_base),
-                       M.d_tris + 3 * (size_t)m.tri_base, m.normals.empty() ? (ptmesh::F4*)nullptr : M.d_normals + 3 * (size_t)m.tri_base,
-                       M.d_orig + m.tri_base, m.uvs.empty() ? (float*)nullptr : M.d_uvs + 6 * (size_t)m.tri_base);
-    PT_HIP(hipGetLastError());
-    uint32_t stats_host[ptlbvh::kStats] = {};
-    if (int rc = mesh_fit_and_read(h, M, k, 2 * T - 1, stats_host)) return rc;
-    total_ms += m.build_ms;
+    if (int rc = build_mesh_device(h, M, k, P)) return rc;
+    total_ms += M.mesh[k].build_ms;
   }
   mesh_finish_pass(M, cam);
   M.topo_builder = PT_MESH_BUILDER_DEVICE;
@@ -349,31 +354,36 @@ int build_meshes_device(pt_handle h, pt_context::MeshSet& M, const ptcamera::Bas
   return PT_OK;
 }
 
-// A pose change under PT_MESH_POSE_REFIT: topology, slot order and orig stand (whichever builder made them); the frames are
+// Mesh k of M refitted to the frame of P: topology, slot order and orig stand (whichever builder made them); the frames are
 // formed again from the device copy of the world frames, the corner normals go through the direction transform into their slots,
 // and the boxes and the pad follow.  uvs are not touched.
+static int refit_mesh(pt_handle h, pt_context::MeshSet& M, size_t k, const ptlbvh::Pose& P) {
+  pt_context::MeshSet::DeviceBuild& D = M.dev;
+  pt_context::MeshSet::One& m = M.mesh[k];
+  const uint32_t T = m.n_triangles;
+  uint32_t* stats = D.stats + ptlbvh::kStats * k;
+  uint32_t stats_host[ptlbvh::kStats] = {m.n_nodes, m.depth, m.max_leaf, 0u};
+  PT_HIP(hipEventRecord(h->mesh_event[0], h->stream));
+  PT_HIP(hipMemcpyAsync(stats, stats_host, sizeof(stats_host), hipMemcpyHostToDevice, h->stream));
+  PT_HIP(hipStreamSynchronize(h->stream));   // (stats_host is written again below)
+  hipLaunchKernelGGL(ptlbvh::lbvh_slots_kernel, dim3(ptlbvh::blocks_for(T)), dim3(ptlbvh::kBlock), 0, h->stream, T,
+                     (const uint32_t*)(M.d_orig + m.tri_base), P, (const float*)(D.world + ptlbvh::kFrameFloats * (size_t)m.tri_base),
+                     m.normals.empty() ? (const float*)nullptr : (const float*)(D.corner + 9 * (size_t)m.tri_base), (const float*)nullptr,
+                     M.d_tris + 3 * (size_t)m.tri_base, m.normals.empty() ? (ptmesh::F4*)nullptr : M.d_normals + 3 * (size_t)m.tri_base,
+                     (uint32_t*)nullptr, (float*)nullptr);
+  PT_HIP(hipGetLastError());
+  return mesh_fit_and_read(h, M, k, m.n_nodes, stats_host);
+}
+
+// A pose change under PT_MESH_POSE_REFIT: every mesh of M refitted to the frame of `cam`.
 int refit_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam) {
   if (int rc = drain_for_meshes(h, M)) return rc;
   M.built = false;
-  pt_context::MeshSet::DeviceBuild& D = M.dev;
   const ptlbvh::Pose P = ptlbvh::pose_of(cam);
   double total_ms = 0;
   for (size_t k = 0; k < M.mesh.size(); ++k) {
-    pt_context::MeshSet::One& m = M.mesh[k];
-    const uint32_t T = m.n_triangles;
-    uint32_t* stats = D.stats + ptlbvh::kStats * k;
-    uint32_t stats_host[ptlbvh::kStats] = {m.n_nodes, m.depth, m.max_leaf, 0u};
-    PT_HIP(hipEventRecord(h->mesh_event[0], h->stream));
-    PT_HIP(hipMemcpyAsync(stats, stats_host, sizeof(stats_host), hipMemcpyHostToDevice, h->stream));
-    PT_HIP(hipStreamSynchronize(h->stream));   // (stats_host is written again below)
-    hipLaunchKernelGGL(ptlbvh::lbvh_slots_kernel, dim3(ptlbvh::blocks_for(T)), dim3(ptlbvh::kBlock), 0, h->stream, T,
-                       (const uint32_t*)(M.d_orig + m.tri_base), P, (const float*)(D.world + ptlbvh::kFrameFloats * (size_t)m.tri_base),
-                       m.normals.empty() ? (const float*)nullptr : (const float*)(D.corner + 9 * (size_t)m.tri_base), (const float*)nullptr,
-                       M.d_tris + 3 * (size_t)m.tri_base, m.normals.empty() ? (ptmesh::F4*)nullptr : M.d_normals + 3 * (size_t)m.tri_base,
-                       (uint32_t*)nullptr, (float*)nullptr);
-    PT_HIP(hipGetLastError());
-    if (int rc = mesh_fit_and_read(h, M, k, m.n_nodes, stats_host)) return rc;
-    total_ms += m.build_ms;
+    if (int rc = refit_mesh(h, M, k, P)) return rc;
+    total_ms += M.mesh[k].build_ms;
   }
   mesh_finish_pass(M, cam);
   note_mesh_pass(h, PT_MESH_LAST_REFIT, total_ms);

@@ -55,7 +55,10 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
            "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect", "pt_set_mesh_normals",
            "pt_get_mesh_normals_info", "pt_mesh_shade", "pt_set_mesh_texture", "pt_get_mesh_texture_info", "pt_mesh_texel",
-           "pt_set_mesh_build", "pt_get_mesh_build_info", "pt_mesh_tree"]
+           "pt_set_mesh_build", "pt_get_mesh_build_info", "pt_mesh_tree", "pt_update_mesh_vertices", "pt_get_mesh_update_info"]
+MESH_UPDATE_REFIT, MESH_UPDATE_REBUILD = 0, 1
+MESH_UPDATE_MODES = {"refit": MESH_UPDATE_REFIT, "rebuild": MESH_UPDATE_REBUILD}
+MESH_UPDATE_HOST_MEMORY, MESH_UPDATE_DEVICE_MEMORY = 0, 1
 MESH_BUILDER_HOST, MESH_BUILDER_DEVICE = 0, 1
 MESH_BUILDERS = {"host": MESH_BUILDER_HOST, "device": MESH_BUILDER_DEVICE}
 MESH_POSE_REBUILD, MESH_POSE_REFIT = 0, 1
@@ -437,6 +440,22 @@ class MeshBuildInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved")}
 
 
+class MeshUpdate(C.Structure):
+    """pt_mesh_update"""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("memory", C.c_int32), ("n_vertices", C.c_uint32),
+                ("vertices", C.c_void_p), ("n_normals", C.c_uint32), ("normals", C.c_void_p)]
+
+
+class MeshUpdateInfo(C.Structure):
+    """pt_mesh_update_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("last_kind", C.c_int32), ("updates", C.c_uint64), ("refits", C.c_uint64),
+                ("rebuilds", C.c_uint64), ("fallbacks", C.c_uint64), ("last_frames_ms", C.c_double), ("last_tree_ms", C.c_double),
+                ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
+
+
 class MeshNormalsInfo(C.Structure):
     """pt_mesh_normals_info"""
     _fields_ = [("struct_size", C.c_uint32), ("has_normals", C.c_uint32), ("per_corner", C.c_uint32), ("n_normals", C.c_uint32),
@@ -665,6 +684,8 @@ def load_library(diag=False):
     L.pt_mesh_texel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_set_mesh_build.argtypes = [C.c_void_p, C.POINTER(MeshBuildOptions)]
     L.pt_get_mesh_build_info.argtypes = [C.c_void_p, C.POINTER(MeshBuildInfo)]
+    L.pt_update_mesh_vertices.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshUpdate)]
+    L.pt_get_mesh_update_info.argtypes = [C.c_void_p, C.POINTER(MeshUpdateInfo)]
     L.pt_mesh_tree.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
@@ -743,6 +764,7 @@ class Renderer:
         cfg.stop_prob, cfg.refractive_index = stop_prob, refractive_index
         cfg.aa_noise_type, cfg.sample_precision = aa_noise_type, sample_precision
         cfg.device = device
+        self._device = device
         cfg.max_work_items = max_work_items if max_work_items else width * height
         cfg.iterations_per_batch = iterations_per_batch
         cfg.stream = stream
@@ -1087,6 +1109,52 @@ class Renderer:
         last_ms, device_bytes."""
         info = MeshBuildInfo(struct_size=C.sizeof(MeshBuildInfo))
         self._check(self._lib.pt_get_mesh_build_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
+    def _update_array(self, what, a):
+        """(pointer, rows, memory, keep-alive) of vertices / normals for pt_mesh_update: a float32 numpy array (or anything numpy
+        converts), or a contiguous float32 torch tensor on this renderer's device, which is passed by its data_ptr()."""
+        if type(a).__module__.split(".")[0] == "torch":
+            import torch
+            if a.dtype != torch.float32:
+                raise ValueError("%s: a tensor must be float32 (got %s)" % (what, a.dtype))
+            if a.device.type != "cuda" or a.device.index != getattr(self, "_device", 0):
+                raise ValueError("%s: a tensor must lie on the renderer's device cuda:%d (got %s)" % (what, getattr(self, "_device", 0), a.device))
+            if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] == 0 or not a.is_contiguous():
+                raise ValueError("%s must be a contiguous tensor of shape (N, 3), N >= 1" % what)
+            return a.data_ptr(), int(a.shape[0]), MESH_UPDATE_DEVICE_MEMORY, a
+        arr = np.ascontiguousarray(a, dtype=np.float32)
+        if arr.ndim != 2 or arr.shape[1] != 3 or len(arr) == 0:
+            raise ValueError("%s must be an array of shape (N, 3), N >= 1" % what)
+        return arr.ctypes.data, len(arr), MESH_UPDATE_HOST_MEMORY, arr
+
+    def update_mesh_vertices(self, k, vertices, normals=None, mode="refit"):
+        """pt_update_mesh_vertices: new positions (V, 3) for the vertices of mesh k of the scene in force -- the same V, the same
+        triangles -- and, for a mesh with normals, optionally new normals (N, 3) in the attached layout; normals None keeps the
+        attached ones.  mode "refit" keeps the tree's topology and refits its boxes, "rebuild" builds the mesh's tree again.
+        vertices / normals are float32 numpy arrays, or contiguous float32 torch tensors on the renderer's device: those are read
+        in place, device to device, after torch's current stream has been synchronised.  Both must lie in the same memory."""
+        if mode not in MESH_UPDATE_MODES:
+            raise ValueError("mode must be one of %s (got %r)" % (sorted(MESH_UPDATE_MODES), mode))
+        vp, nv, memory, keep_v = self._update_array("vertices", vertices)
+        np_, nn, keep_n = None, 0, None
+        if normals is not None:
+            np_, nn, memory_n, keep_n = self._update_array("normals", normals)
+            if memory_n != memory:
+                raise ValueError("vertices and normals must both be numpy arrays or both be tensors on the device")
+        if memory == MESH_UPDATE_DEVICE_MEMORY:
+            import torch
+            torch.cuda.current_stream(keep_v.device).synchronize()   # the writes are complete before the library reads
+        u = MeshUpdate(struct_size=C.sizeof(MeshUpdate), mode=MESH_UPDATE_MODES[mode], memory=memory, n_vertices=nv, vertices=vp,
+                       n_normals=nn, normals=np_)
+        self._check(self._lib.pt_update_mesh_vertices(self.handle, int(k), C.byref(u)))
+        del keep_v, keep_n
+
+    def mesh_update_info(self):
+        """pt_get_mesh_update_info as a dict: last_kind, updates, refits, rebuilds, fallbacks, last_frames_ms, last_tree_ms,
+        device_bytes."""
+        info = MeshUpdateInfo(struct_size=C.sizeof(MeshUpdateInfo))
+        self._check(self._lib.pt_get_mesh_update_info(self.handle, C.byref(info)))
         return info.as_dict()
 
     def mesh_tree(self, k):
