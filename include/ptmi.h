@@ -773,6 +773,34 @@ typedef struct pt_mesh_update_info {  /* 64 bytes */
 } pt_mesh_update_info;
 int pt_get_mesh_update_info(pt_handle h, pt_mesh_update_info* out);
 
+/* Which instance of the trace kernels a launch took -- an EXTENSION, read-only and additive: PTMI_ABI_VERSION stays 5, no existing
+ * struct moves and nothing that is launched changes.  The trace kernel, the pt_trace_paths kernel and the feature kernel are each
+ * one template instantiated per (camera, bounce, geometry) (csrc/ptmi_trace_variant.h: 57, 19 and 5 instances); the camera, the
+ * guides and the scene in force pick the instance at every launch.  pt_get_trace_variant reports what the most recent launch of
+ * each family picked, as pt_nif_kernel_name does for the NIF: `trace` the last trace launch of pt_path_trace, `paths` the last
+ * pt_trace_paths, `features` the last computation of the feature buffers (pt_feature_buffers, pt_denoise; they are cached, so a
+ * call that finds them valid launches nothing and counts nothing).  camera, bounce and geometry are the coordinates the selector
+ * computed for that launch (PT_TRACE_CAMERA_*, PT_TRACE_BOUNCE_*, PT_TRACE_GEOMETRY_*: the values of ptvariant::Camera, Bounce and
+ * Geometry).  index is the instance's dense number in its family: geometry major, then bounce, then camera, the one invalid pair
+ * (LIGHT_GUIDE_PLAMPS, SPHERES) left out -- 0..56 for `trace`; 0..18 for `paths`, whose kernels read the camera at run time;
+ * 0..4, the geometry, for `features`, whose kernels ignore the bounce and the lens.  launches counts the family's launches since
+ * pt_create.  Before the first launch of a family its camera, bounce, geometry and index are -1 and its count is 0.
+ * Validation, in this order: a NULL out, struct_size, then a NULL handle (pt_last_error(NULL)); PT_ERR_INVALID_ARGUMENT each. */
+enum { PT_TRACE_CAMERA_BUILTIN = 0, PT_TRACE_CAMERA_POSE = 1, PT_TRACE_CAMERA_LENS = 2 };
+enum { PT_TRACE_BOUNCE_PLAIN = 0, PT_TRACE_BOUNCE_ENV_GUIDE = 1, PT_TRACE_BOUNCE_LIGHT_GUIDE = 2, PT_TRACE_BOUNCE_LIGHT_GUIDE_PLAMPS = 3 };
+enum { PT_TRACE_GEOMETRY_SPHERES = 0, PT_TRACE_GEOMETRY_POLY = 1, PT_TRACE_GEOMETRY_MESH = 2, PT_TRACE_GEOMETRY_SMOOTH = 3, PT_TRACE_GEOMETRY_TEX = 4 };
+typedef struct pt_trace_variant_launch { /* 24 bytes */
+  int32_t camera, bounce, geometry;   /* PT_TRACE_CAMERA_*, PT_TRACE_BOUNCE_*, PT_TRACE_GEOMETRY_*; -1 before the first launch */
+  int32_t index;                      /* the instance's dense number in its family; -1 before the first launch */
+  uint64_t launches;                  /* launches of the family since pt_create */
+} pt_trace_variant_launch;
+typedef struct pt_trace_variant_info { /* 80 bytes */
+  uint32_t struct_size;               /* in: sizeof(pt_trace_variant_info) */
+  uint32_t reserved;
+  pt_trace_variant_launch trace, paths, features;
+} pt_trace_variant_info;
+int pt_get_trace_variant(pt_handle h, pt_trace_variant_info* out);
+
 /* Runtime camera -- an EXTENSION: the reference's camera is compile-time, a pinhole at the origin looking down -z with +y up
  * (codelets.cpp:68-75,162-163); only the field of view is a setting.  pt_set_camera gives it a position, an orientation and an
  * optional thin lens.  Additive: PTMI_ABI_VERSION stays 5 and no existing struct moves.

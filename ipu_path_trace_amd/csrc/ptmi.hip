@@ -517,6 +517,22 @@ static ptvariant::Variant variant_in_force(pt_handle h, const ptd::TraceParams& 
   return ptvariant::select({P.lens_a > 0.f, P.cam_pose != 0, h->guide_set, P.lights.n != 0, h->light.polygons, h->scene_n != 0,
                             h->scene_poly, h->scene_mesh, h->mesh.smooth(), h->mesh.textured()});
 }
+// pt_get_trace_variant: the variant a launch site computed and the index it launched, into the family's record of the handle.
+static void note_variant(pt_trace_variant_launch& r, const ptvariant::Variant& v, int index) {
+  r.camera = (int32_t)v.camera;
+  r.bounce = (int32_t)v.bounce;
+  r.geometry = (int32_t)v.geometry;
+  r.index = index;
+  r.launches += 1;
+}
+static_assert(PT_TRACE_CAMERA_BUILTIN == (int)ptvariant::Camera::BUILTIN && PT_TRACE_CAMERA_POSE == (int)ptvariant::Camera::POSE &&
+              PT_TRACE_CAMERA_LENS == (int)ptvariant::Camera::LENS && PT_TRACE_BOUNCE_PLAIN == (int)ptvariant::Bounce::PLAIN &&
+              PT_TRACE_BOUNCE_ENV_GUIDE == (int)ptvariant::Bounce::ENV_GUIDE && PT_TRACE_BOUNCE_LIGHT_GUIDE == (int)ptvariant::Bounce::LIGHT_GUIDE &&
+              PT_TRACE_BOUNCE_LIGHT_GUIDE_PLAMPS == (int)ptvariant::Bounce::LIGHT_GUIDE_PLAMPS &&
+              PT_TRACE_GEOMETRY_SPHERES == (int)ptvariant::Geometry::SPHERES && PT_TRACE_GEOMETRY_POLY == (int)ptvariant::Geometry::POLY &&
+              PT_TRACE_GEOMETRY_MESH == (int)ptvariant::Geometry::MESH && PT_TRACE_GEOMETRY_SMOOTH == (int)ptvariant::Geometry::SMOOTH &&
+              PT_TRACE_GEOMETRY_TEX == (int)ptvariant::Geometry::TEX, "include/ptmi.h states the values of ptmi_trace_variant.h");
+static_assert(sizeof(pt_trace_variant_launch) == 24 && sizeof(pt_trace_variant_info) == 80, "pt_trace_variant_* layout");
 template <int I> constexpr int kCam = (int)ptvariant::at(I).camera;
 template <int I> constexpr int kBounce = (int)ptvariant::at(I).bounce;
 template <int I> constexpr int kGeom = (int)ptvariant::at(I).geometry;
@@ -553,7 +569,9 @@ static int stage_trace(pt_handle h, StepEvents& ev, ptd::TraceParams& P, const B
     if (!launch_trace_variant(h, P, b.g))   // A/B switches of the profiling build (diag/ptmi_trace_variants.h), read per launch
 #endif
     {   // camera, guide and scene in force pick the instance: with none of them set, the kernel that always ran
-      const int i = ptvariant::index(variant_in_force(h, P));
+      const ptvariant::Variant var = variant_in_force(h, P);
+      const int i = ptvariant::index(var);
+      note_variant(h->variant_trace, var, i);   // (pt_get_trace_variant)
       if (i >= ptvariant::kTraceTexFirst)   // a mesh in force has a texture (pt_set_mesh_texture): the instances with the second argument
         hipLaunchKernelGGL(kTraceTexKernels[i - ptvariant::kTraceTexFirst], dim3(b.g.blocks), dim3(ptd::kTraceBlock), ptd::hit_table_bytes(P.n_objects),
                            h->trace_stream, P, tex_params(h));
@@ -2013,6 +2031,7 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
   const ptvariant::Variant var = variant_in_force(h, P);   // the instance of the production kernel's bounce and geometry (the camera: read at run time)
   const int i = ptvariant::paths_index(var.bounce, var.geometry);
+  note_variant(h->variant_paths, var, i);   // (pt_get_trace_variant)
   if (i >= ptvariant::kPathsTexFirst)   // the textured twins (pt_set_mesh_texture)
     hipLaunchKernelGGL(kPathsTexKernels[i - ptvariant::kPathsTexFirst], dim3(((uint32_t)n + 127) / 128), dim3(128),
                        ptd::hit_table_bytes(P.n_objects), h->stream, P, tex_params(h), d_u, d_v, d_s, (uint32_t)n, d_out);
@@ -2022,6 +2041,27 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
   PT_HIP(hipGetLastError());
   PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_path_record), hipMemcpyDeviceToHost, h->stream));
   PT_HIP(hipStreamSynchronize(h->stream));
+  return PT_OK;
+}
+
+// The instance each kernel family's last launch took (include/ptmi.h): the handle's three records, as the launch sites left them.
+int pt_get_trace_variant(pt_handle h, pt_trace_variant_info* out) {
+  std::string bad;
+  if (!out)
+    bad = "pt_get_trace_variant: null output";
+  else if (out->struct_size != sizeof(pt_trace_variant_info))
+    bad = "pt_get_trace_variant: struct_size must be " + std::to_string(sizeof(pt_trace_variant_info)) + " (got " + std::to_string(out->struct_size) + ")";
+  else if (!h)
+    bad = "pt_get_trace_variant: null handle";
+  if (!bad.empty()) {
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->trace = h->variant_trace;
+  out->paths = h->variant_paths;
+  out->features = h->variant_features;
   return PT_OK;
 }
 

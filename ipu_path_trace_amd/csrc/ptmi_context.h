@@ -270,6 +270,9 @@ struct pt_context {
   double mesh_last_ms = 0;
   hipEvent_t mesh_event[2] = {nullptr, nullptr};     // start / stop of one mesh's device work on `stream`
 
+  // pt_get_trace_variant: what the selector picked at the last launch of each kernel family, written at the launch sites
+  pt_trace_variant_launch variant_trace{-1, -1, -1, -1, 0}, variant_paths{-1, -1, -1, -1, 0}, variant_features{-1, -1, -1, -1, 0};
+
   // camera (pt_set_camera): the values as given, and the frame made from them once (ptmi_camera.h)
   pt_camera camera = ptcamera::default_camera();
   ptcamera::Basis camera_basis = ptcamera::basis(ptcamera::default_camera());

@@ -33,7 +33,9 @@ int ensure_features(pt_handle h) {
   P.lens_a = 0.f;        // ... through a pinhole
   P.emitted = nullptr;
   const uint32_t px = h->cfg.width * h->cfg.height;
-  const int i = (int)variant_in_force(h, P).geometry;   // the geometry level alone picks the instance
+  const ptvariant::Variant var = variant_in_force(h, P);
+  const int i = (int)var.geometry;   // the geometry level alone picks the instance
+  note_variant(h->variant_features, var, i);   // (pt_get_trace_variant)
   if (i >= ptvariant::kFeatureTexFirst)   // pt_set_mesh_texture: albedo = colour x texel
     hipLaunchKernelGGL(ptd::features_kernel_tex, dim3((px + ptd::kFeatureBlock - 1) / ptd::kFeatureBlock), dim3(ptd::kFeatureBlock), 0,
                        h->stream, P, tex_params(h), h->d_feat[0], h->d_feat[1]);

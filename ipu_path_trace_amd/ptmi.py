@@ -55,7 +55,16 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_set_env_guide_from_environment", "pt_get_env_guide_info", "pt_get_env_guide_tables", "pt_set_scene_ex",
            "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect", "pt_set_mesh_normals",
            "pt_get_mesh_normals_info", "pt_mesh_shade", "pt_set_mesh_texture", "pt_get_mesh_texture_info", "pt_mesh_texel",
-           "pt_set_mesh_build", "pt_get_mesh_build_info", "pt_mesh_tree", "pt_update_mesh_vertices", "pt_get_mesh_update_info"]
+           "pt_set_mesh_build", "pt_get_mesh_build_info", "pt_mesh_tree", "pt_update_mesh_vertices", "pt_get_mesh_update_info",
+           "pt_get_trace_variant"]
+# pt_get_trace_variant: the values of ptvariant::Camera, Bounce and Geometry (csrc/ptmi_trace_variant.h), and the three families' sizes
+TRACE_CAMERA_BUILTIN, TRACE_CAMERA_POSE, TRACE_CAMERA_LENS = 0, 1, 2
+TRACE_BOUNCE_PLAIN, TRACE_BOUNCE_ENV_GUIDE, TRACE_BOUNCE_LIGHT_GUIDE, TRACE_BOUNCE_LIGHT_GUIDE_PLAMPS = 0, 1, 2, 3
+TRACE_GEOMETRY_SPHERES, TRACE_GEOMETRY_POLY, TRACE_GEOMETRY_MESH, TRACE_GEOMETRY_SMOOTH, TRACE_GEOMETRY_TEX = 0, 1, 2, 3, 4
+TRACE_CAMERAS = ("BUILTIN", "POSE", "LENS")
+TRACE_BOUNCES = ("PLAIN", "ENV_GUIDE", "LIGHT_GUIDE", "LIGHT_GUIDE_PLAMPS")
+TRACE_GEOMETRIES = ("SPHERES", "POLY", "MESH", "SMOOTH", "TEX")
+TRACE_INSTANCES, TRACE_PATHS_INSTANCES, TRACE_FEATURE_INSTANCES = 57, 19, 5
 MESH_UPDATE_REFIT, MESH_UPDATE_REBUILD = 0, 1
 MESH_UPDATE_MODES = {"refit": MESH_UPDATE_REFIT, "rebuild": MESH_UPDATE_REBUILD}
 MESH_UPDATE_HOST_MEMORY, MESH_UPDATE_DEVICE_MEMORY = 0, 1
@@ -456,6 +465,20 @@ class MeshUpdateInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "struct_size"}
 
 
+class TraceVariantLaunch(C.Structure):
+    """pt_trace_variant_launch"""
+    _fields_ = [("camera", C.c_int32), ("bounce", C.c_int32), ("geometry", C.c_int32), ("index", C.c_int32), ("launches", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TraceVariantInfo(C.Structure):
+    """pt_trace_variant_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("trace", TraceVariantLaunch), ("paths", TraceVariantLaunch),
+                ("features", TraceVariantLaunch)]
+
+
 class MeshNormalsInfo(C.Structure):
     """pt_mesh_normals_info"""
     _fields_ = [("struct_size", C.c_uint32), ("has_normals", C.c_uint32), ("per_corner", C.c_uint32), ("n_normals", C.c_uint32),
@@ -686,6 +709,7 @@ def load_library(diag=False):
     L.pt_get_mesh_build_info.argtypes = [C.c_void_p, C.POINTER(MeshBuildInfo)]
     L.pt_update_mesh_vertices.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshUpdate)]
     L.pt_get_mesh_update_info.argtypes = [C.c_void_p, C.POINTER(MeshUpdateInfo)]
+    L.pt_get_trace_variant.argtypes = [C.c_void_p, C.POINTER(TraceVariantInfo)]
     L.pt_mesh_tree.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     L.pt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.pt_get_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
@@ -995,6 +1019,15 @@ class Renderer:
         buf = C.create_string_buffer(512)
         self._check(self._lib.pt_nif_kernel_name(self.handle, buf, len(buf)))
         return buf.value.decode()
+
+    def trace_variant(self):
+        """pt_get_trace_variant: which instance of the trace kernels the last launch of each family took, as a dict of three
+        dicts -- "trace" (path_trace), "paths" (trace_paths), "features" (feature_buffers / denoise) -- each of camera, bounce,
+        geometry (TRACE_CAMERA_*, TRACE_BOUNCE_*, TRACE_GEOMETRY_*), index (the dense number in the family: of 57, 19 and 5) and
+        launches.  Before a family's first launch its four coordinates are -1 and its count 0."""
+        info = TraceVariantInfo(struct_size=C.sizeof(TraceVariantInfo))
+        self._check(self._lib.pt_get_trace_variant(self.handle, C.byref(info)))
+        return {"trace": info.trace.as_dict(), "paths": info.paths.as_dict(), "features": info.features.as_dict()}
 
     def calibrate_nif(self, launches=4):
         """The NIF stage of the last path_trace's largest batch again, alone on the device.
