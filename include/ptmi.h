@@ -238,13 +238,21 @@ int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
  * claim an entry's class where they claim its (u, v) pair and hand every path the BGR of its class's row.  class_ms is then 0
  * and pt_nif_sharing_stats.share_ms covers the claim of both levels, the resolve and the expand pass; with PT_NIF_SHARE_BATCH
  * and with the memo, class_ms is the level's own claim, resolve and spread passes.
+ * Such a step keeps its classes in a CLASS MAP where it can: a coordinate of [0, 1) has one of 15361 classes, so a pair of them
+ * is a number below 15361^2 and its class row is one 32-bit word of a 944 MB map -- no key, no probe; whatever else a queue may
+ * hold (a coordinate of 1 or above, NaN) goes to a small hashed tail of 2^16 slots, and a full tail means rows evaluated alone.
+ * The step claims an entry's class with that one word, counts the raw pairs in a pass of its own that nothing waits for
+ * (evaluations and overflowed keep their values), runs no resolve pass, and gives the words it took back at its end, so the
+ * map is cleared once in a handle's life.  The map is allocated by the first such step if it fits a quarter of the free device
+ * memory; otherwise the step uses the hashed class table as before, and that is no error.  table_slots then reports the map's
+ * words plus the tail's slots.
  * The caller sets struct_size = sizeof(pt_nif_class_stats). */
 typedef struct pt_nif_class_stats {
   uint32_t struct_size;          /* sizeof(pt_nif_class_stats), set by the caller */
   int32_t ran;                   /* the last path_trace ran the class level */
   uint64_t mlp_rows;             /* rows the NIF kernels executed in the last path_trace (= evaluations if the level did not run) */
   uint64_t alone;                /* rows evaluated alone because no slot of the class table was free */
-  uint64_t table_slots;          /* class table capacity in use (0 if the level did not run) */
+  uint64_t table_slots;          /* class table capacity in use (0 if the level did not run); with the class map: its 15361^2 words + the tail's slots */
   double class_ms;               /* device time of the level's own claim, resolve and spread passes (batch scope, the memo); 0 where the sharing passes claim the class (step scope without the memo) (HIP events, read lazily) */
 } pt_nif_class_stats;
 int pt_get_nif_class_stats(pt_handle h, pt_nif_class_stats* out);

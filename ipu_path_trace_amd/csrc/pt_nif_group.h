@@ -30,6 +30,8 @@
 //   served_bgr(s)        the BGR of a served slot, for expand
 //   count(served, fresh) the table's own counters, a claim tile's sums at a time (only a table that serves has any)
 //   key_of(u, v)         the key an entry claims: the 64 raw bits for ShareTable and MemoTable
+//   kCountsOnly          the claim pass appends and counts but writes no owner word and no value (RawCountTable)
+//   kMapped              expand follows a pending class word through the class map itself (ClassMap)
 //
 // The class level of N(b).  ClassTable is ShareTable with another key_of: ptshare::class_key, under which two entries are
 // equal when the NIF kernels compute the same output for them (ptmi_share_plan.h).  That is a property of the kernels'
@@ -42,6 +44,11 @@
 // the same pass, and what its raw slot's value and its owner word get is a CLASS-store index, or a pending class word
 // (ptmi_share_plan.h: owner_class).  Resolve takes up to two hops, the NIF kernels run over the class queue, and E(b) gathers
 // from the class store: no class pass of its own on the NIF stream, no spread, and no BGR in the step store.
+//
+// The mapped step (the fused step wherever the class map is held or fits; ptmi_share_plan.h).  ClassMap indexes the class of a
+// regular (u, v) directly: S(b) is C(b), class_map_claim, which touches no raw table; the raw pairs are claimed and counted by
+// R(b), group_claim over RawCountTable, behind A(b) on the accumulate stream, for the statistics alone; E(b) follows a pending class
+// word itself, so no resolve pass runs; class_map_release_kernel gives the step's words back at its end.
 #pragma once
 
 #include "ptmi_share_plan.h"
@@ -112,6 +119,8 @@ struct ShareTable {
   uint32_t slot_mask;
   static constexpr bool kServes = false;
   static constexpr bool kClasses = false;
+  static constexpr bool kCountsOnly = false;
+  static constexpr bool kMapped = false;
   static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return raw_key(u, v); }
   __device__ __forceinline__ unsigned long long* key(uint32_t s) const { return keys + s; }
   __device__ __forceinline__ void append(uint32_t, bool, uint32_t) const {}
@@ -136,6 +145,28 @@ struct ShareClassTable : ShareTable {
   static constexpr bool kClasses = true;
 };
 
+// R(b) of a mapped step: the raw table as the raw-pair pass sees it.  The pass claims keys, appends to the batch's distinct queue
+// and counts overflows exactly as ShareTable's claim does -- evaluations, overflowed and what pt_calibrate_nif replays keep their
+// values -- and writes neither owner[q] nor a slot's value: nothing in the step reads what it produces.
+struct RawCountTable : ShareTable {
+  static constexpr bool kCountsOnly = true;
+};
+
+// The class map of a mapped step (ptmi_share_plan.h): words[0 .. kClassMapWords) one word per regular class, behind them the
+// values of the hashed tail, whose keys are tail_keys[0 .. tail_mask]; the batch's class queue as in ShareClassTable.  As a table
+// of group_expand: an owner word that is not a row is a pending class word, and the word it names is a row by then.
+struct ClassMap {
+  uint32_t* words;
+  unsigned long long* tail_keys;
+  uint32_t tail_mask;
+  float* c_u; float* c_v;
+  uint32_t* c_count;
+  uint32_t c_base;
+  unsigned long long* c_alone;
+  static constexpr bool kServes = false;
+  static constexpr bool kMapped = true;
+};
+
 // slot_mask + 1 slots of pt_nif_memo.h
 struct MemoTable {
   MemoSlot* slots;
@@ -145,6 +176,8 @@ struct MemoTable {
   unsigned long long* counters;   // kMemoCounters
   static constexpr bool kServes = true;
   static constexpr bool kClasses = false;
+  static constexpr bool kCountsOnly = false;
+  static constexpr bool kMapped = false;
   static __device__ __forceinline__ unsigned long long key_of(float u, float v) { return raw_key(u, v); }
   __device__ __forceinline__ unsigned long long* key(uint32_t s) const { return &slots[s].key; }
   // valid only if published by an earlier step (publish runs after every lookup of its step): a claim of this step whose
@@ -348,9 +381,12 @@ __device__ __forceinline__ void group_claim(const GroupQueue& Q, const Table& T)
       Q.d_u[i] = u[k]; Q.d_v[i] = v[k];
       uint32_t g = Q.base + i;
       if constexpr (Table::kClasses) g = c_slot[k];   // what the slot and the owner word name is the class row, not the raw one
-      T.append(g, (fresh & bit) != 0, slot[k]);
-      if (fresh & bit) T.claim(slot[k], g);
-      Q.owner[q] = g;
+      if constexpr (!Table::kCountsOnly) {
+        T.append(g, (fresh & bit) != 0, slot[k]);
+        if (fresh & bit) T.claim(slot[k], g);
+        Q.owner[q] = g;
+      }
+    } else if constexpr (Table::kCountsOnly) {   // (the raw-pair pass: no owner word)
     } else if (served & bit) {
       T.stamp(slot[k]);
       Q.owner[q] = ptshare::owner_served(slot[k]);
@@ -391,7 +427,10 @@ __device__ __forceinline__ void group_expand(const GroupExpand& E, const Table& 
   const uint32_t r = blockIdx.y, local = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x;
   if (local >= E.region_count[r]) return;
   const uint32_t q = r * E.region_cap + local;
-  const uint32_t o = E.owner[q];
+  uint32_t o = E.owner[q];
+  if constexpr (Table::kMapped) {   // a pending class word: its class's word holds the row since the C(b) that claimed it, which N(b) is behind
+    if (!ptshare::owner_is_store(o)) o = T.words[ptshare::owner_slot(o)];
+  }
   const float* bgr = E.bgr + 3 * (size_t)o;
   if constexpr (Table::kServes) {
     if (!ptshare::owner_is_store(o)) bgr = T.served_bgr(ptshare::owner_slot(o));
@@ -417,6 +456,119 @@ __global__ __launch_bounds__(kShareBlock) void memo_expand_kernel(GroupExpand E,
 __global__ __launch_bounds__(kShareBlock) __attribute__((amdgpu_waves_per_eu(6))) void share_class_claim_kernel(GroupQueue Q, ShareClassTable T) { group_claim(Q, T); }
 __global__ __launch_bounds__(kShareBlock) void share_class_resolve_kernel(GroupQueue Q, ShareClassTable T) { group_resolve(Q, T); }
 __global__ __launch_bounds__(kShareBlock) void share_class_expand_kernel(GroupExpand E, ShareClassTable T) { group_expand(E, T); }
+
+// ---- the mapped step (ptmi_share_plan.h: the class map).  C(b): one lane per queue entry, in the claim pass's tiles.  An entry
+// computes its class slot and looks at the word: a row goes straight into owner[q]; kMapEmpty is taken with a 32-bit CAS to
+// kMapClaimed, and the winner appends its (u, v) to the batch's class queue (one reservation per tile) and stores the row into
+// the word and into owner[q]; whoever sees kMapClaimed writes a pending class word, which E(b) follows.  An irregular entry finds
+// its slot through the tail's keys first, by the tables' probe rule; one that finds none, or whose key is the empty marker, is a
+// row of its own, counted in *c_alone.  No raw table is touched.
+__device__ __forceinline__ void class_map_claim(const GroupQueue& Q, const ClassMap& M) {
+  constexpr uint32_t K = ptshare::kClaimK, W = ptshare::kClaimWaves;
+  __shared__ uint32_t s_appends[W], s_alone[W];
+  __shared__ uint32_t s_first;
+  const uint32_t r = blockIdx.y, tile = blockIdx.x;
+  const uint32_t count = Q.region_count[r];
+  if (ptshare::claim_tile_idle(tile, count)) return;   // uniform over the workgroup
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const size_t q0 = (size_t)r * Q.region_cap;
+  uint32_t valid = 0, fresh = 0, alone = 0;
+  float u[K], v[K];
+  uint32_t slot[K], word[K];
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {   // (no branch around the loads, as in group_claim)
+    const uint32_t local = ptshare::claim_entry(tile, threadIdx.x, k);
+    const uint32_t at = local < count ? local : count - 1u;
+    u[k] = Q.q_u[q0 + at]; v[k] = Q.q_v[q0 + at];
+    valid |= (local < count ? 1u : 0u) << k;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {   // the words of the regular entries, all in flight together
+    slot[k] = ptshare::class_map_index(u[k], v[k]);
+    word[k] = ptshare::kMapEmpty;
+    if (slot[k] != ptshare::kClassIrregular) word[k] = __hip_atomic_load(M.words + slot[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    if (!((valid >> k) & 1u)) continue;
+    if (slot[k] == ptshare::kClassIrregular) {   // the tail: the key's slot first, then its word as for a regular entry
+      const unsigned long long key = ptshare::class_key(u[k], v[k]);
+      bool none = true;
+      if (key != kShareEmpty) {
+        uint32_t s = share_hash(key) & M.tail_mask;
+#pragma unroll 1
+        for (uint32_t p = 0;;) {
+          unsigned long long c = __hip_atomic_load(M.tail_keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (c == kShareEmpty) c = atomicCAS(M.tail_keys + s, kShareEmpty, key);
+          if (c == kShareEmpty || c == key) { none = false; break; }
+          if (++p == kShareMaxProbes) break;
+          s = (s + 1u) & M.tail_mask;
+        }
+        if (!none) {
+          slot[k] = ptshare::kClassMapWords + s;
+          word[k] = __hip_atomic_load(M.words + slot[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+      if (none) { alone |= 1u << k; continue; }
+    }
+    if (word[k] == ptshare::kMapEmpty) {
+      word[k] = atomicCAS(M.words + slot[k], ptshare::kMapEmpty, ptshare::kMapClaimed);
+      if (word[k] == ptshare::kMapEmpty) fresh |= 1u << k;
+    }
+  }
+  const uint32_t append = fresh | alone;
+  uint32_t n_append = 0, n_alone = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    n_append += (uint32_t)__popcll(__ballot((append >> k) & 1u));
+    n_alone += (uint32_t)__popcll(__ballot((alone >> k) & 1u));
+  }
+  if (lane == 0) { s_appends[wave] = n_append; s_alone[wave] = n_alone; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t total = ptshare::claim_wave_offset(s_appends, W);
+    s_first = total ? atomicAdd(M.c_count, total) : 0u;
+    const uint32_t over = ptshare::claim_wave_offset(s_alone, W);
+    if (over) atomicAdd(M.c_alone, (unsigned long long)over);
+  }
+  __syncthreads();
+  uint32_t next = s_first + ptshare::claim_wave_offset(s_appends, wave);
+#pragma unroll
+  for (uint32_t k = 0; k < K; ++k) {
+    const uint32_t bit = 1u << k;
+    const size_t q = q0 + ptshare::claim_entry(tile, threadIdx.x, k);
+    const uint64_t m = __ballot((append & bit) != 0);
+    if (append & bit) {
+      const uint32_t i = next + lane_rank(m);
+      M.c_u[i] = u[k]; M.c_v[i] = v[k];
+      const uint32_t g = M.c_base + i;
+      if (fresh & bit) __hip_atomic_store(M.words + slot[k], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      Q.owner[q] = g;
+    } else if (valid & bit) {
+      Q.owner[q] = ptshare::owner_is_store(word[k]) ? word[k] : ptshare::owner_class(slot[k]);
+    }
+    next += (uint32_t)__popcll(m);
+  }
+}
+
+__global__ __launch_bounds__(kShareBlock) void class_map_claim_kernel(GroupQueue Q, ClassMap M) { class_map_claim(Q, M); }
+__global__ __launch_bounds__(kShareBlock) void class_map_expand_kernel(GroupExpand E, ClassMap M) { group_expand(E, M); }
+// R(b): the raw-pair pass (RawCountTable)
+__global__ __launch_bounds__(kShareBlock) void share_raw_claim_kernel(GroupQueue Q, RawCountTable T) { group_claim(Q, T); }
+
+// The release at the end of a mapped step: the word of every regular row of the step's class store goes back to kMapEmpty, so
+// that the map is never cleared as a whole (about 6.6 M stores at 1104 x 1000 x 300 spp against a memset of 944 MB).  Rows of
+// irregular classes live in the tail, which the host clears.  Grid (x, batches): batch y's class queue is c_u / c_v + y * region
+// with c_count[y] rows; grid-stride over them.
+__global__ __launch_bounds__(kShareBlock) void class_map_release_kernel(const float* c_u, const float* c_v, const uint32_t* c_count,
+                                                                        uint32_t region, uint32_t* words) {
+  const uint32_t n = c_count[blockIdx.y];
+  const size_t base = (size_t)blockIdx.y * region;
+  for (uint32_t i = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x; i < n; i += gridDim.x * (uint32_t)kShareBlock) {
+    const uint32_t slot = ptshare::class_map_index(c_u[base + i], c_v[base + i]);
+    if (slot != ptshare::kClassIrregular) words[slot] = ptshare::kMapEmpty;
+  }
+}
 
 // The class level: claim and resolve over a batch's distinct queue (one region; Q.owner: [position in the distinct queue], the
 // class-store index of the entry's class owner; Q.d_u / d_v: the batch's class queue), and the spread behind the NIF launch.

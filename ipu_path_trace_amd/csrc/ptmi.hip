@@ -157,6 +157,7 @@ int pt_create(const pt_config* cfg, pt_handle* out) {
     for (DevBuf<float>* rad : {&B.rad_r, &B.rad_g, &B.rad_b}) PT_HIPC(dev_alloc(*rad, h->batch_paths_cap));
     PT_HIPC(hipEventCreateWithFlags(&B.traced, hipEventDisableTiming));
     PT_HIPC(hipEventCreateWithFlags(&B.accumulated, hipEventDisableTiming));
+    PT_HIPC(hipEventCreateWithFlags(&B.raw_read, hipEventDisableTiming));
   }
   PT_HIPC(hipEventCreateWithFlags(&h->chunk_fork, hipEventDisableTiming));
   for (int i = 0; i + 1 < pt_context::kChunkSets; ++i) {
@@ -197,6 +198,7 @@ int pt_destroy(pt_handle h) {
   for (auto& B : h->bb) {
     if (B.traced) (void)hipEventDestroy(B.traced);
     if (B.accumulated) (void)hipEventDestroy(B.accumulated);
+    if (B.raw_read) (void)hipEventDestroy(B.raw_read);
   }
   for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->chunk_join)
@@ -493,7 +495,9 @@ static void forget_replay_state(pt_handle h) {   // pt_calibrate_nif may only re
 // every pixel's fp32 sum in iteration order.  With NIF sharing or the memo (ptmi_nif_group.h), S(b) runs behind T(b) and E(b) ahead of A(b),
 // and N(b) itself is class claim + resolve, the NIF launch over the batch's class queue, and the spread, all on `stream` -- with
 // the memo or at batch scope.  A step-scope step without the memo is fused (StepMode::fused): S(b) claims the class too, N(b) is the resolve and the NIF launch
-// over the class queue, and E(b) reads the class store.
+// over the class queue, and E(b) reads the class store.  Where the class map is held or fits, the fused step is mapped
+// (StepMode::mapped): S(b) is the class claim C(b) alone, N(b) has no resolve, the raw-pair pass R(b) follows A(b) on acc_stream
+// with the raw table's hand-off clear behind the last one, and the map's release follows that.
 
 // One batch: its sample iterations, trace grid and buffer set, and (grouped) where its distinct queue lies in the store.
 struct Batch {
@@ -591,7 +595,7 @@ static int stage_nif(pt_handle h, StepEvents& ev, const StepMode& mode, const Ba
   PT_HIP(hipEventRecord(B.traced, h->trace_stream));
   PT_HIP(hipStreamWaitEvent(h->stream, B.traced, 0));
   hipEvent_t done = nullptr;
-  if (mode.grouped() && resolve_on_nif_stream(mode))   // the resolve pass of S(b), behind its claims (B.traced)
+  if (mode.grouped() && resolve_on_nif_stream(mode) && !mode.mapped)   // the resolve pass of S(b), behind its claims (B.traced); a mapped step has none
     if (int rc = stage_resolve(h, ev, mode, b, h->stream)) return rc;
   if (mode.classes && !mode.fused())   // (fused: S(b) claimed the classes and filled the class queue)
     if (int rc = stage_class_claim(h, ev, b)) return rc;
@@ -682,18 +686,26 @@ static int enqueue_path_trace(pt_handle h) {
     b.store_cap = b.g.blocks * b.g.region_cap;
     b.class_base = mode.classes ? i * (uint32_t)h->queue_cap : 0u;
     store_cap = std::max(store_cap, b.store_cap);
+    if (mode.mapped && ptplan::ring_predecessor(i, h->ring_depth) != ptplan::kNoBatch)   // R(b - depth) has read the set's q_u / q_v
+      PT_HIP(hipStreamWaitEvent(h->trace_stream, b.B->raw_read, 0));
     if (int rc = stage_trace(h, ev, P, b)) return rc;
     if (mode.grouped())
       if (int rc = stage_group(h, ev, mode, b, e_class_cleared)) return rc;
     if (int rc = stage_nif(h, ev, mode, b)) return rc;
-    if (handoff && i + 1 == batches)   // behind the last S(b) and its B.traced: the table is not read again in this step
-      if (int rc = enqueue_table_handoff(h, ev, e_clean)) return rc;
+    if (handoff && i + 1 == batches && !mode.mapped)   // behind the last S(b) and its B.traced: the table is not read again in this step
+      if (int rc = enqueue_table_handoff(h, ev, e_clean, h->trace_stream)) return rc;
     if (mode.grouped())
       if (int rc = stage_expand(h, ev, mode, b)) return rc;
     if (int rc = stage_accumulate(h, ev, b)) return rc;
+    if (mode.mapped)
+      if (int rc = stage_raw_pairs(h, ev, b)) return rc;
+    if (handoff && i + 1 == batches && mode.mapped)    // ... of a mapped step: behind the last R(b)
+      if (int rc = enqueue_table_handoff(h, ev, e_clean, h->acc_stream)) return rc;
   }
   if (e_clean) PT_HIP(hipStreamWaitEvent(h->stream, e_clean, 0));   // the step ends with its table clean for the next one
 
+  if (mode.mapped)   // behind the last E(b), ahead of e_acc and so of the step's end
+    if (int rc = stage_map_release(h, ev, store_cap, batches)) return rc;
   if (int rc = ev.record(h->acc_stream, e_acc, e_acc_i)) return rc;
   PT_HIP(hipStreamWaitEvent(h->stream, e_acc, 0));          // later work on `stream` sees the accumulated film
   if (mode.memo)
@@ -772,6 +784,7 @@ int pt_path_trace(pt_handle h) {
   h->group.share_mode_last = 0; h->group.share_evals = 0; h->group.share_overflowed = 0; h->group.share_ms = 0;
   h->group.memo_ran = false; h->group.memo_served = 0; h->group.memo_inserted = 0; h->group.memo_ms = 0;
   h->group.class_ran = false; h->group.class_rows = 0; h->group.class_alone = 0; h->group.class_ms = 0;
+  h->group.class_map_ran = false;
   h->spans_pending = false;
   h->stats.nif_flops_per_sample = (h->env_const || h->env_map) ? 0 : h->nif_flops;
   h->stats.first_sample = h->sample_cursor;
@@ -797,6 +810,8 @@ int pt_path_trace(pt_handle h) {
   // sharing off, otherwise not known (a failed step may have stopped anywhere between its claims and its clear)
   h->group.share_clean_slots = ptshare::mark_after_step(h->group.share_clean_slots,
       StepMode{h->group.share_mode_last, h->group.memo_ran}.kind(), h->group.share_slots, !failed);
+  // ... and the class map: released by a mapped step that ran to its end, untouched by every other step
+  h->group.class_map_clean = ptshare::map_mark_after_step(h->group.class_map_clean, h->group.class_map_ran, !failed);
   if (rc) return rc;   // h->error names the failing call
   for (hipError_t e : {s0, s1, s2, s3})
     if (e != hipSuccess) return fail(h, PT_ERR_HIP, std::string("path_trace: ") + hipGetErrorString(e));

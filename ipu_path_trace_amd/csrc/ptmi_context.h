@@ -169,6 +169,7 @@ struct pt_context {
     DevBuf<float> rad_r, rad_g, rad_b;
     hipEvent_t traced = nullptr;       // trace kernel of the batch using this set has finished
     hipEvent_t accumulated = nullptr;  // accumulate kernel has consumed this set
+    hipEvent_t raw_read = nullptr;     // (mapped step) the raw-pair pass R(b) has read the set's q_u / q_v
     // geometry of the last batch whose NIF stage ran on this set (pt_calibrate_nif replays the larger one): 0 = none yet
     uint32_t last_paths = 0, last_regions = 0, last_region_cap = 0;
     // ... and, if that batch ran with sharing on, where its distinct queue lies: count index (-1 = not shared), store base
@@ -382,6 +383,15 @@ struct pt_context {
     bool class_ran = false;                    // the last pt_path_trace ran the level
     uint64_t class_rows = 0, class_alone = 0;
     double class_ms = 0;
+    // The class map of a mapped step (ptmi_share_plan.h; pt_nif_group.h: ClassMap): kClassMapWords words and the tail's values
+    // behind them, and the tail's keys.  Allocated by the first step that may take it (ptshare::class_map_fits), set to kMapEmpty
+    // once and released row by row at the end of every step that used it; class_map_clean is the mark of that (map_mark_after_step).
+    DevBuf<uint32_t> d_class_map;
+    DevBuf<unsigned long long> d_class_tail_keys;
+    uint32_t class_tail_slots = 0;             // 0 = no map held
+    bool class_map_clean = false;
+    bool class_map_failed = false;             // its allocation failed: the hashed class table from now on
+    bool class_map_ran = false;                // the last pt_path_trace was a mapped step
 
     // persistent memo of decoded NIF values (pt_set_nif_memo).  Unlike the sharing table it outlives the step:
     // it is cleared at allocation, on a new generation (pt_upload_nif, pt_clear_nif_memo, a failed pt_path_trace) and by the

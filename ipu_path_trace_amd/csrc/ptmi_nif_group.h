@@ -192,6 +192,10 @@ struct StepMode {
   // passes in N(b) as the memo does: its tables forget a pair from batch to batch, so 2.5 times as many entries append, and
   // their class lookups on the trace stream cost it more than the NIF stream saves (profiles/r29_class_in_claim.txt)
   bool fused() const { return classes && !memo && share == PT_NIF_SHARE_STEP; }
+  // a fused step that indexes its classes in the class map (prepare_class_level; pt_nif_group.h: ClassMap): S(b) is C(b), the
+  // class claim alone; the raw-pair pass R(b) runs behind A(b) on the accumulate stream, off the step's critical path; E(b) follows a
+  // pending class word itself and no resolve pass runs; the step ends with the release of the words it took
+  bool mapped = false;
   bool grouped() const { return share || memo; }   // N runs over distinct queues in the step store
   bool step_scope() const { return memo || share == PT_NIF_SHARE_STEP; }
   ptshare::StepKind kind() const {   // what the step does to the sharing table (ptmi_share_plan.h: the clean-table hand-off)
@@ -241,11 +245,28 @@ static void free_class_buffers(pt_handle h) {
   h->group.d_class_u.reset(); h->group.d_class_v.reset(); h->group.d_class_bgr.reset();
   h->group.class_regions = 0;
   h->group.d_class_owner.reset();
+  h->group.d_class_map.reset(); h->group.d_class_tail_keys.reset();
+  h->group.class_tail_slots = 0;
+  h->group.class_map_clean = false;
 }
 
+// The class map and its tail (ptmi_share_plan.h), the stream drained first.  New memory: nothing is known of it.
+static int alloc_class_map(pt_handle h, uint32_t tail_slots) {
+  PT_HIP(hipStreamSynchronize(h->stream));
+  h->group.d_class_map.reset(); h->group.d_class_tail_keys.reset();
+  h->group.class_tail_slots = 0;
+  h->group.class_map_clean = false;
+  PT_HIP(dev_alloc(h->group.d_class_map, (size_t)ptshare::kClassMapWords + tail_slots));
+  PT_HIP(dev_alloc(h->group.d_class_tail_keys, tail_slots));
+  h->group.class_tail_slots = tail_slots;
+  return PT_OK;
+}
+
+// (slots = 0: a mapped step, which needs no hashed table -- one it holds stays)
 static int alloc_class_buffers(pt_handle h, uint32_t slots, size_t batches) {
   PT_HIP(hipStreamSynchronize(h->stream));
-  if (!h->group.d_class_keys || (h->group.class_diag_slots ? slots != h->group.class_slots : slots > h->group.class_slots)) {
+  if (!slots) {
+  } else if (!h->group.d_class_keys || (h->group.class_diag_slots ? slots != h->group.class_slots : slots > h->group.class_slots)) {
     h->group.d_class_keys.reset(); h->group.d_class_vals.reset();
     h->group.class_slots = 0;
     PT_HIP(dev_alloc(h->group.d_class_keys, slots));
@@ -286,11 +307,17 @@ static int prepare_class_level(pt_handle h, StepEvents& ev, size_t batches, Step
   classes = false;
   if (h->env_map || h->group.class_failed) return PT_OK;
   const uint64_t free_b = free_device_bytes();
-  const uint32_t slots = h->group.class_diag_slots ? h->group.class_diag_slots : ptshare::class_slots(batches * (uint64_t)h->queue_cap, free_b);
   ptshare::ClassHeld held;
-  held.table_slots = h->group.d_class_keys ? (h->group.class_diag_slots ? (h->group.class_slots == slots ? slots : 0) : h->group.class_slots) : 0;
   held.store_regions = h->group.class_regions;
   held.owner_maps = h->group.d_class_owner ? 1 : 0;
+  // the class map: a step-scope step without the memo and without a capacity the test build forced on either table, if the map is
+  // held or fits together with the class store the step is about to take; such a step needs no hashed class table
+  const bool mapped = mode.share == PT_NIF_SHARE_STEP && !mode.memo && !h->group.class_diag_slots && !h->group.share_diag_slots &&
+                      !h->group.class_map_failed &&
+                      ptshare::class_map_fits(h->group.class_tail_slots != 0, ptshare::kClassTailSlots, free_b,
+                                              ptshare::class_bytes(0, batches, h->queue_cap, held));
+  const uint32_t slots = mapped ? 0u : h->group.class_diag_slots ? h->group.class_diag_slots : ptshare::class_slots(batches * (uint64_t)h->queue_cap, free_b);
+  held.table_slots = h->group.d_class_keys ? (h->group.class_diag_slots ? (h->group.class_slots == slots ? slots : 0) : h->group.class_slots) : 0;
   if (!ptshare::class_fits(slots, batches, h->queue_cap, held, free_b)) return PT_OK;
   if (alloc_class_buffers(h, slots, batches) != PT_OK) {   // give back what was taken and run without the level from now on
     (void)hipGetLastError();
@@ -299,7 +326,22 @@ static int prepare_class_level(pt_handle h, StepEvents& ev, size_t batches, Step
     h->error.clear();
     return PT_OK;
   }
-  PT_HIP(hipMemsetAsync(h->group.d_class_keys, 0xff, (size_t)h->group.class_slots * 8, h->stream));
+  if (mapped && !h->group.class_tail_slots && alloc_class_map(h, ptshare::kClassTailSlots) != PT_OK) {   // the hashed table from now on
+    (void)hipGetLastError();
+    h->group.d_class_map.reset(); h->group.d_class_tail_keys.reset();
+    h->group.class_map_failed = true;
+    h->error.clear();
+    return prepare_class_level(h, ev, batches, mode, cleared);
+  }
+  if (mapped) {
+    if (!ptshare::map_clear_skippable(h->group.class_map_clean)) {   // the first step on this map, or the one behind a failed step
+      PT_HIP(hipMemsetAsync(h->group.d_class_map, 0xff, ((size_t)ptshare::kClassMapWords + h->group.class_tail_slots) * 4, h->stream));
+      PT_HIP(hipMemsetAsync(h->group.d_class_tail_keys, 0xff, (size_t)h->group.class_tail_slots * 8, h->stream));
+    }
+    mode.mapped = h->group.class_map_ran = true;
+  } else {
+    PT_HIP(hipMemsetAsync(h->group.d_class_keys, 0xff, (size_t)h->group.class_slots * 8, h->stream));
+  }
   PT_HIP(hipMemsetAsync(h->group.d_class_count, 0, batches * 4, h->stream));
   PT_HIP(hipMemsetAsync(h->group.d_class_over, 0, 8, h->stream));
   classes = true;
@@ -346,10 +388,11 @@ static int stage_class_spread(pt_handle h, StepEvents& ev, const Batch& b, hipEv
 // Behind the last S(b) of a step-scope step, which is the table's last reader: the clear for the NEXT step, on the trace
 // stream, where it runs beside the last NIF launches instead of ahead of the next step's T(0).  `clean` is recorded behind
 // it; the step's end waits for it, and pt_path_trace sets the mark (ptshare::mark_after_step) once the step has returned.
-static int enqueue_table_handoff(pt_handle h, StepEvents& ev, hipEvent_t& clean) {
-  PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
+// A mapped step's last reader of the table is R(b) of its last batch, on the accumulate stream: the clear follows it there.
+static int enqueue_table_handoff(pt_handle h, StepEvents& ev, hipEvent_t& clean, hipStream_t s) {
+  PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, s));
   size_t at = 0;
-  return ev.record(h->trace_stream, clean, at);
+  return ev.record(s, clean, at);
 }
 
 static ptd::ShareTable share_table(pt_handle h) { return {h->group.d_share_keys, h->group.d_share_vals, h->group.share_slots - 1u}; }
@@ -363,6 +406,18 @@ static ptd::ShareClassTable share_class_table(pt_handle h, const Batch& b) {
   T.c_base = b.class_base;
   T.c_alone = h->group.d_class_over;
   return T;
+}
+// the mapped step's class map for batch b: the map, the tail and the batch's class queue (class region b)
+static ptd::ClassMap class_map(pt_handle h, const Batch& b) {
+  ptd::ClassMap M;
+  M.words = h->group.d_class_map;
+  M.tail_keys = h->group.d_class_tail_keys;
+  M.tail_mask = h->group.class_tail_slots - 1u;
+  M.c_u = h->group.d_class_u + b.class_base; M.c_v = h->group.d_class_v + b.class_base;
+  M.c_count = h->group.d_class_count + b.index;
+  M.c_base = b.class_base;
+  M.c_alone = h->group.d_class_over;
+  return M;
 }
 static ptd::MemoTable memo_table(pt_handle h) {
   return {h->group.d_memo, h->group.memo_slots - 1u, h->group.memo_step, h->group.d_memo_slot, h->group.d_memo_ctr};
@@ -417,7 +472,8 @@ static int stage_group(pt_handle h, StepEvents& ev, const StepMode& mode, const 
         } else {
           if (mode.share == PT_NIF_SHARE_BATCH)   // one table per batch
             PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, h->trace_stream));
-          if (mode.fused()) hipLaunchKernelGGL(ptd::share_class_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_class_table(h, b));
+          if (mode.mapped) hipLaunchKernelGGL(ptd::class_map_claim_kernel, tiles, block, 0, h->trace_stream, Q, class_map(h, b));   // C(b)
+          else if (mode.fused()) hipLaunchKernelGGL(ptd::share_class_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_class_table(h, b));
           else hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, h->trace_stream, Q, share_table(h));
         }
         PT_HIP(hipGetLastError());
@@ -439,9 +495,41 @@ static int stage_expand(pt_handle h, StepEvents& ev, const StepMode& mode, const
     X.q_tr = B.q_tr; X.q_tg = B.q_tg; X.q_tb = B.q_tb; X.q_path = B.q_path;
     X.rad_r = B.rad_r; X.rad_g = B.rad_g; X.rad_b = B.rad_b;
     if (mode.memo) hipLaunchKernelGGL(ptd::memo_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, memo_table(h));
+    else if (mode.mapped) hipLaunchKernelGGL(ptd::class_map_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, class_map(h, b));
     else if (mode.fused()) hipLaunchKernelGGL(ptd::share_class_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, share_class_table(h, b));
     else hipLaunchKernelGGL(ptd::share_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, share_table(h));
     PT_HIP(hipGetLastError());
+    return PT_OK;
+  });
+}
+
+// R(b) of a mapped step, behind A(b) on the accumulate stream: the raw pairs of the batch's queue, claimed and counted in the raw
+// table (pt_nif_group.h: RawCountTable).  Nothing in the step reads what it leaves -- the distinct queue and the counts are for
+// the statistics and pt_calibrate_nif -- so the trace stream does not carry it; but it reads the set's q_u / q_v, which
+// T(b + depth) rewrites: the set's raw_read is recorded behind it, and T(b + depth) waits for that as for B.accumulated (which
+// A(b) has recorded ahead of it: R(b) holds back no one who waits for the accumulated film alone).  Behind N(b) on the NIF stream
+// the pass made that stream the busiest of the three (97.9 % of a step) and a step 3.7 % longer (profiles/r32_class_map.txt).
+static int stage_raw_pairs(pt_handle h, StepEvents& ev, const Batch& b) {
+  if (int rc = ev.timed(h->acc_stream, pt_context::kSpanShare, [&]() -> int {
+        hipLaunchKernelGGL(ptd::share_raw_claim_kernel, b.claim_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, group_queue(h, b),
+                           ptd::RawCountTable{share_table(h)});
+        PT_HIP(hipGetLastError());
+        return PT_OK;
+      })) return rc;
+  PT_HIP(hipEventRecord(b.B->raw_read, h->acc_stream));
+  return PT_OK;
+}
+
+// The end of a mapped step, on the accumulate stream behind the last E(b): the words of the step's class rows go back to
+// kMapEmpty (counts on the device), and the tail is cleared.  pt_path_trace sets the mark once the step has returned.
+static int stage_map_release(pt_handle h, StepEvents& ev, uint32_t store_cap, uint32_t batches) {
+  return ev.timed(h->acc_stream, pt_context::kSpanShare, [&]() -> int {
+    const dim3 grid(std::min<uint32_t>(ptd::kMemoGrid, (store_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock), batches);
+    hipLaunchKernelGGL(ptd::class_map_release_kernel, grid, dim3(ptd::kShareBlock), 0, h->acc_stream, h->group.d_class_u, h->group.d_class_v,
+                       h->group.d_class_count, (uint32_t)h->queue_cap, h->group.d_class_map);
+    PT_HIP(hipGetLastError());
+    PT_HIP(hipMemsetAsync(h->group.d_class_map + ptshare::kClassMapWords, 0xff, (size_t)h->group.class_tail_slots * 4, h->acc_stream));
+    PT_HIP(hipMemsetAsync(h->group.d_class_tail_keys, 0xff, (size_t)h->group.class_tail_slots * 8, h->acc_stream));
     return PT_OK;
   });
 }
@@ -493,7 +581,7 @@ int pt_get_nif_class_stats(pt_handle h, pt_nif_class_stats* out) {
   out->ran = h->group.class_ran;
   out->mlp_rows = h->group.class_ran ? h->group.class_rows : h->group.share_evals;
   out->alone = h->group.class_ran ? h->group.class_alone : 0;
-  out->table_slots = h->group.class_ran ? h->group.class_slots : 0;
+  out->table_slots = !h->group.class_ran ? 0 : h->group.class_map_ran ? ptshare::kClassMapWords + h->group.class_tail_slots : h->group.class_slots;
   out->class_ms = h->group.class_ms;
   return PT_OK;
 }
@@ -568,7 +656,8 @@ int pt_diag_set_nif_memo_slots(pt_handle h, uint32_t slots) {
 // test build only: the claim and resolve passes over a queue the caller supplies, with buffers of its own (the handle gives
 // the device and the stream; nothing of its sharing state is touched).  u, v: [n_regions x region_cap] as the trace kernel
 // lays its queue out; region_count[r] <= region_cap entries of region r are live.  memo = 0: a ShareTable of table_slots
-// slots (a power of two).  memo = 1: a MemoTable, `passes` times (1 or 2) over the same queue with a publish of zeros between
+// slots (a power of two).  memo = 2: the same table through the raw-pair pass of a mapped step (RawCountTable), which leaves the
+// owner map as it was filled, 0xff in every byte, and runs no resolve.  memo = 1: a MemoTable, `passes` times (1 or 2) over the same queue with a publish of zeros between
 // them, as two steps would run; the outputs are the last pass's.  Out, on the host: owner [n_regions x region_cap] (live
 // entries), the distinct queue d_u / d_v (same capacity; store index = position), its length, the overflow count, the memo's
 // four counters (memo = 1; may be null) and the table's keys [table_slots] (may be null).
@@ -578,7 +667,7 @@ int pt_diag_claim_resolve(pt_handle h, int32_t memo, uint32_t passes, const floa
   if (!h || !u || !v || !region_count || !owner || !d_u || !d_v || !d_count || !overflowed) return PT_ERR_INVALID_ARGUMENT;
   const uint64_t n64 = (uint64_t)n_regions * region_cap;
   if (n_regions == 0 || region_cap == 0 || n64 >= ptshare::kMaxStoreEntries || table_slots < 2 || table_slots > ptshare::kMaxSlots ||
-      (table_slots & (table_slots - 1u)) || passes < 1 || passes > (memo ? 2u : 1u))
+      (table_slots & (table_slots - 1u)) || passes < 1 || passes > (memo == 1 ? 2u : 1u) || memo < 0 || memo > 2)
     return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_claim_resolve: sizes out of range");
   for (uint32_t r = 0; r < n_regions; ++r)
     if (region_count[r] > region_cap) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_claim_resolve: a region's count exceeds its capacity");
@@ -601,7 +690,7 @@ int pt_diag_claim_resolve(pt_handle h, int32_t memo, uint32_t passes, const floa
   Q.d_u = du; Q.d_v = dv; Q.d_count = len; Q.base = 0; Q.overflowed = over;
   const dim3 grid((region_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock, n_regions), tiles(ptshare::claim_tiles(region_cap), n_regions);
   const dim3 block(ptd::kShareBlock);
-  if (memo) {
+  if (memo == 1) {
     PT_HIP(dev_alloc(slots, table_slots)); PT_HIP(dev_alloc(d_slot, n)); PT_HIP(dev_alloc(ctr, ptd::kMemoCounters)); PT_HIP(dev_alloc(bgr, 3 * n));
     PT_HIP(hipMemsetAsync(slots, 0xff, (size_t)table_slots * sizeof(ptd::MemoSlot), s));
     PT_HIP(hipMemsetAsync(ctr, 0, ptd::kMemoCounters * 8, s));
@@ -626,19 +715,24 @@ int pt_diag_claim_resolve(pt_handle h, int32_t memo, uint32_t passes, const floa
     PT_HIP(hipMemsetAsync(keys, 0xff, (size_t)table_slots * 8, s));
     PT_HIP(hipMemsetAsync(len, 0, 4, s));
     const ptd::ShareTable T{keys, vals, table_slots - 1u};
-    hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, s, Q, T);
-    PT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ptd::share_resolve_kernel, grid, block, 0, s, Q, T);
-    PT_HIP(hipGetLastError());
+    if (memo == 2) {
+      hipLaunchKernelGGL(ptd::share_raw_claim_kernel, tiles, block, 0, s, Q, ptd::RawCountTable{T});
+      PT_HIP(hipGetLastError());
+    } else {
+      hipLaunchKernelGGL(ptd::share_claim_kernel, tiles, block, 0, s, Q, T);
+      PT_HIP(hipGetLastError());
+      hipLaunchKernelGGL(ptd::share_resolve_kernel, grid, block, 0, s, Q, T);
+      PT_HIP(hipGetLastError());
+    }
   }
   PT_HIP(hipMemcpyAsync(owner, own, n * 4, hipMemcpyDeviceToHost, s));
   PT_HIP(hipMemcpyAsync(d_u, du, n * 4, hipMemcpyDeviceToHost, s));
   PT_HIP(hipMemcpyAsync(d_v, dv, n * 4, hipMemcpyDeviceToHost, s));
   PT_HIP(hipMemcpyAsync(d_count, len, 4, hipMemcpyDeviceToHost, s));
   PT_HIP(hipMemcpyAsync(overflowed, over, 8, hipMemcpyDeviceToHost, s));
-  if (memo && memo_counters) PT_HIP(hipMemcpyAsync(memo_counters, ctr, ptd::kMemoCounters * 8, hipMemcpyDeviceToHost, s));
+  if (memo == 1 && memo_counters) PT_HIP(hipMemcpyAsync(memo_counters, ctr, ptd::kMemoCounters * 8, hipMemcpyDeviceToHost, s));
   if (table_keys) {
-    if (memo) PT_HIP(hipMemcpy2DAsync(table_keys, 8, slots, sizeof(ptd::MemoSlot), 8, table_slots, hipMemcpyDeviceToHost, s));
+    if (memo == 1) PT_HIP(hipMemcpy2DAsync(table_keys, 8, slots, sizeof(ptd::MemoSlot), 8, table_slots, hipMemcpyDeviceToHost, s));
     else PT_HIP(hipMemcpyAsync(table_keys, keys, (size_t)table_slots * 8, hipMemcpyDeviceToHost, s));
   }
   PT_HIP(hipStreamSynchronize(s));
@@ -755,6 +849,102 @@ int pt_diag_share_class_claim(pt_handle h, const float* u, const float* v, const
   PT_HIP(hipMemcpyAsync(h_over, over, 16, hipMemcpyDeviceToHost, s));
   PT_HIP(hipStreamSynchronize(s));
   counters[0] = h_len[0]; counters[1] = h_over[0]; counters[2] = h_len[1]; counters[3] = h_over[1];
+  return PT_OK;
+}
+
+// test build only: C(b) of a mapped step over a queue the caller supplies (laid out as for pt_diag_claim_resolve), with a class
+// map and a tail of tail_slots slots (a power of two) of its own, `launches` times (1 or 2) over the same queue and the same
+// class queue.  release_between: a release (and the counts reset) between the two launches, as two steps would run; otherwise
+// the second launch finds what the first left, as a later batch of one step would.  A release follows the last launch.
+// Out, on the host, of the last launch: owner [n_regions x region_cap] (live entries: the words C wrote), rows (the same after
+// E(b)'s hop: positions in the class queue), the class queue c_u / c_v (same capacity, twice over: rows evaluated alone append
+// per launch) and counters[4]: the class queue's length, the rows evaluated alone, the words of map and tail that are not
+// kMapEmpty before the last release, and after it.
+}  // extern "C"
+namespace ptd {
+__global__ __launch_bounds__(kShareBlock) void diag_map_hop_kernel(const uint32_t* region_count, uint32_t region_cap, const uint32_t* owner,
+                                                                   const uint32_t* words, uint32_t* rows) {
+  const uint32_t r = blockIdx.y, local = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x;
+  if (local >= region_count[r]) return;
+  const size_t q = (size_t)r * region_cap + local;
+  const uint32_t o = owner[q];
+  rows[q] = ptshare::owner_is_store(o) ? o : words[ptshare::owner_slot(o)];
+}
+__global__ __launch_bounds__(kShareBlock) void diag_map_count_kernel(const uint32_t* words, uint32_t n, unsigned long long* taken) {
+  uint32_t mine = 0;
+  for (uint32_t i = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x; i < n; i += gridDim.x * (uint32_t)kShareBlock)
+    mine += words[i] != ptshare::kMapEmpty ? 1u : 0u;
+  if (mine) atomicAdd(taken, (unsigned long long)mine);   // (few words are taken: few atomics)
+}
+}  // namespace ptd
+extern "C" {
+int pt_diag_class_map_claim(pt_handle h, const float* u, const float* v, const uint32_t* region_count, uint32_t n_regions,
+                            uint32_t region_cap, uint32_t tail_slots, uint32_t launches, int32_t release_between, uint32_t* owner,
+                            uint32_t* rows, float* c_u, float* c_v, uint64_t* counters) {
+  if (!h || !u || !v || !region_count || !owner || !rows || !c_u || !c_v || !counters) return PT_ERR_INVALID_ARGUMENT;
+  const uint64_t n64 = (uint64_t)n_regions * region_cap;
+  if (n_regions == 0 || region_cap == 0 || 2 * n64 >= ptshare::kMaxStoreEntries || tail_slots < 2 || tail_slots > ptshare::kClassTailMaxSlots ||
+      (tail_slots & (tail_slots - 1u)) || launches < 1 || launches > 2)
+    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_class_map_claim: sizes out of range");
+  for (uint32_t r = 0; r < n_regions; ++r)
+    if (region_count[r] > region_cap) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_diag_class_map_claim: a region's count exceeds its capacity");
+  const size_t n = (size_t)n64, n_words = (size_t)ptshare::kClassMapWords + tail_slots;
+  PT_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t s = h->stream;
+  DevBuf<float> q_u, q_v, cu, cv;
+  DevBuf<uint32_t> counts, own, row, len, words;
+  DevBuf<unsigned long long> over, tail_keys;   // over: [0] rows alone, [1] and [2] words taken before and after the last release
+  PT_HIP(dev_alloc(q_u, n)); PT_HIP(dev_alloc(q_v, n)); PT_HIP(dev_alloc(cu, 2 * n)); PT_HIP(dev_alloc(cv, 2 * n));
+  PT_HIP(dev_alloc(counts, n_regions)); PT_HIP(dev_alloc(own, n)); PT_HIP(dev_alloc(row, n)); PT_HIP(dev_alloc(len, 1)); PT_HIP(dev_alloc(over, 3));
+  PT_HIP(dev_alloc(words, n_words)); PT_HIP(dev_alloc(tail_keys, tail_slots));
+  PT_HIP(hipMemcpyAsync(q_u, u, n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(q_v, v, n * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemcpyAsync(counts, region_count, (size_t)n_regions * 4, hipMemcpyHostToDevice, s));
+  PT_HIP(hipMemsetAsync(over, 0, 24, s));
+  PT_HIP(hipMemsetAsync(len, 0, 4, s));
+  PT_HIP(hipMemsetAsync(words, 0xff, n_words * 4, s));
+  PT_HIP(hipMemsetAsync(tail_keys, 0xff, (size_t)tail_slots * 8, s));
+  ptd::GroupQueue Q;
+  Q.q_u = q_u; Q.q_v = q_v; Q.region_count = counts; Q.region_cap = region_cap; Q.owner = own;
+  Q.d_u = nullptr; Q.d_v = nullptr; Q.d_count = nullptr; Q.base = 0; Q.overflowed = nullptr;   // (C touches no distinct queue)
+  const ptd::ClassMap M{words, tail_keys, tail_slots - 1u, cu, cv, len, 0u, over};
+  const dim3 grid((region_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock, n_regions), tiles(ptshare::claim_tiles(region_cap), n_regions);
+  const dim3 block(ptd::kShareBlock), count_grid(ptd::kMemoGrid);
+  auto release = [&]() -> int {   // as stage_map_release: one batch, whose class queue is the whole store
+    hipLaunchKernelGGL(ptd::class_map_release_kernel, dim3(std::min<uint32_t>(ptd::kMemoGrid, (uint32_t)((2 * n + ptd::kShareBlock - 1u) / ptd::kShareBlock)), 1),
+                       block, 0, s, cu, cv, len, 0u, words);
+    PT_HIP(hipGetLastError());
+    PT_HIP(hipMemsetAsync(words + ptshare::kClassMapWords, 0xff, (size_t)tail_slots * 4, s));
+    PT_HIP(hipMemsetAsync(tail_keys, 0xff, (size_t)tail_slots * 8, s));
+    return PT_OK;
+  };
+  for (uint32_t launch = 0; launch < launches; ++launch) {
+    if (launch && release_between) {
+      if (int rc = release()) return rc;
+      PT_HIP(hipMemsetAsync(len, 0, 4, s));
+      PT_HIP(hipMemsetAsync(over, 0, 8, s));
+    }
+    PT_HIP(hipMemsetAsync(own, 0xff, n * 4, s));
+    hipLaunchKernelGGL(ptd::class_map_claim_kernel, tiles, block, 0, s, Q, M);
+    PT_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(ptd::diag_map_hop_kernel, grid, block, 0, s, counts, region_cap, own, words, row);
+  PT_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ptd::diag_map_count_kernel, count_grid, block, 0, s, words, (uint32_t)n_words, over + 1);
+  PT_HIP(hipGetLastError());
+  if (int rc = release()) return rc;
+  hipLaunchKernelGGL(ptd::diag_map_count_kernel, count_grid, block, 0, s, words, (uint32_t)n_words, over + 2);
+  PT_HIP(hipGetLastError());
+  uint32_t h_len = 0;
+  unsigned long long h_over[3] = {0, 0, 0};
+  PT_HIP(hipMemcpyAsync(owner, own, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(rows, row, n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(c_u, cu, 2 * n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(c_v, cv, 2 * n * 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(&h_len, len, 4, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipMemcpyAsync(h_over, over, 24, hipMemcpyDeviceToHost, s));
+  PT_HIP(hipStreamSynchronize(s));
+  counters[0] = h_len; counters[1] = h_over[0]; counters[2] = h_over[1]; counters[3] = h_over[2];
   return PT_OK;
 }
 #endif

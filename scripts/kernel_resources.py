@@ -5,7 +5,7 @@ usage: python scripts/kernel_resources.py [filter-substring] [-DPTMI_DIAG_BUILD 
        python scripts/kernel_resources.py --step-budget [--small] [-D...]
 
 --step-budget: the kernels a NIF step launches beside its NIF launches -- the trace kernel instances, share_*,
-memo_lookup / memo_resolve / memo_expand, the fused step's share_class_*, the class level's class_* (NIF stream) and both accumulate kernels -- against what fits beside two NIF waves per SIMD
+memo_lookup / memo_resolve / memo_expand, the fused step's share_class_*, the mapped step's class_map_* and share_raw_claim, the class level's class_* (NIF stream) and both accumulate kernels -- against what fits beside two NIF waves per SIMD
 (DESIGN.md sections 4.1 and 4.2): at most 80 allocated VGPRs (2 x 216 of a SIMD's 512 are the NIF pair's; registers are
 allocated in granules of 8), no scratch, at most 3 KiB of LDS.  Exit status 1 if one is over.  The opt-in trace instances that
 sections 4.12 and 4.16 document as over -- the guided ones (frame slots reserved beside their SGPR spills) and the mesh ones
@@ -31,7 +31,8 @@ BUDGET_VGPRS, BUDGET_SCRATCH, BUDGET_LDS = 80, 0, 3072
 VGPR_GRANULE = 8
 SMALL_KERNELS = ("share_claim_kernel", "share_resolve_kernel", "share_expand_kernel", "memo_lookup_kernel", "memo_resolve_kernel",
                  "memo_expand_kernel", "class_claim_kernel", "class_resolve_kernel", "class_spread_kernel", "share_class_claim_kernel",
-                 "share_class_resolve_kernel", "share_class_expand_kernel", "accumulate_kernel", "accumulate4_kernel")
+                 "share_class_resolve_kernel", "share_class_expand_kernel", "class_map_claim_kernel", "class_map_expand_kernel",
+                 "share_raw_claim_kernel", "class_map_release_kernel", "accumulate_kernel", "accumulate4_kernel")
 # opt-in trace instances, with a guide or a mesh: over budget by the compiler's frame slots or by design, recorded in DESIGN.md 4.12 / 4.16
 KNOWN_OVER = ("_guide", "_lights", "_plamps", "_mesh")
 

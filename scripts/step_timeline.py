@@ -9,7 +9,7 @@ claim pass are the sharing handle's, the last --last of them the timed ones.  Pe
 kernel's end), the time a NIF launch is running, the share of the step with none.  Per batch b (--batches): A(b)'s begin and
 end relative to N(b+1)'s begin and end, and T(b+3)'s begin relative to A(b)'s end -- the edge that closes the ring of batch
 sets.  Then per-launch means of T, claim, resolve, N, E, A and the table's clear (a fill kernel of
-more than 0.2 ms) and, where the NIF stage has its class level, of its class claim, class resolve and spread passes; and for
+more than 0.2 ms), of a mapped step's raw-pair pass and release and, where the NIF stage has its class level, of its class claim, class resolve and spread passes; and for
 how much of a step each stream has a kernel of the step running."""
 import argparse
 import csv
@@ -32,6 +32,10 @@ def load(path):
 
 def kind(name):
     if "film_accumulate" in name: return "film"
+    if "class_map_claim" in name: return "claim"          # the mapped step's passes: C(b) is its claim; R(b), E(b) and the release
+    if "share_raw_claim" in name: return "raw"
+    if "class_map_expand" in name: return "expand"
+    if "class_map_release" in name: return "release"
     if "share_class_claim" in name: return "claim"       # the fused step's passes: the class is claimed inside the claim pass
     if "share_class_resolve" in name: return "resolve"
     if "share_class_expand" in name: return "expand"
@@ -79,8 +83,9 @@ def main():
     shared = [s for s in steps if any(kind(r[2]) == "claim" for r in s)]
     print("%s: %d steps in the trace, %d with a claim pass; the last %d are the timed ones" % (a.label, len(steps), len(shared), a.last))
     timed = shared[-a.last:]
-    KINDS = ("trace", "claim", "resolve", "cclaim", "cresolve", "nif", "spread", "expand", "acc")
+    KINDS = ("trace", "claim", "resolve", "raw", "cclaim", "cresolve", "nif", "spread", "expand", "acc", "release")
     per = {k: [] for k in KINDS + ("clear",)}
+    kernel_ms, launches = [], []
     busy = {}
     streams = {k: set() for k in per}
     idle = []
@@ -92,6 +97,8 @@ def main():
         t0 = min(r[0] for r in core + clears)
         t1 = max(r[1] for r in core + clears)
         span = (t1 - t0) / 1e6
+        kernel_ms.append(sum(r[1] - r[0] for r in core + clears) / 1e6)
+        launches.append(len(core) + len(clears))
         nif_ms = union_ms([(r[0], r[1]) for r in by["nif"]])
         idle.append(100.0 * (1.0 - nif_ms / span))
         for k in by:
@@ -125,6 +132,8 @@ def main():
         if per[k]:
             print("%s %-8s n %4d  mean per launch %.3f ms  per step %.2f ms  streams %s"
                   % (a.label, k, len(per[k]), statistics.mean(per[k]), sum(per[k]) / max(1, len(timed)), sorted(streams[k])))
+    if kernel_ms:
+        print("%s kernel time per step %.1f ms in %.0f launches (clears included)" % (a.label, statistics.mean(kernel_ms), statistics.mean(launches)))
     for q in sorted(busy):
         print("%s stream %s has a kernel of the step running for %.1f %% of a step on average" % (a.label, q, statistics.mean(busy[q])))
     if idle:
