@@ -3,8 +3,10 @@
 // (batch deal, trace grid, index reciprocal: plain C++), ptmi_share_plan.h that of NIF sharing and the memo (owner word, table
 // sizes: plain C++), ptmi_context.h the buffer owners and the per-handle state, ptmi_nif_pack.h the NIF normalisation and weight
 // packing, ptmi_nif_launch.h the queue bindings, the kernel launchers and the step's event allocator, ptmi_nif_group.h NIF
-// sharing and the memo (buffers, the step's mode, the stages S and E, their entry points), ptmi_film_comm.h the resident film,
-// tile costs and the RCCL hand-off, ptmi_denoise.h the feature buffers and the denoiser, ptmi_nif_train.h the NIF trainer.
+// sharing and the memo (buffers, the step's mode, the stages S and E, their entry points), ptmi_probe.h the one path of the query
+// entry points (caller arrays up, one kernel, the answers back), ptmi_mesh_api.h the meshes' entry points, ptmi_film_comm.h the
+// resident film, tile costs and the RCCL hand-off, ptmi_denoise.h the feature buffers and the denoiser, ptmi_nif_train.h the NIF
+// trainer.
 //
 // Build (see __graft_entry__.build): hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 // -ffp-contract=off is part of the numerical contract (pt_device_math.h).
@@ -56,6 +58,7 @@
 #include "ptmi_nif_train_check.h"
 #include "ptmi_step_plan.h"
 #include "ptmi_context.h"
+#include "ptmi_probe.h"
 #include "ptmi_nif_pack.h"
 #include "ptmi_nif_launch.h"
 #ifdef PTMI_DIAG_BUILD
@@ -65,6 +68,7 @@
 static void comm_release(pt_handle h);   // ptmi_film_comm.h: orderly end of the handle's communicator (finalize, polled; abort on expiry)
 static void memo_new_generation(pt_handle h);
 static void drop_env_map(pt_handle h);
+static void drop_meshes(pt_handle h);   // ptmi_mesh_api.h
 static void forget_replay_state(pt_handle h);
 static void env_guide_follow(pt_handle h);
 
@@ -746,32 +750,6 @@ static int resolve_stage_times(pt_handle h) {
   return PT_OK;
 }
 
-// n caller items through one of the guide's hook kernels: inputs up, `launch` on the stream, outputs back, one wait.
-// Whatever fails, no copy from or to the caller's buffers is left pending when the call returns.
-struct GuideSpan { const void* host_in; void* host_out; size_t bytes; char* dev; };
-template <class Launch>
-static int guide_hook(pt_handle h, GuideSpan* spans, int n_spans, Launch launch) {
-  PT_HIP(hipSetDevice(h->cfg.device));
-  auto run = [&]() -> int {
-    size_t total = 0;
-    for (int i = 0; i < n_spans; ++i) total += (spans[i].bytes + 15) / 16 * 16;
-    if (int rc = ensure_scratch(h, total)) return rc;
-    char* p = h->d_scratch;
-    for (int i = 0; i < n_spans; ++i) { spans[i].dev = p; p += (spans[i].bytes + 15) / 16 * 16; }
-    for (int i = 0; i < n_spans; ++i)
-      if (spans[i].host_in) PT_HIP(hipMemcpyAsync(spans[i].dev, spans[i].host_in, spans[i].bytes, hipMemcpyHostToDevice, h->stream));
-    launch();
-    PT_HIP(hipGetLastError());
-    for (int i = 0; i < n_spans; ++i)
-      if (spans[i].host_out) PT_HIP(hipMemcpyAsync(spans[i].host_out, spans[i].dev, spans[i].bytes, hipMemcpyDeviceToHost, h->stream));
-    PT_HIP(hipStreamSynchronize(h->stream));
-    return PT_OK;
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  return rc;
-}
-
 extern "C" {
 
 int pt_path_trace(pt_handle h) {
@@ -942,53 +920,25 @@ int pt_synchronize(pt_handle h) {
   return PT_OK;
 }
 
-// n lookups (u, v) into the scratch buffer as a dense queue of one region, *count its length; the four device pointers in Q.
-// The copies are queued on `stream` and read the caller's buffers and *count.
-struct ScratchQueue { float *u, *v, *bgr; uint32_t* count; };
-static int upload_scratch_queue(pt_handle h, const float* u, const float* v, const uint32_t* count, ScratchQueue& Q) {
-  const size_t n = *count;
-  if (int rc = ensure_scratch(h, n * 4 * 2 + n * 12 + 16)) return rc;
-  Q.u = scratch_as<float>(h);
-  Q.v = Q.u + n;
-  Q.bgr = Q.v + n;
-  Q.count = reinterpret_cast<uint32_t*>(Q.bgr + 3 * n);
-  PT_HIP(hipMemcpyAsync(Q.u, u, n * 4, hipMemcpyHostToDevice, h->stream));
-  PT_HIP(hipMemcpyAsync(Q.v, v, n * 4, hipMemcpyHostToDevice, h->stream));
-  PT_HIP(hipMemcpyAsync(Q.count, count, 4, hipMemcpyHostToDevice, h->stream));
-  return PT_OK;
-}
-
-// pt_nif_infer and (map) pt_env_map_lookup: that queue through the NIF or the map, the decoded BGR back to the caller.
-// Whatever fails, no copy from or to the caller's buffers is left pending when the call returns.
-static int scratch_lookup(pt_handle h, bool map, const float* u, const float* v, size_t n, float* bgr) {
-  PT_HIP(hipSetDevice(h->cfg.device));
+// pt_nif_infer and (map) pt_env_map_lookup: n lookups (u, v) as a dense queue of one region, `cnt` its length, through the NIF
+// or the map; the decoded BGR back to the caller.
+static int lookup_probe(pt_handle h, bool map, const float* u, const float* v, size_t n, float* bgr, const char* too_many) {
   const uint32_t cnt = (uint32_t)n;
-  auto run = [&]() -> int {
-    ScratchQueue Q;
-    if (int rc = upload_scratch_queue(h, u, v, &cnt, Q)) return rc;
+  return probe(h, n, {1ull << 31, too_many}, std::tuple{in(u), in(v), out(bgr, 3), in_once(&cnt)},
+               [&](const float* q_u, const float* q_v, float* q_bgr, const uint32_t* q_count) -> int {
     ptd::NifParams N = h->nif;   // (the map kernel reads the queue fields alone)
-    bind_dense_queue(N, Q.u, Q.v, Q.count, cnt, Q.bgr);
+    bind_dense_queue(N, q_u, q_v, q_count, cnt, q_bgr);
     const std::string name = h->nif_kernel;   // after a map lookup pt_nif_kernel_name keeps reporting the last step's stage
     const int rc = map ? launch_envmap(h, N) : launch_nif(h, N, h->n_cus);
     if (map) h->nif_kernel = name;
-    if (rc) return rc;
-    PT_HIP(hipGetLastError());
-    PT_HIP(hipMemcpyAsync(bgr, Q.bgr, n * 12, hipMemcpyDeviceToHost, h->stream));
-    PT_HIP(hipStreamSynchronize(h->stream));
-    return PT_OK;
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  return rc;
+    return rc;
+  });
 }
 
 int pt_nif_infer(pt_handle h, const float* u, const float* v, size_t n, float* bgr) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->nif_valid) return fail(h, PT_ERR_NOT_READY, "pt_upload_nif has not been called");
-  if (n == 0) return PT_OK;
-  if (!u || !v || !bgr) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many samples");
-  return scratch_lookup(h, false, u, v, n, bgr);
+  return lookup_probe(h, false, u, v, n, bgr, "too many samples");
 }
 
 int pt_set_env_map(pt_handle h, const float* bgr, uint32_t width, uint32_t height, int32_t filter) {
@@ -1037,10 +987,7 @@ int pt_set_env_map(pt_handle h, const float* bgr, uint32_t width, uint32_t heigh
 int pt_env_map_lookup(pt_handle h, const float* u, const float* v, size_t n, float* bgr) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->env_map) return fail(h, PT_ERR_NOT_READY, "pt_set_env_map has not been called (or a NIF or a constant has replaced the map)");
-  if (n == 0) return PT_OK;
-  if (!u || !v || !bgr) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many lookups");
-  return scratch_lookup(h, true, u, v, n, bgr);
+  return lookup_probe(h, true, u, v, n, bgr, "too many lookups");
 }
 
 // The guide's two tables are built on the host (ptmi_env_guide.h) and copied; the new copies are complete before the old ones
@@ -1112,7 +1059,7 @@ int pt_set_env_guide(pt_handle h, const pt_env_guide* g) {
 
 // The cell masses of a rows x cols grid with S x S samples per cell, summed on the device from the environment in force, then
 // the tables (ptguide::build_from_masses) into T.  Nothing of the handle changes but the scratch-free buffers made and freed
-// here: the dense queue has the layout pt_nif_infer gives it (u, v, bgr, count in one allocation) and goes through the same
+// here: the dense queue is bound as pt_nif_infer binds its own (u, v, bgr, count in one allocation) and goes through the same
 // launcher, which is why the image it stands for is pt_nif_infer's / pt_env_map_lookup's, value for value.  It bypasses NIF
 // sharing and the memo, and what pt_nif_kernel_name reports is put back.
 static int build_guide_from_environment(pt_handle h, uint32_t rows, uint32_t cols, uint32_t S, float alpha, ptguide::Table& T,
@@ -1236,8 +1183,7 @@ int pt_set_env_guide_from_environment(pt_handle h, const pt_env_guide_auto* a) {
 
 int pt_get_env_guide_info(pt_handle h, pt_env_guide_info* out) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_env_guide_info))
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_env_guide_info: struct_size must be " + std::to_string(sizeof(pt_env_guide_info)));
+  if (int rc = check_info(h, out, "pt_get_env_guide_info")) return rc;
   pt_env_guide_info I{};
   I.struct_size = sizeof(pt_env_guide_info);
   I.set = h->guide_set ? 1 : 0;
@@ -1278,30 +1224,20 @@ int pt_env_guide_sample(pt_handle h, const uint32_t* g1, const uint32_t* g2, con
                         uint32_t* out_cell) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->guide_set) return fail(h, PT_ERR_NOT_READY, "pt_set_env_guide has not been called (or the guide has been cleared)");
-  if (n == 0) return PT_OK;
-  if (!g1 || !g2 || !g3 || !out_uv || !out_cell) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many samples");
-  GuideSpan s[5] = {{g1, nullptr, n * 4, nullptr}, {g2, nullptr, n * 4, nullptr}, {g3, nullptr, n * 4, nullptr},
-                    {nullptr, out_uv, n * 8, nullptr}, {nullptr, out_cell, n * 4, nullptr}};
-  return guide_hook(h, s, 5, [&]() {
-    hipLaunchKernelGGL(ptd::env_guide_sample_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, h->guide,
-                       reinterpret_cast<const uint32_t*>(s[0].dev), reinterpret_cast<const uint32_t*>(s[1].dev),
-                       reinterpret_cast<const uint32_t*>(s[2].dev), (uint32_t)n, reinterpret_cast<float*>(s[3].dev),
-                       reinterpret_cast<uint32_t*>(s[4].dev));
+  return probe(h, n, {1ull << 31, "too many samples"}, std::tuple{in(g1), in(g2), in(g3), out(out_uv, 2), out(out_cell)},
+               [&](const uint32_t* w1, const uint32_t* w2, const uint32_t* w3, float* uv, uint32_t* cell) -> int {
+    hipLaunchKernelGGL(ptd::env_guide_sample_kernel, probe_grid(n), dim3(kProbeBlock), 0, h->stream, h->guide, w1, w2, w3, (uint32_t)n, uv, cell);
+    return PT_OK;
   });
 }
 
 int pt_env_guide_eval(pt_handle h, const float* dir_world, size_t n, uint32_t* out_cell, float* out_g) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->guide_set) return fail(h, PT_ERR_NOT_READY, "pt_set_env_guide has not been called (or the guide has been cleared)");
-  if (n == 0) return PT_OK;
-  if (!dir_world || !out_cell || !out_g) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many directions");
-  GuideSpan s[3] = {{dir_world, nullptr, n * 12, nullptr}, {nullptr, out_cell, n * 4, nullptr}, {nullptr, out_g, n * 4, nullptr}};
-  return guide_hook(h, s, 3, [&]() {
-    hipLaunchKernelGGL(ptd::env_guide_eval_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, h->guide, h->azimuth,
-                       reinterpret_cast<const float*>(s[0].dev), (uint32_t)n, reinterpret_cast<uint32_t*>(s[1].dev),
-                       reinterpret_cast<float*>(s[2].dev));
+  return probe(h, n, {1ull << 31, "too many directions"}, std::tuple{in(dir_world, 3), out(out_cell), out(out_g)},
+               [&](const float* dir, uint32_t* cell, float* g) -> int {
+    hipLaunchKernelGGL(ptd::env_guide_eval_kernel, probe_grid(n), dim3(kProbeBlock), 0, h->stream, h->guide, h->azimuth, dir, (uint32_t)n, cell, g);
+    return PT_OK;
   });
 }
 
@@ -1355,8 +1291,7 @@ int pt_get_light_guide_flags(pt_handle h, uint32_t* flags) {
 
 int pt_get_light_guide_info(pt_handle h, pt_light_guide_info* out) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_light_guide_info))
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_light_guide_info: struct_size must be " + std::to_string(sizeof(pt_light_guide_info)));
+  if (int rc = check_info(h, out, "pt_get_light_guide_info")) return rc;
   const ptlight::Table& T = h->light;
   memset(out, 0, sizeof(*out));
   out->struct_size = sizeof(*out);
@@ -1382,25 +1317,29 @@ static void light_hook_params(pt_handle h, ptd::TraceParams& P) {
   fill_light_params(h, P, true);
 }
 
+// ... and of the mesh hooks (ptmi_mesh_api.h): the trees in the world frame, whatever the camera, and the WORLD-space table of a
+// scene that holds a mesh.
+static int mesh_probe_params(pt_handle h, ptd::TraceParams& P) {
+  if (int rc = ensure_meshes(h, true)) return rc;
+  memset(&P, 0, sizeof(P));
+  fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->mesh.row);
+  bind_meshes(h, P);
+  return PT_OK;
+}
+
 int pt_light_guide_sample(pt_handle h, const float* origin, const float* normal, const uint32_t* g1, const uint32_t* g2,
                           const uint32_t* g3, size_t n, float* out_dir, int32_t* out_light) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->light_set || !h->light.active())
     return fail(h, PT_ERR_NOT_READY, "no active light guide: pt_set_light_guide has not been called, or the scene has no emitter with mass");
-  if (n == 0) return PT_OK;
-  if (!origin || !normal || !g1 || !g2 || !g3 || !out_dir || !out_light) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many samples");
-  ptd::TraceParams P;
-  light_hook_params(h, P);
-  GuideSpan s[7] = {{origin, nullptr, n * 12, nullptr}, {normal, nullptr, n * 12, nullptr}, {g1, nullptr, n * 4, nullptr},
-                    {g2, nullptr, n * 4, nullptr},      {g3, nullptr, n * 4, nullptr},      {nullptr, out_dir, n * 12, nullptr},
-                    {nullptr, out_light, n * 4, nullptr}};
-  return guide_hook(h, s, 7, [&]() {
-    hipLaunchKernelGGL(h->light.polygons ? ptd::light_guide_sample_plamps_kernel : ptd::light_guide_sample_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
-                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev),
-                       reinterpret_cast<const uint32_t*>(s[2].dev), reinterpret_cast<const uint32_t*>(s[3].dev),
-                       reinterpret_cast<const uint32_t*>(s[4].dev), (uint32_t)n, reinterpret_cast<float*>(s[5].dev),
-                       reinterpret_cast<int32_t*>(s[6].dev));
+  return probe(h, n, {1ull << 31, "too many samples"},
+               std::tuple{in(origin, 3), in(normal, 3), in(g1), in(g2), in(g3), out(out_dir, 3), out(out_light)},
+               [&](const float* o, const float* nrm, const uint32_t* w1, const uint32_t* w2, const uint32_t* w3, float* dir, int32_t* light) -> int {
+    ptd::TraceParams P;
+    light_hook_params(h, P);
+    hipLaunchKernelGGL(h->light.polygons ? ptd::light_guide_sample_plamps_kernel : ptd::light_guide_sample_kernel, probe_grid(n),
+                       dim3(kProbeBlock), 0, h->stream, P, o, nrm, w1, w2, w3, (uint32_t)n, dir, light);
+    return PT_OK;
   });
 }
 
@@ -1409,27 +1348,14 @@ int pt_light_guide_eval(pt_handle h, const float* origin, const float* normal, c
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->light_set || !h->light.active())
     return fail(h, PT_ERR_NOT_READY, "no active light guide: pt_set_light_guide has not been called, or the scene has no emitter with mass");
-  if (n == 0) return PT_OK;
-  if (!origin || !normal || !dir || !out_sum || !out_pe) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31)) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many directions");
-  ptd::TraceParams P;
-  light_hook_params(h, P);
-  GuideSpan s[5] = {{origin, nullptr, n * 12, nullptr}, {normal, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr},
-                    {nullptr, out_sum, n * 4, nullptr}, {nullptr, out_pe, n * 4, nullptr}};
-  return guide_hook(h, s, 5, [&]() {
-    hipLaunchKernelGGL(h->light.polygons ? ptd::light_guide_eval_plamps_kernel : ptd::light_guide_eval_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
-                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev),
-                       reinterpret_cast<const float*>(s[2].dev), (uint32_t)n, reinterpret_cast<float*>(s[3].dev),
-                       reinterpret_cast<float*>(s[4].dev));
+  return probe(h, n, {1ull << 31, "too many directions"}, std::tuple{in(origin, 3), in(normal, 3), in(dir, 3), out(out_sum), out(out_pe)},
+               [&](const float* o, const float* nrm, const float* d, float* sum, float* pe) -> int {
+    ptd::TraceParams P;
+    light_hook_params(h, P);
+    hipLaunchKernelGGL(h->light.polygons ? ptd::light_guide_eval_plamps_kernel : ptd::light_guide_eval_kernel, probe_grid(n),
+                       dim3(kProbeBlock), 0, h->stream, P, o, nrm, d, (uint32_t)n, sum, pe);
+    return PT_OK;
   });
-}
-
-// A scene without a mesh takes over: the MESH instances stop running and the meshes' memory goes back (hipFree waits for the device).
-static void drop_meshes(pt_handle h) {
-  if (!h->scene_mesh && h->mesh.mesh.empty()) return;
-  h->scene_mesh = false;
-  (void)hipSetDevice(h->cfg.device);
-  h->mesh = pt_context::MeshSet{};
 }
 
 int pt_set_scene(pt_handle h, const pt_scene_object* objects, uint32_t n) {
@@ -1497,493 +1423,6 @@ int pt_set_scene_ex(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, 
   return PT_OK;
 }
 
-// pt_set_scene_ex with meshes.  Everything is checked, copied, built and on the device before the scene in force changes: a
-// rejection or a failed allocation leaves it as it was.
-int pt_set_scene_meshes(pt_handle h, const pt_scene_object_ex* objects, uint32_t n, uint32_t stride, const pt_mesh* meshes,
-                        uint32_t n_meshes) {
-  if (!objects && n == 0 && stride == sizeof(pt_scene_object_ex) && !meshes && n_meshes == 0) {   // the built-in scene
-    if (!h) { g_create_error = "pt_set_scene_meshes: null handle"; return PT_ERR_INVALID_ARGUMENT; }
-    return pt_set_scene(h, nullptr, 0);
-  }
-  const std::string bad = ptmesh::check(objects, n, stride, meshes, n_meshes);
-  if (!bad.empty()) {   // the scene in force stays
-    if (h) h->error = bad; else g_create_error = bad;
-    return PT_ERR_INVALID_ARGUMENT;
-  }
-  if (!h) { g_create_error = "pt_set_scene_meshes: null handle"; return PT_ERR_INVALID_ARGUMENT; }
-  if (n_meshes == 0) return pt_set_scene_ex(h, objects, n, stride);   // no mesh row: pt_set_scene_ex's scene, on its kernels
-  PT_HIP(hipSetDevice(h->cfg.device));
-  try {   // (the host copies are large -- 48 bytes per triangle and the builder's arrays: no exception crosses the C boundary)
-  pt_context::MeshSet M;
-  size_t triangles = 0, nodes = 0;
-  for (uint32_t i = 0, m = 0; i < n; ++i) {
-    if (objects[i].shape != PT_SHAPE_MESH) continue;
-    pt_context::MeshSet::One one{};
-    one.object_index = i;
-    one.n_triangles = meshes[m].n_triangles;
-    one.n_vertices = meshes[m].n_vertices;
-    M.indices.insert(M.indices.end(), meshes[m].indices, meshes[m].indices + 3 * (size_t)meshes[m].n_triangles);
-    one.tri_base = (uint32_t)triangles;
-    one.node_base = (uint32_t)nodes;
-    ptmesh::world_frames(meshes[m], M.world);
-    M.mesh.push_back(one);
-    triangles += one.n_triangles;
-    nodes += 2 * (size_t)one.n_triangles - 1;
-    m += 1;
-  }
-  PT_HIP(dev_alloc(M.d_nodes, nodes));
-  PT_HIP(dev_alloc(M.d_tris, 3 * triangles));
-  PT_HIP(dev_alloc(M.d_orig, triangles));
-  const ptcamera::Basis& cb = h->camera_basis;
-  if (mesh_device_option(h))   // (pt_set_mesh_build: the options outlive the scene, so their storage comes with every scene)
-    if (int rc = ensure_mesh_device(h, M)) return rc;
-  if (int rc = update_meshes(h, M, cb.identity ? nullptr : &cb)) return rc;
-  // commit: the table as stored -- a mesh row with shape 4, its material and colour, and zeros
-  pt_scene_object_ex stored[PT_MAX_SCENE_OBJECTS];
-  std::copy(objects, objects + n, stored);
-  for (uint32_t i = 0; i < n; ++i)
-    if (stored[i].shape == PT_SHAPE_MESH) { stored[i].radius = 0.f; for (int k = 0; k < 3; ++k) stored[i].centre[k] = 0.f; }
-  ptscene::normalise_ex(stored, n);   // (a mesh row: normal and vertex 0, as a sphere's)
-  bool poly = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    memcpy(&h->scene[i], &stored[i], sizeof(pt_scene_object));
-    memcpy(h->scene_vertex[i], stored[i].vertex, sizeof(stored[i].vertex));
-    poly = poly || ptscene::is_polygon(stored[i].shape);
-  }
-  h->scene_n = n;
-  h->scene_poly = poly;   // (which rows are polygons: the light guide's polygon lamps and pt_get_scene_ex ask; the MESH instances run)
-  h->mesh = std::move(M);
-  h->scene_mesh = true;
-  h->feature_gen += 1;
-  rebuild_light_guide(h);
-  return PT_OK;
-  } catch (const std::bad_alloc&) {   // nothing of the scene in force has changed yet
-    return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_scene_meshes: out of host memory for the meshes' copies");
-  }
-}
-
-int pt_get_mesh_info(pt_handle h, uint32_t mesh, pt_mesh_info* out) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_mesh_info))
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_info: struct_size must be " + std::to_string(sizeof(pt_mesh_info)));
-  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
-  if (mesh >= count)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_info: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
-  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
-  memset(out, 0, sizeof(*out));
-  out->struct_size = sizeof(*out);
-  out->object_index = m.object_index;
-  out->n_triangles = m.n_triangles;
-  out->n_nodes = m.n_nodes;
-  out->max_leaf = m.max_leaf;
-  out->depth = m.depth;
-  out->device_bytes = (2 * (uint64_t)m.n_triangles - 1) * sizeof(ptmesh::Node) + (uint64_t)m.n_triangles * (3 * sizeof(ptmesh::F4) + sizeof(uint32_t));
-  out->build_ms = m.build_ms;
-  out->pad = m.pad;
-  return PT_OK;
-}
-
-// Who builds the trees and what a pose change does to them (include/ptmi.h).  Everything the device paths need is allocated here,
-// before the options change: a failed allocation leaves them as they were.
-int pt_set_mesh_build(pt_handle h, const pt_mesh_build_options* o) {
-  const pt_mesh_build_options defaults{sizeof(pt_mesh_build_options), PT_MESH_BUILDER_HOST, PT_MESH_POSE_REBUILD};
-  const pt_mesh_build_options& O = o ? *o : defaults;
-  std::string bad;
-  if (O.struct_size != sizeof(pt_mesh_build_options))
-    bad = "pt_set_mesh_build: struct_size must be " + std::to_string(sizeof(pt_mesh_build_options)) + " (got " + std::to_string(O.struct_size) + ")";
-  else if (O.builder != PT_MESH_BUILDER_HOST && O.builder != PT_MESH_BUILDER_DEVICE)
-    bad = "pt_set_mesh_build: builder must be 0 (host) or 1 (device) (got " + std::to_string(O.builder) + ")";
-  else if (O.on_pose != PT_MESH_POSE_REBUILD && O.on_pose != PT_MESH_POSE_REFIT)
-    bad = "pt_set_mesh_build: on_pose must be 0 (rebuild) or 1 (refit) (got " + std::to_string(O.on_pose) + ")";
-  if (!bad.empty()) {
-    if (h) h->error = bad; else g_create_error = bad;
-    return PT_ERR_INVALID_ARGUMENT;
-  }
-  if (!h) { g_create_error = "pt_set_mesh_build: null handle"; return PT_ERR_INVALID_ARGUMENT; }
-  const bool device = O.builder == PT_MESH_BUILDER_DEVICE || O.on_pose == PT_MESH_POSE_REFIT;
-  if (device && h->scene_n && h->scene_mesh)
-    if (int rc = ensure_mesh_device(h, h->mesh)) return rc;
-  if (O.builder != h->mesh_builder) {   // the trees of the scene in force are the other builder's: stale, and no refit may keep them
-    h->mesh.built = false;
-    h->mesh.topo_builder = -1;
-  }
-  h->mesh_builder = O.builder;
-  h->mesh_on_pose = O.on_pose;
-  return PT_OK;
-}
-
-int pt_get_mesh_build_info(pt_handle h, pt_mesh_build_info* out) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_mesh_build_info))
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_build_info: struct_size must be " + std::to_string(sizeof(pt_mesh_build_info)));
-  memset(out, 0, sizeof(*out));
-  out->struct_size = sizeof(*out);
-  out->builder = h->mesh_builder;
-  out->on_pose = h->mesh_on_pose;
-  out->sort_on_device = PT_LBVH_DEVICE_SORT;
-  out->host_builds = h->mesh_host_builds;
-  out->device_builds = h->mesh_device_builds;
-  out->refits = h->mesh_refits;
-  out->last_kind = h->mesh_last_kind;
-  out->last_ms = h->mesh_last_ms;
-  out->device_bytes = (h->scene_n && h->scene_mesh) ? h->mesh.dev.bytes : 0u;
-  return PT_OK;
-}
-
-static_assert(sizeof(pt_mesh_node) == sizeof(ptmesh::Node) && sizeof(pt_mesh_build_options) == 12 && sizeof(pt_mesh_build_info) == 64,
-              "pt_mesh_node / pt_mesh_build_* layout");
-int pt_mesh_tree(pt_handle h, uint32_t mesh, pt_mesh_node* nodes, uint32_t node_capacity, uint32_t* orig, uint32_t orig_capacity) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_tree: the scene in force holds no mesh (pt_set_scene_meshes)");
-  if (mesh >= h->mesh.mesh.size())
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: mesh " + std::to_string(mesh) + " of " + std::to_string(h->mesh.mesh.size()) + " in the scene in force");
-  if ((!nodes && node_capacity) || (!orig && orig_capacity)) return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: a null buffer with a capacity");
-  if (int rc = ensure_meshes(h)) return rc;   // the camera in force, exactly as a render
-  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
-  if (nodes && node_capacity < m.n_nodes)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: node_capacity must be >= " + std::to_string(m.n_nodes) + " (got " + std::to_string(node_capacity) + ")");
-  if (orig && orig_capacity < m.n_triangles)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_tree: orig_capacity must be >= " + std::to_string(m.n_triangles) + " (got " + std::to_string(orig_capacity) + ")");
-  if (nodes) PT_HIP(hipMemcpy(nodes, h->mesh.d_nodes + m.node_base, m.n_nodes * sizeof(ptmesh::Node), hipMemcpyDeviceToHost));
-  if (orig) PT_HIP(hipMemcpy(orig, h->mesh.d_orig + m.tri_base, m.n_triangles * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return PT_OK;
-}
-
-// New vertices (and normals) for mesh `mesh` of the scene in force (include/ptmi.h; ptmi_mesh_update.h).  Everything is allocated,
-// copied into staging and checked on the device before a byte of the geometry in force changes.
-static_assert(sizeof(pt_mesh_update) == 40 && offsetof(pt_mesh_update, vertices) == 16 && offsetof(pt_mesh_update, normals) == 32 &&
-              sizeof(pt_mesh_update_info) == 64, "pt_mesh_update* layout");
-int pt_update_mesh_vertices(pt_handle h, uint32_t mesh, const pt_mesh_update* u) {
-  std::string bad;
-  if (!u) bad = "pt_update_mesh_vertices: null update";
-  else if (u->struct_size != sizeof(pt_mesh_update))
-    bad = "pt_update_mesh_vertices: struct_size must be " + std::to_string(sizeof(pt_mesh_update)) + " (got " + std::to_string(u->struct_size) + ")";
-  else if (u->mode != PT_MESH_UPDATE_REFIT && u->mode != PT_MESH_UPDATE_REBUILD)
-    bad = "pt_update_mesh_vertices: mode must be 0 (refit) or 1 (rebuild) (got " + std::to_string(u->mode) + ")";
-  else if (u->memory != PT_MESH_UPDATE_HOST_MEMORY && u->memory != PT_MESH_UPDATE_DEVICE_MEMORY)
-    bad = "pt_update_mesh_vertices: memory must be 0 (host) or 1 (device) (got " + std::to_string(u->memory) + ")";
-  else if (!u->vertices) bad = "pt_update_mesh_vertices: null vertices";
-  else if (!u->normals && u->n_normals != 0) bad = "pt_update_mesh_vertices: null normals with n_normals = " + std::to_string(u->n_normals);
-  else if (u->normals && u->n_normals == 0) bad = "pt_update_mesh_vertices: normals with n_normals = 0";
-  if (!bad.empty()) {
-    if (h) h->error = bad; else g_create_error = bad;
-    return PT_ERR_INVALID_ARGUMENT;
-  }
-  if (!h) { g_create_error = "pt_update_mesh_vertices: null handle"; return PT_ERR_INVALID_ARGUMENT; }
-  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
-  if (mesh >= count)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_update_mesh_vertices: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
-  pt_context::MeshSet& M = h->mesh;
-  pt_context::MeshSet::One& m = M.mesh[mesh];
-  const std::string at = "pt_update_mesh_vertices: mesh " + std::to_string(mesh) + ": ";
-  if (u->n_vertices != m.n_vertices)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, at + "n_vertices must equal the mesh's " + std::to_string(m.n_vertices) + " (got " + std::to_string(u->n_vertices) + ")");
-  if (u->normals && m.normals.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, at + "normals for a mesh without normals (pt_set_mesh_normals)");
-  if (u->normals && u->n_normals != m.n_normals)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, at + "n_normals must equal the attached " + std::to_string(m.n_normals) + " (got " + std::to_string(u->n_normals) + ")");
-  // storage: nothing of the scene changes here
-  if (int rc = drain_for_meshes(h, M)) return rc;
-  const uint64_t dev_before = M.dev.bytes;
-  if (int rc = ensure_mesh_device(h, M)) return rc;
-  M.upd.bytes += M.dev.bytes - dev_before;
-  if (int rc = ensure_mesh_update(h, M)) return rc;
-  // staging, the check, and the commit
-  pt_context::MeshSet::Update& U = M.upd;
-  const hipMemcpyKind kind = u->memory == PT_MESH_UPDATE_DEVICE_MEMORY ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const uint32_t T = m.n_triangles;
-  const uint32_t* indices = U.indices + 3 * (size_t)m.tri_base;
-  const float* normals = u->normals ? (const float*)U.normals : nullptr;
-  const uint32_t* normal_indices = !u->normals ? nullptr : m.per_corner ? U.normal_indices + 3 * (size_t)m.tri_base : indices;
-  const dim3 grid(ptupdate::blocks_for(T)), block(ptupdate::kBlock);
-  unsigned long long* fault = reinterpret_cast<unsigned long long*>((uint64_t*)U.fault);
-  uint64_t fault_host[2] = {ptupdate::kNoFault, ptupdate::kNoFault};
-  PT_HIP(hipEventRecord(h->mesh_update_event[0], h->stream));
-  PT_HIP(hipMemcpyAsync(U.vertices, u->vertices, 12 * (size_t)m.n_vertices, kind, h->stream));
-  if (normals) PT_HIP(hipMemcpyAsync(U.normals, u->normals, 12 * (size_t)m.n_normals, kind, h->stream));
-  PT_HIP(hipMemsetAsync(U.fault, 0xff, sizeof(fault_host), h->stream));
-  hipLaunchKernelGGL(ptupdate::mesh_update_check_kernel, grid, block, 0, h->stream, T, indices, (const float*)U.vertices, normal_indices, normals, fault);
-  PT_HIP(hipGetLastError());
-  PT_HIP(hipMemcpyAsync(fault_host, U.fault, sizeof(fault_host), hipMemcpyDeviceToHost, h->stream));
-  PT_HIP(hipStreamSynchronize(h->stream));
-  if (fault_host[0] != ptupdate::kNoFault || fault_host[1] != ptupdate::kNoFault)   // the geometry in force stands
-    return mesh_update_rejection(h, M, mesh, fault_host[0], fault_host[1]);
-  hipLaunchKernelGGL(ptupdate::mesh_update_commit_kernel, grid, block, 0, h->stream, T, indices, (const float*)U.vertices, normal_indices, normals,
-                     M.dev.world + ptlbvh::kFrameFloats * (size_t)m.tri_base, normals ? M.dev.corner + 9 * (size_t)m.tri_base : (float*)nullptr);
-  PT_HIP(hipGetLastError());
-  PT_HIP(hipEventRecord(h->mesh_update_event[1], h->stream));
-  PT_HIP(hipEventSynchronize(h->mesh_update_event[1]));
-  float frames_ms = 0.f;
-  PT_HIP(hipEventElapsedTime(&frames_ms, h->mesh_update_event[0], h->mesh_update_event[1]));
-  m.world_stale = true;
-  m.normals_stale = m.normals_stale || normals != nullptr;
-  h->feature_gen += 1;
-  // the tree (a pass that fails leaves the trees marked stale: the next call that traces builds them from the new frames)
-  int tree_kind = PT_MESH_LAST_NONE;
-  bool fallback = false;
-  if (int rc = mesh_update_tree(h, M, mesh, u->mode, tree_kind, fallback)) return rc;
-  h->mesh_updates += 1;
-  (tree_kind == PT_MESH_LAST_REFIT ? h->mesh_update_refits : h->mesh_update_rebuilds) += 1;
-  h->mesh_update_fallbacks += fallback ? 1 : 0;
-  h->mesh_update_last_kind = tree_kind;
-  h->mesh_update_frames_ms = frames_ms;
-  h->mesh_update_tree_ms = h->mesh_last_ms;
-  return PT_OK;
-}
-
-int pt_get_mesh_update_info(pt_handle h, pt_mesh_update_info* out) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_mesh_update_info))
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_update_info: struct_size must be " + std::to_string(sizeof(pt_mesh_update_info)));
-  memset(out, 0, sizeof(*out));
-  out->struct_size = sizeof(*out);
-  out->last_kind = h->mesh_update_last_kind;
-  out->updates = h->mesh_updates;
-  out->refits = h->mesh_update_refits;
-  out->rebuilds = h->mesh_update_rebuilds;
-  out->fallbacks = h->mesh_update_fallbacks;
-  out->last_frames_ms = h->mesh_update_frames_ms;
-  out->last_tree_ms = h->mesh_update_tree_ms;
-  out->device_bytes = (h->scene_n && h->scene_mesh) ? h->mesh.upd.bytes : 0u;
-  return PT_OK;
-}
-
-int pt_mesh_intersect(pt_handle h, const float* origin, const float* dir, size_t n, int32_t mode, float* out_t, int32_t* out_object,
-                      int32_t* out_triangle) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_intersect: the scene in force holds no mesh (pt_set_scene_meshes)");
-  if (mode != PT_MESH_INTERSECT_BVH && mode != PT_MESH_INTERSECT_BRUTE)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_mesh_intersect: mode must be 0 (BVH) or 1 (brute force) (got " + std::to_string(mode) + ")");
-  if (n == 0) return PT_OK;
-  if (!origin || !dir || !out_t || !out_object || !out_triangle) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31) / 3) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many rays");
-  if (int rc = ensure_meshes(h, true)) return rc;   // the world frame, whatever the camera
-  ptd::TraceParams P;
-  memset(&P, 0, sizeof(P));
-  fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->mesh.row);
-  bind_meshes(h, P);
-  GuideSpan s[5] = {{origin, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr}, {nullptr, out_t, n * 4, nullptr},
-                    {nullptr, out_object, n * 4, nullptr}, {nullptr, out_triangle, n * 4, nullptr}};
-  return guide_hook(h, s, 5, [&]() {
-    hipLaunchKernelGGL(mode == PT_MESH_INTERSECT_BRUTE ? ptd::mesh_intersect_brute_kernel : ptd::mesh_intersect_kernel,
-                       dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P, reinterpret_cast<const float*>(s[0].dev),
-                       reinterpret_cast<const float*>(s[1].dev), (uint32_t)n, reinterpret_cast<float*>(s[2].dev),
-                       reinterpret_cast<int32_t*>(s[3].dev), reinterpret_cast<int32_t*>(s[4].dev));
-  });
-}
-
-// Vertex normals of mesh `mesh` of the scene in force.  Checked and copied on the host, and the device buffer allocated, before
-// anything of the mesh changes; the trees are then marked stale, so that the next call that traces re-expands the normals into the
-// slot order of the frame it traces in (build_meshes), exactly as after a pose change.
-int pt_set_mesh_normals(pt_handle h, uint32_t mesh, const float* normals, uint32_t n_normals, const uint32_t* normal_indices) {
-  if (!h) { g_create_error = "pt_set_mesh_normals: null handle"; return PT_ERR_INVALID_ARGUMENT; }
-  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
-  if (mesh >= count)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_mesh_normals: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
-  pt_context::MeshSet& M = h->mesh;
-  pt_context::MeshSet::One& m = M.mesh[mesh];
-  try {
-  if (!normals && n_normals == 0 && !normal_indices) {   // remove: the mesh is flat again
-    if (m.normals.empty()) return PT_OK;
-    std::vector<float>().swap(m.normals);
-    std::vector<uint32_t>().swap(m.normal_indices);
-    m.n_normals = 0; m.per_corner = false; m.normals_stale = false;
-  } else {
-    const std::string bad = ptmesh::check_normals(mesh, m.n_vertices, m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, normals,
-                                                  n_normals, normal_indices);
-    if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the mesh keeps what it had
-    std::vector<float> corner;
-    ptmesh::corner_normals(m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, normals, normal_indices, corner);
-    std::vector<uint32_t> kept;   // (pt_update_mesh_vertices looks new per-corner normals up by the caller's indices)
-    if (normal_indices) kept.assign(normal_indices, normal_indices + 3 * (size_t)m.n_triangles);
-    if (!M.d_normals) {
-      PT_HIP(hipSetDevice(h->cfg.device));
-      size_t triangles = 0;
-      for (const pt_context::MeshSet::One& o : M.mesh) triangles += o.n_triangles;
-      const hipError_t e = dev_alloc(M.d_normals, 3 * triangles);
-      if (e != hipSuccess)
-        return fail(h, hip_status(e), "pt_set_mesh_normals: allocating " + std::to_string(3 * triangles * sizeof(ptmesh::F4)) + " bytes: " + hipGetErrorString(e));
-    }
-    if (mesh_device_option(h))   // (pt_set_mesh_build: the triangle-order copy the device paths expand from)
-      if (int rc = ensure_mesh_device(h, M, true, false)) return rc;
-    m.normals.swap(corner);
-    m.normal_indices.swap(kept);
-    m.n_normals = n_normals; m.per_corner = normal_indices != nullptr; m.normals_stale = false;
-    if (int rc = upload_mesh_corners(h, M, mesh)) return rc;
-  }
-  drop_mesh_update_normals(M);
-  } catch (const std::bad_alloc&) {
-    return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_mesh_normals: out of host memory for the normals' copy");
-  }
-  M.built = false;        // the next trace rebuilds: rows' flags and the normals in slot order
-  M.topo_builder = -1;    // (a build, never a refit: pt_set_mesh_build)
-  h->feature_gen += 1;
-  return PT_OK;
-}
-
-int pt_get_mesh_normals_info(pt_handle h, uint32_t mesh, pt_mesh_normals_info* out) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_mesh_normals_info))
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_normals_info: struct_size must be " + std::to_string(sizeof(pt_mesh_normals_info)));
-  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
-  if (mesh >= count)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_normals_info: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
-  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
-  memset(out, 0, sizeof(*out));
-  out->struct_size = sizeof(*out);
-  out->has_normals = m.normals.empty() ? 0u : 1u;
-  out->per_corner = m.per_corner ? 1u : 0u;
-  out->n_normals = m.n_normals;
-  out->device_bytes = m.normals.empty() ? 0u : (uint64_t)m.n_triangles * 3 * sizeof(ptmesh::F4);
-  return PT_OK;
-}
-
-int pt_mesh_shade(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object, int32_t* out_triangle,
-                  float* out_bary, float* out_normal) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_shade: the scene in force holds no mesh (pt_set_scene_meshes)");
-  if (n == 0) return PT_OK;
-  if (!origin || !dir || !out_t || !out_object || !out_triangle || !out_bary || !out_normal) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31) / 3) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many rays");
-  if (int rc = ensure_meshes(h, true)) return rc;   // the world frame, whatever the camera
-  ptd::TraceParams P;
-  memset(&P, 0, sizeof(P));
-  fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->mesh.row);
-  bind_meshes(h, P);
-  GuideSpan s[7] = {{origin, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr}, {nullptr, out_t, n * 4, nullptr},
-                    {nullptr, out_object, n * 4, nullptr}, {nullptr, out_triangle, n * 4, nullptr}, {nullptr, out_bary, n * 8, nullptr},
-                    {nullptr, out_normal, n * 12, nullptr}};
-  return guide_hook(h, s, 7, [&]() {
-    hipLaunchKernelGGL(ptd::mesh_shade_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P,
-                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev), (uint32_t)n,
-                       reinterpret_cast<float*>(s[2].dev), reinterpret_cast<int32_t*>(s[3].dev), reinterpret_cast<int32_t*>(s[4].dev),
-                       reinterpret_cast<float*>(s[5].dev), reinterpret_cast<float*>(s[6].dev));
-  });
-}
-
-// The texture of mesh `mesh` of the scene in force.  Checked and copied on the host, and every device buffer allocated and filled,
-// before anything of the mesh changes; the trees are then marked stale, so that the next call that traces re-expands the uvs into
-// the slot order of the frame it traces in (build_meshes), exactly as after a pose change.
-int pt_set_mesh_texture(pt_handle h, uint32_t mesh, const pt_mesh_texture* t) {
-  if (!h) { g_create_error = "pt_set_mesh_texture: null handle"; return PT_ERR_INVALID_ARGUMENT; }
-  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
-  if (mesh >= count)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_set_mesh_texture: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
-  pt_context::MeshSet& M = h->mesh;
-  pt_context::MeshSet::One& m = M.mesh[mesh];
-  const auto drain = [&]() -> hipError_t {   // a step in flight may still read the image and the descriptors
-    for (hipStream_t s : {h->stream, h->trace_stream, h->acc_stream})
-      if (s) if (hipError_t e = hipStreamSynchronize(s)) return e;
-    return hipSuccess;
-  };
-  try {
-  if (!t) {   // remove: the mesh has its one colour again
-    if (m.uvs.empty()) return PT_OK;
-    PT_HIP(hipSetDevice(h->cfg.device));
-    PT_HIP(drain());
-    ptmesh::TexDesc table[PT_MAX_SCENE_OBJECTS];   // the new table in a temporary: committed only once it is on the device
-    memcpy(table, M.desc, sizeof(table));
-    table[m.object_index] = ptmesh::TexDesc{};
-    PT_HIP(hipMemcpy(M.d_desc, table, sizeof(table), hipMemcpyHostToDevice));
-    memcpy(M.desc, table, sizeof(table));
-    M.d_texels[mesh].reset();
-    std::vector<float>().swap(m.uvs);
-    m.n_uvs = 0; m.tex_w = m.tex_h = 0; m.tex_filter = m.tex_wrap = 0; m.uv_per_corner = false;
-  } else {
-    const std::string bad = ptmesh::check_texture(mesh, m.n_vertices, m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, t);
-    if (!bad.empty()) return fail(h, PT_ERR_INVALID_ARGUMENT, bad);   // the mesh keeps what it had
-    std::vector<float> corner;
-    ptmesh::corner_uvs(m.n_triangles, M.indices.data() + 3 * (size_t)m.tri_base, t->uvs, t->uv_indices, corner);
-    std::vector<ptmesh::F4> texels;
-    ptmesh::texel_vectors(t, texels);
-    if (M.d_texels.size() < M.mesh.size()) M.d_texels.resize(M.mesh.size());
-    PT_HIP(hipSetDevice(h->cfg.device));
-    if (!M.d_uvs) {
-      size_t triangles = 0;
-      for (const pt_context::MeshSet::One& o : M.mesh) triangles += o.n_triangles;
-      DevBuf<float> uvs;
-      DevBuf<ptmesh::TexDesc> desc;
-      hipError_t e = dev_alloc(uvs, 6 * triangles);
-      if (e == hipSuccess) e = dev_alloc(desc, PT_MAX_SCENE_OBJECTS);
-      if (e == hipSuccess) e = hipMemset(uvs, 0, 6 * triangles * sizeof(float));
-      if (e != hipSuccess)
-        return fail(h, hip_status(e), "pt_set_mesh_texture: allocating " + std::to_string(6 * triangles * sizeof(float) + sizeof(M.desc)) + " bytes: " + hipGetErrorString(e));
-      M.d_uvs = std::move(uvs);
-      M.d_desc = std::move(desc);
-    }
-    DevBuf<ptmesh::F4> image;
-    hipError_t e = dev_alloc(image, texels.size());
-    if (e == hipSuccess) e = hipMemcpy(image, texels.data(), texels.size() * sizeof(ptmesh::F4), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-      return fail(h, hip_status(e), "pt_set_mesh_texture: allocating " + std::to_string(texels.size() * sizeof(ptmesh::F4)) + " bytes: " + hipGetErrorString(e));
-    if (mesh_device_option(h))   // (pt_set_mesh_build: the triangle-order copy the device builder expands from)
-      if (int rc = ensure_mesh_device(h, M, false, true)) return rc;
-    PT_HIP(drain());
-    ptmesh::TexDesc d{};
-    d.texels = image; d.width = t->width; d.height = t->height; d.filter = t->filter; d.wrap = t->wrap;
-    ptmesh::TexDesc table[PT_MAX_SCENE_OBJECTS];   // the new table in a temporary: a failed copy leaves the host's table, and with it
-    memcpy(table, M.desc, sizeof(table));          // every later upload, without a pointer into the image freed on the way out
-    table[m.object_index] = d;
-    PT_HIP(hipMemcpy(M.d_desc, table, sizeof(table), hipMemcpyHostToDevice));
-    memcpy(M.desc, table, sizeof(table));
-    M.d_texels[mesh] = std::move(image);   // (frees the image it replaces)
-    m.uvs.swap(corner);
-    m.n_uvs = t->n_uvs; m.tex_w = t->width; m.tex_h = t->height; m.tex_filter = t->filter; m.tex_wrap = t->wrap;
-    m.uv_per_corner = t->uv_indices != nullptr;
-    if (int rc = upload_mesh_corners(h, M, mesh)) return rc;
-  }
-  } catch (const std::bad_alloc&) {
-    return fail(h, PT_ERR_OUT_OF_MEMORY, "pt_set_mesh_texture: out of host memory for the texture's copy");
-  }
-  M.built = false;        // the next trace rebuilds: rows' flags and the uvs in slot order
-  M.topo_builder = -1;    // (a build, never a refit: pt_set_mesh_build)
-  h->feature_gen += 1;
-  return PT_OK;
-}
-
-int pt_get_mesh_texture_info(pt_handle h, uint32_t mesh, pt_mesh_texture_info* out) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!out || out->struct_size != sizeof(pt_mesh_texture_info))
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_texture_info: struct_size must be " + std::to_string(sizeof(pt_mesh_texture_info)));
-  const size_t count = (h->scene_n && h->scene_mesh) ? h->mesh.mesh.size() : 0;
-  if (mesh >= count)
-    return fail(h, PT_ERR_INVALID_ARGUMENT, "pt_get_mesh_texture_info: mesh " + std::to_string(mesh) + " of " + std::to_string(count) + " in the scene in force");
-  const pt_context::MeshSet::One& m = h->mesh.mesh[mesh];
-  memset(out, 0, sizeof(*out));
-  out->struct_size = sizeof(*out);
-  if (m.uvs.empty()) return PT_OK;
-  out->has_texture = 1u;
-  out->per_corner = m.uv_per_corner ? 1u : 0u;
-  out->width = m.tex_w; out->height = m.tex_h;
-  out->filter = m.tex_filter; out->wrap = m.tex_wrap;
-  out->n_uvs = m.n_uvs;
-  out->device_bytes = (uint64_t)m.n_triangles * 6 * sizeof(float) + (uint64_t)m.tex_w * m.tex_h * sizeof(ptmesh::F4);
-  return PT_OK;
-}
-
-int pt_mesh_texel(pt_handle h, const float* origin, const float* dir, size_t n, float* out_t, int32_t* out_object, int32_t* out_triangle,
-                  float* out_uv, float* out_bgr) {
-  if (!h) return PT_ERR_INVALID_ARGUMENT;
-  if (!h->scene_n || !h->scene_mesh) return fail(h, PT_ERR_NOT_READY, "pt_mesh_texel: the scene in force holds no mesh (pt_set_scene_meshes)");
-  if (n == 0) return PT_OK;
-  if (!origin || !dir || !out_t || !out_object || !out_triangle || !out_uv || !out_bgr) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  if (n >= (1ull << 31) / 3) return fail(h, PT_ERR_INVALID_ARGUMENT, "too many rays");
-  if (int rc = ensure_meshes(h, true)) return rc;   // the world frame, whatever the camera
-  ptd::TraceParams P;
-  memset(&P, 0, sizeof(P));
-  fill_scene(P, h->scene, h->scene_n, nullptr, h->scene_poly ? h->scene_vertex : nullptr, h->mesh.row);
-  bind_meshes(h, P);
-  const ptd::TexParams X = tex_params(h);   // (no textured mesh: every row's flag is 0 and the kernel reads neither pointer)
-  GuideSpan s[7] = {{origin, nullptr, n * 12, nullptr}, {dir, nullptr, n * 12, nullptr}, {nullptr, out_t, n * 4, nullptr},
-                    {nullptr, out_object, n * 4, nullptr}, {nullptr, out_triangle, n * 4, nullptr}, {nullptr, out_uv, n * 8, nullptr},
-                    {nullptr, out_bgr, n * 12, nullptr}};
-  return guide_hook(h, s, 7, [&]() {
-    hipLaunchKernelGGL(ptd::mesh_texel_kernel, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, h->stream, P, X,
-                       reinterpret_cast<const float*>(s[0].dev), reinterpret_cast<const float*>(s[1].dev), (uint32_t)n,
-                       reinterpret_cast<float*>(s[2].dev), reinterpret_cast<int32_t*>(s[3].dev), reinterpret_cast<int32_t*>(s[4].dev),
-                       reinterpret_cast<float*>(s[5].dev), reinterpret_cast<float*>(s[6].dev));
-  });
-}
-
 int pt_get_scene_ex(pt_handle h, pt_scene_object_ex* out, uint32_t capacity, uint32_t* n) {
   if (!n) return h ? fail(h, PT_ERR_INVALID_ARGUMENT, "null count") : PT_ERR_INVALID_ARGUMENT;
   pt_scene_object builtin[ptd::kBuiltinObjects];
@@ -2025,38 +1464,24 @@ int pt_trace_paths(pt_handle h, const uint16_t* u, const uint16_t* v, const uint
                    pt_path_record* out) {
   if (!h) return PT_ERR_INVALID_ARGUMENT;
   if (!h->settings_valid) return fail(h, PT_ERR_NOT_READY, "pt_set_render_settings has not been called");
-  if (n == 0) return PT_OK;
-  if (!u || !v || !sample_index || !out) return fail(h, PT_ERR_INVALID_ARGUMENT, "null buffer");
-  PT_HIP(hipSetDevice(h->cfg.device));
   static_assert(sizeof(pt_path_record) == sizeof(ptd::PathRecordOut), "pt_path_record layout");
-  const size_t bytes = n * (2 + 2 + 4) + 16 + n * sizeof(pt_path_record);
-  int rc = ensure_scratch(h, bytes);
-  if (rc) return rc;
-  char* base = h->d_scratch;
-  ptd::PathRecordOut* d_out = reinterpret_cast<ptd::PathRecordOut*>(base);
-  uint32_t* d_s = reinterpret_cast<uint32_t*>(base + n * sizeof(pt_path_record));
-  uint16_t* d_u = reinterpret_cast<uint16_t*>(d_s + n);
-  uint16_t* d_v = d_u + n;
-  PT_HIP(hipMemcpyAsync(d_s, sample_index, n * 4, hipMemcpyHostToDevice, h->stream));
-  PT_HIP(hipMemcpyAsync(d_u, u, n * 2, hipMemcpyHostToDevice, h->stream));
-  PT_HIP(hipMemcpyAsync(d_v, v, n * 2, hipMemcpyHostToDevice, h->stream));
-  if (int rc = ensure_meshes(h)) return rc;
-  ptd::TraceParams P;
-  fill_trace_params(h, P);
-  P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
-  const ptvariant::Variant var = variant_in_force(h, P);   // the instance of the production kernel's bounce and geometry (the camera: read at run time)
-  const int i = ptvariant::paths_index(var.bounce, var.geometry);
-  note_variant(h->variant_paths, var, i);   // (pt_get_trace_variant)
-  if (i >= ptvariant::kPathsTexFirst)   // the textured twins (pt_set_mesh_texture)
-    hipLaunchKernelGGL(kPathsTexKernels[i - ptvariant::kPathsTexFirst], dim3(((uint32_t)n + 127) / 128), dim3(128),
-                       ptd::hit_table_bytes(P.n_objects), h->stream, P, tex_params(h), d_u, d_v, d_s, (uint32_t)n, d_out);
-  else
-    hipLaunchKernelGGL(kPathsKernels[i], dim3(((uint32_t)n + 127) / 128), dim3(128),
-                       ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
-  PT_HIP(hipGetLastError());
-  PT_HIP(hipMemcpyAsync(out, d_out, n * sizeof(pt_path_record), hipMemcpyDeviceToHost, h->stream));
-  PT_HIP(hipStreamSynchronize(h->stream));
-  return PT_OK;
+  return probe(h, n, kNoProbeLimit, std::tuple{out_as<ptd::PathRecordOut>(out), in(sample_index), in(u), in(v)},
+               [&](ptd::PathRecordOut* d_out, const uint32_t* d_s, const uint16_t* d_u, const uint16_t* d_v) -> int {
+    if (int rc = ensure_meshes(h)) return rc;
+    ptd::TraceParams P;
+    fill_trace_params(h, P);
+    P.emitted = nullptr;   // (the trace-paths kernel counts nothing)
+    const ptvariant::Variant var = variant_in_force(h, P);   // the instance of the production kernel's bounce and geometry (the camera: read at run time)
+    const int i = ptvariant::paths_index(var.bounce, var.geometry);
+    note_variant(h->variant_paths, var, i);   // (pt_get_trace_variant)
+    if (i >= ptvariant::kPathsTexFirst)   // the textured twins (pt_set_mesh_texture)
+      hipLaunchKernelGGL(kPathsTexKernels[i - ptvariant::kPathsTexFirst], dim3(((uint32_t)n + 127) / 128), dim3(128),
+                         ptd::hit_table_bytes(P.n_objects), h->stream, P, tex_params(h), d_u, d_v, d_s, (uint32_t)n, d_out);
+    else
+      hipLaunchKernelGGL(kPathsKernels[i], dim3(((uint32_t)n + 127) / 128), dim3(128),
+                         ptd::hit_table_bytes(P.n_objects), h->stream, P, d_u, d_v, d_s, (uint32_t)n, d_out);
+    return PT_OK;
+  });
 }
 
 // The instance each kernel family's last launch took (include/ptmi.h): the handle's three records, as the launch sites left them.
@@ -2082,6 +1507,7 @@ int pt_get_trace_variant(pt_handle h, pt_trace_variant_info* out) {
 
 }  // extern "C"
 
+#include "ptmi_mesh_api.h"
 #include "ptmi_film_comm.h"
 #include "ptmi_denoise.h"
 #include "ptmi_nif_train.h"

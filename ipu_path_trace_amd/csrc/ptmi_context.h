@@ -1,7 +1,7 @@
 // ptmi_context.h -- the owners of device and pinned memory, per-handle state (pt_context), error helpers, trace parameters
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with ptmi_nif_group.h
-// among the stages of a step], ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_probe.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with
+// ptmi_nif_group.h among the stages of a step], ptmi_mesh_api.h, ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
 #pragma once
 
 using ptplan::TraceGrid;
@@ -218,6 +218,7 @@ struct pt_context {
       std::vector<float> uvs;
     };
     std::vector<One> mesh;                 // in declaration order
+    size_t triangles() const { size_t t = 0; for (const One& m : mesh) t += m.n_triangles; return t; }   // of all meshes
     std::vector<float> world;              // twelve floats per triangle (v0, e1, e2, n), the meshes one after the other
     DevBuf<ptmesh::Node> d_nodes;          // mesh m at node_base = sum over the meshes before it of 2 T - 1
     DevBuf<ptmesh::F4> d_tris;             // three per slot, mesh m's slots from tri_base
@@ -476,6 +477,13 @@ inline int hip_status(hipError_t e) {
 int fail(pt_handle h, int code, const std::string& msg) {
   h->error = msg;
   return code;
+}
+
+// The pt_get_*_info entry points' check of their output: null, or a struct of another size than this library's.
+template <class Info>
+int check_info(pt_handle h, const Info* out, const char* who) {
+  if (out && out->struct_size == sizeof(Info)) return PT_OK;
+  return fail(h, PT_ERR_INVALID_ARGUMENT, std::string(who) + ": struct_size must be " + std::to_string(sizeof(Info)));
 }
 
 // (a name for Buf::alloc that an error message quotes: PT_HIP(dev_alloc(h->d_film, n)) reads "dev_alloc(h->d_film, n): ...")

@@ -1,7 +1,7 @@
 // ptmi_film_comm.h -- resident film, per-tile costs and the RCCL hand-off of HDR tiles (entry points of include/ptmi.h)
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with ptmi_nif_group.h
-// among the stages of a step], ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_probe.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with
+// ptmi_nif_group.h among the stages of a step], ptmi_mesh_api.h, ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
 #pragma once
 
 // ---- multi-GPU film hand-off over RCCL --------------------------------------------------------------------------

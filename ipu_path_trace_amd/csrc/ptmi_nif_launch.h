@@ -1,8 +1,8 @@
 // ptmi_nif_launch.h -- the two bindings of a NIF queue, the launchers of the NIF kernels: fused (pt_nif.h), layer by layer
 // (pt_nif_gemm.h), float32 (pt_nif_f32.h), and the event allocator of a step
 // Part of the one translation unit ptmi.hip (host side of include/ptmi.h); included there, in this order:
-// ptmi_step_plan.h, ptmi_context.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with ptmi_nif_group.h
-// among the stages of a step], ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
+// ptmi_step_plan.h, ptmi_context.h, ptmi_probe.h, ptmi_nif_pack.h, ptmi_nif_launch.h, [ptmi.hip: the entry points, with
+// ptmi_nif_group.h among the stages of a step], ptmi_mesh_api.h, ptmi_film_comm.h, ptmi_denoise.h, ptmi_nif_train.h.
 #pragma once
 
 namespace {
