@@ -709,6 +709,50 @@ typedef struct pt_mesh_node {         /* 32 bytes: a node as the kernels read it
 } pt_mesh_node;
 int pt_mesh_tree(pt_handle h, uint32_t mesh, pt_mesh_node* nodes, uint32_t node_capacity, uint32_t* orig, uint32_t orig_capacity);
 
+/* SAH trees built on the device -- an EXTENSION, opt-in and additive: PTMI_ABI_VERSION stays 5, no existing struct or enum moves,
+ * no trace kernel is added or changed, and a process that never calls pt_set_mesh_device_tree builds what it built before.
+ *
+ * The option.  kind says WHICH tree PT_MESH_BUILDER_DEVICE builds: PT_MESH_DEVICE_TREE_LINEAR (the default: the linear BVH above,
+ * of which "tree quality is below SAH" stays true) or PT_MESH_DEVICE_TREE_SAH.  The kind belongs to the handle and survives
+ * pt_set_scene*, as the build options do.  Under PT_MESH_BUILDER_HOST it is accepted and inert.  A change of kind while builder
+ * is DEVICE makes the trees of the scene in force stale, exactly as a change of builder does: they are built again before
+ * whatever traces next, and no refit keeps a tree of the other kind.  Validation, in this order, before any device call: kind
+ * ("pt_set_mesh_device_tree: kind must be 0 (linear) or 1 (sah) (got N)"), then a NULL handle; both through pt_last_error(NULL)
+ * when the handle is NULL.
+ *
+ * The rule.  The tree of PT_MESH_DEVICE_TREE_SAH IS the host builder's (ptmesh::build, csrc/ptmi_mesh.h) of the same kernel-frame
+ * triangles, byte for byte: the nodes (padded boxes, skip, leaf word), the slot -> triangle map, n_nodes, depth, max_leaf and pad.
+ * It can be, because the host builder's reductions are min / max and integer counts (exact in any order), its cost scan is a
+ * fixed loop with strict <, its partition is stable, and library and test programs are compiled with -ffp-contract=off.
+ * csrc/pt_mesh_sah.h states the rule and its parallel form -- breadth-first over the open ranges of one index array; per level:
+ * centroid bounds and 3 x 16 bins per open range by integer atomics on order-preserving words, one thread per range for the two
+ * scans, and a stable partition by a prefix sum of the goes-left flags -- ONE set of functions for the kernels and the test
+ * program (tests/mesh_sah_main.cpp).  The host reads two words per level (the next level's range counts) and stops when no range
+ * is open; last_levels reports how many levels the last build ran (the tree's depth - 1).  The depth cap of 48 is the host's;
+ * 48 levels are out of reach of small valid fixtures in binary32, so the test program exercises the cap at 2 and 3.
+ * Everything traced through such a tree is what the host builder's tree gives: they are the same bytes.
+ *
+ * Where it applies.  Every build PT_MESH_BUILDER_DEVICE runs: pt_set_scene_meshes, a pose change under PT_MESH_POSE_REBUILD, the
+ * build after pt_set_mesh_normals / pt_set_mesh_texture, and pt_update_mesh_vertices(..., PT_MESH_UPDATE_REBUILD), which rebuilds
+ * that one mesh.  Refits keep the SAH topology (the refit above serves any depth-first tree).
+ *
+ * Counters.  A SAH device build counts in pt_mesh_build_info.device_builds with last_kind == PT_MESH_LAST_DEVICE_BUILD, and in
+ * sah_builds here; last_ms is that pass's device time.
+ *
+ * Memory.  While the kind is SAH under a device option (builder DEVICE or on_pose REFIT) the handle holds, beside the above, the
+ * SAH builder's arrays for the LARGEST mesh: about 143 BYTES PER TRIANGLE -- boxes (24), two index arrays and two range maps (16),
+ * the flags' prefix sums (4), six words per node for 2 T nodes (48), the open lists and splits of a level (44 per 5 triangles)
+ * and a 1368-byte bin table per 33 triangles (42).  They are allocated by pt_set_mesh_device_tree for the scene in force, by
+ * pt_set_mesh_build when it turns a device option on under the kind, and at every pt_set_scene_meshes under both; a build
+ * allocates nothing.  PT_ERR_OUT_OF_MEMORY leaves the previous kind, or the previous scene, in force.  device_bytes reports the
+ * addition (pt_mesh_build_info.device_bytes includes it); it is given back with the scene.  The builder is written for
+ * meshes of at most PT_MAX_MESH_TRIANGLES (2^22) triangles, which is all a scene can hold. */
+enum { PT_MESH_DEVICE_TREE_LINEAR = 0, PT_MESH_DEVICE_TREE_SAH = 1 };
+int pt_set_mesh_device_tree(pt_handle h, int32_t kind);        /* which tree PT_MESH_BUILDER_DEVICE builds; default LINEAR */
+typedef struct pt_mesh_device_tree_info { uint32_t struct_size; int32_t kind; uint64_t sah_builds;
+  uint32_t last_levels, reserved; double last_ms; uint64_t device_bytes; } pt_mesh_device_tree_info;   /* 40 bytes */
+int pt_get_mesh_device_tree_info(pt_handle h, pt_mesh_device_tree_info* out);
+
 /* Animated meshes: one mesh's vertices replaced on the device and its tree refitted or rebuilt -- an EXTENSION, opt-in and
  * additive: PTMI_ABI_VERSION stays 5, no existing struct moves, no trace, NIF, sharing or accumulate kernel is added or changed,
  * and a process that never calls pt_update_mesh_vertices launches what it launched before, call for call.

@@ -246,8 +246,13 @@ struct pt_context {
       DevBuf<uint8_t> sort_tmp;                      // the radix sort's temporary storage
       size_t cap = 0;                                // triangles of the largest mesh
       uint64_t bytes = 0;
+      // pt_set_mesh_device_tree (ptmi_mesh_sah.h): the SAH builder's arrays (ptsah::Work) for the largest mesh, allocated while
+      // the kind is PT_MESH_DEVICE_TREE_SAH under a device option
+      DevBuf<uint32_t> sah_words;
+      uint64_t sah_bytes = 0;
     } dev;
     int topo_builder = -1;                           // the builder whose topology lies on the device for these triangles (-1: none a refit may use)
+    int topo_kind = 0;                               // ... and, for the device builder, the kind of tree (PT_MESH_DEVICE_TREE_*)
     // pt_update_mesh_vertices (ptmi_mesh_update.h): allocated by the first update of the scene, beside `dev` -- empty for a
     // handle that never updates a mesh
     struct Update {
@@ -271,6 +276,11 @@ struct pt_context {
   int32_t mesh_last_kind = 0;
   double mesh_last_ms = 0;
   hipEvent_t mesh_event[2] = {nullptr, nullptr};     // start / stop of one mesh's device work on `stream`
+  // pt_set_mesh_device_tree: which tree the device builder builds; belongs to the handle like the options above
+  int32_t mesh_device_tree = 0;                      // PT_MESH_DEVICE_TREE_LINEAR
+  uint64_t mesh_sah_builds = 0;
+  uint32_t mesh_sah_last_levels = 0;
+  double mesh_sah_last_ms = 0;
 
   // pt_get_trace_variant: what the selector picked at the last launch of each kernel family, written at the launch sites
   pt_trace_variant_launch variant_trace{-1, -1, -1, -1, 0}, variant_paths{-1, -1, -1, -1, 0}, variant_features{-1, -1, -1, -1, 0};
@@ -668,9 +678,10 @@ int build_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam
 namespace {
 
 // The trees of M for the frame of `cam`, by the options in force (pt_set_mesh_build): a refit where trees of these triangles by
-// the builder in force lie on the device and only the frame changes, else a build by that builder.
+// the builder in force (and, on the device, of the kind in force) lie on the device and only the frame changes, else a build by
+// that builder.
 int update_meshes(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam) {
-  if (h->mesh_on_pose == PT_MESH_POSE_REFIT && M.topo_builder == h->mesh_builder && M.dev.world) return refit_meshes(h, M, cam);
+  if (h->mesh_on_pose == PT_MESH_POSE_REFIT && mesh_topology_in_force(h, M) && M.dev.world) return refit_meshes(h, M, cam);
   if (h->mesh_builder == PT_MESH_BUILDER_DEVICE) return build_meshes_device(h, M, cam);
   return build_meshes(h, M, cam);
 }

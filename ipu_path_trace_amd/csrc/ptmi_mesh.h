@@ -281,8 +281,8 @@ inline Box tri_box(const float* fr) {
 
 class Builder {
  public:
-  Builder(const float* frames, uint32_t n_triangles, Built& out, float pad_scale)
-      : fr_(frames), n_(n_triangles), out_(out), pad_scale_(pad_scale) {}
+  Builder(const float* frames, uint32_t n_triangles, Built& out, float pad_scale, uint32_t max_depth = kMaxDepthSah)
+      : fr_(frames), n_(n_triangles), out_(out), pad_scale_(pad_scale), max_depth_(max_depth) {}
 
   void run() {
     out_ = Built{};
@@ -336,7 +336,7 @@ class Builder {
       out_.nodes[self].skip = self + 1u;
       return;
     }
-    uint32_t mid = depth < kMaxDepthSah ? sah_split(b, e) : b;
+    uint32_t mid = depth < max_depth_ ? sah_split(b, e) : b;
     if (mid <= b || mid >= e) mid = b + count / 2;   // no split by SAH: halve the range as it lies
     node(b, mid, depth + 1);
     node(mid, e, depth + 1);
@@ -401,6 +401,7 @@ class Builder {
   uint32_t n_;
   Built& out_;
   float pad_scale_;
+  uint32_t max_depth_;
   std::vector<Box> boxes_;
   std::vector<float> centre_;
   std::vector<uint32_t> idx_;
@@ -408,8 +409,10 @@ class Builder {
 
 // The tree over n_triangles frames in the kernel's frame (n_triangles >= 1).  pad_scale: the library always takes the default;
 // tests/mesh_bvh_main.cpp builds one exact fixture with 0, where boxes without a margin show the walk's NaN and tie rules.
-inline void build(const float* frames, uint32_t n_triangles, Built& out, float pad_scale = kPadScale) {
-  Builder(frames, n_triangles, out, pad_scale).run();
+// max_depth: the depth from which ranges are halved as they lie; the library always takes the default -- 48 levels are out of
+// reach of small valid fixtures in binary32, so tests/mesh_sah_main.cpp exercises the cap at 2 and 3.
+inline void build(const float* frames, uint32_t n_triangles, Built& out, float pad_scale = kPadScale, uint32_t max_depth = kMaxDepthSah) {
+  Builder(frames, n_triangles, out, pad_scale, max_depth).run();
 }
 
 }  // namespace ptmesh

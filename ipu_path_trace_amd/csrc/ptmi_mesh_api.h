@@ -156,7 +156,40 @@ int pt_get_mesh_build_info(pt_handle h, pt_mesh_build_info* out) {
   out->refits = h->mesh_refits;
   out->last_kind = h->mesh_last_kind;
   out->last_ms = h->mesh_last_ms;
-  out->device_bytes = (h->scene_n && h->scene_mesh) ? h->mesh.dev.bytes : 0u;
+  out->device_bytes = (h->scene_n && h->scene_mesh) ? h->mesh.dev.bytes + h->mesh.dev.sah_bytes : 0u;
+  return PT_OK;
+}
+
+// Which tree PT_MESH_BUILDER_DEVICE builds (include/ptmi.h).  The SAH builder's arrays are allocated here, before the kind
+// changes: a failed allocation leaves it as it was.
+static_assert(sizeof(pt_mesh_device_tree_info) == 40, "pt_mesh_device_tree_info layout");
+int pt_set_mesh_device_tree(pt_handle h, int32_t kind) {
+  if (kind != PT_MESH_DEVICE_TREE_LINEAR && kind != PT_MESH_DEVICE_TREE_SAH) {
+    const std::string bad = "pt_set_mesh_device_tree: kind must be 0 (linear) or 1 (sah) (got " + std::to_string(kind) + ")";
+    if (h) h->error = bad; else g_create_error = bad;
+    return PT_ERR_INVALID_ARGUMENT;
+  }
+  if (!h) { g_create_error = "pt_set_mesh_device_tree: null handle"; return PT_ERR_INVALID_ARGUMENT; }
+  if (kind == PT_MESH_DEVICE_TREE_SAH && mesh_device_option(h) && h->scene_n && h->scene_mesh)
+    if (int rc = ensure_mesh_device(h, h->mesh, false, false, true)) return rc;
+  if (kind != h->mesh_device_tree && h->mesh_builder == PT_MESH_BUILDER_DEVICE) {   // the other kind's trees: stale, and no refit may keep them
+    h->mesh.built = false;
+    h->mesh.topo_builder = -1;
+  }
+  h->mesh_device_tree = kind;
+  return PT_OK;
+}
+
+int pt_get_mesh_device_tree_info(pt_handle h, pt_mesh_device_tree_info* out) {
+  if (!h) return PT_ERR_INVALID_ARGUMENT;
+  if (int rc = check_info(h, out, "pt_get_mesh_device_tree_info")) return rc;
+  memset(out, 0, sizeof(*out));
+  out->struct_size = sizeof(*out);
+  out->kind = h->mesh_device_tree;
+  out->sah_builds = h->mesh_sah_builds;
+  out->last_levels = h->mesh_sah_last_levels;
+  out->last_ms = h->mesh_sah_last_ms;
+  out->device_bytes = (h->scene_n && h->scene_mesh) ? h->mesh.dev.sah_bytes : 0u;
   return PT_OK;
 }
 

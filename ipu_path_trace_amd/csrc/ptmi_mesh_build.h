@@ -6,6 +6,7 @@
 // use arrival counters, the first thread to arrive returns (pt_mesh_build.h: arrive).
 #pragma once
 #include "pt_mesh_build.h"
+#include "pt_mesh_sah.h"
 
 // The keys are sorted by the radix sort below (pt_mesh_build_info.sort_on_device = 1).  rocprim's radix sort is not used: its
 // host side reads an environment variable, which the product library must not do, and its one-sweep kernels look back at other
@@ -168,6 +169,11 @@ __global__ void lbvh_pad_kernel(uint32_t threads, Node* nodes, const uint32_t* _
 namespace {
 
 inline bool mesh_device_option(pt_handle h) { return h->mesh_builder == PT_MESH_BUILDER_DEVICE || h->mesh_on_pose == PT_MESH_POSE_REFIT; }
+// Do the trees on the device (if any) have the topology a build by the options in force would give them: the builder's and, on
+// the device, the kind's (pt_set_mesh_device_tree).  Only then may a refit keep them.
+inline bool mesh_topology_in_force(pt_handle h, const pt_context::MeshSet& M) {
+  return M.topo_builder == h->mesh_builder && (h->mesh_builder != PT_MESH_BUILDER_DEVICE || M.topo_kind == h->mesh_device_tree);
+}
 
 inline ptlbvh::Scratch mesh_scratch(const pt_context::MeshSet::DeviceBuild& D) {
   uint32_t* w = D.words;
@@ -188,8 +194,9 @@ int upload_mesh_corners(pt_handle h, pt_context::MeshSet& M, size_t mesh) {
 
 // Everything the device paths need for the meshes of M, allocated and filled unless it is there already: the world frames, the
 // triangle-order corner normals and uvs (where a mesh has them, or is about to: want_normals / want_uvs), and the builder's
-// arrays for the largest mesh.  A failed allocation leaves M with what it had (a part that did get allocated stays, unused).
-int ensure_mesh_device(pt_handle h, pt_context::MeshSet& M, bool want_normals = false, bool want_uvs = false) {
+// arrays for the largest mesh -- the SAH builder's too while that kind is in force, or about to be (want_sah).  A failed
+// allocation leaves M with what it had (a part that did get allocated stays, unused).
+int ensure_mesh_device(pt_handle h, pt_context::MeshSet& M, bool want_normals = false, bool want_uvs = false, bool want_sah = false) {
   PT_HIP(hipSetDevice(h->cfg.device));
   pt_context::MeshSet::DeviceBuild& D = M.dev;
   size_t total = 0, cap = 0;
@@ -220,6 +227,11 @@ int ensure_mesh_device(pt_handle h, pt_context::MeshSet& M, bool want_normals = 
     D.words = std::move(words); D.stats = std::move(stats); D.sort_tmp = std::move(sort_tmp);
     D.cap = cap;
     D.bytes += 2 * cap * 12 + n_words * 4 + ptlbvh::kStats * M.mesh.size() * 4 + sort_bytes;
+  }
+  if ((want_sah || h->mesh_device_tree == PT_MESH_DEVICE_TREE_SAH) && !D.sah_words) {
+    const size_t words = ptsah::work_words((uint32_t)D.cap);
+    if ((e = dev_alloc(D.sah_words, words)) != hipSuccess) return oom(e, words * 4);
+    D.sah_bytes = words * 4;
   }
   bool fresh = false;
   if ((want_normals || M.smooth()) && !D.corner) {
@@ -337,7 +349,11 @@ static int build_mesh_device(pt_handle h, pt_context::MeshSet& M, size_t k, cons
   return mesh_fit_and_read(h, M, k, 2 * T - 1, stats_host);
 }
 
-// build_meshes on the device: every mesh of M in the frame of `cam`.
+}  // (namespace: ptmi_mesh_sah.h opens its own)
+#include "ptmi_mesh_sah.h"
+namespace {
+
+// build_meshes on the device: every mesh of M in the frame of `cam`, by the kind of tree in force.
 int build_meshes_device(pt_handle h, pt_context::MeshSet& M, const ptcamera::Basis* cam) {
   if (int rc = drain_for_meshes(h, M)) return rc;
   M.built = false;
@@ -345,12 +361,14 @@ int build_meshes_device(pt_handle h, pt_context::MeshSet& M, const ptcamera::Bas
   const ptlbvh::Pose P = ptlbvh::pose_of(cam);
   double total_ms = 0;
   for (size_t k = 0; k < M.mesh.size(); ++k) {
-    if (int rc = build_mesh_device(h, M, k, P)) return rc;
+    if (int rc = build_mesh_device_of_kind(h, M, k, P)) return rc;
     total_ms += M.mesh[k].build_ms;
   }
   mesh_finish_pass(M, cam);
   M.topo_builder = PT_MESH_BUILDER_DEVICE;
+  M.topo_kind = h->mesh_device_tree;
   note_mesh_pass(h, PT_MESH_LAST_DEVICE_BUILD, total_ms);
+  note_sah_build(h, total_ms);
   return PT_OK;
 }
 

@@ -145,11 +145,11 @@ int mesh_update_rejection(pt_handle h, pt_context::MeshSet& M, uint32_t mesh, ui
 }
 
 // The tree pass after a commit, for mesh k alone where the trees of the scene are valid: a refit in the frame they are built for,
-// or a build by the builder in force.  Stale trees (or another builder's topology) are built whole, for the camera in force, as
+// or a build by the builder in force.  Stale trees (or another builder's or kind's topology) are built whole, for the camera in force, as
 // the next trace would have built them.  kind: the PT_MESH_LAST_* of what ran.
 int mesh_update_tree(pt_handle h, pt_context::MeshSet& M, size_t k, int32_t mode, int& kind, bool& fallback) {
   fallback = false;
-  if (!M.built || M.topo_builder != h->mesh_builder) {
+  if (!M.built || !mesh_topology_in_force(h, M)) {
     const ptcamera::Basis& cb = h->camera_basis;
     const uint64_t refits = h->mesh_refits;
     if (int rc = update_meshes(h, M, cb.identity ? nullptr : &cb)) return rc;
@@ -164,8 +164,9 @@ int mesh_update_tree(pt_handle h, pt_context::MeshSet& M, size_t k, int32_t mode
     if (int rc = refit_mesh(h, M, k, ptlbvh::pose_of(cam))) return rc;
     kind = PT_MESH_LAST_REFIT;
   } else if (h->mesh_builder == PT_MESH_BUILDER_DEVICE) {
-    if (int rc = build_mesh_device(h, M, k, ptlbvh::pose_of(cam))) return rc;
+    if (int rc = build_mesh_device_of_kind(h, M, k, ptlbvh::pose_of(cam))) return rc;
     kind = PT_MESH_LAST_DEVICE_BUILD;
+    note_sah_build(h, M.mesh[k].build_ms);
   } else {
     try {
       if (int rc = refresh_mesh_host(h, M)) return rc;

@@ -112,6 +112,7 @@ std::vector<OptionSpec> PathTracerApp::addToolOptions() {
       {"denoise-sigma-depth", 0, "0.1", false, false, "Relative depth stop of the denoiser; <= 0 disables it."},
       {"save-features", 0, "false", false, true, "Also write the first-hit feature buffers at every save: <basename>_normal.exr (world x, y, z in the B, G, R channels), _albedo.exr (B, G, R) and _depth.exr (the hit distance in all three channels)."},
       {"mesh-builder", 0, "host", false, false, "host | device: who builds the trees of --scene's meshes -- binned SAH on one host thread, or a linear BVH built by kernels (pt_set_mesh_build; faster to build, somewhat slower to trace). The image is bit-identical either way."},
+      {"mesh-device-tree", 0, "linear", false, false, "linear | sah: which tree --mesh-builder device builds -- a linear BVH, or the host builder's binned-SAH tree, byte for byte, built by kernels (pt_set_mesh_device_tree; slower to build than the linear tree, traces as the host's). Inert under --mesh-builder host. The image is bit-identical either way."},
       {"nif-memo-gib", 0, "0", false, false, "GiB of device memory for a memo of decoded NIF values kept across steps, per logical device (0 = off). Exact: the image is bit-identical to off. Escaped paths whose (u, v) an earlier step evaluated are served from it; the memo is forgotten when a new NIF is loaded."},
   };
 }
@@ -121,6 +122,13 @@ std::int32_t meshBuilderMode(const std::string& name) {
   if (name == "host") return PT_MESH_BUILDER_HOST;
   if (name == "device") return PT_MESH_BUILDER_DEVICE;
   throw std::runtime_error("--mesh-builder must be one of host, device; got '" + name + "'");
+}
+
+// --mesh-device-tree (an extension: pt_set_mesh_device_tree)
+std::int32_t meshDeviceTreeKind(const std::string& name) {
+  if (name == "linear") return PT_MESH_DEVICE_TREE_LINEAR;
+  if (name == "sah") return PT_MESH_DEVICE_TREE_SAH;
+  throw std::runtime_error("--mesh-device-tree must be one of linear, sah; got '" + name + "'");
 }
 
 // --share-nif-evaluations (an extension: the reference evaluates the NIF on every escaped path, PathTracerApp.cpp:147-198)
@@ -517,6 +525,7 @@ void PathTracerApp::init(const OptionMap& options) {
   nifSharing = nifSharingMode(args.str("share-nif-evaluations"));
   nifMemo = nifMemoBytes(args.str("nif-memo-gib"));
   meshBuilder = meshBuilderMode(args.str("mesh-builder"));
+  meshDeviceTree = meshDeviceTreeKind(args.str("mesh-device-tree"));
   // --denoise (an extension): the values are checked here, before any device is attached
   denoise = args.flag("denoise");
   saveFeatures = args.flag("save-features");
@@ -747,6 +756,8 @@ void PathTracerApp::attach() {
       const pt_mesh_build_options mo{(std::uint32_t)sizeof(pt_mesh_build_options), meshBuilder, PT_MESH_POSE_REBUILD};
       if (pt_set_mesh_build(h, &mo)) throw std::runtime_error(std::string("--mesh-builder: ") + pt_last_error(h));
     }
+    if (meshDeviceTree != PT_MESH_DEVICE_TREE_LINEAR)   // (the default makes no call at all)
+      if (pt_set_mesh_device_tree(h, meshDeviceTree)) throw std::runtime_error(std::string("--mesh-device-tree: ") + pt_last_error(h));
     if (!sceneMeshes.empty()) {   // the file holds a mesh
       std::vector<pt_mesh> views;
       for (const objreader::Mesh& m : sceneMeshes)

@@ -93,6 +93,7 @@ private:
   double finalSamplesPerSec = 0.0;
   std::int32_t nifSharing = PT_NIF_SHARE_OFF;
   std::int32_t meshBuilder = PT_MESH_BUILDER_HOST;   ///< --mesh-builder: who builds the meshes' trees (pt_set_mesh_build)
+  std::int32_t meshDeviceTree = PT_MESH_DEVICE_TREE_LINEAR;   ///< --mesh-device-tree: which tree the device builder builds (pt_set_mesh_device_tree)
   std::uint64_t nifEscaped = 0, nifEvaluations = 0;
   std::uint64_t nifMemo = 0;   ///< --nif-memo-gib in bytes per logical device, 0 = off
   std::uint64_t memoServed = 0, memoEscaped = 0, memoRows = 0;

@@ -56,7 +56,7 @@ EXPORTS = ["pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_upl
            "pt_get_scene_ex", "pt_set_scene_meshes", "pt_get_mesh_info", "pt_mesh_intersect", "pt_set_mesh_normals",
            "pt_get_mesh_normals_info", "pt_mesh_shade", "pt_set_mesh_texture", "pt_get_mesh_texture_info", "pt_mesh_texel",
            "pt_set_mesh_build", "pt_get_mesh_build_info", "pt_mesh_tree", "pt_update_mesh_vertices", "pt_get_mesh_update_info",
-           "pt_get_trace_variant"]
+           "pt_get_trace_variant", "pt_set_mesh_device_tree", "pt_get_mesh_device_tree_info"]
 # pt_get_trace_variant: the values of ptvariant::Camera, Bounce and Geometry (csrc/ptmi_trace_variant.h), and the three families' sizes
 TRACE_CAMERA_BUILTIN, TRACE_CAMERA_POSE, TRACE_CAMERA_LENS = 0, 1, 2
 TRACE_BOUNCE_PLAIN, TRACE_BOUNCE_ENV_GUIDE, TRACE_BOUNCE_LIGHT_GUIDE, TRACE_BOUNCE_LIGHT_GUIDE_PLAMPS = 0, 1, 2, 3
@@ -73,6 +73,8 @@ MESH_BUILDERS = {"host": MESH_BUILDER_HOST, "device": MESH_BUILDER_DEVICE}
 MESH_POSE_REBUILD, MESH_POSE_REFIT = 0, 1
 MESH_POSES = {"rebuild": MESH_POSE_REBUILD, "refit": MESH_POSE_REFIT}
 MESH_LAST_NONE, MESH_LAST_HOST_BUILD, MESH_LAST_DEVICE_BUILD, MESH_LAST_REFIT = 0, 1, 2, 3
+MESH_DEVICE_TREE_LINEAR, MESH_DEVICE_TREE_SAH = 0, 1
+MESH_DEVICE_TREES = {"linear": MESH_DEVICE_TREE_LINEAR, "sah": MESH_DEVICE_TREE_SAH}
 MESH_NODE_DTYPE = np.dtype([("lo", np.float32, 3), ("hi", np.float32, 3), ("skip", np.uint32), ("leaf", np.uint32)])   # pt_mesh_node
 TEX_FILTER_NEAREST, TEX_FILTER_BILINEAR = 0, 1
 TEX_FILTERS = {"nearest": TEX_FILTER_NEAREST, "bilinear": TEX_FILTER_BILINEAR}
@@ -449,6 +451,15 @@ class MeshBuildInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved")}
 
 
+class MeshDeviceTreeInfo(C.Structure):
+    """pt_mesh_device_tree_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("sah_builds", C.c_uint64), ("last_levels", C.c_uint32),
+                ("reserved", C.c_uint32), ("last_ms", C.c_double), ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("struct_size", "reserved")}
+
+
 class MeshUpdate(C.Structure):
     """pt_mesh_update"""
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("memory", C.c_int32), ("n_vertices", C.c_uint32),
@@ -707,6 +718,8 @@ def load_library(diag=False):
     L.pt_mesh_texel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pt_set_mesh_build.argtypes = [C.c_void_p, C.POINTER(MeshBuildOptions)]
     L.pt_get_mesh_build_info.argtypes = [C.c_void_p, C.POINTER(MeshBuildInfo)]
+    L.pt_set_mesh_device_tree.argtypes = [C.c_void_p, C.c_int32]
+    L.pt_get_mesh_device_tree_info.argtypes = [C.c_void_p, C.POINTER(MeshDeviceTreeInfo)]
     L.pt_update_mesh_vertices.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(MeshUpdate)]
     L.pt_get_mesh_update_info.argtypes = [C.c_void_p, C.POINTER(MeshUpdateInfo)]
     L.pt_get_trace_variant.argtypes = [C.c_void_p, C.POINTER(TraceVariantInfo)]
@@ -1143,6 +1156,20 @@ class Renderer:
         last_ms, device_bytes."""
         info = MeshBuildInfo(struct_size=C.sizeof(MeshBuildInfo))
         self._check(self._lib.pt_get_mesh_build_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
+    def set_mesh_device_tree(self, kind="linear"):
+        """pt_set_mesh_device_tree: which tree the device builder builds -- "linear" (the default: a linear BVH) or "sah" (the
+        host builder's binned-SAH tree, byte for byte, built by kernels).  The kind belongs to the renderer and outlives the
+        scene; under set_mesh_build("host") it is accepted and inert."""
+        if not isinstance(kind, str) or kind not in MESH_DEVICE_TREES:
+            raise ValueError("kind must be one of %s (got %r)" % (sorted(MESH_DEVICE_TREES), kind))
+        self._check(self._lib.pt_set_mesh_device_tree(self.handle, MESH_DEVICE_TREES[kind]))
+
+    def mesh_device_tree_info(self):
+        """pt_get_mesh_device_tree_info as a dict: kind, sah_builds, last_levels, last_ms, device_bytes."""
+        info = MeshDeviceTreeInfo(struct_size=C.sizeof(MeshDeviceTreeInfo))
+        self._check(self._lib.pt_get_mesh_device_tree_info(self.handle, C.byref(info)))
         return info.as_dict()
 
     def _update_array(self, what, a):
