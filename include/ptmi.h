@@ -103,7 +103,7 @@ typedef struct pt_stats {
   uint64_t nif_flops_per_sample; /* NifModel::analyseModel formula (NifModel.cpp:129-133) */
   double path_trace_ms;          /* sum over trace-kernel launches  (path_trace_cycle_count) */
   double nif_ms;                 /* sum over NIF-kernel launches    (nif_cycle_count) */
-  double accumulate_ms;          /* sum over accumulate launches */
+  double accumulate_ms;          /* sum over accumulate launches (on the class map they expand too: pt_nif_class_stats) */
   double total_ms;               /* whole path_trace program        (iter_cycle_count x iterations) */
   uint32_t trace_launches, nif_launches, accumulate_launches;
   uint32_t first_sample;         /* absolute index of the step's first sample iteration (the RNG is keyed by pixel and this index) */
@@ -221,7 +221,7 @@ typedef struct pt_nif_sharing_stats {
   uint64_t evaluations;          /* distinct (u, v) bit pairs the last path_trace handed to its NIF stage: the distinct queues' length (= escaped with sharing off); the rows the network ran are pt_nif_class_stats.mlp_rows */
   uint64_t overflowed;           /* entries evaluated alone because no table slot was free */
   uint64_t table_slots;          /* table capacity in use (0 with sharing off) */
-  double share_ms;               /* device time of the sharing passes (HIP events, read lazily like the stage times); at step scope without the memo these claim the class too (pt_nif_class_stats), and their time is all here */
+  double share_ms;               /* device time of the sharing passes (HIP events, read lazily like the stage times); at step scope without the memo these claim the class too (pt_nif_class_stats), and their time is all here; on the class map with the expansion inside the accumulate passes: the class claim, the raw-pair pass and the release */
 } pt_nif_sharing_stats;
 int pt_set_nif_sharing(pt_handle h, int32_t mode);
 int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
@@ -246,6 +246,9 @@ int pt_get_nif_sharing_stats(pt_handle h, pt_nif_sharing_stats* out);
  * map is cleared once in a handle's life.  The map is allocated by the first such step if it fits a quarter of the free device
  * memory; otherwise the step uses the hashed class table as before, and that is no error.  table_slots then reports the map's
  * words plus the tail's slots.
+ * A step on the map over a worklist of a multiple of four items has no expand pass: its accumulate passes form the escaped
+ * paths' radiance themselves, from the class rows.  pt_nif_sharing_stats.share_ms then covers the class claim, the raw-pair
+ * pass and the release, and pt_stats.accumulate_ms the accumulate passes with the expansion inside.
  * The caller sets struct_size = sizeof(pt_nif_class_stats). */
 typedef struct pt_nif_class_stats {
   uint32_t struct_size;          /* sizeof(pt_nif_class_stats), set by the caller */

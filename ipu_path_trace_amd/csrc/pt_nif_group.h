@@ -48,7 +48,9 @@
 // The mapped step (the fused step wherever the class map is held or fits; ptmi_share_plan.h).  ClassMap indexes the class of a
 // regular (u, v) directly: S(b) is C(b), class_map_claim, which touches no raw table; the raw pairs are claimed and counted by
 // R(b), group_claim over RawCountTable, behind A(b) on the accumulate stream, for the statistics alone; E(b) follows a pending class
-// word itself, so no resolve pass runs; class_map_release_kernel gives the step's words back at its end.
+// word itself, so no resolve pass runs; class_map_release_kernel gives the step's words back at its end.  Over a worklist of a
+// multiple of four items E(b) is inside A(b), accumulate_mapped_kernel: the per-path radiance of an escaped path is never
+// written.
 #pragma once
 
 #include "ptmi_share_plan.h"
@@ -556,17 +558,140 @@ __global__ __launch_bounds__(kShareBlock) void class_map_expand_kernel(GroupExpa
 // R(b): the raw-pair pass (RawCountTable)
 __global__ __launch_bounds__(kShareBlock) void share_raw_claim_kernel(GroupQueue Q, RawCountTable T) { group_claim(Q, T); }
 
+// A(b) of a mapped step with E(b) inside (n % 4 == 0; other worklists keep class_map_expand_kernel and accumulate_kernel): what
+// accumulate4_kernel does, but the radiance of an escaped path is formed here, from the class store, and never written.  The
+// trace kernel has left the inverse slot map in q_path (ptmi_share_plan.h: kNoQueueSlot): a contributing path (bit 7 of its
+// record) reads its slot q; with a slot, its row is owner[q] -- through the map, if that is a pending class word, exactly as
+// group_expand goes for kMapped -- and it adds held[2] * q_tr[q], held[1] * q_tg[q], held[0] * q_tb[q]: group_expand's own
+// expressions, the products rounded to fp32 before the add (no contraction), so film and records are the bytes of E(b) + A(b).
+// Without a slot it ended on an emitter and adds rad_*[path], which the trace kernel wrote.  Nothing is read for a path that does
+// not contribute: what an earlier batch left in its q_path word may be no slot of this batch.
+struct MappedGather {
+  const uint32_t* slot;      // [path]: the inverse map (the set's q_path)
+  const uint32_t* owner;     // [queue slot]
+  const uint32_t* words;     // the class map and, behind it, the tail's values
+  const float* bgr;          // the step's class store
+  const float* q_tr; const float* q_tg; const float* q_tb;
+  const float* rad_r; const float* rad_g; const float* rad_b;   // emitters
+};
+// A path's chain is three dependent loads -- slot, owner word, row and throughputs -- and a thread keeps three groups' chains
+// in flight, one stage apart.  A group is two CONSECUTIVE work items in two consecutive iterations: four paths, like an iteration
+// of accumulate4_kernel, but six accumulators instead of twelve.  While the 24 values of group j are on their way, so are the
+// owner words of group j + 1 and the records and slots of group j + 2, and the thread waits for memory once per group.  (Four
+// items a thread and two whole iterations side by side, 48 values, took 112 VGPRs; four items, three stages, 85; either held to
+// the 80 of the step's budget had scratch: scripts/kernel_resources.py --step-budget.)  A pixel's adds stay in iteration order.
+// The arrays indexed by a path or a queue slot are read at 32-bit BYTE offsets from their uniform base: one register of address
+// per load, not two.  The host launches the kernel only where that holds (ptshare::kMaxSlotsAt32: 4 * queue_cap < 2^32; a
+// batch's path indices are below its queue_cap).  Row indices of the class store reach further and keep 64-bit addresses.
+struct MappedStage {
+  uint32_t pl;      // the group's path records, iteration k in the low half; 0 past the batch's last iteration
+  uint32_t q[4];    // the slots of the contributing paths (2 * iteration + item); kNoQueueSlot for every other path and for one that ended on an emitter
+  uint32_t o[4];    // owner[q] (of slot 0 for a path without one: not looked at)
+  __device__ __forceinline__ bool has(uint32_t c) const { return q[c] != ptshare::kNoQueueSlot; }
+  __device__ __forceinline__ uint32_t slot(uint32_t c) const { return has(c) ? q[c] : 0u; }   // a slot to read in any case
+};
+template <class T>
+__device__ __forceinline__ T at32(const T* base, uint32_t index) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "4-byte elements, one or two of them");
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (uint32_t)(index * 4u));
+}
+// records and slots of the group that starts at iteration k (no branch around the loads: an iteration past the last reads the last)
+__device__ __forceinline__ void mapped_load_slots(const MappedGather& G, const uint8_t* plen, uint32_t n, uint32_t iters, uint32_t i,
+                                                  uint32_t k, MappedStage& s) {
+  uint32_t w[2];
+  uint2 v[2];
+#pragma unroll
+  for (uint32_t j = 0; j < 2; ++j) {
+    const uint32_t p = (k + j < iters ? k + j : iters - 1u) * n + i;   // a batch's path indices stay below 2^31 (pt_create): 32-bit index arithmetic
+    w[j] = *reinterpret_cast<const uint16_t*>(plen + p);
+    v[j] = at32(reinterpret_cast<const uint2*>(G.slot), p);
+    if (k + j >= iters) w[j] = 0u;
+  }
+  s.pl = w[0] | (w[1] << 16);
+  const uint32_t q[4] = {v[0].x, v[0].y, v[1].x, v[1].y};
+#pragma unroll
+  for (uint32_t c = 0; c < 4; ++c) s.q[c] = ((s.pl >> (8u * c + 7u)) & 1u) ? q[c] : ptshare::kNoQueueSlot;   // whatever else the word holds is no slot of this batch
+}
+__device__ __forceinline__ void mapped_load_owners(const MappedGather& G, MappedStage& s) {
+#pragma unroll
+  for (uint32_t c = 0; c < 4; ++c) s.o[c] = at32(G.owner, s.slot(c));
+}
+__global__ __launch_bounds__(256) void accumulate_mapped_kernel(uint32_t n, uint32_t iters, const uint8_t* plen, MappedGather G, Accum A,
+                                                                 unsigned long long* counters) {
+  const uint32_t i = 2u * (blockIdx.x * blockDim.x + threadIdx.x);
+  uint32_t segs = 0, esc = 0;
+  if (i < n) {
+    float2 r = *reinterpret_cast<const float2*>(A.r + i), g = *reinterpret_cast<const float2*>(A.g + i),
+           b = *reinterpret_cast<const float2*>(A.b + i);
+    uint32_t len[2] = {0, 0};
+    MappedStage sa, sb, sc;   // the groups at iterations k, k + 2, k + 4
+    mapped_load_slots(G, plen, n, iters, i, 0u, sa);
+    mapped_load_slots(G, plen, n, iters, i, 2u, sb);
+    mapped_load_owners(G, sa);
+    float* const rc[2] = {&r.x, &r.y};
+    float* const gc[2] = {&g.x, &g.y};
+    float* const bc[2] = {&b.x, &b.y};
+    for (uint32_t k = 0; k < iters; k += 2u) {
+      mapped_load_slots(G, plen, n, iters, i, k + 4u, sc);
+      mapped_load_owners(G, sb);
+      // the group at k: x = the blue, green and red of a path's row, t = its throughputs.  No branch around the loads (a path
+      // without a slot reads row 0 and slot 0, and nothing of it is looked at), so that they go out with the two above.
+      float x[4][3], t[4][3];
+#pragma unroll
+      for (uint32_t c = 0; c < 4; ++c) {
+        uint32_t o = sa.has(c) ? sa.o[c] : 0u;
+        if (!ptshare::owner_is_store(o)) o = G.words[ptshare::owner_slot(o)];   // a pending class word: rare, and the one load that is waited for
+        const float* held = G.bgr + 3 * (size_t)o;
+        x[c][0] = held[0]; x[c][1] = held[1]; x[c][2] = held[2];
+        t[c][0] = at32(G.q_tr, sa.slot(c)); t[c][1] = at32(G.q_tg, sa.slot(c)); t[c][2] = at32(G.q_tb, sa.slot(c));
+      }
+      const uint32_t w = sa.pl;
+      len[0] += (w & 0x7fu) + ((w >> 16) & 0x7fu); len[1] += ((w >> 8) & 0x7fu) + ((w >> 24) & 0x7fu);
+#pragma unroll
+      for (uint32_t c = 0; c < 4; ++c) {   // iteration k's two items, then iteration k + 1's
+        if (!((w >> (8u * c + 7u)) & 1u)) continue;
+        float vr = x[c][2] * t[c][0], vg = x[c][1] * t[c][1], vb = x[c][0] * t[c][2];   // held[2] * tr, held[1] * tg, held[0] * tb
+        if (!sa.has(c)) {   // ended on an emitter: what the trace kernel wrote
+          const uint32_t p = (k + (c >> 1)) * n + i + (c & 1u);
+          vr = G.rad_r[p]; vg = G.rad_g[p]; vb = G.rad_b[p];
+        }
+        *rc[c & 1u] += vr; *gc[c & 1u] += vg; *bc[c & 1u] += vb;
+      }
+      esc += (uint32_t)__popc(w & 0x80808080u);
+      sa = sb; sb = sc;
+    }
+    *reinterpret_cast<float2*>(A.r + i) = r;
+    *reinterpret_cast<float2*>(A.g + i) = g;
+    *reinterpret_cast<float2*>(A.b + i) = b;
+    uint2 cnt = *reinterpret_cast<const uint2*>(A.count + i), ln = *reinterpret_cast<const uint2*>(A.length + i);
+    cnt.x += iters; cnt.y += iters;
+    ln.x += len[0]; ln.y += len[1];
+    *reinterpret_cast<uint2*>(A.count + i) = cnt;
+    *reinterpret_cast<uint2*>(A.length + i) = ln;
+    segs = len[0] + len[1];
+  }
+  accumulate_counters(segs, esc, counters);
+}
+
 // The release at the end of a mapped step: the word of every regular row of the step's class store goes back to kMapEmpty, so
 // that the map is never cleared as a whole (about 6.6 M stores at 1104 x 1000 x 300 spp against a memset of 944 MB).  Rows of
-// irregular classes live in the tail, which the host clears.  Grid (x, batches): batch y's class queue is c_u / c_v + y * region
-// with c_count[y] rows; grid-stride over them.
+// irregular classes live in the tail, which batch 0's workgroups clear whole in the same launch: its tail_slots values behind
+// the map and its keys.  Grid (x, batches): batch y's class queue is c_u / c_v + y * region with c_count[y] rows; grid-stride
+// over them.
 __global__ __launch_bounds__(kShareBlock) void class_map_release_kernel(const float* c_u, const float* c_v, const uint32_t* c_count,
-                                                                        uint32_t region, uint32_t* words) {
+                                                                        uint32_t region, uint32_t* words, unsigned long long* tail_keys,
+                                                                        uint32_t tail_slots) {
   const uint32_t n = c_count[blockIdx.y];
   const size_t base = (size_t)blockIdx.y * region;
   for (uint32_t i = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x; i < n; i += gridDim.x * (uint32_t)kShareBlock) {
     const uint32_t slot = ptshare::class_map_index(c_u[base + i], c_v[base + i]);
     if (slot != ptshare::kClassIrregular) words[slot] = ptshare::kMapEmpty;
+  }
+  if (blockIdx.y == 0) {
+    for (uint32_t i = blockIdx.x * (uint32_t)kShareBlock + threadIdx.x; i < tail_slots; i += gridDim.x * (uint32_t)kShareBlock) {
+      words[ptshare::kClassMapWords + i] = ptshare::kMapEmpty;
+      tail_keys[i] = kShareEmpty;
+    }
   }
 }
 

@@ -403,6 +403,7 @@ struct pt_context {
     bool class_map_clean = false;
     bool class_map_failed = false;             // its allocation failed: the hashed class table from now on
     bool class_map_ran = false;                // the last pt_path_trace was a mapped step
+    uint32_t expand_launches = 0;              // E(b) launches of the last pt_path_trace (0 where A(b) expands: StepMode::expand_in_accumulate)
 
     // persistent memo of decoded NIF values (pt_set_nif_memo).  Unlike the sharing table it outlives the step:
     // it is cleared at allocation, on a new generation (pt_upload_nif, pt_clear_nif_memo, a failed pt_path_trace) and by the

@@ -196,6 +196,9 @@ struct StepMode {
   // class claim alone; the raw-pair pass R(b) runs behind A(b) on the accumulate stream, off the step's critical path; E(b) follows a
   // pending class word itself and no resolve pass runs; the step ends with the release of the words it took
   bool mapped = false;
+  // a mapped step over a worklist of a multiple of four items: no E(b); the trace kernels write the inverse slot map and A(b)
+  // forms the escaped paths' radiance itself (pt_nif_group.h: accumulate_mapped_kernel).  Other worklists keep E(b) + A(b).
+  bool expand_in_accumulate = false;
   bool grouped() const { return share || memo; }   // N runs over distinct queues in the step store
   bool step_scope() const { return memo || share == PT_NIF_SHARE_STEP; }
   ptshare::StepKind kind() const {   // what the step does to the sharing table (ptmi_share_plan.h: the clean-table hand-off)
@@ -389,6 +392,7 @@ static int stage_class_spread(pt_handle h, StepEvents& ev, const Batch& b, hipEv
 // stream, where it runs beside the last NIF launches instead of ahead of the next step's T(0).  `clean` is recorded behind
 // it; the step's end waits for it, and pt_path_trace sets the mark (ptshare::mark_after_step) once the step has returned.
 // A mapped step's last reader of the table is R(b) of its last batch, on the accumulate stream: the clear follows it there.
+// (The last R(b) and the clear on the trace stream, behind C(b), lost an alternating A/B: profiles/r34_expand_in_accumulate.txt.)
 static int enqueue_table_handoff(pt_handle h, StepEvents& ev, hipEvent_t& clean, hipStream_t s) {
   PT_HIP(hipMemsetAsync(h->group.d_share_keys, 0xff, (size_t)h->group.share_slots * 8, s));
   size_t at = 0;
@@ -499,6 +503,7 @@ static int stage_expand(pt_handle h, StepEvents& ev, const StepMode& mode, const
     else if (mode.fused()) hipLaunchKernelGGL(ptd::share_class_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, share_class_table(h, b));
     else hipLaunchKernelGGL(ptd::share_expand_kernel, b.group_grid(), dim3(ptd::kShareBlock), 0, h->acc_stream, X, share_table(h));
     PT_HIP(hipGetLastError());
+    h->group.expand_launches += 1;
     return PT_OK;
   });
 }
@@ -520,16 +525,14 @@ static int stage_raw_pairs(pt_handle h, StepEvents& ev, const Batch& b) {
   return PT_OK;
 }
 
-// The end of a mapped step, on the accumulate stream behind the last E(b): the words of the step's class rows go back to
-// kMapEmpty (counts on the device), and the tail is cleared.  pt_path_trace sets the mark once the step has returned.
+// The end of a mapped step, on the accumulate stream behind the last A(b): the words of the step's class rows go back to
+// kMapEmpty (counts on the device), and the tail is cleared, in one launch.  pt_path_trace sets the mark once the step has returned.
 static int stage_map_release(pt_handle h, StepEvents& ev, uint32_t store_cap, uint32_t batches) {
   return ev.timed(h->acc_stream, pt_context::kSpanShare, [&]() -> int {
     const dim3 grid(std::min<uint32_t>(ptd::kMemoGrid, (store_cap + ptd::kShareBlock - 1u) / ptd::kShareBlock), batches);
     hipLaunchKernelGGL(ptd::class_map_release_kernel, grid, dim3(ptd::kShareBlock), 0, h->acc_stream, h->group.d_class_u, h->group.d_class_v,
-                       h->group.d_class_count, (uint32_t)h->queue_cap, h->group.d_class_map);
+                       h->group.d_class_count, (uint32_t)h->queue_cap, h->group.d_class_map, h->group.d_class_tail_keys, h->group.class_tail_slots);
     PT_HIP(hipGetLastError());
-    PT_HIP(hipMemsetAsync(h->group.d_class_map + ptshare::kClassMapWords, 0xff, (size_t)h->group.class_tail_slots * 4, h->acc_stream));
-    PT_HIP(hipMemsetAsync(h->group.d_class_tail_keys, 0xff, (size_t)h->group.class_tail_slots * 8, h->acc_stream));
     return PT_OK;
   });
 }
@@ -750,6 +753,13 @@ int pt_diag_set_nif_class_capacity(pt_handle h, uint32_t slots) {
   return PT_OK;
 }
 
+// test build only: how many E(b) the last pt_path_trace launched -- 0 in a mapped step whose accumulate passes expand
+int pt_diag_expand_launches(pt_handle h, uint32_t* launches) {
+  if (!h || !launches) return PT_ERR_INVALID_ARGUMENT;
+  *launches = h->group.expand_launches;
+  return PT_OK;
+}
+
 // test build only: the class level's claim and resolve over a distinct queue the caller supplies -- one region of n rows --
 // with buffers of its own and a ClassTable of table_slots slots (a power of two).  Out, on the host: owner [n] (the position
 // in the class queue of every row's class owner), the class queue c_u / c_v [n], its length and the rows evaluated alone.
@@ -912,10 +922,8 @@ int pt_diag_class_map_claim(pt_handle h, const float* u, const float* v, const u
   const dim3 block(ptd::kShareBlock), count_grid(ptd::kMemoGrid);
   auto release = [&]() -> int {   // as stage_map_release: one batch, whose class queue is the whole store
     hipLaunchKernelGGL(ptd::class_map_release_kernel, dim3(std::min<uint32_t>(ptd::kMemoGrid, (uint32_t)((2 * n + ptd::kShareBlock - 1u) / ptd::kShareBlock)), 1),
-                       block, 0, s, cu, cv, len, 0u, words);
+                       block, 0, s, cu, cv, len, 0u, words, tail_keys, tail_slots);
     PT_HIP(hipGetLastError());
-    PT_HIP(hipMemsetAsync(words + ptshare::kClassMapWords, 0xff, (size_t)tail_slots * 4, s));
-    PT_HIP(hipMemsetAsync(tail_keys, 0xff, (size_t)tail_slots * 8, s));
     return PT_OK;
   };
   for (uint32_t launch = 0; launch < launches; ++launch) {

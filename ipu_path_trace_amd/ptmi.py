@@ -765,6 +765,7 @@ def load_library(diag=False):
         L.pt_diag_set_nif_memo_slots.argtypes = [C.c_void_p, C.c_uint32]
         L.pt_diag_claim_resolve.argtypes = [C.c_void_p, C.c_int32, C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p] * 7
         L.pt_diag_set_nif_class_capacity.argtypes = [C.c_void_p, C.c_uint32]
+        L.pt_diag_expand_launches.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.pt_diag_class_claim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
         L.pt_diag_share_class_claim.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 4 + [C.c_void_p] * 6
         L.pt_diag_class_map_claim.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 4 + [C.c_int32] + [C.c_void_p] * 5

@@ -32,7 +32,8 @@ VGPR_GRANULE = 8
 SMALL_KERNELS = ("share_claim_kernel", "share_resolve_kernel", "share_expand_kernel", "memo_lookup_kernel", "memo_resolve_kernel",
                  "memo_expand_kernel", "class_claim_kernel", "class_resolve_kernel", "class_spread_kernel", "share_class_claim_kernel",
                  "share_class_resolve_kernel", "share_class_expand_kernel", "class_map_claim_kernel", "class_map_expand_kernel",
-                 "share_raw_claim_kernel", "class_map_release_kernel", "accumulate_kernel", "accumulate4_kernel")
+                 "share_raw_claim_kernel", "class_map_release_kernel", "accumulate_kernel", "accumulate4_kernel",
+                 "accumulate_mapped_kernel")
 # opt-in trace instances, with a guide or a mesh: over budget by the compiler's frame slots or by design, recorded in DESIGN.md 4.12 / 4.16
 KNOWN_OVER = ("_guide", "_lights", "_plamps", "_mesh")
 

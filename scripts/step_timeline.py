@@ -45,7 +45,7 @@ def kind(name):
     if "class_resolve" in name: return "cresolve"
     if "class_spread" in name: return "spread"
     if "share_expand" in name or "memo_expand" in name: return "expand"
-    if "accumulate4_kernel" in name or "accumulate_kernel" in name: return "acc"
+    if "accumulate4_kernel" in name or "accumulate_kernel" in name or "accumulate_mapped_kernel" in name: return "acc"   # (mapped: the pass expands too)
     if "trace_kernel" in name: return "trace"
     if "nif_kernel" in name: return "nif"
     if "fill" in name.lower() or "memset" in name.lower(): return "fill"
@@ -112,6 +112,9 @@ def main():
         print("%s step %d: %d batches, span %.2f ms, NIF running %.2f ms, no NIF launch running %.1f %% of the step, first N begins at %.2f ms; clears: %s"
               % (a.label, si, len(by["nif"]), span, nif_ms, idle[-1], head,
                  ", ".join("%.2f ms at %.2f" % ((r[1] - r[0]) / 1e6, (r[0] - t0) / 1e6) for r in clears) or "none"))
+        if by["claim"]:
+            print("%s step %d: the last claim pass ends at %.2f ms, the last trace kernel at %.2f ms" % (
+                a.label, si, (max(r[1] for r in by["claim"]) - t0) / 1e6, (max(r[1] for r in by["trace"]) - t0) / 1e6))
         A, N, T = by["acc"], by["nif"], by["trace"]
         if len(A) != len(N) or len(T) != len(N):
             continue
